@@ -2,13 +2,19 @@
 """bench.py - frames/s of the full cuboid_detection point-cloud chain (crop -> voxel -> RANSAC
 plane -> extract -> Euclidean clusters -> per-cluster ICP) on synthetic 640x480 D435 frames.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of `--frames` frames per GPU, already
 resident in HBM when the timed region starts, followed by the gather of the fixed-size pose
 records of all ranks (one all_gather per batch; RCCL over xGMI for N > 1).  Weak scaling:
 per-GPU work is fixed, value = all frames of all ranks / time (max over ranks).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what runs
+after the timed region: the self-check against a serial pass (and the exclusive ICP launch
+time it yields), the single-frame latencies, the extra legs of the N = 1 line and the CPU
+baseline with its oracle check.  --dump-outputs DIR writes the records of the last timed
+step as DIR/<field>.npy.
 """
 import argparse
 import json
@@ -164,6 +170,33 @@ def cpu_baseline(frames, prm, tpl, budget_s=20.0, max_frames=96, gpu_records=Non
     return out
 
 
+DUMP_MAX_FRAMES = 16384   # ~2000 bytes per frame in the dump: at most ~33 MB
+
+
+def dump_outputs(records, out_dir):
+    """--dump-outputs: the per-frame records the timed path returned in its last step (all ranks' frames, frame order), one
+    .npy per field - float64 for the counters, flags and double fields, float32 for the float ones.  Above DUMP_MAX_FRAMES
+    frames a fixed, seeded sample of them is written, with its frame numbers in frame_index.npy."""
+    from perception_amd import capi
+    os.makedirs(out_dir, exist_ok=True)
+    r = np.frombuffer(np.ascontiguousarray(records, np.uint8).tobytes(), dtype=np.dtype(capi.CdFrameResult))
+    arrays = {}
+    if len(r) > DUMP_MAX_FRAMES:
+        idx = np.sort(np.random.default_rng(0).choice(len(r), DUMP_MAX_FRAMES, replace=False))
+        r = r[idx]
+        arrays["frame_index"] = idx.astype(np.float64)
+    c = r["clusters"]
+    arrays["frame_counts"] = np.stack([r[k] for k in ("status", "n_cropped", "n_voxels", "n_plane", "n_objects", "n_clusters",
+                                                      "ransac_iterations", "flags")], axis=1).astype(np.float64)
+    arrays["plane"] = r["plane"].astype(np.float32)
+    arrays["cluster_stats"] = np.stack([c[k] for k in ("size", "iterations", "converged", "accepted", "template_slot", "fitness")],
+                                       axis=2).astype(np.float64)
+    arrays["cluster_T"] = c["T"].astype(np.float32)
+    arrays["cluster_pose"] = c["pose"].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without a launcher: start N fresh rank processes (one per GPU) and relay rank 0's JSON line.
     Runs BEFORE this process imports torch or touches HIP - a process that has initialised the GPU must never be
@@ -249,10 +282,15 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=(3, 5),
                     help="3: the headline workload (256 D435 frames per GPU, one template); 5: the multi-template stress of "
                          "BASELINE config 5 (1 M-point frames, five cuboids, five templates, every cluster x every template)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-frame latency measurement (BASELINE config 2; runs after the timed region)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the self-check of the timed path's records (runs after the timed region)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra legs of the default N = 1 line (config 5, the 21 400-point template, host-fed): they run after the timed region and are never part of `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: the self-check, the single-frame "
+                         "latencies, the extra legs and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (all ranks' frames) as DIR/<field>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its oracle check")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the single-frame latency measurement (BASELINE config 2; runs after the timed region)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the self-check of the timed path's records (runs after the timed region)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the extra legs of the default N = 1 line (config 5, the 21 400-point template, host-fed): they run after the timed region and are never part of `value`")
     ap.add_argument("--legs-config5-frames", type=int, default=64, help="frames per batch of the config-5 leg")
     ap.add_argument("--guess", choices=("none", "sne", "track"), default="none",
                     help="after the headline measurement, a separately labelled leg with per-frame initial guesses (opt-in ICP guess; "
@@ -279,6 +317,8 @@ def main():
         args.warmup = max(4, args.inflight)
     if args.steps < 1 or args.warmup < 0 or args.frames < 1:
         raise SystemExit("bench.py: --steps/--frames must be >= 1, --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_latency = args.no_verify = args.no_legs = True
 
     env_world = int(os.environ["WORLD_SIZE"]) if "WORLD_SIZE" in os.environ else None
     if env_world is None and (args.gpus or 1) > 1:
@@ -408,6 +448,8 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(allrec, args.dump_outputs)
 
     # single-frame latency (BASELINE config 2), not part of the timed region
     t = ctx.timing()

@@ -25,7 +25,7 @@ def _bench(args, env_extra=None):
 
 def test_one_rank_through_rccl_gather_is_verified():
     """World size 1 but the record gather goes through torch.distributed/nccl (= RCCL): same code path as N > 1."""
-    out = _bench(["--gpus", "1", "--frames", "24", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], {"CUBOID_BENCH_FORCE_DIST": "1"})
+    out = _bench(["--gpus", "1", "--frames", "24", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"], {"CUBOID_BENCH_FORCE_DIST": "1"})
     assert out["n_gpus"] == 1 and out["config"]["rccl_ranks"] == 1
     assert out["verified"] is True
     assert out["icp"]["frames"] == 24 and out["single_frame_ms"]["median"] > 0
@@ -35,7 +35,7 @@ def test_two_ranks_nccl_gather():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs 2 GPUs on the box (the round-end scaling run covers N = 2/4/8)")
-    out = _bench(["--gpus", "2", "--frames", "24", "--steps", "4", "--warmup", "1"])
+    out = _bench(["--gpus", "2", "--frames", "24", "--steps", "4", "--warmup", "1", "--full"])
     assert out["n_gpus"] == 2 and out["config"]["rccl_ranks"] == 2
     assert out["verified"] is True
     assert out["icp"]["frames"] == 48          # every rank's records arrived, in frame order

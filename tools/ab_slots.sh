@@ -4,7 +4,7 @@
 #   main   = the shipped library (two slots)
 #   slots3 = three clusters in flight per workgroup (make VARIANT=slots3 FLAGS_EXTRA=-DCD_PIPE_SLOTS=3)
 cd "$(dirname "$0")/.."
-run() { python bench.py "$@" --steps 300 --no-latency --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py "$@" --steps 300 --full --no-latency --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());print('%s: %.0f frames/s  icp launch %.2f ms verified %s' % (sys.argv[1], d['value'], d['roofline']['avg_launch_ms'], d['verified']))" "$LABEL"; }
 for rep in 1 2 3; do
   [ -f perception_amd/lib/variants/libprev.so ] && LABEL="prev   wg 256 inflight 4" CUBOID_HIP_LIB=perception_amd/lib/variants/libprev.so run --inflight 4

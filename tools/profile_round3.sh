@@ -18,6 +18,6 @@ echo "serial stats done"
 python3 tools/big_template_ms.py 1 32 256 > $OUT/big_template_ms.txt 2>&1
 echo "big template done"
 CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python3 tools/probe_icp_work.py $OUT/icp_work.json > /dev/null 2>&1 || echo "work probe failed"
-python3 bench.py > $OUT/bench_line.json 2> /dev/null
-python3 bench.py --config 5 > $OUT/bench_line_config5.json 2> /dev/null
+python3 bench.py --full > $OUT/bench_line.json 2> /dev/null
+python3 bench.py --full --config 5 > $OUT/bench_line_config5.json 2> /dev/null
 echo "bench lines done"

@@ -35,7 +35,7 @@ cd $R
 tools/serial_kernel_ms.sh > $OUT/serial_kernel_ms.txt 2>&1 && cp gpurun_out/serial_kernel_stats.csv $OUT/serial_kernel_stats.csv
 echo "serial stats done"
 CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python3 tools/probe_icp_work.py $OUT/icp_work.json > /dev/null 2>&1 || echo "work probe failed"
-python3 bench.py > $OUT/bench_line.json 2> /dev/null
+python3 bench.py --full > $OUT/bench_line.json 2> /dev/null
 echo "bench line done"
-python3 bench.py --config 5 > $OUT/bench_line_config5.json 2> /dev/null
+python3 bench.py --full --config 5 > $OUT/bench_line_config5.json 2> /dev/null
 echo "config 5 line done"
