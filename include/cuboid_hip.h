@@ -160,7 +160,7 @@ typedef struct cd_frame_result {
 void cd_default_params(cd_params* p);
 int cd_abi_version(void);
 /* sizeof() of the ABI structs, for FFI layers to verify their mirror of this header:
- * which = 0 cd_params, 1 cd_cluster_result, 2 cd_frame_result, 3 cd_timing. */
+ * which = 0 cd_params, 1 cd_cluster_result, 2 cd_frame_result, 3 cd_timing, 4 cd_depth_camera. */
 int cd_struct_size(int which);
 
 /* Object lifetimes (replaces construction/destruction of the PCL objects and the node's
@@ -317,6 +317,51 @@ int cd_process_batch_device(cd_context* ctx, const void* d_frames, size_t stride
                             int points_per_frame, int n_frames, const cd_params* prm,
                             cd_frame_result* results, int32_t* plane_inliers,
                             int32_t* labels);
+
+/* Depth-image input: what the D435 produces before its driver builds /camera/depth/color/points on the CPU, deprojected on
+ * the device (depth_image_proc-style, from sensor_msgs/Image + CameraInfo).  Depth is 16UC1 with tightly packed rows
+ * (step == 2 * width); the optional colour is rgb8 registered pixel for pixel to the depth (step == 3 * width).  Pixel (u, v)
+ * becomes record v * width + u of an ORGANIZED cloud of 16-byte records x, y, z float32 + packed rgb, by canonical rule C7
+ * (float32, no contraction, IEEE '/'):
+ *     z = (float)d * depth_scale,  x = (((float)u - cx) / fx) * z,  y = (((float)v - cy) / fy) * z,
+ *     rgb word = (r << 16) | (g << 8) | b (0 without colour);
+ *     d == 0 is invalid: x = y = z = quiet NaN (0x7FC00000), the rgb word as for a valid pixel.
+ * A batch of F frames is F images back to back (depth: F * width * height uint16, colour: F * width * height * 3 bytes).
+ * Bad input (null depth, width * height 0 or over max_points, n_frames out of 1 .. max_frames, an unknown colour mode, colour
+ * requested with a NULL pointer, fx / fy / depth_scale not finite or <= 0) is CD_ERR_INVALID_ARG before anything is copied
+ * or launched. */
+enum { CD_COLOR_NONE = 0, CD_COLOR_RGB8 = 1 };
+typedef struct cd_depth_camera {      /* sensor_msgs/CameraInfo of the depth stream; int32/float only, no padding holes */
+    int32_t width, height;            /* width*height <= the context's max_points */
+    float fx, fy, cx, cy;             /* K[0], K[4], K[2], K[5]; plumb_bob with D == 0 only */
+    float depth_scale;                /* metres per unit (D435: 0.001) */
+    int32_t color;                    /* CD_COLOR_NONE | CD_COLOR_RGB8 */
+} cd_depth_camera;
+
+/* The D435 depth stream of the reference's README.md:74-78: 640 x 480, K of its CameraInfo, 1 mm per unit, no colour. */
+void cd_default_depth_camera(cd_depth_camera* cam);
+
+/* One frame, host in and host out: the organized cloud (width * height records, NaN where the depth is 0) that a node
+ * publishes for the image, in a PointCloud2 layout of the caller's choice - `stride_bytes` (a multiple of 4, >= 12) per
+ * record, x,y,z at 0/4/8, the rgb word at rgb_offset (-1: none; a multiple of 4, >= 12), every other byte zero.  `capacity`
+ * records fit in out_records; *out_n receives width * height (also when the capacity is too small: CD_ERR_CAPACITY). */
+int cd_depth_to_cloud(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color,
+                      void* out_records, size_t stride_bytes, int rgb_offset, int capacity, int* out_n);
+
+/* Whole chain on n_frames depth images: exactly cd_process_batch on the canonical organized clouds - stride 16,
+ * points_per_frame = width * height, rgb_offset 12 with colour and -1 without (prm->rgb_offset is IGNORED).  Results,
+ * cd_get_cluster_results / cd_get_frame_cloud / cd_get_cluster_points and cd_get_timing (the deprojection counts in
+ * stage [0]) are those of that call.  The images are uploaded into buffers of their own (one copy each, on the context's
+ * stream) and deprojected on the device. */
+int cd_process_depth_batch(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color,
+                           int n_frames, const cd_params* prm, cd_frame_result* results, int32_t* plane_inliers,
+                           int32_t* labels);
+
+/* Same, images already resident in device memory of the context's GPU (ordering as cd_process_batch_device: the caller has
+ * completed its writes before the call). */
+int cd_process_depth_batch_device(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* d_depth, const uint8_t* d_color,
+                                  int n_frames, const cd_params* prm, cd_frame_result* results, int32_t* plane_inliers,
+                                  int32_t* labels);
 
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */

@@ -95,9 +95,12 @@ class BatchPipeline:
             cx.process_batch_device(d_ptr, stride, n_points, n_frames, prm, results=res)
         return capi.results_to_array(res)[:n_frames].copy(), cx.timing()
 
-    def submit(self, d_ptr, stride, n_points, n_frames, prm, host=False):
-        """Queue one batch that is already resident in device memory (d_ptr: device pointer of F x N records), or - host=True -
-        one that sits in HOST memory (pinned for full PCIe rate): what a ROS callback has (gps.cpp:43-49)."""
+    def _run_depth(self, i, depth_ptr, color_ptr, n_frames, cam, prm):
+        cx, res = self.contexts[i], self._results[i]
+        cx.process_depth_batch_host_ptr(depth_ptr, color_ptr, n_frames, cam, prm, results=res)
+        return capi.results_to_array(res)[:n_frames].copy(), cx.timing()
+
+    def _free_context(self):
         # a context runs one batch at a time: take a free one, else wait for the first to finish (batches differ in length: a
         # fixed rotation would hold the submission behind the slowest)
         from concurrent.futures import FIRST_COMPLETED, wait
@@ -105,8 +108,22 @@ class BatchPipeline:
         if not free:
             wait(self._busy, return_when=FIRST_COMPLETED)
             free = [j for j in range(self.inflight) if self._busy[j].done()]
-        i = free[0]
+        return free[0]
+
+    def submit(self, d_ptr, stride, n_points, n_frames, prm, host=False):
+        """Queue one batch that is already resident in device memory (d_ptr: device pointer of F x N records), or - host=True -
+        one that sits in HOST memory (pinned for full PCIe rate): what a ROS callback has (gps.cpp:43-49)."""
+        i = self._free_context()
         fut = self._pool.submit(self._run, i, d_ptr, stride, n_points, n_frames, prm, host)
+        self._busy[i] = fut
+        return fut
+
+    def submit_depth(self, depth_ptr, color_ptr, n_frames, cam, prm):
+        """Queue one batch of depth images in HOST memory (depth_ptr: F x H x W uint16; color_ptr: F x H x W x 3 rgb8 registered
+        to it, or None; pinned for full PCIe rate): cd_process_depth_batch, the images deprojected on the device.  Same Future
+        as submit()."""
+        i = self._free_context()
+        fut = self._pool.submit(self._run_depth, i, depth_ptr, color_ptr, n_frames, cam, prm)
         self._busy[i] = fut
         return fut
 

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "cd_process_batch", "cd_process_frame", "cd_process_batch_device", "cd_get_cluster_results", "cd_pose_to_position_quaternion",
     "cd_bbox_corners", "cd_get_timing", "cd_get_frame_cloud", "cd_get_cluster_points", "cd_ground_plane", "cd_set_frame_guesses",
     "cd_template_lattice_faces", "cd_template_nearest", "cd_lattice_detect", "cd_passthrough",
+    "cd_default_depth_camera", "cd_depth_to_cloud", "cd_process_depth_batch", "cd_process_depth_batch_device",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -39,6 +40,7 @@ CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME = 0, 1, 2
 
 
 CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
+CD_COLOR_NONE, CD_COLOR_RGB8 = 0, 1
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -100,6 +102,15 @@ class CdTiming(C.Structure):
     ]
 
 
+class CdDepthCamera(C.Structure):
+    """cd_depth_camera: CameraInfo of a 16UC1 depth stream (optionally with an rgb8 image registered to it)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("depth_scale", C.c_float), ("color", C.c_int32),
+    ]
+
+
 FRAME_RESULT_BYTES = C.sizeof(CdFrameResult)
 
 
@@ -128,6 +139,18 @@ def default_params():
     p.icp_euclidean_fitness_epsilon = 0.0004
     p.icp_accept_fitness = 0.0004
     return p
+
+
+def default_depth_camera():
+    """The D435 depth stream of the reference's README.md:74-78 (640 x 480, K of its CameraInfo), 1 mm per unit, no
+    colour.  Pure Python mirror of cd_default_depth_camera()."""
+    cam = CdDepthCamera()
+    cam.width, cam.height = 640, 480
+    cam.fx = cam.fy = 384.0898742675781
+    cam.cx, cam.cy = 322.4656677246094, 240.64073181152344
+    cam.depth_scale = 0.001
+    cam.color = CD_COLOR_NONE
+    return cam
 
 
 _lib = None
@@ -184,6 +207,11 @@ def load_library(path=None):
     lib.cd_template_nearest.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_lattice_detect.argtypes = [vp, C.c_size_t, C.c_int, vp]
     lib.cd_passthrough.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, ip]
+    lib.cd_default_depth_camera.argtypes = [C.POINTER(CdDepthCamera)]
+    lib.cd_default_depth_camera.restype = None
+    lib.cd_depth_to_cloud.argtypes = [vp, C.POINTER(CdDepthCamera), vp, vp, vp, C.c_size_t, C.c_int, C.c_int, ip]
+    for f in (lib.cd_process_depth_batch, lib.cd_process_depth_batch_device):
+        f.argtypes = [vp, C.POINTER(CdDepthCamera), vp, vp, C.c_int, C.POINTER(CdParams), vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -418,6 +446,51 @@ class Context:
         d2 = np.empty(max(n, 1), np.float32)
         self._check(self.lib.cd_template_nearest(self.h, slot, _ptr(a), stride, n, _ptr(idx), _ptr(d2)))
         return idx[:n], d2[:n]
+
+    def depth_to_cloud(self, cam, depth, color=None, stride_bytes=16, rgb_offset=12):
+        """One depth image (H, W) uint16 (+ colour (H, W, 3) uint8 when cam.color is CD_COLOR_RGB8) -> the organized cloud as
+        (W * H, stride_bytes / 4) uint32 records: x,y,z at words 0..2 (NaN where the depth is 0), the packed rgb at rgb_offset
+        (-1: none), the rest zero."""
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        c = None if color is None else np.ascontiguousarray(color, dtype=np.uint8)
+        n = int(cam.width) * int(cam.height)
+        out = np.zeros((max(n, 1), stride_bytes // 4), np.uint32)
+        cnt = C.c_int()
+        self._check(self.lib.cd_depth_to_cloud(self.h, C.byref(cam), _ptr(d), _ptr(c), _ptr(out), stride_bytes, rgb_offset, n,
+                                               C.byref(cnt)))
+        return out[:cnt.value]
+
+    def process_depth_batch(self, depth, color, cam, prm, want_indices=False):
+        """depth (F, H, W) uint16, color (F, H, W, 3) uint8 or None (cam.color decides whether it is read): the chain on the
+        organized clouds the images deproject to.  Returns (results, plane_inliers, labels) as process_batch does."""
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        assert d.ndim == 3
+        c = None if color is None else np.ascontiguousarray(color, dtype=np.uint8)
+        F, N = d.shape[0], d.shape[1] * d.shape[2]
+        res = (CdFrameResult * F)()
+        pi = np.empty((F, N), np.int32) if want_indices else None
+        lb = np.empty((F, N), np.int32) if want_indices else None
+        self._check(self.lib.cd_process_depth_batch(self.h, C.byref(cam), _ptr(d), _ptr(c), F, C.byref(prm),
+                                                    C.cast(res, C.c_void_p), _ptr(pi), _ptr(lb)))
+        return res, pi, lb
+
+    def process_depth_batch_device(self, depth, color, cam, prm, results=None, plane_inliers=None, labels=None):
+        """depth: contiguous torch uint16 tensor (F, H, W) in HBM, color: uint8 tensor (F, H, W, 3) or None (data_ptr(); the
+        caller has synchronised the stream that wrote them, as for process_batch_device)."""
+        assert depth.is_contiguous() and depth.dim() == 3 and (color is None or color.is_contiguous())
+        F = depth.shape[0]
+        res = results if results is not None else (CdFrameResult * F)()
+        self._check(self.lib.cd_process_depth_batch_device(self.h, C.byref(cam), C.c_void_p(depth.data_ptr()),
+                                                           None if color is None else C.c_void_p(color.data_ptr()), F, C.byref(prm),
+                                                           C.cast(res, C.c_void_p), _ptr(plane_inliers), _ptr(labels)))
+        return res
+
+    def process_depth_batch_host_ptr(self, depth_ptr, color_ptr, n_frames, cam, prm, results=None):
+        """cd_process_depth_batch on raw HOST pointers (e.g. pinned torch tensors' data_ptr()): the uploads are part of the call."""
+        res = results if results is not None else (CdFrameResult * n_frames)()
+        self._check(self.lib.cd_process_depth_batch(self.h, C.byref(cam), C.c_void_p(depth_ptr), C.c_void_p(color_ptr) if color_ptr else None,
+                                                    n_frames, C.byref(prm), C.cast(res, C.c_void_p), None, None))
+        return res
 
     def timing(self):
         t = CdTiming()

@@ -30,6 +30,10 @@ struct cd_context {
     // input staging (host-pointer API)
     char* d_in = nullptr;
     size_t d_in_bytes = 0;
+    // depth-image input (cd_process_depth_batch): upload buffers of their own, allocated at the context's capacity on first use
+    // (d_in is the deprojection's destination, is re-allocated by ensure_input and is the read-back staging area)
+    uint16_t* d_depth = nullptr;
+    uint8_t* d_color = nullptr;
     // per-frame scalars
     FrameState* d_fs = nullptr;
     FrameState* h_fs = nullptr;
@@ -1211,8 +1215,15 @@ int check_params(cd_context* c, const cd_params* p) {
     return CD_OK;
 }
 
+// depth images of a batch on the device, deprojected into the records d_frames of process_batch_impl (k_depth.hip)
+struct DepthJob {
+    const cd_depth_camera* cam;
+    const uint16_t* depth;
+    const uint8_t* color;   // nullptr: no colour
+};
+
 int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N, int F, const cd_params* p,
-                       cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
+                       cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, const DepthJob* dj = nullptr) {
     int st = check_params(c, p);
     if (st) return st;
     if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
@@ -1224,6 +1235,9 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     GateHold front;
     if (c->front_concurrent > 0) front.enter(&g_front_gate[c->device & (MAX_DEVICES - 1)], c->front_concurrent);
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    if (dj)   // (stage [0] of the timing includes the deprojection)
+        LAUNCH(c, launch_deproject(c->stream, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, dj->cam->fx, dj->cam->fy, dj->cam->cx,
+                                   dj->cam->cy, dj->cam->depth_scale, (float4*)const_cast<void*>(d_frames)));
     struct ZeroedScope {   // the stages skip their own fills for the duration of this call only
         cd_context* c;
         ~ZeroedScope() { c->batch_zeroed = false; c->fs_initialised = false; }
@@ -1543,6 +1557,7 @@ int cd_struct_size(int which) {
         case 1: return (int)sizeof(cd_cluster_result);
         case 2: return (int)sizeof(cd_frame_result);
         case 3: return (int)sizeof(cd_timing);
+        case 4: return (int)sizeof(cd_depth_camera);
         default: return -1;
     }
 }
@@ -1563,6 +1578,8 @@ void cd_destroy(cd_context* c) {
     if (c->d_super) hipFree(c->d_super);
     if (c->d_lat) hipFree(c->d_lat);
     if (c->d_tileC) hipFree(c->d_tileC);
+    if (c->d_depth) hipFree(c->d_depth);
+    if (c->d_color) hipFree(c->d_color);
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
     if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
     for (auto& e : c->ev2) if (e) hipEventDestroy(e);
@@ -2482,6 +2499,97 @@ static int download_records(cd_context* c, const float4* d_pts, int m, size_t st
     return CD_OK;
 }
 
+// ---- depth-image input (k_depth.hip) ---------------------------------------------------------------------------------------
+// every check of the header's list, before anything is copied or launched
+static int check_depth(cd_context* c, const cd_depth_camera* cam, const void* depth, const void* color, int n_frames) {
+    if (!cam) return fail(c, CD_ERR_INVALID_ARG, "depth camera is NULL");
+    if (!depth) return fail(c, CD_ERR_INVALID_ARG, "depth image is NULL");
+    if (cam->width <= 0 || cam->height <= 0 || (long long)cam->width * cam->height > (long long)c->N)
+        return fail(c, CD_ERR_INVALID_ARG, "width * height must be in 1 .. the context's max_points");
+    if (n_frames <= 0 || n_frames > c->F) return fail(c, CD_ERR_INVALID_ARG, "n_frames must be in 1 .. the context's max_frames");
+    if (cam->color != CD_COLOR_NONE && cam->color != CD_COLOR_RGB8) return fail(c, CD_ERR_INVALID_ARG, "unknown colour mode");
+    if (cam->color == CD_COLOR_RGB8 && !color) return fail(c, CD_ERR_INVALID_ARG, "colour requested with a NULL colour image");
+    for (float v : {cam->fx, cam->fy, cam->depth_scale})
+        if (!(std::isfinite(v) && v > 0.f)) return fail(c, CD_ERR_INVALID_ARG, "fx, fy and depth_scale must be finite and > 0");
+    return CD_OK;
+}
+
+// host images -> the context's depth / colour buffers (one copy each, on the context's stream)
+static int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, DepthJob* dj) {
+    const size_t px = (size_t)cam->width * cam->height * n_frames;
+    if (!c->d_depth) HIPCHK(c, dalloc(&c->d_depth, (size_t)c->N * c->F));
+    HIPCHK(c, hipMemcpyAsync(c->d_depth, depth, px * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    dj->cam = cam;
+    dj->depth = c->d_depth;
+    dj->color = nullptr;
+    if (cam->color == CD_COLOR_RGB8) {
+        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        HIPCHK(c, hipMemcpyAsync(c->d_color, color, px * 3, hipMemcpyHostToDevice, c->stream));
+        dj->color = c->d_color;
+    }
+    return CD_OK;
+}
+
+static int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames,
+                                       const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    int st = check_params(c, p);
+    if (st) return st;
+    if (!results) return fail(c, CD_ERR_INVALID_ARG, "results is NULL");
+    st = check_depth(c, cam, depth, color, n_frames);
+    if (st) return st;
+    cd_params q = *p;
+    q.rgb_offset = cam->color == CD_COLOR_RGB8 ? 12 : -1;   // the canonical records: x y z rgb, 16 bytes
+    const int P = cam->width * cam->height;
+    st = ensure_input(c, (size_t)P * n_frames * sizeof(float4));
+    if (st) return st;
+    DepthJob dj{cam, depth, cam->color == CD_COLOR_RGB8 ? color : nullptr};
+    if (!on_device) {
+        st = upload_depth(c, cam, depth, color, n_frames, &dj);
+        if (st) return st;
+    }
+    return process_batch_impl(c, c->d_in, sizeof(float4), P, n_frames, &q, results, plane_inliers, labels, &dj);
+}
+
+static int cd_depth_to_cloud_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, void* out_records,
+                                  size_t stride, int rgb_offset, int capacity, int* out_n) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    if (!out_n || capacity < 0 || (capacity > 0 && !out_records) || stride < 12 || (stride & 3) ||
+        (rgb_offset >= 0 && (rgb_offset < 12 || (rgb_offset & 3) || (size_t)rgb_offset + 4 > stride)))
+        return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    int st = check_depth(c, cam, depth, color, 1);
+    if (st) return st;
+    *out_n = 0;
+    invalidate_last(c);
+    const int P = cam->width * cam->height;
+    if (P > capacity) { *out_n = P; return fail(c, CD_ERR_CAPACITY, "output capacity too small"); }
+    // one buffer: the canonical records, then (256-byte aligned) the caller's layout that goes back
+    const size_t rec_bytes = (size_t)P * sizeof(float4);
+    st = ensure_input(c, ((rec_bytes + 255) & ~(size_t)255) + (size_t)P * stride);
+    if (st) return st;
+    DepthJob dj;
+    st = upload_depth(c, cam, depth, color, 1, &dj);
+    if (st) return st;
+    LAUNCH(c, launch_deproject(c->stream, dj.depth, dj.color, cam->width, cam->height, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->depth_scale,
+                               reinterpret_cast<float4*>(c->d_in)));
+    st = download_records(c, reinterpret_cast<const float4*>(c->d_in), P, stride, rgb_offset, 0u, out_records, rec_bytes);
+    if (st) return st;
+    *out_n = P;
+    return CD_OK;
+}
+
+void cd_default_depth_camera(cd_depth_camera* cam) {
+    if (!cam) return;
+    std::memset(cam, 0, sizeof(*cam));
+    cam->width = 640; cam->height = 480;                                  // README.md:74-75 of the reference
+    cam->fx = cam->fy = 384.0898742675781f;                              // K[0], K[4] (README.md:78)
+    cam->cx = 322.4656677246094f; cam->cy = 240.64073181152344f;        // K[2], K[5]
+    cam->depth_scale = 0.001f;                                           // 16UC1 in millimetres (the RealSense driver's unit)
+    cam->color = CD_COLOR_NONE;
+}
+
 int cd_get_frame_cloud(cd_context* c, int frame, int which, void* out_records, size_t stride, int rgb_offset, int capacity, int* out_n) {
     if (!c) return CD_ERR_INVALID_ARG;
     hipSetDevice(c->device);
@@ -2629,6 +2737,18 @@ int cd_process_batch(cd_context* c, const void* frames, size_t stride, int point
 int cd_ground_plane(cd_context* c, const void* points, size_t stride, int n, const cd_params* p, float coeff[4], void* out_records, int capacity, int* out_n, int* out_n_inliers) {
     if (!c) return CD_ERR_INVALID_ARG;
     return with_scan_retry(c, [&]() { return cd_ground_plane_impl(c, points, stride, n, p, coeff, out_records, capacity, out_n, out_n_inliers); });
+}
+int cd_depth_to_cloud(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, void* out_records, size_t stride, int rgb_offset, int capacity, int* out_n) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_depth_to_cloud_impl(c, cam, depth, color, out_records, stride, rgb_offset, capacity, out_n); });
+}
+int cd_process_depth_batch(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_process_depth_batch_impl(c, cam, depth, color, n_frames, p, results, plane_inliers, labels, false); });
+}
+int cd_process_depth_batch_device(cd_context* c, const cd_depth_camera* cam, const uint16_t* d_depth, const uint8_t* d_color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_process_depth_batch_impl(c, cam, d_depth, d_color, n_frames, p, results, plane_inliers, labels, true); });
 }
 
 int cd_get_timing(const cd_context* c, cd_timing* out) {

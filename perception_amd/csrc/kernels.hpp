@@ -111,4 +111,15 @@ void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const
                     unsigned long long* busy_out, IcpParams prm);
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2);
 
+// k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
+// records x y z rgb (canonical rule C7)
+struct DeprojectParams {
+    int width, height;
+    float fx, fy, cx, cy, depth_scale;
+    uint32_t stepu, stepv;   // BLOCK pixels further on: columns, rows (modulo the frame)
+    size_t total;            // pixels of the batch
+};
+void launch_deproject(hipStream_t s, const uint16_t* depth, const uint8_t* color, int width, int height, int n_frames, float fx,
+                      float fy, float cx, float cy, float depth_scale, float4* out);
+
 }  // namespace cd

@@ -189,6 +189,29 @@ def frames(start, count, k_obj=None, width=WIDTH, height=HEIGHT):
     return np.stack([frame(start + i, k_obj, width, height) for i in range(count)], axis=0)
 
 
+DEPTH_SCALE = 0.001     # metres per unit of depth_frame's 16UC1 image (the RealSense driver's millimetres)
+
+
+def depth_frame(index, k_obj=None, width=WIDTH, height=HEIGHT):
+    """Frame `index` as the camera delivers it, before any point cloud: (depth uint16 (height, width), rgb8 uint8
+    (height, width, 3)) of the same render() scene.  depth = round(z / 0.001) clipped to 1..65535, 0 where render marks
+    the pixel invalid; the colour is render's packed rgb unpacked.  The intrinsics are depth_camera_params(width, height)."""
+    rec = frame(index, k_obj, width, height)
+    z = rec[:, 2].astype(np.float64)
+    bad = np.isnan(z)
+    d = np.clip(np.round(np.where(bad, 0.0, z) / DEPTH_SCALE), 1, 65535).astype(np.uint16)
+    d[bad] = 0
+    c = rec[:, 3].view(np.uint32)
+    rgb = np.stack([(c >> 16) & 255, (c >> 8) & 255, c & 255], axis=1).astype(np.uint8)
+    return d.reshape(height, width), rgb.reshape(height, width, 3)
+
+
+def depth_camera_params(width=WIDTH, height=HEIGHT):
+    """(fx, fy, cx, cy) of render()'s pinhole at that sensor size (the 640x480 intrinsics scaled, as _ray_dirs does)."""
+    sx, sy = width / float(WIDTH), height / float(HEIGHT)
+    return FX * sx, FY * sy, CX * sx, CY * sy
+
+
 def truth_poses(scene):
     """4x4 template->camera pose of each cuboid (for the pose-error report)."""
     out = []
