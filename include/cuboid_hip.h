@@ -51,7 +51,8 @@ typedef enum cd_status {
     CD_ERR_CAPACITY = -2,      /* input larger than the context / output buffer too small   */
     CD_ERR_DEVICE = -3,        /* HIP runtime error or no usable device                     */
     CD_ERR_NO_MODEL = -4,      /* RANSAC found no plane (PCL: empty inliers+coefficients)   */
-    CD_ERR_FEW_CORRESPONDENCES = -5, /* ICP source has < 3 points (PCL: "Not enough correspondences") */
+    CD_ERR_FEW_CORRESPONDENCES = -5, /* ICP source has < 3 points, or (cd_icp with a maximum correspondence distance)
+                                        an iteration kept < 3 correspondences (PCL: "Not enough correspondences") */
     CD_ERR_LEAF_TOO_SMALL = -6,/* voxel grid would overflow int32 indices (PCL warns)       */
     CD_ERR_NO_TEMPLATE = -7    /* template slot empty                                       */
 } cd_status;
@@ -244,7 +245,10 @@ int cd_cluster(cd_context* ctx, const void* xyz, size_t stride_bytes, int n,
                int* out_k);
 
 /* S6: icp.align + getFinalTransformation + hasConverged + getFitnessScore
- * (icp.cpp:170-182).  aligned (may be NULL) receives n*3 floats. */
+ * (icp.cpp:170-182).  aligned (may be NULL) receives n*3 floats.
+ * With a maximum correspondence distance (cd_set_icp_max_correspondence_distance) an iteration that keeps fewer than 3
+ * correspondences stops the ICP before its update, as PCL does: CD_ERR_FEW_CORRESPONDENCES, with out filled (T and
+ * iterations as before that iteration, converged = accepted = 0, the fitness of T over all points) and aligned = T * source. */
 int cd_icp(cd_context* ctx, int slot, const void* src_xyz, size_t stride_bytes, int n,
            const cd_params* prm, cd_cluster_result* out, float* aligned);
 
@@ -308,6 +312,24 @@ int cd_ground_plane(cd_context* ctx, const void* points, size_t stride_bytes, in
  * (scene -> template), frame f of the following cd_process_batch* calls uses guesses[16 f .. 16 f + 15] for each of its
  * clusters (the granularity of the reference: one sne pose per frame, icp.cpp:130-134).  n_frames = 0 clears them. */
 int cd_set_frame_guesses(cd_context* ctx, const float* guesses, int n_frames);
+
+/* IterativeClosestPoint::setMaxCorrespondenceDistance (the line icp.cpp:175 / opd.cpp:225 leave commented out): context
+ * state that applies to every ICP of the following cd_icp, cd_process_frame, cd_process_batch[_device] and
+ * cd_process_depth_batch[_device] calls on ctx.  Default: unbounded.  Rule C8: source point i keeps its
+ * correspondence iff (double)d2_i <= max_distance * max_distance (the boundary is kept), d2_i being the float32 squared
+ * distance to its nearest template point (the search itself is unchanged); only kept correspondences enter the
+ * transformation estimate and the MSE of the convergence test; fewer than 3 stop the ICP before that iteration's update
+ * (converged = accepted = 0, T and iterations as they were; in a batch that is a result, the frame's status stays CD_OK).
+ * getFitnessScore is unchanged: all points, unbounded.  +inf, and any distance whose square is >= FLT_MAX (PCL's default
+ * sqrt(DBL_MAX) among them), is unbounded: the default path, byte for byte.  Negative or NaN: CD_ERR_INVALID_ARG, the
+ * setting stays as it was. */
+int cd_set_icp_max_correspondence_distance(cd_context* ctx, double max_distance);
+int cd_get_icp_max_correspondence_distance(const cd_context* ctx, double* out);
+
+/* Host-only (no context, no GPU): rule C8's conversion.  *out_d2_max = the largest float32 f with (double)f <= d * d
+ * (what the kernels compare d2 against), *out_bounded = 0 when d * d >= FLT_MAX (nothing is ever rejected), else 1.
+ * Either pointer may be NULL.  Negative or NaN d: CD_ERR_INVALID_ARG. */
+int cd_icp_correspondence_threshold(double max_distance, float* out_d2_max, int* out_bounded);
 
 /* Same, input already resident in device memory (HBM) of the context's GPU.  A context works on its own
  * non-blocking HIP stream: there is no implicit ordering against the NULL stream or any other stream, so the

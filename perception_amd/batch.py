@@ -74,15 +74,19 @@ class BatchPipeline:
     streams that share a queue run one after the other; 16 for multi-template batches, whose contexts have two more
     streams each) before the HIP runtime starts, as bench.py does.
 
-    submit() returns a Future of (records uint8[F, FRAME_RESULT_BYTES], CdTiming)."""
+    submit() returns a Future of (records uint8[F, FRAME_RESULT_BYTES], CdTiming).
+    icp_max_correspondence_distance: IterativeClosestPoint::setMaxCorrespondenceDistance for every context (None:
+    unbounded, the default; rule C8)."""
 
-    def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2):
+    def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2, icp_max_correspondence_distance=None):
         from concurrent.futures import ThreadPoolExecutor
         self.inflight = max(1, int(inflight))
         self.contexts = [capi.Context(max_points=max_points, max_frames=max_frames, device_id=device_id) for _ in range(self.inflight)]
         for cx in self.contexts:
             for slot, xyz in templates_by_slot.items():
                 cx.set_template(slot, xyz)
+            if icp_max_correspondence_distance is not None:
+                cx.set_icp_max_correspondence_distance(icp_max_correspondence_distance)
         self._results = [(capi.CdFrameResult * max_frames)() for _ in range(self.inflight)]
         self._busy = [None] * self.inflight
         self._pool = ThreadPoolExecutor(self.inflight)

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "cd_bbox_corners", "cd_get_timing", "cd_get_frame_cloud", "cd_get_cluster_points", "cd_ground_plane", "cd_set_frame_guesses",
     "cd_template_lattice_faces", "cd_template_nearest", "cd_lattice_detect", "cd_passthrough",
     "cd_default_depth_camera", "cd_depth_to_cloud", "cd_process_depth_batch", "cd_process_depth_batch_device",
+    "cd_set_icp_max_correspondence_distance", "cd_get_icp_max_correspondence_distance", "cd_icp_correspondence_threshold",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -206,6 +207,9 @@ def load_library(path=None):
     lib.cd_template_lattice_faces.argtypes = [vp, C.c_int]
     lib.cd_template_nearest.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_lattice_detect.argtypes = [vp, C.c_size_t, C.c_int, vp]
+    lib.cd_set_icp_max_correspondence_distance.argtypes = [vp, C.c_double]
+    lib.cd_get_icp_max_correspondence_distance.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.cd_icp_correspondence_threshold.argtypes = [C.c_double, C.POINTER(C.c_float), ip]
     lib.cd_passthrough.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, C.c_int, ip]
     lib.cd_default_depth_camera.argtypes = [C.POINTER(CdDepthCamera)]
     lib.cd_default_depth_camera.restype = None
@@ -424,6 +428,16 @@ class Context:
         g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
         self._check(self.lib.cd_set_frame_guesses(self.h, g.ctypes.data_as(C.POINTER(C.c_float)), g.shape[0]))
 
+    def set_icp_max_correspondence_distance(self, d):
+        """IterativeClosestPoint::setMaxCorrespondenceDistance for every later ICP of this context (rule C8); None = unbounded."""
+        self._check(self.lib.cd_set_icp_max_correspondence_distance(self.h, float("inf") if d is None else float(d)))
+
+    def icp_max_correspondence_distance(self):
+        """The distance as set (+inf: unbounded, the default)."""
+        v = C.c_double()
+        self._check(self.lib.cd_get_icp_max_correspondence_distance(self.h, C.byref(v)))
+        return v.value
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -507,6 +521,16 @@ def lattice_detect(xyz):
     if nf < 0:
         raise CuboidError(nf, "cd_lattice_detect")
     return [tuple(int(v) for v in out[f]) for f in range(nf)]
+
+
+def icp_correspondence_threshold(d):
+    """Host-only rule C8 conversion: (largest float32 f with float64(f) <= d*d, bounded flag); None = unbounded."""
+    lib = load_library()
+    f, b = C.c_float(), C.c_int()
+    st = lib.cd_icp_correspondence_threshold(float("inf") if d is None else float(d), C.byref(f), C.byref(b))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_icp_correspondence_threshold")
+    return f.value, int(b.value)
 
 
 def results_to_array(res):

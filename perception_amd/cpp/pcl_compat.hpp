@@ -341,6 +341,10 @@ public:
     void setTransformationEpsilon(double e) { prm_.icp_transformation_epsilon = e; }
     void setEuclideanFitnessEpsilon(double e) { prm_.icp_euclidean_fitness_epsilon = e; }
     void setRANSACOutlierRejectionThreshold(double) {}   // inert in PCL too: no rejector is installed (icp.cpp:177)
+    // the line icp.cpp:175 / opd.cpp:225 leave commented out (rule C8); PCL's default sqrt(DBL_MAX) bounds nothing.  Every
+    // object shares the device's context, so align() hands the context this object's value before each ICP.
+    void setMaxCorrespondenceDistance(double d) { max_corr_ = d; }
+    double getMaxCorrespondenceDistance() const { return max_corr_; }
     // align(output, guess): pcl::Registration's second overload (row-major 4x4, scene -> template)
     void align(PointCloud<PointSource>& output, const Matrix4& guess) {
         prm_.icp_use_guess = CD_GUESS_PARAMS;
@@ -356,6 +360,10 @@ public:
         const int n = (int)src_->points.size();
         std::vector<float> al((size_t)std::max(n, 1) * 3);
         cd_cluster_result r;
+        if (cd_set_icp_max_correspondence_distance(Device::instance().ctx(), max_corr_) != CD_OK) {
+            std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx()));
+            return;
+        }
         const int st = cd_icp(Device::instance().ctx(), slot_, src_->points.data(), sizeof(PointSource), n, &prm_, &r, al.data());
         if (st != CD_OK && st != CD_ERR_FEW_CORRESPONDENCES) { std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx())); return; }
         if (st == CD_ERR_FEW_CORRESPONDENCES) std::fprintf(stderr, "[pclhip::IterativeClosestPoint] Not enough correspondences found. Relax your threshold parameters.\n");
@@ -377,6 +385,7 @@ public:
 private:
     cd_params prm_;
     int slot_ = 0, iterations_ = 0;
+    double max_corr_ = std::sqrt(std::numeric_limits<double>::max());
     typename PointCloud<PointSource>::ConstPtr src_;
     typename PointCloud<PointTarget>::ConstPtr tgt_;
     Matrix4 final_;

@@ -174,6 +174,15 @@ struct IcpParams {
     int32_t don_idle;      // tests: workgroups 0 .. don_idle-1 never take from the queue - everything they run reaches them by hand-over
     int32_t don_fault;     // tests: 1 = the first donor claims a mailbox entry and never publishes it (the loss path must be REPORTED)
 };
+// Rule C8 (cd_set_icp_max_correspondence_distance), a kernel argument of its own after IcpParams: k_icp_pipe hands IcpParams
+// to its out-of-line solve through a stack copy, which a larger IcpParams would grow in the default instantiations too.
+// bounded != 0 selects the BOUNDED instantiation of every ICP kernel, which keeps a correspondence iff d2 <= d2_max (the largest
+// float whose double is <= d * d); ncorr: kept-correspondence counts of the sliced / persistent drivers, [cluster][it % 3].
+struct IcpBound {
+    float d2_max;
+    int32_t bounded;
+    uint32_t* ncorr;
+};
 // k_icp_pipe's hand-over of RUNNING clusters (IcpParams::donate): words of the control block
 constexpr int DON_AVAIL = 0;      // workgroups waiting for a cluster minus clusters promised to them
 constexpr int DON_FINISHED = 1;   // clusters of the launch that are done (or were never started: pre-marked)

@@ -132,6 +132,13 @@ struct cd_context {
     std::vector<float> frame_guess;
     float* d_guess = nullptr;
     size_t guess_cap = 0;
+    // ICP maximum correspondence distance (cd_set_icp_max_correspondence_distance, rule C8): the distance as set, its float
+    // threshold on d2 and whether it bounds anything; d_ncorr: kept-correspondence counts of the sliced / persistent drivers
+    double icp_max_dist = std::numeric_limits<double>::infinity();
+    float icp_d2_max = std::numeric_limits<float>::infinity();
+    int icp_bounded = 0;
+    uint32_t* d_ncorr = nullptr;
+    size_t ncorr_cap = 0;
     IcpState *d_st = nullptr, *h_st = nullptr;
     unsigned long long *d_acc = nullptr, *d_accf = nullptr, *h_accf = nullptr;
     hipEvent_t ev[8] = {nullptr};
@@ -871,6 +878,10 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1), c->stream));   // (+ the wave-time word of k_icp_lat)
     }
+    if (c->icp_bounded) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3]
+        if (int st = grow_device(c, &c->d_ncorr, &c->ncorr_cap, 3 * (size_t)ncl)) return st;
+        HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
+    }
     if (pl->guess_mode != CD_GUESS_NONE)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
         LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? 1 : 0, c->d_src0, c->d_src));
     return CD_OK;
@@ -901,6 +912,16 @@ IcpParams icp_params(const cd_context* c, const cd_params* p, bool* crowded) {
     ip.don_idle = c->don_idle;
     ip.don_fault = c->don_fault;
     return ip;
+}
+
+// rule C8: every driver runs its BOUNDED instantiation when the context's distance bounds anything (after icp_setup, which
+// sizes d_ncorr)
+IcpBound icp_bound(const cd_context* c) {
+    IcpBound b;
+    b.d2_max = c->icp_d2_max;
+    b.bounded = c->icp_bounded;
+    b.ncorr = c->d_ncorr;
+    return b;
 }
 
 // after the host synchronise of the driver that ended the stage: the launch time (ev[5] -> ev[6]) and the point pairs tested
@@ -942,9 +963,9 @@ int icp_run_lat(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* don
     if (!pl.pre_zeroed) HIPCHK(c, hipMemsetAsync(c->d_queue, 0, 2 * sizeof(int), c->stream));   // head of the cluster queue, count of finished workgroups
     if (pl.lat_direct) std::memset(c->h_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1));   // (what the zeroed device array used to bring back for clusters the kernel skips)
     if (pl.lat_direct)
-        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->h_order, c->h_cl, c->h_st, c->h_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, c->h_accf + ncl, ip));
+        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->h_order, c->h_cl, c->h_st, c->h_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, c->h_accf + ncl, ip, icp_bound(c)));
     else
-        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, nullptr, ip));
+        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, nullptr, ip, icp_bound(c)));
     c->timing.icp_kernel_launches = 1;
     c->timing.icp_regime = (cpw << 16) | std::min(n_wg, 0xffff);
     if (n_lat < pl.n_live) {   // mixed batch
@@ -1019,10 +1040,10 @@ int icp_run_grouped(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool*
     }
     if (wg_of[1] > 0)
         LAUNCH(c, launch_icp_pipe(s1, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                        c->d_queue, wg_of[1], c->d_wgtab + tab_of[1], ipg));
+                        c->d_queue, wg_of[1], c->d_wgtab + tab_of[1], ipg, icp_bound(c)));
     if (wg_of[2] > 0)
         LAUNCH(c, launch_icp_pipe_big(s2, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tplk, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid,
-                            c->d_super, c->d_tcell, c->d_src, c->d_src0, c->d_nn, c->d_queue, wg_of[2], c->d_wgtab + tab_of[2], ipg));
+                            c->d_super, c->d_tcell, c->d_src, c->d_src0, c->d_nn, c->d_queue, wg_of[2], c->d_wgtab + tab_of[2], ipg, icp_bound(c)));
     if (s1 != c->stream && wg_of[1] > 0) {
         HIPCHK(c, hipEventRecord(c->ev2[2], s1));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev2[2], 0));
@@ -1078,13 +1099,13 @@ int icp_run_whole(cd_context* c, const IcpPlan& pl, IcpParams ip, bool* done) {
     }
     if (pl.pipe_ok)
         LAUNCH(c, launch_icp_pipe(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                        c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip));
+                        c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip, icp_bound(c)));
     else if (pl.big_ok)
         LAUNCH(c, launch_icp_pipe_big(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tplk, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_super, c->d_tcell,
-                            c->d_src, c->d_src0, c->d_nn, c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip));
+                            c->d_src, c->d_src0, c->d_nn, c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip, icp_bound(c)));
     else
         LAUNCH(c, launch_icp_cluster(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlo, c->d_thi, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                           c->d_queue, wg_cap, ip));
+                           c->d_queue, wg_cap, ip, icp_bound(c)));
     if (si != c->stream) {
         HIPCHK(c, hipEventRecord(c->ev2[2], si));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev2[2], 0));
@@ -1134,7 +1155,7 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool*
     ctl[1] = c->icp_persist == 2 ? 1 : 0;
     HIPCHK(c, xfer(c, c->d_queue + 4, ctl, sizeof(int) * 6, hipMemcpyHostToDevice));
     LAUNCH(c, launch_icp_persist(c->stream, nwork, G, ip.max_iter + 3, c->d_work, c->d_cl, c->d_st, c->d_acc, c->d_accf, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid,
-                       c->d_src, c->d_src0, c->d_nn, c->d_d2, pl.qslice, (unsigned*)(c->d_queue + 4), c->d_queue + 5, n_open, c->d_queue + 6, ip));
+                       c->d_src, c->d_src0, c->d_nn, c->d_d2, pl.qslice, (unsigned*)(c->d_queue + 4), c->d_queue + 5, n_open, c->d_queue + 6, ip, icp_bound(c)));
     HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     HIPCHK(c, xfer(c, ctl + 8, c->d_queue + 5, sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
@@ -1154,6 +1175,7 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool*
     HIPCHK(c, xfer(c, c->d_st, c->h_st, sizeof(IcpState) * 2 * ncl, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * (size_t)ncl, c->stream));
+    if (c->icp_bounded) HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
     long long span = 0;
     for (int k = 0; k < ncl; ++k) span = std::max(span, (long long)c->h_cl[k].src_off + c->h_cl[k].n);
     HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)span, hipMemcpyDeviceToDevice, c->stream));
@@ -1175,7 +1197,7 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* 
     int group = 8;
     while (nwork > 0 && it < max_launch) {
         const int g = std::min(group, max_launch - it);
-        for (int q = 0; q < g; ++q) LAUNCH(c, launch_icp_iter(c->stream, it++, nactive, ncl, c->d_work2, c->d_cl, c->d_st, c->d_acc, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid, c->d_src, c->d_nn, c->d_d2, pl.qslice, c->d_queue, c->n_cu, ip));
+        for (int q = 0; q < g; ++q) LAUNCH(c, launch_icp_iter(c->stream, it++, nactive, ncl, c->d_work2, c->d_cl, c->d_st, c->d_acc, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid, c->d_src, c->d_nn, c->d_d2, pl.qslice, c->d_queue, c->n_cu, ip, icp_bound(c)));
         HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         bool all = true;
@@ -1598,6 +1620,7 @@ void cd_destroy(cd_context* c) {
     for (void* p : dev) if (p) hipFree(p);
     if (c->d_koffx) hipFree(c->d_koffx);
     if (c->d_guess) hipFree(c->d_guess);
+    if (c->d_ncorr) hipFree(c->d_ncorr);
     if (c->d_super) hipFree(c->d_super);
     if (c->d_lat) hipFree(c->d_lat);
     if (c->d_tileC) hipFree(c->d_tileC);
@@ -2464,6 +2487,8 @@ static int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stri
         HIPCHK(c, copy_sync(c, tmp.data(), c->d_src, sizeof(float4) * n, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) { aligned[3 * i] = tmp[i].x; aligned[3 * i + 1] = tmp[i].y; aligned[3 * i + 2] = tmp[i].z; }
     }
+    // rule C8: an ICP that stopped for fewer than three kept correspondences (only a bounded one can: every other ends converged)
+    if (c->h_st[0].status == CD_OK && c->icp_bounded && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;
     return c->h_st[0].status;
 }
 
@@ -2704,6 +2729,36 @@ static int cd_ground_plane_impl(cd_context* c, const void* points, size_t stride
     *out_n = no;
     if (!c->h_have[0]) return CD_ERR_NO_MODEL;
     coeff[0] = c->h_model[0].x; coeff[1] = c->h_model[0].y; coeff[2] = c->h_model[0].z; coeff[3] = c->h_model[0].w;
+    return CD_OK;
+}
+
+// rule C8: the largest float32 f with (double)f <= d * d (one IEEE double multiply), and whether it bounds anything - it does
+// not when d * d >= FLT_MAX, which no finite float d2 exceeds
+int cd_icp_correspondence_threshold(double d, float* out_d2_max, int* out_bounded) {
+    if (!(d >= 0.0)) return CD_ERR_INVALID_ARG;   // negative or NaN
+    const double dd = d * d;
+    float f = (float)dd;
+    if ((double)f > dd) f = std::nextafter(f, 0.f);   // (rounded up: one float down; +inf above FLT_MAX comes down to FLT_MAX)
+    if (out_d2_max) *out_d2_max = f;
+    if (out_bounded) *out_bounded = dd >= (double)std::numeric_limits<float>::max() ? 0 : 1;
+    return CD_OK;
+}
+
+int cd_set_icp_max_correspondence_distance(cd_context* c, double max_distance) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    float d2 = 0.f;
+    int bounded = 0;
+    if (cd_icp_correspondence_threshold(max_distance, &d2, &bounded) != CD_OK)
+        return fail(c, CD_ERR_INVALID_ARG, "the maximum correspondence distance is negative or NaN");
+    c->icp_max_dist = max_distance;
+    c->icp_d2_max = d2;
+    c->icp_bounded = bounded;
+    return CD_OK;
+}
+
+int cd_get_icp_max_correspondence_distance(const cd_context* c, double* out) {
+    if (!c || !out) return CD_ERR_INVALID_ARG;
+    *out = c->icp_max_dist;
     return CD_OK;
 }
 

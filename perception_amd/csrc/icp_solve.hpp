@@ -155,6 +155,16 @@ __device__ inline void umeyama_from_moments(const unsigned long long* A, int n, 
     T[15] = 1.f;
 }
 
+// Rule C8 (cd_set_icp_max_correspondence_distance): the BOUNDED instantiations of the ICP kernels keep a correspondence iff its
+// float d2 <= IcpParams::d2_max and count the kept ones next to the moment sums; the solve then divides by that count.  Fewer
+// than three is PCL's "Not enough correspondences": the ICP stops BEFORE this iteration's update - Tfinal and iters stay,
+// converged = 0 - and T becomes the identity, so that the in-place X <- T X that follows leaves the points where they are.
+constexpr int ICP_MIN_CORR = 3;
+__device__ __forceinline__ void icp_stop_few(IcpState& so) {
+    for (int i = 0; i < 16; ++i) so.T[i] = (i % 5 == 0) ? 1.f : 0.f;
+    so.converged = 0;
+}
+
 __device__ __forceinline__ void xform(const float* T, float x, float y, float z, float& ox, float& oy, float& oz) {
     ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
     oy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];

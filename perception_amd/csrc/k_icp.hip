@@ -3,8 +3,10 @@
 // Replaces pcl::IterativeClosestPoint<PointXYZ,PointXYZ>::align + getFitnessScore (reference:
 // cuboid_detection/src/iterative_closest_point.cpp:170-182,
 // object_detection/src/object_pose_detection.cpp:220-235; maxIter 5000, transformation
-// epsilon 1e-9, euclidean fitness epsilon = icp_fitness_score, no max correspondence distance,
-// no rejectors).
+// epsilon 1e-9, euclidean fitness epsilon = icp_fitness_score, no rejectors).  The reference leaves
+// setMaxCorrespondenceDistance commented out; cd_set_icp_max_correspondence_distance provides it (rule C8,
+// DESIGN.md): every kernel below has a BOUNDED instantiation that keeps a correspondence iff its d2 <= d2_max,
+// after the same exact, unbounded search, and counts the kept ones for the solve.
 //
 // One launch == one PCL iteration for ALL clusters of ALL frames in the batch:
 //   prologue (one lane per block, redundantly - it is ~2 us of scalar work and removes every
@@ -653,10 +655,12 @@ __device__ __forceinline__ void store_queries(const QueryRegs& q, int nk, int* n
 // One thread per cluster: TransformationEstimationSVD + final_transformation_ update +
 // DefaultConvergenceCriteria for launch `it`, from the moments launch it-1 accumulated.
 // Writes the state slot k_icp_iter(it) consumes, keeps the `done` flag in both parity slots and
-// clears the moment buffer launch it+1 will accumulate into.
+// clears the moment buffer launch it+1 will accumulate into.  BOUNDED (rule C8): n = the kept correspondences that launch
+// it-1 counted in bnd.ncorr; fewer than three stop the ICP before the update (icp_stop_few).
+template <bool BOUNDED>
 __global__ void __launch_bounds__(WAVE) k_icp_solve(int it, int ncl, const IcpCluster* __restrict__ cl,
                                                     IcpState* __restrict__ st, unsigned long long* __restrict__ acc,
-                                                    int* __restrict__ queue, IcpParams prm) {
+                                                    int* __restrict__ queue, IcpParams prm, IcpBound bnd) {
     const int k = blockIdx.x * WAVE + threadIdx.x;
     if (k == 0) *queue = 0;   // work queue of the k_icp_iter launch that follows
     if (k >= ncl) return;
@@ -667,47 +671,57 @@ __global__ void __launch_bounds__(WAVE) k_icp_solve(int it, int ncl, const IcpCl
     if (it > 0) {
         const IcpCluster c = cl[k];
         const unsigned long long* A = acc + ((size_t)k * 3 + (it - 1) % 3) * 16;
-        float T[16];
-        umeyama_from_moments(A, c.n, T);
-        // final_transformation_ = transformation_ * final_transformation_
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j)
-                so.Tfinal[4 * i + j] = ((T[4 * i] * sin->Tfinal[j] + T[4 * i + 1] * sin->Tfinal[4 + j]) +
-                                        T[4 * i + 2] * sin->Tfinal[8 + j]) + T[4 * i + 3] * sin->Tfinal[12 + j];
-        so.iters = sin->iters + 1;
-        int done = 0;
-        // DefaultConvergenceCriteria::hasConverged
-        if (so.iters >= prm.max_iter) {
-            done = 1;
+        const int n = BOUNDED ? (int)bnd.ncorr[(size_t)k * 3 + (it - 1) % 3] : c.n;
+        if (BOUNDED && n < ICP_MIN_CORR) {
+            so.done = 1;
+            icp_stop_few(so);
         } else {
-            const double cos_angle = 0.5 * (double)(((T[0] + T[5]) + T[10]) - 1.0f);
-            const double translation_sqr = (double)((T[3] * T[3] + T[7] * T[7]) + T[11] * T[11]);
-            if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
+            float T[16];
+            umeyama_from_moments(A, n, T);
+            // final_transformation_ = transformation_ * final_transformation_
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j)
+                    so.Tfinal[4 * i + j] = ((T[4 * i] * sin->Tfinal[j] + T[4 * i + 1] * sin->Tfinal[4 + j]) +
+                                            T[4 * i + 2] * sin->Tfinal[8 + j]) + T[4 * i + 3] * sin->Tfinal[12 + j];
+            so.iters = sin->iters + 1;
+            int done = 0;
+            // DefaultConvergenceCriteria::hasConverged
+            if (so.iters >= prm.max_iter) {
                 done = 1;
             } else {
-                const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)c.n;
-                if (fabs(mse - sin->prev_mse) < prm.abs_mse) done = 1;
-                else if (fabs(mse - sin->prev_mse) / sin->prev_mse < prm.rel_mse) done = 1;
-                so.prev_mse = mse;
+                const double cos_angle = 0.5 * (double)(((T[0] + T[5]) + T[10]) - 1.0f);
+                const double translation_sqr = (double)((T[3] * T[3] + T[7] * T[7]) + T[11] * T[11]);
+                if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
+                    done = 1;
+                } else {
+                    const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
+                    if (fabs(mse - sin->prev_mse) < prm.abs_mse) done = 1;
+                    else if (fabs(mse - sin->prev_mse) / sin->prev_mse < prm.rel_mse) done = 1;
+                    so.prev_mse = mse;
+                }
             }
+            so.done = done;
+            so.converged = done;
+            for (int i = 0; i < 16; ++i) so.T[i] = T[i];
         }
-        so.done = done;
-        so.converged = done;
-        for (int i = 0; i < 16; ++i) so.T[i] = T[i];
     }
     *sout = so;
     unsigned long long* Z = acc + ((size_t)k * 3 + (it + 1) % 3) * 16;
     for (int i = 0; i < 16; ++i) Z[i] = 0ull;
+    if (BOUNDED) bnd.ncorr[(size_t)k * 3 + (it + 1) % 3] = 0u;
 }
 
 // Persistent: one workgroup per CU.  The template image and this lane's run boxes stay resident
 // while the workgroup pulls (cluster, slice) work items from an atomic queue (zeroed by k_icp_solve).
+// BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; bnd.ncorr[cluster][it % 3] counts them.
+template <bool BOUNDED>
 __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, const IcpWork* __restrict__ work,
                                                            const IcpCluster* __restrict__ cl, const IcpState* __restrict__ st,
                                                            unsigned long long* __restrict__ acc,
                                                            const float4* __restrict__ tpl, const float4* __restrict__ tlo,
                                                            const float4* __restrict__ thi, const IcpGrid* __restrict__ grids,
-                                                           float4* src, int* nn, float* d2buf, int qslice, int* queue) {
+                                                           float4* src, int* nn, float* d2buf, int qslice, int* queue,
+                                                           IcpBound bnd) {
     __shared__ float4 s_tpl[ICPT_IMG];
     __shared__ unsigned long long s_scr[8 * ICP_QSLICE];   // moment scratch, 8 terms at a time (32 KiB)
     __shared__ int s_item[3];   // [0], [1]: work items (double-buffered), [2]: chunk_needed flag
@@ -779,7 +793,12 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, c
         unsigned long long S[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) S[k] = 0ull;
-        if (threadIdx.x < nq) {
+        const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
+        if constexpr (BOUNDED) {
+            const unsigned long long kb = ballot64(keep);
+            if (lane == 0 && kb) atomicAdd(&bnd.ncorr[(size_t)wk.cluster * 3 + it % 3], (uint32_t)__popcll(kb));
+        }
+        if (keep) {
             const int i = threadIdx.x;
             const float4 p = pts[i];
             const float4 qq = tp[nnq[i]];
@@ -863,7 +882,9 @@ __device__ __forceinline__ bool grid_barrier(unsigned* bar, unsigned target, int
 }
 
 // one PCL iteration's state update of a cluster from the moment sums of the previous iteration (what k_icp_solve does)
+template <bool BOUNDED>
 __device__ void persist_solve(IcpState& so, const unsigned long long* A, int n, const IcpParams& prm) {
+    if (BOUNDED && n < ICP_MIN_CORR) { so.done = 1; icp_stop_few(so); return; }
     float T[16];
     umeyama_from_moments(A, n, T);
     float Tf[16];
@@ -905,18 +926,22 @@ extern "C" int cd_debug_persist(unsigned long long* out, int reset) {
 #else
 #define PERSIST_PHASE(k)
 #endif
+// BOUNDED (rule C8): as k_icp_iter + k_icp_solve - the kept correspondences are counted in bnd.ncorr[cluster][it % 3]
+template <bool BOUNDED>
 __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int max_it, const IcpWork* __restrict__ work,
                                                               const IcpCluster* __restrict__ cl, IcpState* st,
                                                               unsigned long long* acc, unsigned long long* __restrict__ accf,
                                                               const float4* __restrict__ tpl, const float4* __restrict__ tlo,
                                                               const float4* __restrict__ thi, const IcpGrid* __restrict__ grids,
                                                               float4* src, const float4* __restrict__ src0, int* nn, float* d2buf,
-                                                              int qslice, unsigned* bar, int* abort_flag, int n_open, int* closed, IcpParams prm) {
+                                                              int qslice, unsigned* bar, int* abort_flag, int n_open, int* closed, IcpParams prm,
+                                                              IcpBound bnd) {
     __shared__ float4 s_tpl[ICPT_IMG];
     __shared__ unsigned long long s_scr[8 * ICP_QSLICE];   // moment scratch, 8 terms at a time (32 KiB)
     __shared__ IcpState s_st[PERSIST_ITEMS];               // state of the clusters of this workgroup's items
     __shared__ unsigned long long s_A[16];
     __shared__ int s_flag, s_ok;
+    __shared__ uint32_t s_nv;   // (BOUNDED) kept correspondences of the previous iteration
     const int lane = threadIdx.x & 63;
     const int G = gridDim.x;
     int n_items = 0;
@@ -941,10 +966,12 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
                 if (threadIdx.x < 16)
                     s_A[threadIdx.x] = __hip_atomic_load(acc + ((size_t)wk.cluster * 3 + (it - 1) % 3) * 16 + threadIdx.x, __ATOMIC_RELAXED,
                                                          __HIP_MEMORY_SCOPE_AGENT);
+                if (BOUNDED && threadIdx.x == 16)
+                    s_nv = __hip_atomic_load(bnd.ncorr + (size_t)wk.cluster * 3 + (it - 1) % 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __syncthreads();
                 if (threadIdx.x == 0) {
                     IcpState so = s_st[j];
-                    persist_solve(so, s_A, c.n, prm);
+                    persist_solve<BOUNDED>(so, s_A, BOUNDED ? (int)s_nv : c.n, prm);
                     s_st[j] = so;
                     // one count per cluster that closes in iteration `it`, into the slot of that iteration (see the exit test)
                     if (wk.tile == 0 && so.done) __hip_atomic_fetch_add(closed + (it & 3), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -954,6 +981,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
             PERSIST_PHASE(0)
             if (wk.tile == 0 && threadIdx.x < 16)   // the sums of iteration it + 1 start from zero (slot last read in iteration it - 1)
                 __hip_atomic_store(acc + ((size_t)wk.cluster * 3 + (it + 1) % 3) * 16 + threadIdx.x, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (BOUNDED && wk.tile == 0 && threadIdx.x == 16)
+                __hip_atomic_store(bnd.ncorr + (size_t)wk.cluster * 3 + (it + 1) % 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int done_now = s_st[j].done;
             const int q0 = wk.tile * qslice;
             const int nq = min(qslice, c.n - q0);
@@ -1008,7 +1037,13 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
             unsigned long long S[16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) S[k] = 0ull;
-            if (threadIdx.x < nq) {
+            const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
+            if constexpr (BOUNDED) {
+                const unsigned long long kb = ballot64(keep);
+                if (lane == 0 && kb)
+                    __hip_atomic_fetch_add(bnd.ncorr + (size_t)wk.cluster * 3 + it % 3, (uint32_t)__popcll(kb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            if (keep) {
                 const int i = threadIdx.x;
                 const float4 p = pts[i];
                 const float4 qq = tp[nnq[i]];
@@ -1135,6 +1170,8 @@ __device__ __forceinline__ void block_sum16(unsigned long long (&S)[16], unsigne
     __syncthreads();
 }
 
+// BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; s_nv counts them (one LDS add per wave)
+template <bool BOUNDED>
 __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int* __restrict__ order,
                                                               const IcpCluster* __restrict__ cl, IcpState* __restrict__ st,
                                                               unsigned long long* __restrict__ accf,
@@ -1143,19 +1180,21 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                                                               const IcpGrid* __restrict__ grids,
                                                               const unsigned short* __restrict__ tcell, float4* src,
                                                               const float4* __restrict__ src0, int* nn, int* queue,
-                                                              IcpParams prm) {
+                                                              IcpParams prm, IcpBound bnd) {
     __shared__ float4 s_tpl[ICPT_IMG];
     __shared__ unsigned short s_cs[ICP_MAX_CELLS + 8];   // cell start table of the staged template
     __shared__ unsigned long long s_part[ICPT_WAVES][16];
     __shared__ unsigned long long s_tot[16];
     __shared__ IcpState s_so;   // the cluster's ICP state (T = current transformation_, Tfinal = accumulated)
     __shared__ int s_flag[2];   // [0] queue item, [1] done
+    __shared__ uint32_t s_nv;   // (BOUNDED) kept correspondences of the current iteration
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     RunBoxes bx;
     int staged = -1;
     for (;;) {
         __syncthreads();
         if (threadIdx.x == 0) s_flag[0] = atomicAdd(queue, 1);
+        if (BOUNDED && threadIdx.x == 0) s_nv = 0u;
         __syncthreads();
         const int item = s_flag[0];
         if (item >= ncl) break;
@@ -1188,6 +1227,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
             unsigned long long S[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) S[i] = 0ull;
+            uint32_t nv = 0u;   // (BOUNDED: this wave's kept correspondences, wave-uniform)
             for (int q0 = 0; q0 < c.n; q0 += ICPT_THREADS) {
                 const int nq = min(ICPT_THREADS, c.n - q0);
                 const int myq = q0 + wave * WAVE + lane;   // a wave takes 64 consecutive points: coalesced, and neighbours in
@@ -1240,26 +1280,36 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     }
                     staged = -1;
                 }
+                if constexpr (BOUNDED) nv += (uint32_t)__popcll(ballot64(lane < nk && q.pbest <= bnd.d2_max));
                 if (lane < nk) {
                     nnq[myq] = q.pbi;
-                    const float4 qq = resident ? s_tpl[q.pbi] : tp[q.pbi];
-                    const float pv[3] = {q.px, q.py, q.pz}, qv[3] = {qq.x, qq.y, qq.z};
+                    if (!BOUNDED || q.pbest <= bnd.d2_max) {
+                        const float4 qq = resident ? s_tpl[q.pbi] : tp[q.pbi];
+                        const float pv[3] = {q.px, q.py, q.pz}, qv[3] = {qq.x, qq.y, qq.z};
 #pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        S[a] += (unsigned long long)fixq(pv[a], FIX_SHIFT);
-                        S[3 + a] += (unsigned long long)fixq(qv[a], FIX_SHIFT);
+                        for (int a = 0; a < 3; ++a) {
+                            S[a] += (unsigned long long)fixq(pv[a], FIX_SHIFT);
+                            S[3 + a] += (unsigned long long)fixq(qv[a], FIX_SHIFT);
 #pragma unroll
-                        for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] += (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
+                            for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] += (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
+                        }
+                        S[15] += (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
                     }
-                    S[15] += (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
                 }
             }
             CD_PHASE(3)
+            if constexpr (BOUNDED) { if (lane == 0 && nv) atomicAdd(&s_nv, nv); }
             block_sum16(S, s_part, s_tot);
             CD_PHASE(4)
-            if (threadIdx.x == 0) {   // solve for iteration it+1 (same code as k_icp_solve)
+            const int n_used = BOUNDED ? (int)s_nv : c.n;
+            if (BOUNDED && threadIdx.x == 0 && n_used < ICP_MIN_CORR) {   // rule C8: too few correspondences, stop before the update
+                IcpState so = s_so;
+                icp_stop_few(so);
+                s_so = so;
+                s_flag[1] = 1;
+            } else if (threadIdx.x == 0) {   // solve for iteration it+1 (same code as k_icp_solve)
                 float Tn[16];
-                umeyama_from_moments(s_tot, c.n, Tn);
+                umeyama_from_moments(s_tot, n_used, Tn);
                 float Tf[16];
                 for (int i = 0; i < 4; ++i)
                     for (int j = 0; j < 4; ++j)
@@ -1276,13 +1326,14 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
                         done = 1;
                     } else {
-                        const double mse = unfix(s_tot[15], FIX_SHIFT_D2) / (double)c.n;
+                        const double mse = unfix(s_tot[15], FIX_SHIFT_D2) / (double)n_used;
                         if (fabs(mse - s_so.prev_mse) < prm.abs_mse) done = 1;
                         else if (fabs(mse - s_so.prev_mse) / s_so.prev_mse < prm.rel_mse) done = 1;
                         s_so.prev_mse = mse;
                     }
                 }
                 for (int i = 0; i < 16; ++i) s_so.T[i] = Tn[i];
+                if (BOUNDED) { s_so.converged = done; s_nv = 0u; }
                 s_flag[1] = done;
             }
             __syncthreads();
@@ -1338,7 +1389,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
             block_sum16(S, s_part, s_tot);
             if (threadIdx.x == 0) {
                 s_so.done = 1;
-                s_so.converged = 1;
+                if (!BOUNDED) s_so.converged = 1;   // (BOUNDED: set by the solve - 0 after a stop for too few correspondences)
                 st[2 * (size_t)k] = s_so;
                 st[2 * (size_t)k + 1] = s_so;
                 accf[k] = s_tot[0];
@@ -1385,11 +1436,28 @@ struct PipeSlot {
                                     // through to memory (agent scope), then it leaves
     int take;                       // 1: the cluster has just arrived from another workgroup - this step reads them past L1 / L2 (agent scope)
 };
+// the slot of the BOUNDED instantiations (rule C8): + the kept correspondences of the current step, an order-free count next to
+// the moment sums (zeroed with them; a hand-over happens between steps, so like them it never travels).  The default layout -
+// and so the LDS budget of common.hpp - stays as it is.
+struct PipeSlotN : PipeSlot {
+    uint32_t nv, pad;
+};
+template <bool BOUNDED> struct PipeSlotSel { using T = PipeSlot; };
+template <> struct PipeSlotSel<true> { using T = PipeSlotN; };
 
 // Umeyama + convergence test of one iteration (lane 0 of the finishing wave); same code as k_icp_solve.
-__device__ __noinline__ int pipe_solve(PipeSlot* sl, const IcpParams& prm) {
+// BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
+// (Out-of-line callees are plain overloads below, not template instances: a linkonce function has no exact definition,
+// so its callers could not use its register usage - k_icp_pipe would allocate more registers around the call.)
+template <bool BOUNDED>
+__device__ __forceinline__ int pipe_solve_body(typename PipeSlotSel<BOUNDED>::T* sl, const IcpParams& prm) {
+    int n = sl->n;
+    if constexpr (BOUNDED) {
+        n = (int)sl->nv;
+        if (n < ICP_MIN_CORR) { icp_stop_few(sl->so); return 1; }
+    }
     float Tn[16];
-    umeyama_from_moments(sl->acc, sl->n, Tn);
+    umeyama_from_moments(sl->acc, n, Tn);
     float Tf[16];
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j)
@@ -1406,15 +1474,18 @@ __device__ __noinline__ int pipe_solve(PipeSlot* sl, const IcpParams& prm) {
         if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
             done = 1;
         } else {
-            const double mse = unfix(sl->acc[15], FIX_SHIFT_D2) / (double)sl->n;
+            const double mse = unfix(sl->acc[15], FIX_SHIFT_D2) / (double)n;
             if (fabs(mse - sl->so.prev_mse) < prm.abs_mse) done = 1;
             else if (fabs(mse - sl->so.prev_mse) / sl->so.prev_mse < prm.rel_mse) done = 1;
             sl->so.prev_mse = mse;
         }
     }
     for (int i = 0; i < 16; ++i) sl->so.T[i] = Tn[i];
+    if constexpr (BOUNDED) sl->so.converged = done;
     return done;
 }
+__device__ __noinline__ int pipe_solve(PipeSlot* sl, const IcpParams& prm) { return pipe_solve_body<false>(sl, prm); }
+__device__ __noinline__ int pipe_solve(PipeSlotN* sl, const IcpParams& prm) { return pipe_solve_body<true>(sl, prm); }
 
 // next cluster from the global queue into the slot (lane 0 of the finishing wave)
 // (items [gbeg, gend) of `order`: the clusters that share the workgroup's template)
@@ -1487,13 +1558,15 @@ __device__ __forceinline__ void state_load_agent(IcpState& dst, const IcpState* 
     const unsigned* s = reinterpret_cast<const unsigned*>(src);
     for (int i = 0; i < (int)(sizeof(IcpState) / 4); ++i) d[i] = __hip_atomic_load(s + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ int pipe_active_slots(const PipeSlot* slots) {
+template <class Slot>
+__device__ __forceinline__ int pipe_active_slots(const Slot* slots) {
     int a = 0;
     for (int i = 0; i < PIPE_SLOTS; ++i) a += (slots[i].phase == PH_ITER || slots[i].phase == PH_FIT) ? 1 : 0;
     return a;
 }
 // lane 0 of the finishing wave, cluster not converged: returns true when the slot's cluster went to the mailbox
-__device__ __noinline__ bool pipe_give(PipeSlot* sl, const PipeSlot* slots, IcpState* st, int* don, bool fault) {
+template <class Slot>
+__device__ __forceinline__ bool pipe_give_body(Slot* sl, const Slot* slots, IcpState* st, int* don, bool fault) {
     bool gone = false;
     if (pipe_active_slots(slots) >= 2) {
         state_store_agent(&st[2 * (size_t)sl->k], sl->so);
@@ -1508,6 +1581,12 @@ __device__ __noinline__ bool pipe_give(PipeSlot* sl, const PipeSlot* slots, IcpS
     if (!gone) __hip_atomic_fetch_add(don + DON_AVAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // promise returned
     sl->give = 0;
     return gone;
+}
+__device__ __noinline__ bool pipe_give(PipeSlot* sl, const PipeSlot* slots, IcpState* st, int* don, bool fault) {
+    return pipe_give_body(sl, slots, st, don, fault);
+}
+__device__ __noinline__ bool pipe_give(PipeSlotN* sl, const PipeSlotN* slots, IcpState* st, int* don, bool fault) {
+    return pipe_give_body(sl, slots, st, don, fault);
 }
 // thread 0 of a workgroup with nothing left: the id of a cluster to carry on with, or -1 when the launch is finished
 // Both bail-outs are REPORTED (DON_ERR; the host fails the call with CD_ERR_DEVICE): an entry that was claimed and never
@@ -1542,7 +1621,8 @@ __device__ __noinline__ int pipe_wait_for_cluster(int* don, int total, int entry
 //              every workgroup) - the grid walk reads the cell-sorted copy `tpl` point by point, the wave-per-query search the
 //              k-d ordered copy `tplk` patch by patch (search_patches_big); LDS holds the cell start table and the patch boxes.
 //              Same pipeline, same arithmetic, same tie rule: bit-identical results (keys carry 16-bit positions).
-template <bool BIG>
+// BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; the slot's nv counts them.
+template <bool BIG, bool BOUNDED>
 __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ order,
                                               const IcpCluster* __restrict__ cl, IcpState* st,
                                               unsigned long long* __restrict__ accf,
@@ -1553,10 +1633,11 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                                               const unsigned short* __restrict__ tcell, float4* src,
                                               const float4* __restrict__ src0, int* nn, int* queue,
                                               const int* __restrict__ wgtab, IcpParams prm,
-                                              const float4* __restrict__ tplk, const IcpSuper* __restrict__ supers) {
+                                              const float4* __restrict__ tplk, const IcpSuper* __restrict__ supers, const IcpBound& bnd) {
     __shared__ float4 s_tpl[BIG ? 1 : ICPT_IMG];
     __shared__ unsigned short s_cs[ICP_MAX_CELLS + 8];
-    __shared__ PipeSlot s_slot[PIPE_SLOTS];
+    using Slot = typename PipeSlotSel<BOUNDED>::T;
+    __shared__ Slot s_slot[PIPE_SLOTS];
     __shared__ unsigned short s_kd[BIG ? 1 : ICPT_IMG];   // k-d patch order -> stored position (tlo/thi are the PATCH boxes)
     __shared__ unsigned long long s_far[ICPT_WAVES];   // one word per wave: the running minimum of the far query it is on
     __shared__ float4 s_plo[BIG ? ICP_BIG_PATCHES : 1], s_phi[BIG ? ICP_BIG_PATCHES : 1];   // BIG: boxes of all k-d patches
@@ -1625,8 +1706,9 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
     }
     if (threadIdx.x == 0) {
         for (int sidx = 0; sidx < PIPE_SLOTS; ++sidx) {
-            PipeSlot* sl = &s_slot[sidx];
+            Slot* sl = &s_slot[sidx];
             for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
+            if constexpr (BOUNDED) sl->nv = 0u;
             sl->arrived = 0; sl->epoch = 0; sl->it = 0; sl->n = 0; sl->src_off = 0; sl->k = 0; sl->next_pass = 0; sl->give = 0; sl->take = 0;
             sl->phase = sidx < prm.pipe_slots ? PH_FILL : PH_EXHAUSTED;   // (a slot the launch does not use is dropped at its first visit)
         }
@@ -1650,7 +1732,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
     while (live) {
         for (int sidx = 0; sidx < PIPE_SLOTS; ++sidx) {
             if (!((live >> sidx) & 1u)) continue;
-            PipeSlot* sl = &s_slot[sidx];
+            Slot* sl = &s_slot[sidx];
             const int want = (int)((my_ep >> (8 * sidx)) & 0xffu);
             while (__hip_atomic_load(&sl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != want) __builtin_amdgcn_s_sleep(2);
             __threadfence_block();
@@ -1796,7 +1878,9 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                         if (phase == PH_ITER) {
                             if (give) __hip_atomic_store(&nnq[myq], q.pbi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             else nnq[myq] = q.pbi;
-                            if (fast) {
+                            if (BOUNDED && !(q.pbest <= bnd.d2_max)) {
+                                // rejected (rule C8): adds nothing
+                            } else if (fast) {
 #pragma unroll
                                 for (int a = 0; a < 3; ++a) {
                                     S[a] = fixq_fast(pv[a], FIX_SHIFT);
@@ -1820,6 +1904,10 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                         }
                     }
                     wave_fold_to_lds(S, phase == PH_ITER ? 16 : 1, sl->acc);
+                    if constexpr (BOUNDED) {
+                        const unsigned long long kb = ballot64(lane < nk && phase == PH_ITER && q.pbest <= bnd.d2_max);
+                        if (lane == 0 && kb) atomicAdd(&sl->nv, (uint32_t)__popcll(kb));
+                    }
                     CD_PHASE(5)
                 }
                 CD_PHASE(5)
@@ -1852,7 +1940,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                     } else {
                         if (phase == PH_FIT) {
                             sl->so.done = 1;
-                            sl->so.converged = 1;
+                            if (!BOUNDED) sl->so.converged = 1;   // (BOUNDED: set by pipe_solve - 0 after a stop for too few correspondences)
                             st[2 * (size_t)sl->k] = sl->so;
                             st[2 * (size_t)sl->k + 1] = sl->so;
                             accf[sl->k] = sl->acc[0];
@@ -1861,6 +1949,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                         pipe_refill(sl, gbeg, gend, order, cl, st, queue, don, no_queue);
                     }
                     for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
+                    if constexpr (BOUNDED) sl->nv = 0u;
                     sl->arrived = 0;
                     sl->next_pass = 0;
                 }
@@ -1887,12 +1976,13 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
 #endif
         s_take = k;
         if (k >= 0) {
-            PipeSlot* sl = &s_slot[0];
+            Slot* sl = &s_slot[0];
             const IcpCluster c = cl[k];
             sl->src_off = c.src_off; sl->n = c.n; sl->k = k;
             state_load_agent(sl->so, &st[2 * (size_t)k]);
             sl->phase = PH_ITER; sl->it = sl->so.iters; sl->give = 0; sl->take = 1;
             for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
+            if constexpr (BOUNDED) sl->nv = 0u;
             sl->arrived = 0; sl->next_pass = 0;
         }
     }
@@ -1909,6 +1999,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
 #endif
 }
 
+template <bool BOUNDED>
 __global__ void __launch_bounds__(ICPT_THREADS) k_icp_pipe(int ncl, const int* __restrict__ order,
                                                            const IcpCluster* __restrict__ cl, IcpState* st,
                                                            unsigned long long* __restrict__ accf,
@@ -1918,9 +2009,10 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_pipe(int ncl, const int* _
                                                            const IcpGrid* __restrict__ grids,
                                                            const unsigned short* __restrict__ tcell, float4* src,
                                                            const float4* __restrict__ src0, int* nn, int* queue,
-                                                           const int* __restrict__ wgtab, IcpParams prm) {
-    icp_pipe_body<false>(ncl, order, cl, st, accf, tpl, tlo, thi, kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, nullptr, nullptr);
+                                                           const int* __restrict__ wgtab, IcpParams prm, IcpBound bnd) {
+    icp_pipe_body<false, BOUNDED>(ncl, order, cl, st, accf, tpl, tlo, thi, kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, nullptr, nullptr, bnd);
 }
+template <bool BOUNDED>
 __global__ void __launch_bounds__(ICPT_THREADS) k_icp_pipe_big(int ncl, const int* __restrict__ order,
                                                                const IcpCluster* __restrict__ cl, IcpState* st,
                                                                unsigned long long* __restrict__ accf,
@@ -1931,8 +2023,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_pipe_big(int ncl, const in
                                                                const unsigned short* __restrict__ tcell, float4* src,
                                                                const float4* __restrict__ src0, int* nn, int* queue,
                                                                const int* __restrict__ wgtab, IcpParams prm,
-                                                               const float4* __restrict__ tplk, const IcpSuper* __restrict__ supers) {
-    icp_pipe_body<true>(ncl, order, cl, st, accf, tpl, tlo, thi, kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, tplk, supers);
+                                                               const float4* __restrict__ tplk, const IcpSuper* __restrict__ supers, IcpBound bnd) {
+    icp_pipe_body<true, BOUNDED>(ncl, order, cl, st, accf, tpl, tlo, thi, kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, tplk, supers, bnd);
 }
 
 // getFitnessScore(): mean squared NN distance of T_final * (original source)
@@ -2022,12 +2114,17 @@ void launch_icp_apply_guess(hipStream_t s, int ncl, int max_n, const IcpCluster*
 
 void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpCluster* cl, IcpState* st,
                      unsigned long long* acc, const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm) {
+                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0) return;
-    hipLaunchKernelGGL(k_icp_solve, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, cl, st, acc, queue, prm);
+    if (bnd.bounded) hipLaunchKernelGGL(k_icp_solve<true>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, cl, st, acc, queue, prm, bnd);
+    else hipLaunchKernelGGL(k_icp_solve<false>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, cl, st, acc, queue, prm, bnd);
     if (n_work <= 0) return;   // every cluster converged: only the state bookkeeping above is needed
-    hipLaunchKernelGGL(k_icp_iter, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, cl, st, acc, tpl, tlo,
-                       thi, grids, src, nn, d2buf, qslice, queue);
+    if (bnd.bounded)
+        hipLaunchKernelGGL(k_icp_iter<true>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, cl, st, acc, tpl, tlo,
+                           thi, grids, src, nn, d2buf, qslice, queue, bnd);
+    else
+        hipLaunchKernelGGL(k_icp_iter<false>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, cl, st, acc, tpl, tlo,
+                           thi, grids, src, nn, d2buf, qslice, queue, bnd);
 }
 void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpCluster* cl, const IcpState* st,
                         int parity, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
@@ -2039,37 +2136,37 @@ void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const Ic
 void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpCluster* cl, IcpState* st,
                          unsigned long long* acc, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
                          const IcpGrid* grids, float4* src, const float4* src0, int* nn, float* d2buf, int qslice, unsigned* bar,
-                         int* abort_flag, int n_open, int* closed, IcpParams prm) {
+                         int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd) {
     if (n_work <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(k_icp_persist, dim3(n_wg), dim3(ICPT_THREADS), 0, s, n_work, max_it, work, cl, st, acc, accf, tpl, tlo, thi, grids,
-                       src, src0, nn, d2buf, qslice, bar, abort_flag, n_open, closed, prm);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_persist<true> : k_icp_persist<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, n_work, max_it, work, cl, st, acc, accf, tpl, tlo, thi, grids,
+                       src, src0, nn, d2buf, qslice, bar, abort_flag, n_open, closed, prm, bnd);
 }
 
 void launch_icp_cluster(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                         const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
                         const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                        int* queue, int n_cu, IcpParams prm) {
+                        int* queue, int n_cu, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0) return;
-    hipLaunchKernelGGL(k_icp_cluster, dim3(ncl < n_cu ? ncl : n_cu), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
-                       grids, tcell, src, src0, nn, queue, prm);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_cluster<true> : k_icp_cluster<false>, dim3(ncl < n_cu ? ncl : n_cu), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
+                       grids, tcell, src, src0, nn, queue, prm, bnd);
 }
 
 void launch_icp_pipe(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                      const float4* tpl, const float4* tlo, const float4* thi, const unsigned short* kdmap, const IcpGrid* grids,
                      const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                     int* queue, int n_wg, const int* wgtab, IcpParams prm) {
+                     int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(k_icp_pipe, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
-                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe<true> : k_icp_pipe<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
+                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, bnd);
 }
 
 void launch_icp_pipe_big(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                          const float4* tpl, const float4* tplk, const float4* tlok, const float4* thik, const unsigned short* kdmap,
                          const IcpGrid* grids, const IcpSuper* supers, const unsigned short* tcell, float4* src, const float4* src0,
-                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm) {
+                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(k_icp_pipe_big, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlok, thik,
-                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, tplk, supers);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe_big<true> : k_icp_pipe_big<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlok, thik,
+                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, tplk, supers, bnd);
 }
 
 }  // namespace cd

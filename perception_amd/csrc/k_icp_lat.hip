@@ -201,7 +201,10 @@ __device__ __forceinline__ int lat_index(const int4* s_face, const LatFaces& F, 
 
 // one PCL iteration's state update from the moment sums (what k_icp_solve / pipe_solve do): TransformationEstimationSVD,
 // final_transformation_ = transformation_ * final_transformation_, DefaultConvergenceCriteria::hasConverged.  Returns done.
+// BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
+template <bool BOUNDED>
 __device__ __forceinline__ int lat_solve(IcpState* so, const unsigned long long* A, int n, const IcpParams& prm) {
+    if (BOUNDED && n < ICP_MIN_CORR) { icp_stop_few(*so); return 1; }
     float Tn[16];
     umeyama_from_moments(A, n, Tn);
     float Tf[16];
@@ -227,6 +230,7 @@ __device__ __forceinline__ int lat_solve(IcpState* so, const unsigned long long*
         }
     }
     for (int i = 0; i < 16; ++i) so->T[i] = Tn[i];
+    if (BOUNDED) so->converged = done;
     return done;
 }
 
@@ -289,12 +293,14 @@ enum { LAT_ITER = 0, LAT_FIT = 1, LAT_EMPTY = 2 };
 #ifndef CD_LAT_WAVES_PER_EU
 #define CD_LAT_WAVES_PER_EU 4   // four waves per SIMD: 128 registers - the single-lane solve is what needs them
 #endif
-template <int CPW, int WPC>
+// BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; s_nv counts them per slot (one popcount of a
+// ballot per pass and wave, one LDS add per wave and round) and takes the place of n in the solve and in the constants' offset
+template <int CPW, int WPC, bool BOUNDED>
 __global__ void __launch_bounds__(CPW * WPC * WAVE, CD_LAT_WAVES_PER_EU)
 k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restrict__ cl, IcpState* __restrict__ st,
           unsigned long long* __restrict__ accf, const IcpLattice* __restrict__ lats, float4* __restrict__ src,
           const float4* __restrict__ src0, int* __restrict__ queue, unsigned long long* __restrict__ busy,
-          unsigned long long* __restrict__ busy_out, IcpParams prm) {
+          unsigned long long* __restrict__ busy_out, IcpParams prm, IcpBound bnd) {
     // (order / cl / st / accf may be the host's pinned arrays: every access to them is one cluster's record at a refill or at
     // the end of its ICP.  busy_out != nullptr: the last workgroup to finish writes the launch's wave-time there - queue[1]
     // counts the finished workgroups)
@@ -304,6 +310,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
     __shared__ IcpState s_so[CPW];
     __shared__ LatSlot s_slot[CPW];
     __shared__ int s_flags[2];   // [0] every slot is empty, [1] some slot was refilled in this round
+    __shared__ unsigned s_nv[BOUNDED ? CPW : 1];   // (BOUNDED) kept correspondences of the slot's current step
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slot = wave / WPC, sub = wave % WPC;
     const long long wg_t0 = wall_clock64();   // (100 MHz: the workgroup's lifetime goes to accf[nitems_all], see the end)
@@ -311,6 +318,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
     auto refill = [&](int s) {
         LatSlot& sl = s_slot[s];
         for (int i = 0; i < 16; ++i) s_acc[s][i] = 0ull;
+        if constexpr (BOUNDED) s_nv[s] = 0u;
         sl.ready = 0;
         for (;;) {
             const int item = atomicAdd(queue, 1);
@@ -377,6 +385,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                 unsigned long long S[16];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) S[i] = 0ull;
+                unsigned nv = 0u;   // (BOUNDED: kept correspondences of this wave's passes, wave-uniform)
                 // (the points of the next pass are requested before the current pass is worked on: one wave per SIMD per cluster has
                 // nothing else to cover an L2 round trip with)
                 float4 pnext = pts[min((sub << 6) + lane, n - 1)];
@@ -394,8 +403,10 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                     // the 16 moment terms of rule C4, accumulated as raw bits (LatFix above: the solver takes the constants off
                     // again).  Valid while every term stays below 2^50 / 2^shift; a point outside that range (coordinates beyond
                     // 256 m, a neighbour more than 128 m away) takes the general conversion - the same integers either way.  Lanes
-                    // without a point add nothing.
-                    if (act) {
+                    // without a point add nothing; BOUNDED: nor do lanes whose correspondence is rejected (rule C8).
+                    const bool keep = act && (!BOUNDED || h.d <= bnd.d2_max);
+                    if constexpr (BOUNDED) nv += (unsigned)__popcll(ballot64(keep));
+                    if (keep) {
                         const float pv[3] = {px, py, pz}, qv[3] = {h.nx, h.ny, h.nz};
                         const float big_c = fmaxf(fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)), fmaxf(fmaxf(fabsf(h.nx), fabsf(h.ny)), fabsf(h.nz)));
                         if (big_c < 256.f && h.d < 16384.f) {
@@ -420,6 +431,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                     }
                 }
                 if (sub < npass) wave_fold_to_lds(S, 16, s_acc[slot]);
+                if constexpr (BOUNDED) { if (sub < npass && lane == 0) atomicAdd(&s_nv[slot], nv); }
                 if (sub == 0 && lane == 0) s_slot[slot].ready = 1;
             } else if (phase == LAT_FIT) {
                 // final X <- T*X (PCL transforms before it tests convergence), then getFitnessScore() of Tfinal * original source
@@ -460,17 +472,20 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
         if (threadIdx.x < CPW) {
             const int s = threadIdx.x;
             LatSlot& sl = s_slot[s];
-            // (every point added the constant of its scale to each sum it touched: see LatFix)
-            const unsigned long long off = (unsigned long long)sl.n * LatFix<FIX_SHIFT>::C, off_d = (unsigned long long)sl.n * LatFix<FIX_SHIFT_D2>::C;
+            // (every point added the constant of its scale to each sum it touched: see LatFix; BOUNDED: every KEPT point, and
+            // the fitness pass below keeps them all)
+            const int nv = BOUNDED && sl.phase == LAT_ITER ? (int)s_nv[s] : sl.n;
+            const unsigned long long off = (unsigned long long)nv * LatFix<FIX_SHIFT>::C, off_d = (unsigned long long)nv * LatFix<FIX_SHIFT_D2>::C;
             if (sl.phase == LAT_ITER && sl.ready) {
                 for (int i = 0; i < 15; ++i) s_acc[s][i] -= off;
                 s_acc[s][15] -= off_d;
-                if (lat_solve(&s_so[s], s_acc[s], sl.n, prm)) sl.phase = LAT_FIT;
+                if (lat_solve<BOUNDED>(&s_so[s], s_acc[s], nv, prm)) sl.phase = LAT_FIT;
                 for (int i = 0; i < 16; ++i) s_acc[s][i] = 0ull;
+                if constexpr (BOUNDED) s_nv[s] = 0u;
                 sl.ready = 0;
             } else if (sl.phase == LAT_FIT) {
                 s_so[s].done = 1;
-                s_so[s].converged = 1;
+                if (!BOUNDED) s_so[s].converged = 1;   // (BOUNDED: lat_solve set it - 0 after a stop for too few correspondences)
                 st[2 * (size_t)sl.k] = s_so[s];
                 st[2 * (size_t)sl.k + 1] = s_so[s];
                 accf[sl.k] = s_acc[s][0] - off_d;
@@ -528,20 +543,23 @@ __global__ void __launch_bounds__(BLOCK) k_lat_nn(const IcpLattice* __restrict__
 template <int CPW, int WPC>
 static void launch_lat_shape(hipStream_t s, int nitems, int n_wg, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                              const IcpLattice* lats, float4* src, const float4* src0, int* queue, unsigned long long* busy, unsigned long long* busy_out,
-                             IcpParams prm) {
-    hipLaunchKernelGGL((k_icp_lat<CPW, WPC>), dim3(n_wg), dim3(CPW * WPC * WAVE), 0, s, nitems, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm);
+                             IcpParams prm, const IcpBound& bnd) {
+    if (bnd.bounded)
+        hipLaunchKernelGGL((k_icp_lat<CPW, WPC, true>), dim3(n_wg), dim3(CPW * WPC * WAVE), 0, s, nitems, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
+    else
+        hipLaunchKernelGGL((k_icp_lat<CPW, WPC, false>), dim3(n_wg), dim3(CPW * WPC * WAVE), 0, s, nitems, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
 }
 void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const int* order, const IcpCluster* cl, IcpState* st,
                     unsigned long long* accf, const IcpLattice* lats, float4* src, const float4* src0, int* queue, unsigned long long* busy,
-                    unsigned long long* busy_out, IcpParams prm) {
+                    unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd) {
     if (nitems <= 0 || n_wg <= 0) return;
-#define CD_LAT_CASE(C, W) if (cpw == C && wpc == W) return launch_lat_shape<C, W>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm);
+#define CD_LAT_CASE(C, W) if (cpw == C && wpc == W) return launch_lat_shape<C, W>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
     CD_LAT_CASE(1, 1) CD_LAT_CASE(1, 2) CD_LAT_CASE(1, 4) CD_LAT_CASE(1, 8) CD_LAT_CASE(1, 16)
     CD_LAT_CASE(2, 1) CD_LAT_CASE(2, 2) CD_LAT_CASE(2, 4)
     CD_LAT_CASE(4, 1) CD_LAT_CASE(4, 2) CD_LAT_CASE(4, 4)
     CD_LAT_CASE(8, 1) CD_LAT_CASE(8, 2)
 #undef CD_LAT_CASE
-    launch_lat_shape<1, 4>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm);
+    launch_lat_shape<1, 4>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
 }
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2) {
     if (n <= 0) return;

@@ -81,11 +81,11 @@ void launch_label_scatter(hipStream_t s, const float4* obj, int N, int F, int T,
 // k_icp.hip
 void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpCluster* cl, IcpState* st,
                      unsigned long long* acc, const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm);
+                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm, const IcpBound& bnd);
 void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpCluster* cl, IcpState* st,
                          unsigned long long* acc, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
                          const IcpGrid* grids, float4* src, const float4* src0, int* nn, float* d2buf, int qslice, unsigned* bar,
-                         int* abort_flag, int n_open, int* closed, IcpParams prm);
+                         int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd);
 void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpCluster* cl, const IcpState* st,
                         int parity, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
                         const IcpGrid* grids, const float4* src0, int* nn, float* d2buf, int qslice);
@@ -95,20 +95,20 @@ void launch_icp_apply_guess(hipStream_t s, int ncl, int max_n, const IcpCluster*
 void launch_icp_pipe(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                      const float4* tpl, const float4* tlo, const float4* thi, const unsigned short* kdmap, const IcpGrid* grids,
                      const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                     int* queue, int n_wg, const int* wgtab, IcpParams prm);
+                     int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
 void launch_icp_pipe_big(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                          const float4* tpl, const float4* tplk, const float4* tlok, const float4* thik, const unsigned short* kdmap,
                          const IcpGrid* grids, const IcpSuper* supers, const unsigned short* tcell, float4* src, const float4* src0,
-                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm);
+                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
 void launch_icp_cluster(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
                         const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
                         const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                        int* queue, int n_cu, IcpParams prm);
+                        int* queue, int n_cu, IcpParams prm, const IcpBound& bnd);
 
 // k_icp_lat.hip : templates that are unions of axis-aligned lattices (IcpLattice) - closed-form nearest neighbour
 void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const int* order, const IcpCluster* cl, IcpState* st,
                     unsigned long long* accf, const IcpLattice* lats, float4* src, const float4* src0, int* queue, unsigned long long* busy,
-                    unsigned long long* busy_out, IcpParams prm);
+                    unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd);
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2);
 
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
