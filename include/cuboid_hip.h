@@ -42,6 +42,7 @@ extern "C" {
 #define CD_MAX_CLUSTERS_PER_FRAME 8 /* cluster slots in the fixed-size per-frame record; a frame with more clusters still
                                      * gets an ICP for every one of them (opd.cpp:376): see cd_get_cluster_results       */
 #define CD_FRAME_MORE_CLUSTERS 1    /* cd_frame_result.flags: n_clusters > CD_MAX_CLUSTERS_PER_FRAME                    */
+#define CD_FRAME_SURFACE_GUESS 2    /* cd_frame_result.flags: the frame's ICP started from its surface guess (CD_GUESS_SURFACE) */
 
 typedef struct cd_context cd_context;
 
@@ -108,14 +109,15 @@ typedef struct cd_params {
      * the pose surface_normal_estimation publishes (icp.cpp:130-134 stores it, :165-167 moves the template by it; both
      * commented out / inert, and iterative_closest_point.launch:17-18 leaves the sne node out), so the guess is opt-in:
      * CD_GUESS_PARAMS uses icp_guess for every ICP of the call, CD_GUESS_PER_FRAME the matrix cd_set_frame_guesses stored
-     * for the cluster's frame.  PCL semantics: the source is first moved by the guess (input_transformed = guess * source,
+     * for the cluster's frame, CD_GUESS_SURFACE the guess the call derives from the frame's own surface fit (see
+     * cd_surface_batch; fused calls only, cd_icp refuses it).  PCL semantics: the source is first moved by the guess (input_transformed = guess * source,
      * float32 4x4 * point), final_transformation_ starts as the guess, the iterations and the convergence tests run on the
      * moved cloud, getFinalTransformation() includes the guess and getFitnessScore() is that of final * source. */
     int32_t icp_use_guess;
     float icp_guess[16];                /* row-major, scene -> template */
 } cd_params;
 
-enum { CD_GUESS_NONE = 0, CD_GUESS_PARAMS = 1, CD_GUESS_PER_FRAME = 2 };
+enum { CD_GUESS_NONE = 0, CD_GUESS_PARAMS = 1, CD_GUESS_PER_FRAME = 2, CD_GUESS_SURFACE = 3 };
 
 enum { CD_PLANE = 0, CD_PLANE_PERPENDICULAR = 1, CD_PLANE_PARALLEL = 2 };
 
@@ -224,6 +226,37 @@ int cd_segment_plane(cd_context* ctx, const void* xyz, size_t stride_bytes, int 
 int cd_surface_frame(cd_context* ctx, const void* xyz, size_t stride_bytes, int n, const float table_normal[3],
                      int invert, const cd_params* prm, cd_surface_frame_result* out);
 
+/* cd_surface_frame over n_frames clouds in one call, every fit of every frame on the device: frame f is n_points[f] records
+ * of `stride_bytes` (a multiple of 4, >= 12; x,y,z at 0/4/8) at xyz + f * points_per_frame * stride_bytes, its table normal
+ * table_normals[3 f .. 3 f + 2].  out[f] and frame_status[f] (CD_OK / CD_ERR_NO_MODEL) are, byte for byte, what
+ * cd_surface_frame returns for that cloud - a failed fit leaves iterations[] of the fits run so far and zeros elsewhere.
+ * The call itself returns CD_OK unless an argument is bad (CD_ERR_INVALID_ARG), a cloud or the batch exceeds the context
+ * (CD_ERR_CAPACITY) or the device fails.  The stage has FrameStates and point buffers of its own (allocated on first use). */
+int cd_surface_batch(cd_context* ctx, const void* xyz, size_t stride_bytes, int points_per_frame, const int32_t* n_points,
+                     int n_frames, const float* table_normals, int invert, const cd_params* prm, cd_surface_frame_result* out,
+                     int32_t* frame_status);
+
+/* Rule C9, host-only (no context, no GPU): the ICP guess of a surface pose.  Rt as sne publishes it ->
+ * position t and quaternion q (cd_pose_to_position_quaternion) -> R(q) in double, q not normalised (poseMsgToEigen) -> of
+ * R F, F = diag(1,1,1), diag(1,-1,-1), diag(-1,1,-1), diag(-1,-1,1), the first that turns the most template faces (outward
+ * normals -x, -y, -z of make_cuboid.py's template) toward the camera -> guess = [R^T | -R^T t] rounded once to float32.  The
+ * guess maps the scene to the template frame, so getFinalTransformation() includes it and the ICP pose stays the object's
+ * pose in the camera frame (the reference's commented-out line moved the template by the pose instead: equal up to rounding
+ * and the choice of F).  A non-finite Rt (or result): CD_ERR_INVALID_ARG. */
+int cd_surface_guess(const float Rt[16], float guess[16]);
+
+/* sne's distance threshold for CD_GUESS_SURFACE (cd_params holds the ground plane's): context state like the correspondence
+ * distance.  Default 0.015, the value of surface_normal_estimation.launch.  Not finite or <= 0: CD_ERR_INVALID_ARG, the
+ * setting stays as it was. */
+int cd_set_surface_distance_threshold(cd_context* ctx, double d);
+int cd_get_surface_distance_threshold(const cd_context* ctx, double* out);
+
+/* The per-frame surface results of the last fused call in CD_GUESS_SURFACE mode (what the sne node publishes: the pose and
+ * the three coefficient messages): frames [first, first + capacity) into out / frame_status (either may be NULL).  Returns the
+ * number copied, or CD_ERR_INVALID_ARG when the last fused call was not in surface mode or another compute call has run since
+ * (the rule of cd_get_cluster_results).  A frame without a ground plane was not fitted: CD_ERR_NO_MODEL, a zero record. */
+int cd_get_surface_results(const cd_context* ctx, int first, int capacity, cd_surface_frame_result* out, int32_t* frame_status);
+
 /* S3 as a call of its own: pcl::ExtractIndices<PCLPointCloud2> (gps.cpp:96-101, opd.cpp:320-326; the fused calls extract
  * internally).  negative == 0: the records at `indices`, in the order of the list; negative != 0: the records whose index
  * is NOT in the list, in their original order (what both launch files use: setNegative(invert = true)).  Records are copied
@@ -312,6 +345,14 @@ int cd_ground_plane(cd_context* ctx, const void* points, size_t stride_bytes, in
  * (scene -> template), frame f of the following cd_process_batch* calls uses guesses[16 f .. 16 f + 15] for each of its
  * clusters (the granularity of the reference: one sne pose per frame, icp.cpp:130-134).  n_frames = 0 clears them. */
 int cd_set_frame_guesses(cd_context* ctx, const float* guesses, int n_frames);
+
+/* CD_GUESS_SURFACE (cd_process_batch[_device], cd_process_frame, cd_process_depth_batch[_device]): after S3 every frame with a
+ * ground plane runs cd_surface_batch's fits on its objects cloud (the CD_CLOUD_OBJECTS read-back), table normal = its own
+ * plane[0..2], invert = 1, threshold = cd_set_surface_distance_threshold, the other plane parameters as prm; rule C9 turns
+ * each pose into the frame's guess (identity where the fit fails), and the ICP runs as CD_GUESS_PER_FRAME would with those
+ * guesses; frames whose guess came from the fit get CD_FRAME_SURFACE_GUESS.  The guesses cd_set_frame_guesses stored are
+ * untouched.  One guess per FRAME, as in the reference: meaningful when a frame holds one object (the cuboid_detection
+ * scenario) - with several boxes the fits run across them (their coplanar tops all go to the first fit). */
 
 /* IterativeClosestPoint::setMaxCorrespondenceDistance (the line icp.cpp:175 / opd.cpp:225 leave commented out): context
  * state that applies to every ICP of the following cd_icp, cd_process_frame, cd_process_batch[_device] and

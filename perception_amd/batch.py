@@ -76,9 +76,12 @@ class BatchPipeline:
 
     submit() returns a Future of (records uint8[F, FRAME_RESULT_BYTES], CdTiming).
     icp_max_correspondence_distance: IterativeClosestPoint::setMaxCorrespondenceDistance for every context (None:
-    unbounded, the default; rule C8)."""
+    unbounded, the default; rule C8).
+    surface_distance_threshold: sne's distance threshold for prm.icp_use_guess = CD_GUESS_SURFACE on every context (None:
+    the default, 0.015)."""
 
-    def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2, icp_max_correspondence_distance=None):
+    def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2, icp_max_correspondence_distance=None,
+                 surface_distance_threshold=None):
         from concurrent.futures import ThreadPoolExecutor
         self.inflight = max(1, int(inflight))
         self.contexts = [capi.Context(max_points=max_points, max_frames=max_frames, device_id=device_id) for _ in range(self.inflight)]
@@ -87,6 +90,8 @@ class BatchPipeline:
                 cx.set_template(slot, xyz)
             if icp_max_correspondence_distance is not None:
                 cx.set_icp_max_correspondence_distance(icp_max_correspondence_distance)
+            if surface_distance_threshold is not None:
+                cx.set_surface_distance_threshold(surface_distance_threshold)
         self._results = [(capi.CdFrameResult * max_frames)() for _ in range(self.inflight)]
         self._busy = [None] * self.inflight
         self._pool = ThreadPoolExecutor(self.inflight)

@@ -13,6 +13,7 @@ CD_ABI_VERSION = 4
 CD_MAX_TEMPLATES = 8
 CD_MAX_CLUSTERS_PER_FRAME = 8
 CD_FRAME_MORE_CLUSTERS = 1
+CD_FRAME_SURFACE_GUESS = 2
 
 CD_OK = 0
 CD_ERR_INVALID_ARG = -1
@@ -34,10 +35,12 @@ EXPORTED_SYMBOLS = [
     "cd_template_lattice_faces", "cd_template_nearest", "cd_lattice_detect", "cd_passthrough",
     "cd_default_depth_camera", "cd_depth_to_cloud", "cd_process_depth_batch", "cd_process_depth_batch_device",
     "cd_set_icp_max_correspondence_distance", "cd_get_icp_max_correspondence_distance", "cd_icp_correspondence_threshold",
+    "cd_surface_batch", "cd_surface_guess", "cd_set_surface_distance_threshold", "cd_get_surface_distance_threshold",
+    "cd_get_surface_results",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
-CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME = 0, 1, 2
+CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE = 0, 1, 2, 3
 
 
 CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
@@ -204,6 +207,12 @@ def load_library(path=None):
     lib.cd_get_cluster_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, ip]
     lib.cd_ground_plane.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(CdParams), f32p, vp, C.c_int, ip, ip]
     lib.cd_set_frame_guesses.argtypes = [vp, f32p, C.c_int]
+    lib.cd_surface_batch.argtypes = [vp, vp, C.c_size_t, C.c_int, i32p, C.c_int, f32p, C.c_int, C.POINTER(CdParams),
+                                     C.POINTER(CdSurfaceFrameResult), i32p]
+    lib.cd_surface_guess.argtypes = [f32p, f32p]
+    lib.cd_set_surface_distance_threshold.argtypes = [vp, C.c_double]
+    lib.cd_get_surface_distance_threshold.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.cd_get_surface_results.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CdSurfaceFrameResult), i32p]
     lib.cd_template_lattice_faces.argtypes = [vp, C.c_int]
     lib.cd_template_nearest.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_lattice_detect.argtypes = [vp, C.c_size_t, C.c_int, vp]
@@ -428,6 +437,46 @@ class Context:
         g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
         self._check(self.lib.cd_set_frame_guesses(self.h, g.ctypes.data_as(C.POINTER(C.c_float)), g.shape[0]))
 
+    def surface_batch(self, clouds, table_normals, prm, invert=True):
+        """cd_surface_batch: cd_surface_frame over a batch of (ragged) clouds, fitted together on the device.
+        clouds: a sequence of (n_f, >=3) arrays or an (F, P, >=3) array; table_normals (F, 3).
+        Returns (frame_status int32[F], CdSurfaceFrameResult array of F)."""
+        clouds = [np.asarray(c, np.float32).reshape(-1, np.shape(c)[-1]) for c in clouds]
+        F = len(clouds)
+        counts = np.array([c.shape[0] for c in clouds], np.int32)
+        P = max(1, int(counts.max()) if F else 1)
+        packed = np.zeros((F, P, 4), np.float32)
+        for f, c in enumerate(clouds):
+            packed[f, :c.shape[0], :3] = c[:, :3]
+        tn = np.ascontiguousarray(table_normals, np.float32).reshape(F, 3)
+        out = (CdSurfaceFrameResult * max(F, 1))()
+        status = np.zeros(max(F, 1), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        st = self.lib.cd_surface_batch(self.h, _ptr(packed), 16, P, counts.ctypes.data_as(i32), F,
+                                       tn.ctypes.data_as(C.POINTER(C.c_float)), 1 if invert else 0, C.byref(prm), out,
+                                       status.ctypes.data_as(i32))
+        self._check(st)
+        return status[:F], out
+
+    def surface_results(self):
+        """cd_get_surface_results: the per-frame surface results of the last CD_GUESS_SURFACE fused call.
+        Returns (frame_status int32[F], CdSurfaceFrameResult array of F)."""
+        out = (CdSurfaceFrameResult * self.max_frames)()
+        status = np.zeros(self.max_frames, np.int32)
+        n = self.lib.cd_get_surface_results(self.h, 0, self.max_frames, out, status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if n < 0:
+            raise CuboidError(n, "cd_get_surface_results: the last fused call was not in CD_GUESS_SURFACE mode")
+        return status[:n].copy(), out[:n]
+
+    def set_surface_distance_threshold(self, d):
+        """sne's distance threshold for CD_GUESS_SURFACE (context state; default 0.015)."""
+        self._check(self.lib.cd_set_surface_distance_threshold(self.h, float(d)))
+
+    def surface_distance_threshold(self):
+        v = C.c_double()
+        self._check(self.lib.cd_get_surface_distance_threshold(self.h, C.byref(v)))
+        return v.value
+
     def set_icp_max_correspondence_distance(self, d):
         """IterativeClosestPoint::setMaxCorrespondenceDistance for every later ICP of this context (rule C8); None = unbounded."""
         self._check(self.lib.cd_set_icp_max_correspondence_distance(self.h, float("inf") if d is None else float(d)))
@@ -531,6 +580,18 @@ def icp_correspondence_threshold(d):
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_correspondence_threshold")
     return f.value, int(b.value)
+
+
+def surface_guess(Rt):
+    """Host-only rule C9: the ICP guess (4x4 float32, scene -> template) of a surface pose Rt (cd_surface_guess)."""
+    lib = load_library()
+    a = np.ascontiguousarray(Rt, np.float32).reshape(16)
+    g = np.zeros(16, np.float32)
+    f32 = C.POINTER(C.c_float)
+    st = lib.cd_surface_guess(a.ctypes.data_as(f32), g.ctypes.data_as(f32))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_surface_guess: non-finite input")
+    return g.reshape(4, 4)
 
 
 def results_to_array(res):

@@ -139,6 +139,21 @@ struct cd_context {
     int icp_bounded = 0;
     uint32_t* d_ncorr = nullptr;
     size_t ncorr_cap = 0;
+    // batched surface-normal estimation (cd_surface_batch, CD_GUESS_SURFACE, stage_surface): FrameStates, plane models and point
+    // buffers of its own, allocated on first use, so that the S2 plane, the clouds and the plane indices of a fused call stay
+    // as they are; s_pts[0..1]: the current and the next cloud of every frame, rows of s_pitch points
+    FrameState *d_sfs = nullptr, *h_sfs = nullptr;
+    float4 *d_smodel = nullptr, *h_smodel = nullptr;
+    int *d_shave = nullptr, *h_shave = nullptr, *d_sactive = nullptr, *h_sactive = nullptr;
+    float4 *d_spts[2] = {nullptr, nullptr};
+    int* d_sidx = nullptr;
+    size_t spts_cap = 0;
+    float4 *d_ssum = nullptr, *h_ssum = nullptr;                  // [F][3] midpoint sums of the three fits (x, y, z, count bits)
+    double surface_thr = 0.015;                                   // cd_set_surface_distance_threshold (surface_normal_estimation.launch)
+    std::vector<float> surface_guess;                             // rule C9 guesses of the last CD_GUESS_SURFACE call, 16 per frame
+    std::vector<cd_surface_frame_result> last_surface;            // cd_get_surface_results
+    std::vector<int32_t> last_surface_status;
+    bool last_surface_ok = false;
     IcpState *d_st = nullptr, *h_st = nullptr;
     unsigned long long *d_acc = nullptr, *d_accf = nullptr, *h_accf = nullptr;
     hipEvent_t ev[8] = {nullptr};
@@ -174,6 +189,7 @@ namespace {
 void invalidate_last(cd_context* c) {
     c->last_clouds = false;
     c->last_first.clear();
+    c->last_surface_ok = false;
 }
 
 int fail(cd_context* c, int code, const char* msg) {
@@ -536,7 +552,8 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
 
 // S2.  in: d_vox + fs.n_v (host mirror h_fs[].n_v must be current).  out: h_model/h_have refined,
 // fs.status updated for NO_MODEL, iterations per frame.
-int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iterations, int* rounds_out) {
+// axes: per-frame constraint axes of a constrained model, 3 floats per frame (nullptr: p->plane_axis for every frame)
+int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iterations, int* rounds_out, const float* axes = nullptr) {
     const int T = c->T;
     const bool mr = c->mirror_reads != 0;
     const float thr = hm::fold_ge(p->plane_distance_threshold);
@@ -579,7 +596,7 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
                 for (int h = rep[f].pos; h < s.n_hyp; ++h) {
                     const float4 m = c->h_models[(size_t)f * MAX_HYP + h];
                     const float mm[4] = {m.x, m.y, m.z, m.w};
-                    if (c->h_valid[(size_t)f * MAX_HYP + h] && !hm::plane_model_valid(p->plane_model, mm, p->plane_axis, p->plane_eps_angle))
+                    if (c->h_valid[(size_t)f * MAX_HYP + h] && !hm::plane_model_valid(p->plane_model, mm, axes ? axes + 3 * f : p->plane_axis, p->plane_eps_angle))
                         c->h_counts[(size_t)f * MAX_HYP + h] = 0;
                 }
             }
@@ -603,7 +620,7 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
     auto upload_have = [&](const float4* models_too = nullptr) -> int {
         for (int f = 0; f < F; ++f) {
             const float mm[4] = {c->h_model[f].x, c->h_model[f].y, c->h_model[f].z, c->h_model[f].w};
-            c->h_active[f] = c->h_have[f] && hm::plane_model_valid(p->plane_model, mm, p->plane_axis, p->plane_eps_angle) ? 1 : 0;
+            c->h_active[f] = c->h_have[f] && hm::plane_model_valid(p->plane_model, mm, axes ? axes + 3 * f : p->plane_axis, p->plane_eps_angle) ? 1 : 0;
         }
         if (mr) return CD_OK;   // (the kernels read h_model / h_active)
         XferBatch xb(c);
@@ -753,6 +770,7 @@ struct TplGroup { int beg, end, live; int kind; long long pts; };
 struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
     int ncl = 0, guess_mode = CD_GUESS_NONE, max_n = 0, qslice = 0;
     size_t guess_need = 0;                       // floats of the guess upload
+    const std::vector<float>* frame_guess = nullptr;   // per-frame guesses: cd_set_frame_guesses' or (CD_GUESS_SURFACE) the call's own
     std::vector<char> in_lat;                    // the cluster takes k_icp_lat
     int n_lat = 0, n_live = 0, lat_max_n = 0;
     std::vector<TplGroup> groups;
@@ -767,12 +785,14 @@ struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
 int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     pl->ncl = ncl;
     // initial guess (pcl::Registration::align(output, guess)); the default - and the reference's live path - is none
-    const int guess_mode = pl->guess_mode = p->icp_use_guess;
+    // (CD_GUESS_SURFACE is CD_GUESS_PER_FRAME with the guesses the call derived itself)
+    const int guess_mode = pl->guess_mode = p->icp_use_guess == CD_GUESS_SURFACE ? CD_GUESS_PER_FRAME : p->icp_use_guess;
+    pl->frame_guess = p->icp_use_guess == CD_GUESS_SURFACE ? &c->surface_guess : &c->frame_guess;
     if (guess_mode != CD_GUESS_NONE) {
         int max_frame = 0;
         for (int k = 0; k < ncl; ++k) { pl->max_n = std::max(pl->max_n, c->h_cl[k].n); max_frame = std::max(max_frame, c->h_cl[k].frame); }
         pl->guess_need = guess_mode == CD_GUESS_PER_FRAME ? 16 * ((size_t)max_frame + 1) : 16;
-        if (guess_mode == CD_GUESS_PER_FRAME && c->frame_guess.size() < pl->guess_need) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_PER_FRAME but cd_set_frame_guesses holds fewer frames than the batch");
+        if (guess_mode == CD_GUESS_PER_FRAME && pl->frame_guess->size() < pl->guess_need) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_PER_FRAME but cd_set_frame_guesses holds fewer frames than the batch");
     }
     // queries per workgroup: 512 when the batch fills the chip, smaller slices (more workgroups) otherwise
     long long qtot = 0;
@@ -827,7 +847,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
             std::memset(&st, 0, sizeof(st));
             for (int i = 0; i < 4; ++i) st.Tfinal[5 * i] = 1.f;
             if (guess_mode != CD_GUESS_NONE)   // final_transformation_ = guess
-                std::memcpy(st.Tfinal, guess_mode == CD_GUESS_PER_FRAME ? c->frame_guess.data() + 16 * (size_t)cl.frame : p->icp_guess, 64);
+                std::memcpy(st.Tfinal, guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() + 16 * (size_t)cl.frame : p->icp_guess, 64);
             st.prev_mse = std::numeric_limits<double>::max();
             if (cl.tpl_m <= 0) { st.done = 1; st.status = CD_ERR_NO_TEMPLATE; }
             else if (cl.n < 3) { st.done = 1; st.status = CD_ERR_FEW_CORRESPONDENCES; }
@@ -862,7 +882,7 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
     const int ncl = pl->ncl;
     if (pl->guess_mode != CD_GUESS_NONE) {
         if (int st = grow_device(c, &c->d_guess, &c->guess_cap, pl->guess_need)) return st;
-        HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? c->frame_guess.data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
+        HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
     }
     if (!pl->lat_direct) {
         XferBatch xb(c);   // (one launch)
@@ -1284,9 +1304,190 @@ int check_params(cd_context* c, const cd_params* p) {
     if (p->template_slot < -1 || p->template_slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "template_slot out of range");
     if (!(p->cluster_tolerance > 0.0)) return fail(c, CD_ERR_INVALID_ARG, "cluster_tolerance must be > 0");
     if (p->plane_model < CD_PLANE || p->plane_model > CD_PLANE_PARALLEL) return fail(c, CD_ERR_INVALID_ARG, "plane_model out of range");
-    if (p->icp_use_guess < CD_GUESS_NONE || p->icp_use_guess > CD_GUESS_PER_FRAME) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess out of range");
+    if (p->icp_use_guess < CD_GUESS_NONE || p->icp_use_guess > CD_GUESS_SURFACE) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess out of range");
     if (p->icp_use_guess == CD_GUESS_PARAMS)
         for (int i = 0; i < 16; ++i) if (!std::isfinite(p->icp_guess[i])) return fail(c, CD_ERR_INVALID_ARG, "icp_guess holds a non-finite value");
+    return CD_OK;
+}
+
+// ---- batched surface-normal estimation (sne.cpp:167-234 over F frames: cd_surface_batch, CD_GUESS_SURFACE) ----------------
+// The three constrained fits run over every frame at once: round i is stage_plane + stage_extract on each frame's current
+// cloud, k_surface_centroid sums the plane points, and the leftover cloud (ExtractIndices(negative = invert), what S3 writes to
+// its object buffer with extract_negative = invert) is the next round's cloud; a frame whose fit fails drops out.  The stages
+// run on the surface stage's own buffers: SurfaceBuffers swaps them in for its lifetime.
+
+int ensure_surface(cd_context* c, size_t pitch) {   // (the per-frame arrays at the context's capacity, the clouds as needed)
+    if (!c->d_sfs) {
+        const size_t F = (size_t)c->F;
+        HIPCHK(c, dalloc(&c->d_sfs, F)); HIPCHK(c, halloc(&c->h_sfs, F));
+        HIPCHK(c, dalloc(&c->d_smodel, F)); HIPCHK(c, halloc(&c->h_smodel, F));
+        HIPCHK(c, dalloc(&c->d_shave, F)); HIPCHK(c, halloc(&c->h_shave, F));
+        HIPCHK(c, dalloc(&c->d_sactive, F)); HIPCHK(c, halloc(&c->h_sactive, F));
+        HIPCHK(c, dalloc(&c->d_ssum, 3 * F)); HIPCHK(c, halloc(&c->h_ssum, 3 * F));
+    }
+    const size_t need = (size_t)c->F * std::max<size_t>(pitch, 1);
+    if (need <= c->spts_cap) return CD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (float4*& q : c->d_spts) { if (q) hipFree(q); q = nullptr; }
+    if (c->d_sidx) hipFree(c->d_sidx);
+    c->d_sidx = nullptr;
+    c->spts_cap = 0;
+    HIPCHK(c, dalloc(&c->d_spts[0], need)); HIPCHK(c, dalloc(&c->d_spts[1], need)); HIPCHK(c, dalloc(&c->d_sidx, need));
+    c->spts_cap = need;
+    return CD_OK;
+}
+
+// For its lifetime the S2/S3 stage drivers work on the surface stage's buffers: FrameStates, models, have / active flags,
+// d_vox = the current clouds (d_spts[0]), d_obj = the next (d_spts[1]), d_plane_idx; row pitch `pitch` points.  Its own
+// scratch fills are done by the stages (batch_zeroed off); everything is put back on every way out.
+struct SurfaceBuffers {
+    cd_context* c;
+    int N, T;
+    bool zeroed;
+    SurfaceBuffers(cd_context* ctx, int pitch) : c(ctx), N(ctx->N), T(ctx->T), zeroed(ctx->batch_zeroed) {
+        swap_all();
+        c->N = pitch;
+        c->T = (pitch + TILE - 1) / TILE;
+        c->batch_zeroed = false;
+    }
+    ~SurfaceBuffers() {
+        swap_all();
+        c->N = N;
+        c->T = T;
+        c->batch_zeroed = zeroed;
+    }
+    void swap_all() {
+        std::swap(c->d_fs, c->d_sfs); std::swap(c->h_fs, c->h_sfs);
+        std::swap(c->d_model, c->d_smodel); std::swap(c->h_model, c->h_smodel);
+        std::swap(c->d_have, c->d_shave); std::swap(c->h_have, c->h_shave);
+        std::swap(c->d_active, c->d_sactive); std::swap(c->h_active, c->h_sactive);
+        std::swap(c->d_vox, c->d_spts[0]); std::swap(c->d_obj, c->d_spts[1]);
+        std::swap(c->d_plane_idx, c->d_sidx);
+    }
+};
+
+// in: the clouds in d_spts[0] (rows of `pitch` points), count[f] points each; axes: 3 floats per frame; run[f] = 0: frame f is
+// not fitted (status CD_ERR_NO_MODEL, zero record).  q: the fit parameters (threshold, probability) as cd_surface_frame takes them.
+int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,
+                  int invert, const cd_params* p, cd_surface_frame_result* res, int32_t* status) {
+    for (int f = 0; f < F; ++f) {
+        std::memset(&res[f], 0, sizeof(res[f]));
+        status[f] = run[(size_t)f] ? CD_OK : CD_ERR_NO_MODEL;
+    }
+    const float thr = hm::fold_ge(p->plane_distance_threshold);
+    std::vector<int> n(count);
+    {
+        SurfaceBuffers sb(c, pitch);
+        for (int i = 0; i < 3; ++i) {   // sne.cpp:183-197
+            cd_params q = *p;
+            q.plane_model = i == 0 ? CD_PLANE_PERPENDICULAR : CD_PLANE_PARALLEL;
+            q.plane_eps_angle = 0.1;                       // sne.cpp:123
+            q.plane_optimize = 1;                          // sne.cpp:118
+            q.plane_max_iterations = 1000;                 // sne.cpp:125
+            q.extract_negative = invert ? 1 : 0;           // S3's object output = the leftover cloud
+            q.crop2_enable = 0;
+            q.bbox_enable = 0;
+            bool any = false;
+            for (int f = 0; f < F; ++f) {   // a fresh FrameState per fit, as load_as gives cd_surface_frame; frames out of the run stay idle
+                FrameState& fs = c->h_fs[f];
+                std::memset(&fs, 0, sizeof(fs));
+                const bool live = status[f] == CD_OK;
+                fs.status = live ? CD_OK : CD_ERR_INVALID_ARG;   // (stage_plane fits the frames whose status is OK or NO_MODEL)
+                fs.n_v = live ? n[(size_t)f] : 0;
+                any = any || live;
+            }
+            if (!any) break;
+            HIPCHK(c, xfer(c, c->d_fs, c->h_fs, sizeof(FrameState) * F, hipMemcpyHostToDevice));
+            std::vector<int> iters;
+            int st = stage_plane(c, F, &q, iters, nullptr, axes);
+            if (st) return st;
+            for (int f = 0; f < F; ++f) {
+                if (status[f] != CD_OK) continue;
+                res[f].iterations[i] = iters[(size_t)f];
+                if (!c->h_have[f]) status[f] = CD_ERR_NO_MODEL;
+            }
+            st = stage_extract(c, F, &q);
+            if (st) return st;
+            LAUNCH(c, launch_surface_centroid(c->stream, c->d_vox, pitch, F, c->d_fs, c->mirror_reads ? c->h_model : c->d_model,
+                                              c->mirror_reads ? c->h_active : c->d_have, thr, invert, c->d_ssum + i, 3));
+            st = sync_fs(c, F, c->mirror_writes && c->copy_kernels);   // n_o: the leftover clouds
+            if (st) return st;
+            for (int f = 0; f < F; ++f) {
+                if (status[f] != CD_OK) continue;
+                n[(size_t)f] = c->h_fs[f].n_o;
+                const float4 m = c->h_model[f];   // (in fit order; sorted below)
+                res[f].coeff[i][0] = m.x; res[f].coeff[i][1] = m.y; res[f].coeff[i][2] = m.z; res[f].coeff[i][3] = m.w;
+            }
+            std::swap(c->d_vox, c->d_obj);
+        }
+    }
+    HIPCHK(c, xfer(c, c->h_ssum, c->d_ssum, sizeof(float4) * 3 * (size_t)F, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int f = 0; f < F; ++f) {
+        cd_surface_frame_result& r = res[f];
+        if (status[f] != CD_OK) {   // (a failed fit leaves the iterations of the fits run so far and nothing else)
+            std::memset(r.coeff, 0, sizeof(r.coeff));
+            continue;
+        }
+        float normals[3][4], mids[3][4];
+        int counts[3];
+        for (int i = 0; i < 3; ++i) {
+            const float4 sm = c->h_ssum[3 * (size_t)f + i];
+            std::memcpy(&counts[i], &sm.w, 4);
+            const float cnt = (float)counts[i];   // pcl::compute3DCentroid: the sums / the count
+            mids[i][0] = sm.x / cnt; mids[i][1] = sm.y / cnt; mids[i][2] = sm.z / cnt; mids[i][3] = 0.f;
+            for (int a = 0; a < 4; ++a) normals[i][a] = r.coeff[i][a];
+        }
+        for (int i = 0; i < 3; ++i)   // sne.cpp:199-212, as cd_surface_frame
+            for (int j = i; j < 3; ++j)
+                if (counts[i] < counts[j]) {
+                    std::swap(counts[i], counts[j]);
+                    for (int a = 0; a < 4; ++a) { std::swap(normals[i][a], normals[j][a]); std::swap(mids[i][a], mids[j][a]); }
+                }
+        hm::surface_frame(normals, mids, r.Rt);
+        for (int i = 0; i < 3; ++i) {
+            r.n_points[i] = counts[i];
+            for (int a = 0; a < 4; ++a) { r.coeff[i][a] = normals[i][a]; r.midpoint[i][a] = mids[i][a]; }
+        }
+    }
+    return CD_OK;
+}
+
+// CD_GUESS_SURFACE: the surface fit of every frame that has a ground plane, on its objects cloud (d_obj, n_o), table normal =
+// its plane, invert = 1, the context's threshold -> c->last_surface*; rule C9 -> c->surface_guess (identity where the fit
+// fails); (*flagged)[f] = 1 where the guess came from the fit
+int surface_guesses(cd_context* c, int F, const cd_params* p, std::vector<char>* flagged) {
+    std::vector<int> count((size_t)F, 0);
+    std::vector<char> run((size_t)F, 0);
+    std::vector<float> axes(3 * (size_t)F, 0.f);
+    int pitch = 1;
+    for (int f = 0; f < F; ++f) {
+        if (!c->h_have[f]) continue;
+        run[(size_t)f] = 1;
+        count[(size_t)f] = c->h_fs[f].n_o;
+        pitch = std::max(pitch, count[(size_t)f]);
+        axes[3 * (size_t)f] = c->h_model[f].x; axes[3 * (size_t)f + 1] = c->h_model[f].y; axes[3 * (size_t)f + 2] = c->h_model[f].z;
+    }
+    int st = ensure_surface(c, (size_t)pitch);
+    if (st) return st;
+    LAUNCH(c, launch_surface_load(c->stream, c->d_obj, sizeof(float4), sizeof(float4) * (size_t)c->N, FS_FIELD(c, n_o), FS_PITCH, pitch, pitch, F, c->d_spts[0]));
+    cd_params q = *p;
+    q.plane_distance_threshold = c->surface_thr;
+    c->last_surface.assign((size_t)F, cd_surface_frame_result());
+    c->last_surface_status.assign((size_t)F, CD_ERR_NO_MODEL);
+    st = stage_surface(c, F, pitch, count, axes.data(), run, 1, &q, c->last_surface.data(), c->last_surface_status.data());
+    if (st) return st;
+    c->surface_guess.assign(16 * (size_t)F, 0.f);
+    flagged->assign((size_t)F, 0);
+    for (int f = 0; f < F; ++f) {
+        float* g = c->surface_guess.data() + 16 * (size_t)f;
+        for (int i = 0; i < 4; ++i) g[5 * i] = 1.f;
+        float h[16];
+        if (c->last_surface_status[(size_t)f] == CD_OK && cd_surface_guess(c->last_surface[(size_t)f].Rt, h) == CD_OK) {
+            std::memcpy(g, h, sizeof(h));
+            (*flagged)[(size_t)f] = 1;
+        }
+    }
     return CD_OK;
 }
 
@@ -1360,6 +1561,11 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     for (int f = 0; f < F; ++f) max_no = std::max(max_no, c->h_fs[f].n_o);
     st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff
     if (st) return st;
+    std::vector<char> surface_flag;   // CD_GUESS_SURFACE: the frames whose guess came from their surface fit
+    if (p->icp_use_guess == CD_GUESS_SURFACE) {
+        st = surface_guesses(c, F, p, &surface_flag);
+        if (st) return st;
+    }
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
     front.release();
     // Every cluster of every frame gets its ICP (opd.cpp:376-413).  The device extracts the ICP sources KICP clusters per
@@ -1513,6 +1719,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     c->last_nv.resize((size_t)F); c->last_no.resize((size_t)F);
     for (int f = 0; f < F; ++f) { c->last_nv[(size_t)f] = c->h_fs[f].n_v; c->last_no[(size_t)f] = c->h_fs[f].n_o; }
     c->last_clouds = true;
+    c->last_surface_ok = p->icp_use_guess == CD_GUESS_SURFACE;
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     // records
     long long balg = 0;
@@ -1527,6 +1734,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
         r.n_objects = s.n_o;
         r.n_clusters = s.n_k;
         r.flags = s.n_k > KICP ? CD_FRAME_MORE_CLUSTERS : 0;
+        if (!surface_flag.empty() && surface_flag[(size_t)f]) r.flags |= CD_FRAME_SURFACE_GUESS;
         r.ransac_iterations = iterations[f];
         if (s.status == CD_OK && !c->h_have[f]) r.status = CD_ERR_NO_MODEL;
         if (c->h_have[f]) { r.plane[0] = c->h_model[f].x; r.plane[1] = c->h_model[f].y; r.plane[2] = c->h_model[f].z; r.plane[3] = c->h_model[f].w; }
@@ -1626,6 +1834,12 @@ void cd_destroy(cd_context* c) {
     if (c->d_tileC) hipFree(c->d_tileC);
     if (c->d_depth) hipFree(c->d_depth);
     if (c->d_color) hipFree(c->d_color);
+    {
+        void* sdev[] = {c->d_sfs, c->d_smodel, c->d_shave, c->d_sactive, c->d_spts[0], c->d_spts[1], c->d_sidx, c->d_ssum};
+        for (void* p : sdev) if (p) hipFree(p);
+        void* shost[] = {c->h_sfs, c->h_smodel, c->h_shave, c->h_sactive, c->h_ssum};
+        for (void* p : shost) if (p) hipHostFree(p);
+    }
     if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
     if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
     for (auto& e : c->ev2) if (e) hipEventDestroy(e);
@@ -2328,6 +2542,44 @@ static int cd_surface_frame_impl(cd_context* c, const void* xyz, size_t stride, 
     return CD_OK;
 }
 
+// cd_surface_frame over a batch: the records go up as they are, k_surface_load unpacks them on the device (no host loop over
+// points) and stage_surface runs the three fits of every frame together
+static int cd_surface_batch_impl(cd_context* c, const void* xyz, size_t stride, int P, const int32_t* n_points, int F,
+                                 const float* table_normals, int invert, const cd_params* p, cd_surface_frame_result* out, int32_t* status) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    invalidate_last(c);
+    int st = check_params(c, p);
+    if (st) return st;
+    if (!n_points || !table_normals || !out || !status || F <= 0 || P < 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    int max_n = 0;
+    for (int f = 0; f < F; ++f) {
+        if (n_points[f] < 0 || n_points[f] > P) return fail(c, CD_ERR_INVALID_ARG, "n_points[f] outside [0, points_per_frame]");
+        max_n = std::max(max_n, (int)n_points[f]);
+    }
+    if (max_n > 0 && !xyz) return fail(c, CD_ERR_INVALID_ARG, "xyz is NULL");
+    if (F > c->F || max_n > c->N) return fail(c, CD_ERR_CAPACITY, "batch larger than the context capacity");
+    const int pitch = std::max(max_n, 1);
+    st = ensure_surface(c, (size_t)pitch);
+    if (st) return st;
+    std::vector<int> count(n_points, n_points + F);
+    for (int f = 0; f < F; ++f) {
+        std::memset(&c->h_sfs[f], 0, sizeof(FrameState));
+        c->h_sfs[f].n_v = count[(size_t)f];
+    }
+    HIPCHK(c, xfer(c, c->d_sfs, c->h_sfs, sizeof(FrameState) * F, hipMemcpyHostToDevice));
+    if (max_n > 0) {
+        const size_t bytes = ((size_t)(F - 1) * P + (size_t)n_points[F - 1]) * stride;
+        st = ensure_input(c, std::max<size_t>(bytes, 16));
+        if (st) return st;
+        if (bytes > 0) HIPCHK(c, hipMemcpyAsync(c->d_in, xyz, bytes, hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, launch_surface_load(c->stream, c->d_in, stride, stride * (size_t)P, (const int*)((char*)c->d_sfs + offsetof(FrameState, n_v)),
+                                      FS_PITCH, pitch, max_n, F, c->d_spts[0]));
+    }
+    const std::vector<char> run((size_t)F, 1);
+    return stage_surface(c, F, pitch, count, table_normals, run, invert, p, out, status);
+}
+
 static int cd_bbox_filter_impl(cd_context* c, const void* xyz, size_t stride, int n, const double P[12], const int32_t rect[4],
                    int32_t* out_indices, int capacity, int* out_n) {
     if (!c) return CD_ERR_INVALID_ARG;
@@ -2471,6 +2723,7 @@ static int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stri
     int st = check_params(c, p);
     if (st) return st;
     if (!src_xyz || !out || n < 0 || stride < 12 || slot < 0 || slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    if (p->icp_use_guess == CD_GUESS_SURFACE) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_SURFACE needs a frame to fit: fused calls only");
     if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
     if (c->tpl_m[slot] <= 0) return fail(c, CD_ERR_NO_TEMPLATE, "template slot is empty");
     st = upload_points(c, src_xyz, stride, n, c->d_src0);
@@ -2762,6 +3015,69 @@ int cd_get_icp_max_correspondence_distance(const cd_context* c, double* out) {
     return CD_OK;
 }
 
+int cd_set_surface_distance_threshold(cd_context* c, double d) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    if (!std::isfinite(d) || !(d > 0.0)) return fail(c, CD_ERR_INVALID_ARG, "the surface distance threshold must be finite and > 0");
+    c->surface_thr = d;
+    return CD_OK;
+}
+
+int cd_get_surface_distance_threshold(const cd_context* c, double* out) {
+    if (!c || !out) return CD_ERR_INVALID_ARG;
+    *out = c->surface_thr;
+    return CD_OK;
+}
+
+int cd_get_surface_results(const cd_context* c, int first, int capacity, cd_surface_frame_result* out, int32_t* frame_status) {
+    if (!c || first < 0 || capacity < 0) return CD_ERR_INVALID_ARG;
+    if (!c->last_surface_ok) return CD_ERR_INVALID_ARG;   // (no fused call in CD_GUESS_SURFACE mode since the last compute call)
+    int n = 0;
+    for (size_t f = (size_t)first; f < c->last_surface.size() && n < capacity; ++f, ++n) {
+        if (out) out[n] = c->last_surface[f];
+        if (frame_status) frame_status[n] = c->last_surface_status[f];
+    }
+    return n;
+}
+
+// rule C9: sne's pose message -> poseMsgToEigen's rotation -> the symmetry variant that turns the most template
+// faces toward the camera -> the inverse, scene -> template, rounded once to float32
+int cd_surface_guess(const float Rt[16], float guess[16]) {
+    if (!Rt || !guess) return CD_ERR_INVALID_ARG;
+    double H[16];
+    for (int i = 0; i < 16; ++i) {
+        if (!std::isfinite(Rt[i])) return CD_ERR_INVALID_ARG;
+        H[i] = (double)Rt[i];
+    }
+    double t[3], q[4];
+    cd_pose_to_position_quaternion(H, t, q);   // sne.cpp:64-96 (tf::Matrix3x3::getRotation)
+    const double x = q[0], y = q[1], z = q[2], w = q[3];   // (not normalised: neither tf nor Eigen does here)
+    const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                            {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                            {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+    static const double Fd[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+    int best = 0, best_score = -1;
+    for (int k = 0; k < 4; ++k) {
+        int score = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double v = (R[0][a] * Fd[k][a] * t[0] + R[1][a] * Fd[k][a] * t[1]) + R[2][a] * Fd[k][a] * t[2];
+            score += v > 0.0 ? 1 : 0;
+        }
+        if (score > best_score) { best_score = score; best = k; }
+    }
+    double M[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 3; ++a) M[r][a] = R[r][a] * Fd[best][a];
+    float g[16];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) g[4 * i + j] = (float)M[j][i];
+        g[4 * i + 3] = (float)(-((M[0][i] * t[0] + M[1][i] * t[1]) + M[2][i] * t[2]));
+    }
+    g[12] = 0.f; g[13] = 0.f; g[14] = 0.f; g[15] = 1.f;
+    for (int i = 0; i < 16; ++i) if (!std::isfinite(g[i])) return CD_ERR_INVALID_ARG;
+    std::memcpy(guess, g, sizeof(g));
+    return CD_OK;
+}
+
 int cd_set_frame_guesses(cd_context* c, const float* guesses, int n_frames) {
     if (!c) return CD_ERR_INVALID_ARG;
     if (n_frames < 0 || (n_frames > 0 && !guesses)) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
@@ -2783,6 +3099,10 @@ int cd_segment_plane(cd_context* c, const void* xyz, size_t stride, int n, const
 int cd_surface_frame(cd_context* c, const void* xyz, size_t stride, int n, const float table_normal[3], int invert, const cd_params* p, cd_surface_frame_result* out) {
     if (!c) return CD_ERR_INVALID_ARG;
     return with_scan_retry(c, [&]() { return cd_surface_frame_impl(c, xyz, stride, n, table_normal, invert, p, out); });
+}
+int cd_surface_batch(cd_context* c, const void* xyz, size_t stride, int points_per_frame, const int32_t* n_points, int n_frames, const float* table_normals, int invert, const cd_params* p, cd_surface_frame_result* out, int32_t* frame_status) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_surface_batch_impl(c, xyz, stride, points_per_frame, n_points, n_frames, table_normals, invert, p, out, frame_status); });
 }
 int cd_bbox_filter(cd_context* c, const void* xyz, size_t stride, int n, const double P[12], const int32_t rect[4], int32_t* out_indices, int capacity, int* out_n) {
     if (!c) return CD_ERR_INVALID_ARG;

@@ -122,4 +122,10 @@ struct DeprojectParams {
 void launch_deproject(hipStream_t s, const uint16_t* depth, const uint8_t* color, int width, int height, int n_frames, float fx,
                       float fy, float cx, float cy, float depth_scale, float4* out);
 
+// k_surface.hip : the batched surface-normal estimation's cloud load and plane midpoints (rule C6 sums)
+void launch_surface_load(hipStream_t s, const void* in, size_t stride, size_t fpitch, const int* count, int count_pitch, int pitch,
+                         int max_count, int F, float4* out);
+void launch_surface_centroid(hipStream_t s, const float4* pts, int pitch, int F, const FrameState* fs, const float4* model,
+                             const int* have, float thr, int invert, float4* out, int out_pitch);
+
 }  // namespace cd
