@@ -163,7 +163,8 @@ typedef struct cd_frame_result {
 void cd_default_params(cd_params* p);
 int cd_abi_version(void);
 /* sizeof() of the ABI structs, for FFI layers to verify their mirror of this header:
- * which = 0 cd_params, 1 cd_cluster_result, 2 cd_frame_result, 3 cd_timing, 4 cd_depth_camera. */
+ * which = 0 cd_params, 1 cd_cluster_result, 2 cd_frame_result, 3 cd_timing, 4 cd_depth_camera, 5 cd_color_gate_params,
+ * 6 cd_color_bbox. */
 int cd_struct_size(int which);
 
 /* Object lifetimes (replaces construction/destruction of the PCL objects and the node's
@@ -426,6 +427,69 @@ int cd_process_depth_batch_device(cd_context* ctx, const cd_depth_camera* cam, c
                                   int n_frames, const cd_params* prm, cd_frame_result* results, int32_t* plane_inliers,
                                   int32_t* labels);
 
+/* Colour gate: the node that PRODUCES the rectangle of the bbox gate, cuboid_detection/scripts/object_detection.py:25-62
+ * (/camera/color/image_raw -> /object_detection/bbox), for every image of a batch on the device.  Canonical rule C10
+ * (DESIGN.md §2), integers only, on rgb8 (the script's bgr8 conversion only swaps channels):
+ *   1. 8-bit HSV, H in 0..179 (cvtColor BGR2HSV): v = max, diff = v - min, s = (diff * sdiv[v] + 2048) >> 12,
+ *      h0 = (v == r) ? g - b : (v == g) ? b - r + 2 diff : r - g + 4 diff, h = (h0 * hdiv[diff] + 2048) >> 12 (arithmetic),
+ *      h += 180 if h < 0; sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)) in double, half to even, 0 at 0;
+ *   2. mask = (h <= h_lo_max || h >= h_hi_min) && s >= s_min && v >= v_min (the script's two inRange calls, or-ed);
+ *   3. opening: one 9x9 erosion (outside the image counts as set) then one 9x9 dilation (outside counts as clear) - erode and
+ *      dilate with 5x5 ones, iterations = 2; the script's threshold(200) on a 0/255 image is the identity;
+ *   4. 8-connected components (image border pixels are ordinary pixels); each component's outer border followed through pixel
+ *      centres (Suzuki-Abe, from the component's first raster pixel); area2 = |shoelace sum| = 2 * contourArea.  Hole borders,
+ *      which RETR_LIST also returns, enclose strictly less than their component's outer border and never win;
+ *   5. the component with the largest area2; ties: the one whose first raster pixel comes first;
+ *   6. rect = (x - margin, y - margin, x + w + margin, y + h + margin) of its pixel bounds x, y, w, h - NOT clipped to the image;
+ *   7. no component: found = 0, rect = (0, 0, 0, 0), which keeps no point (the script publishes nothing and bbox_filter.cpp:23
+ *      keeps its zero-initialised rectangle).  Frames of a batch are independent.
+ * Parity with a real OpenCV build is UNPINNED (OpenCV is not a dependency here, like PCL): the semantics are OpenCV 3.x's 8-bit
+ * paths as the rule states them; perception_amd/color_gate.py restates the rule on the CPU and the device equals it bit for bit. */
+typedef struct cd_color_gate_params {   /* rule C10; int32 only */
+    int32_t h_lo_max, h_hi_min;         /* 10, 175: H in 0 .. h_lo_max or h_hi_min .. 179 */
+    int32_t s_min, v_min;               /* 50, 100 (upper bounds 255)                     */
+    int32_t margin;                     /* 10                                             */
+    int32_t reserved[3];
+} cd_color_gate_params;
+typedef struct cd_color_bbox {
+    int32_t rect[4];                    /* x1, y1, x2, y2 as the Rectangle message        */
+    int32_t found;                      /* 0: no component (rect all zero)                */
+    int32_t area2;                      /* 2 * contourArea of the chosen component        */
+    int32_t n_components;
+    int32_t n_mask;                     /* set pixels after the opening                   */
+} cd_color_bbox;
+void cd_default_color_gate_params(cd_color_gate_params* g);
+
+/* Rule C10 on n_frames tightly packed rgb8 images (width * height * 3 bytes each, back to back): out[f] for every frame.
+ * params == NULL: the defaults.  Null pointers, width * height 0 or over max_points, n_frames outside 1 .. max_frames, H bounds
+ * outside 0..179, S / V minima outside 0..255 or a negative margin: CD_ERR_INVALID_ARG before any copy or launch.
+ * CD_ERR_CAPACITY: a border walk ran past its step bound (8 * width * height: cannot happen on a healthy device); no
+ * rectangle of that call is to be used. */
+int cd_color_bbox_batch(cd_context* ctx, const uint8_t* rgb8, int width, int height, int n_frames,
+                        const cd_color_gate_params* params, cd_color_bbox* out);
+/* Same, images already resident in device memory of the context's GPU (ordering as cd_process_batch_device). */
+int cd_color_bbox_batch_device(cd_context* ctx, const uint8_t* d_rgb8, int width, int height, int n_frames,
+                               const cd_color_gate_params* params, cd_color_bbox* out);
+
+/* Where the gate of the fused calls (cd_params.bbox_enable != 0) takes its rectangle from; bbox_P always comes from cd_params.
+ *   CD_BBOX_PARAMS (default): cd_params.bbox_rect, one rectangle for the whole call.
+ *   CD_BBOX_PER_FRAME: frame f of cd_process_batch[_device], cd_process_depth_batch[_device] and cd_process_frame is gated by
+ *     rects[4 f .. 4 f + 3] of cd_set_frame_bboxes (like cd_set_frame_guesses; n_frames = 0 clears them).  Fewer stored
+ *     rectangles than frames: CD_ERR_INVALID_ARG before anything is launched.
+ *   CD_BBOX_COLOR: cd_process_depth_batch[_device] with CD_COLOR_RGB8 only - rule C10 runs on the batch's colour images before
+ *     the extraction and its rectangles feed the gate on the device (no host round trip).  Every other fused entry point, or a
+ *     depth call without colour: CD_ERR_INVALID_ARG.  `params` (NULL = defaults) are the rule's parameters.
+ * With bbox_enable == 0 the source does not matter; cd_bbox_filter, cd_extract, cd_ground_plane and cd_surface_* ignore it.
+ * An unknown source or bad params: CD_ERR_INVALID_ARG, the setting stays as it was.
+ * cd_get_frame_bboxes: the rectangles the gate of the LAST fused call used, frames [first, first + capacity) (CD_BBOX_COLOR: the
+ * full records; CD_BBOX_PER_FRAME: the stored rectangle, found = 1, the other fields 0).  Returns the number copied, or
+ * CD_ERR_INVALID_ARG when that call's gate was off or read cd_params, or another compute call has run since. */
+enum { CD_BBOX_PARAMS = 0, CD_BBOX_PER_FRAME = 1, CD_BBOX_COLOR = 2 };
+int cd_set_frame_bboxes(cd_context* ctx, const int32_t* rects, int n_frames);
+int cd_set_bbox_source(cd_context* ctx, int source, const cd_color_gate_params* params);
+int cd_get_bbox_source(const cd_context* ctx, int* source);
+int cd_get_frame_bboxes(const cd_context* ctx, int first, int capacity, cd_color_bbox* out);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],
@@ -434,8 +498,8 @@ void cd_bbox_corners(const double pose[16], double length, double width, double 
                      float corners_xyz[24]);
 
 /* Timing of the last cd_process_batch* call, milliseconds per stage measured with HIP
- * events on the context's stream: [0] crop+voxel, [1] plane, [2] extract+cluster,
- * [3] icp, [4] total device time.  Also the ICP kernel's launch count and summed time. */
+ * events on the context's stream: [0] crop+voxel (and, for depth input, the deprojection and - CD_BBOX_COLOR - the colour
+ * gate's stage), [1] plane, [2] extract+cluster, [3] icp, [4] total device time.  Also the ICP kernel's launch count and summed time. */
 typedef struct cd_timing {
     float stage_ms[5];
     float icp_kernel_ms;

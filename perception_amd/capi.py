@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "cd_set_icp_max_correspondence_distance", "cd_get_icp_max_correspondence_distance", "cd_icp_correspondence_threshold",
     "cd_surface_batch", "cd_surface_guess", "cd_set_surface_distance_threshold", "cd_get_surface_distance_threshold",
     "cd_get_surface_results",
+    "cd_default_color_gate_params", "cd_color_bbox_batch", "cd_color_bbox_batch_device", "cd_set_frame_bboxes", "cd_set_bbox_source",
+    "cd_get_bbox_source", "cd_get_frame_bboxes",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -45,6 +47,7 @@ CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE = 0, 1, 2, 
 
 CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
 CD_COLOR_NONE, CD_COLOR_RGB8 = 0, 1
+CD_BBOX_PARAMS, CD_BBOX_PER_FRAME, CD_BBOX_COLOR = 0, 1, 2
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -115,7 +118,27 @@ class CdDepthCamera(C.Structure):
     ]
 
 
+class CdColorGateParams(C.Structure):
+    """cd_color_gate_params: the parameters of canonical rule C10 (the red-object rectangle of the colour branch)."""
+    _fields_ = [("h_lo_max", C.c_int32), ("h_hi_min", C.c_int32), ("s_min", C.c_int32), ("v_min", C.c_int32),
+                ("margin", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class CdColorBBox(C.Structure):
+    """cd_color_bbox: one frame's rectangle (x1, y1, x2, y2; all zero when found == 0) and what it was picked from."""
+    _fields_ = [("rect", C.c_int32 * 4), ("found", C.c_int32), ("area2", C.c_int32), ("n_components", C.c_int32),
+                ("n_mask", C.c_int32)]
+
+
 FRAME_RESULT_BYTES = C.sizeof(CdFrameResult)
+
+
+def default_color_gate_params():
+    """object_detection.py's constants: H 0..10 or 175..179, S >= 50, V >= 100, margin 10.  Pure Python mirror of
+    cd_default_color_gate_params()."""
+    g = CdColorGateParams()
+    g.h_lo_max, g.h_hi_min, g.s_min, g.v_min, g.margin = 10, 175, 50, 100, 10
+    return g
 
 
 def default_params():
@@ -225,6 +248,14 @@ def load_library(path=None):
     lib.cd_depth_to_cloud.argtypes = [vp, C.POINTER(CdDepthCamera), vp, vp, vp, C.c_size_t, C.c_int, C.c_int, ip]
     for f in (lib.cd_process_depth_batch, lib.cd_process_depth_batch_device):
         f.argtypes = [vp, C.POINTER(CdDepthCamera), vp, vp, C.c_int, C.POINTER(CdParams), vp, vp, vp]
+    lib.cd_default_color_gate_params.argtypes = [C.POINTER(CdColorGateParams)]
+    lib.cd_default_color_gate_params.restype = None
+    for f in (lib.cd_color_bbox_batch, lib.cd_color_bbox_batch_device):
+        f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(CdColorGateParams), C.POINTER(CdColorBBox)]
+    lib.cd_set_frame_bboxes.argtypes = [vp, i32p, C.c_int]
+    lib.cd_set_bbox_source.argtypes = [vp, C.c_int, C.POINTER(CdColorGateParams)]
+    lib.cd_get_bbox_source.argtypes = [vp, ip]
+    lib.cd_get_frame_bboxes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CdColorBBox)]
     if path is None:
         _lib = lib
     return lib
@@ -436,6 +467,50 @@ class Context:
             return
         g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
         self._check(self.lib.cd_set_frame_guesses(self.h, g.ctypes.data_as(C.POINTER(C.c_float)), g.shape[0]))
+
+    def color_bbox_batch(self, rgb, params=None):
+        """Rule C10 on rgb (F, H, W, 3) uint8 host images: an array of F CdColorBBox (cd_color_bbox_batch)."""
+        a = np.ascontiguousarray(rgb, dtype=np.uint8)
+        assert a.ndim == 4 and a.shape[3] == 3
+        F, H, W = a.shape[:3]
+        out = (CdColorBBox * max(F, 1))()
+        self._check(self.lib.cd_color_bbox_batch(self.h, _ptr(a), W, H, F, None if params is None else C.byref(params), out))
+        return out
+
+    def color_bbox_batch_device(self, rgb, params=None):
+        """Same on a contiguous torch uint8 tensor (F, H, W, 3) in HBM (the caller has synchronised the stream that wrote it)."""
+        assert rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3
+        F, H, W = (int(v) for v in rgb.shape[:3])
+        out = (CdColorBBox * max(F, 1))()
+        self._check(self.lib.cd_color_bbox_batch_device(self.h, C.c_void_p(rgb.data_ptr()), W, H, F,
+                                                        None if params is None else C.byref(params), out))
+        return out
+
+    def set_frame_bboxes(self, rects):
+        """Per-frame gate rectangles (F, 4) int32 (x1, y1, x2, y2) for the source CD_BBOX_PER_FRAME; None clears."""
+        if rects is None:
+            self._check(self.lib.cd_set_frame_bboxes(self.h, None, 0))
+            return
+        r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+        self._check(self.lib.cd_set_frame_bboxes(self.h, r.ctypes.data_as(C.POINTER(C.c_int32)), r.shape[0]))
+
+    def set_bbox_source(self, source, params=None):
+        """Where the fused calls' gate (prm.bbox_enable) takes its rectangle from: CD_BBOX_PARAMS / _PER_FRAME / _COLOR."""
+        self._check(self.lib.cd_set_bbox_source(self.h, source, None if params is None else C.byref(params)))
+
+    def bbox_source(self):
+        v = C.c_int()
+        self._check(self.lib.cd_get_bbox_source(self.h, C.byref(v)))
+        return v.value
+
+    def frame_bboxes(self, first=0, count=None):
+        """The rectangles the gate of the last fused call used (sources CD_BBOX_PER_FRAME / CD_BBOX_COLOR): a list of CdColorBBox."""
+        cap = self.max_frames if count is None else count
+        out = (CdColorBBox * max(cap, 1))()
+        n = self.lib.cd_get_frame_bboxes(self.h, first, cap, out)
+        if n < 0:
+            raise CuboidError(n, "cd_get_frame_bboxes: the last fused call's gate did not read per-frame rectangles")
+        return [out[i] for i in range(n)]
 
     def surface_batch(self, clouds, table_normals, prm, invert=True):
         """cd_surface_batch: cd_surface_frame over a batch of (ragged) clouds, fitted together on the device.

@@ -154,6 +154,24 @@ struct cd_context {
     std::vector<cd_surface_frame_result> last_surface;            // cd_get_surface_results
     std::vector<int32_t> last_surface_status;
     bool last_surface_ok = false;
+    // colour gate (rule C10, k_color.hip): the sdiv / hdiv tables, one record and one status per frame (device + pinned mirror),
+    // the union-find labels and (images whose packed mask does not fit LDS only) the mask buffers, both allocated on first use
+    int* d_ctab = nullptr;
+    ColorRecord *d_crec = nullptr, *h_crec = nullptr;
+    int *d_cstatus = nullptr, *h_cstatus = nullptr;
+    int* d_clabel = nullptr;
+    size_t clabel_cap = 0;
+    uint32_t* d_cmask = nullptr;
+    size_t cmask_cap = 0;
+    // where the fused calls' gate takes its rectangle from (cd_set_bbox_source), the rectangles cd_set_frame_bboxes stored and
+    // their device copy; call_rects: what the gate kernels of the fused call in flight read (nullptr outside one, and for CD_BBOX_PARAMS)
+    int bbox_source = CD_BBOX_PARAMS;
+    cd_color_gate_params color_prm;
+    std::vector<int32_t> frame_rects;
+    int32_t *d_rects = nullptr, *h_rects = nullptr;
+    FrameRects call_rects{nullptr, 0};
+    std::vector<cd_color_bbox> last_bboxes;                       // cd_get_frame_bboxes
+    bool last_bboxes_ok = false;
     IcpState *d_st = nullptr, *h_st = nullptr;
     unsigned long long *d_acc = nullptr, *d_accf = nullptr, *h_accf = nullptr;
     hipEvent_t ev[8] = {nullptr};
@@ -190,6 +208,7 @@ void invalidate_last(cd_context* c) {
     c->last_clouds = false;
     c->last_first.clear();
     c->last_surface_ok = false;
+    c->last_bboxes_ok = false;
 }
 
 int fail(cd_context* c, int code, const char* msg) {
@@ -668,14 +687,14 @@ int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode = -1) 
     const int* have_p = c->mirror_reads ? c->h_active : c->d_have;
     ZERO_FILL(c, c->d_tileA, sizeof(int) * (size_t)F * T);
     ZERO_FILL(c, c->d_tileB, sizeof(int) * (size_t)F * T);
-    LAUNCH(c, launch_plane_flag_count(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->d_tileA, c->d_tileB));
+    LAUNCH(c, launch_plane_flag_count(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->call_rects, c->d_tileA, c->d_tileB));
     {   // both scans in one launch; the two totals also go straight into the host's FrameState mirror (nothing else of it changes here)
         const bool mirrored = c->mirror_writes && c->copy_kernels;
         const ScanJob ja{c->d_tileA, FS_FIELD(c, n_plane), mirrored ? (int*)((char*)c->h_fs + offsetof(FrameState, n_plane)) : nullptr};
         const ScanJob jb{c->d_tileB, FS_FIELD(c, n_o), mirrored ? (int*)((char*)c->h_fs + offsetof(FrameState, n_o)) : nullptr};
         LAUNCH(c, launch_scan_tiles2(c->stream, ja, jb, F, T, FS_PITCH));
     }
-    LAUNCH(c, launch_extract_scatter(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->d_tileA, c->d_tileB, c->d_plane_idx, c->d_obj));
+    LAUNCH(c, launch_extract_scatter(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->call_rects, c->d_tileA, c->d_tileB, c->d_plane_idx, c->d_obj));
     return CD_OK;
 }
 
@@ -1498,9 +1517,66 @@ struct DepthJob {
     const uint8_t* color;   // nullptr: no colour
 };
 
+// ---- colour gate (rule C10, k_color.hip) ---------------------------------------------------------------------------------------
+static_assert(sizeof(ColorRecord) == sizeof(cd_color_bbox) && offsetof(ColorRecord, rect) == 0 && offsetof(cd_color_bbox, rect) == 0, "the kernel's record is cd_color_bbox");
+int check_color_params(cd_context* c, const cd_color_gate_params* g) {
+    if (g->h_lo_max < 0 || g->h_lo_max > 179 || g->h_hi_min < 0 || g->h_hi_min > 179) return fail(c, CD_ERR_INVALID_ARG, "colour gate: the H bounds must be in 0 .. 179");
+    if (g->s_min < 0 || g->s_min > 255 || g->v_min < 0 || g->v_min > 255) return fail(c, CD_ERR_INVALID_ARG, "colour gate: the S and V minima must be in 0 .. 255");
+    if (g->margin < 0) return fail(c, CD_ERR_INVALID_ARG, "colour gate: the margin must not be negative");
+    return CD_OK;
+}
+
+// the rectangles of F rgb8 images (device-resident, W x H each) into d_crec / d_cstatus, and on into their pinned mirrors
+// (valid after the next synchronisation of the context's stream)
+int stage_color(cd_context* c, const uint8_t* d_rgb, int W, int H, int F, const cd_color_gate_params* g) {
+    const size_t px = (size_t)W * H;
+    if (c->clabel_cap < px * F) {
+        if (c->d_clabel) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_clabel); c->d_clabel = nullptr; c->clabel_cap = 0; }
+        const size_t want = std::max(px * F, std::min((size_t)c->N * c->F, (size_t)640 * 480 * c->F));
+        HIPCHK(c, dalloc(&c->d_clabel, want));
+        c->clabel_cap = want;
+    }
+    uint32_t* gmask = nullptr;
+    if (!color_fits_lds(W, H)) {
+        const size_t want = 2 * (size_t)((W + 31) / 32) * H * F;
+        if (c->cmask_cap < want) {
+            if (c->d_cmask) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_cmask); c->d_cmask = nullptr; c->cmask_cap = 0; }
+            HIPCHK(c, dalloc(&c->d_cmask, want));
+            c->cmask_cap = want;
+        }
+        gmask = c->d_cmask;
+    }
+    const ColorGate cg{g->h_lo_max, g->h_hi_min, g->s_min, g->v_min, g->margin};
+    LAUNCH(c, launch_color_bbox(c->stream, d_rgb, W, H, F, cg, c->d_ctab, gmask, c->d_clabel, px, c->d_crec, c->d_cstatus));
+    HIPCHK(c, xfer(c, c->h_crec, c->d_crec, sizeof(ColorRecord) * (size_t)F, hipMemcpyDeviceToHost));
+    HIPCHK(c, xfer(c, c->h_cstatus, c->d_cstatus, sizeof(int) * (size_t)F, hipMemcpyDeviceToHost));
+    return CD_OK;
+}
+
+// after the synchronisation: a border walk that ran out of steps (cannot happen: the bound is every (pixel, direction) pair)
+int color_status(cd_context* c, int F) {
+    for (int f = 0; f < F; ++f)
+        if (c->h_cstatus[f] != CD_OK) return fail(c, CD_ERR_CAPACITY, "colour gate: a border walk exceeded its step bound");
+    return CD_OK;
+}
+
+// what a fused call's gate needs besides cd_params, checked before anything is copied or launched: `color` = the call is a
+// depth call with registered colour images
+int check_bbox_source(cd_context* c, const cd_params* p, int F, bool color) {
+    if (!p || !p->bbox_enable || c->bbox_source == CD_BBOX_PARAMS) return CD_OK;
+    if (c->bbox_source == CD_BBOX_PER_FRAME) {
+        if (F > 0 && c->frame_rects.size() < 4 * (size_t)F) return fail(c, CD_ERR_INVALID_ARG, "bbox source CD_BBOX_PER_FRAME but cd_set_frame_bboxes holds fewer rectangles than the batch has frames");
+        return CD_OK;
+    }
+    if (!color) return fail(c, CD_ERR_INVALID_ARG, "bbox source CD_BBOX_COLOR needs cd_process_depth_batch[_device] with CD_COLOR_RGB8 images");
+    return CD_OK;
+}
+
 int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N, int F, const cd_params* p,
                        cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, const DepthJob* dj = nullptr) {
     int st = check_params(c, p);
+    if (st) return st;
+    st = check_bbox_source(c, p, F, dj && dj->color);
     if (st) return st;
     if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
     if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
@@ -1510,7 +1586,21 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     BatchGuard in_flight(c->device);
     GateHold front;
     if (c->front_concurrent > 0) front.enter(&g_front_gate[c->device & (MAX_DEVICES - 1)], c->front_concurrent);
+    const int gate_source = p->bbox_enable ? c->bbox_source : CD_BBOX_PARAMS;
+    struct RectScope {   // the gate kernels read per-frame rectangles for the duration of this call only
+        cd_context* c;
+        ~RectScope() { c->call_rects = FrameRects{nullptr, 0}; }
+    } rect_scope{c};
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    if (gate_source == CD_BBOX_PER_FRAME) {
+        std::memcpy(c->h_rects, c->frame_rects.data(), sizeof(int32_t) * 4 * (size_t)F);
+        HIPCHK(c, xfer(c, c->d_rects, c->h_rects, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyHostToDevice));
+        c->call_rects = FrameRects{c->d_rects, 4};
+    } else if (gate_source == CD_BBOX_COLOR) {   // (stage [0] of the timing includes the colour stage); its records feed the gate on the device
+        st = stage_color(c, dj->color, dj->cam->width, dj->cam->height, F, &c->color_prm);
+        if (st) return st;
+        c->call_rects = FrameRects{reinterpret_cast<const int32_t*>(c->d_crec), (int32_t)(sizeof(ColorRecord) / sizeof(int32_t))};   // (rect is the record's first member)
+    }
     if (dj)   // (stage [0] of the timing includes the deprojection)
         LAUNCH(c, launch_deproject(c->stream, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, dj->cam->fx, dj->cam->fy, dj->cam->cx,
                                    dj->cam->cy, dj->cam->depth_scale, (float4*)const_cast<void*>(d_frames)));
@@ -1769,6 +1859,15 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     c->timing.icp_pair_tests_lo = (int32_t)(pairs & 0xffffffffll);
     c->timing.icp_pair_tests_hi = (int32_t)(pairs >> 32);
     c->timing.algorithmic_bytes = balg;
+    if (gate_source != CD_BBOX_PARAMS) {   // cd_get_frame_bboxes: the rectangles this call's gate used
+        c->last_bboxes.assign((size_t)F, cd_color_bbox{});
+        for (int f = 0; f < F; ++f) {
+            if (gate_source == CD_BBOX_COLOR) std::memcpy(&c->last_bboxes[(size_t)f], &c->h_crec[f], sizeof(cd_color_bbox));
+            else { std::memcpy(c->last_bboxes[(size_t)f].rect, c->frame_rects.data() + 4 * (size_t)f, sizeof(int32_t) * 4); c->last_bboxes[(size_t)f].found = 1; }
+        }
+        if (gate_source == CD_BBOX_COLOR) { st = color_status(c, F); if (st) return st; }
+        c->last_bboxes_ok = true;
+    }
     return CD_OK;
 }
 
@@ -1811,6 +1910,8 @@ int cd_struct_size(int which) {
         case 2: return (int)sizeof(cd_frame_result);
         case 3: return (int)sizeof(cd_timing);
         case 4: return (int)sizeof(cd_depth_camera);
+        case 5: return (int)sizeof(cd_color_gate_params);
+        case 6: return (int)sizeof(cd_color_bbox);
         default: return -1;
     }
 }
@@ -1834,6 +1935,12 @@ void cd_destroy(cd_context* c) {
     if (c->d_tileC) hipFree(c->d_tileC);
     if (c->d_depth) hipFree(c->d_depth);
     if (c->d_color) hipFree(c->d_color);
+    {
+        void* cdev[] = {c->d_ctab, c->d_crec, c->d_cstatus, c->d_clabel, c->d_cmask, c->d_rects};
+        for (void* p : cdev) if (p) hipFree(p);
+        void* chost[] = {c->h_crec, c->h_cstatus, c->h_rects};
+        for (void* p : chost) if (p) hipHostFree(p);
+    }
     {
         void* sdev[] = {c->d_sfs, c->d_smodel, c->d_shave, c->d_sactive, c->d_spts[0], c->d_spts[1], c->d_sidx, c->d_ssum};
         for (void* p : sdev) if (p) hipFree(p);
@@ -1942,6 +2049,18 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     ok = ok && dalloc(&c->d_work2, (size_t)c->work_cap) == hipSuccess && halloc(&c->h_work2, (size_t)c->work_cap) == hipSuccess;
     ok = ok && dalloc(&c->d_st, ncl * 2) == hipSuccess && halloc(&c->h_st, ncl * 2) == hipSuccess;
     ok = ok && dalloc(&c->d_acc, ncl * 48) == hipSuccess && dalloc(&c->d_accf, ncl + 1) == hipSuccess && halloc(&c->h_accf, ncl + 1) == hipSuccess;
+    ok = ok && dalloc(&c->d_ctab, (size_t)512) == hipSuccess && dalloc(&c->d_crec, F) == hipSuccess && halloc(&c->h_crec, F) == hipSuccess;
+    ok = ok && dalloc(&c->d_cstatus, F) == hipSuccess && halloc(&c->h_cstatus, F) == hipSuccess;
+    ok = ok && dalloc(&c->d_rects, F * 4) == hipSuccess && halloc(&c->h_rects, F * 4) == hipSuccess;
+    cd_default_color_gate_params(&c->color_prm);
+    if (ok) {   // rule C10 step 1: sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)), in double, half to even
+        std::vector<int> tab(512, 0);
+        for (int i = 1; i < 256; ++i) {
+            tab[(size_t)i] = (int)std::nearbyint((double)(255 << 12) / (double)i);
+            tab[256 + (size_t)i] = (int)std::nearbyint((double)(180 << 12) / (6.0 * (double)i));
+        }
+        ok = copy_sync(c, c->d_ctab, tab.data(), sizeof(int) * 512, hipMemcpyHostToDevice) == hipSuccess;
+    }
     if (ok) {
         // PCL's SAC sampler: boost::mt19937 seeded 12345, uniform_int<>(0, INT_MAX) == mt() >> 1
         std::vector<int> tab((size_t)RND_TABLE);
@@ -2758,7 +2877,9 @@ static int cd_process_batch_impl(cd_context* c, const void* frames, size_t strid
     hipSetDevice(c->device);
     if (!frames || points_per_frame <= 0 || n_frames <= 0) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
     const size_t bytes = (size_t)points_per_frame * n_frames * stride;
-    int st = ensure_input(c, bytes);
+    int st = check_bbox_source(c, p, n_frames, false);   // (before the upload)
+    if (st) return st;
+    st = ensure_input(c, bytes);
     if (st) return st;
     HIPCHK(c, hipMemcpyAsync(c->d_in, frames, bytes, hipMemcpyHostToDevice, c->stream));
     return process_batch_impl(c, c->d_in, stride, points_per_frame, n_frames, p, results, plane_inliers, labels);
@@ -2840,6 +2961,8 @@ static int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam
     if (!results) return fail(c, CD_ERR_INVALID_ARG, "results is NULL");
     st = check_depth(c, cam, depth, color, n_frames);
     if (st) return st;
+    st = check_bbox_source(c, p, n_frames, cam->color == CD_COLOR_RGB8);   // (before the uploads)
+    if (st) return st;
     cd_params q = *p;
     q.rgb_offset = cam->color == CD_COLOR_RGB8 ? 12 : -1;   // the canonical records: x y z rgb, 16 bytes
     const int P = cam->width * cam->height;
@@ -2879,6 +3002,34 @@ static int cd_depth_to_cloud_impl(cd_context* c, const cd_depth_camera* cam, con
     if (st) return st;
     *out_n = P;
     return CD_OK;
+}
+
+// ---- colour gate as a call of its own (rule C10) ------------------------------------------------------------------------------
+static int cd_color_bbox_batch_impl(cd_context* c, const uint8_t* rgb8, int width, int height, int n_frames, const cd_color_gate_params* g,
+                                    cd_color_bbox* out, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    if (!rgb8 || !out) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (width <= 0 || height <= 0 || (long long)width * height > (long long)c->N)
+        return fail(c, CD_ERR_INVALID_ARG, "width * height must be in 1 .. the context's max_points");
+    if (n_frames <= 0 || n_frames > c->F) return fail(c, CD_ERR_INVALID_ARG, "n_frames must be in 1 .. the context's max_frames");
+    cd_color_gate_params def;
+    cd_default_color_gate_params(&def);
+    if (!g) g = &def;
+    int st = check_color_params(c, g);
+    if (st) return st;
+    invalidate_last(c);
+    const uint8_t* d_rgb = rgb8;
+    if (!on_device) {
+        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        HIPCHK(c, hipMemcpyAsync(c->d_color, rgb8, (size_t)width * height * n_frames * 3, hipMemcpyHostToDevice, c->stream));
+        d_rgb = c->d_color;
+    }
+    st = stage_color(c, d_rgb, width, height, n_frames, g);
+    if (st) return st;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_crec, sizeof(cd_color_bbox) * (size_t)n_frames);
+    return color_status(c, n_frames);
 }
 
 void cd_default_depth_camera(cd_depth_camera* cam) {
@@ -3076,6 +3227,57 @@ int cd_surface_guess(const float Rt[16], float guess[16]) {
     for (int i = 0; i < 16; ++i) if (!std::isfinite(g[i])) return CD_ERR_INVALID_ARG;
     std::memcpy(guess, g, sizeof(g));
     return CD_OK;
+}
+
+void cd_default_color_gate_params(cd_color_gate_params* g) {
+    if (!g) return;
+    std::memset(g, 0, sizeof(*g));
+    g->h_lo_max = 10; g->h_hi_min = 175;   // object_detection.py:34-41: H 0..10 and 175..180
+    g->s_min = 50; g->v_min = 100;         // S 50..255, V 100..255
+    g->margin = 10;                        // :62
+}
+
+int cd_set_frame_bboxes(cd_context* c, const int32_t* rects, int n_frames) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    if (n_frames < 0 || (n_frames > 0 && !rects)) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    c->frame_rects.assign(rects, rects + 4 * (size_t)n_frames);
+    return CD_OK;
+}
+
+int cd_set_bbox_source(cd_context* c, int source, const cd_color_gate_params* g) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    if (source != CD_BBOX_PARAMS && source != CD_BBOX_PER_FRAME && source != CD_BBOX_COLOR) return fail(c, CD_ERR_INVALID_ARG, "unknown bbox source");
+    cd_color_gate_params def;
+    cd_default_color_gate_params(&def);
+    if (!g) g = &def;
+    if (int st = check_color_params(c, g)) return st;   // (the setting stays as it was)
+    c->bbox_source = source;
+    c->color_prm = *g;
+    return CD_OK;
+}
+
+int cd_get_bbox_source(const cd_context* c, int* source) {
+    if (!c || !source) return CD_ERR_INVALID_ARG;
+    *source = c->bbox_source;
+    return CD_OK;
+}
+
+int cd_get_frame_bboxes(const cd_context* c, int first, int capacity, cd_color_bbox* out) {
+    if (!c || first < 0 || capacity < 0 || (capacity > 0 && !out)) return CD_ERR_INVALID_ARG;
+    if (!c->last_bboxes_ok) return CD_ERR_INVALID_ARG;   // (the last fused call's gate took its rectangle from cd_params, or another compute call has run since)
+    int n = 0;
+    for (size_t f = (size_t)first; f < c->last_bboxes.size() && n < capacity; ++f, ++n) out[n] = c->last_bboxes[f];
+    return n;
+}
+
+int cd_color_bbox_batch(cd_context* c, const uint8_t* rgb8, int width, int height, int n_frames, const cd_color_gate_params* g, cd_color_bbox* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_color_bbox_batch_impl(c, rgb8, width, height, n_frames, g, out, false); });
+}
+
+int cd_color_bbox_batch_device(cd_context* c, const uint8_t* d_rgb8, int width, int height, int n_frames, const cd_color_gate_params* g, cd_color_bbox* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_color_bbox_batch_impl(c, d_rgb8, width, height, n_frames, g, out, true); });
 }
 
 int cd_set_frame_guesses(cd_context* c, const float* guesses, int n_frames) {

@@ -184,6 +184,13 @@ __device__ __forceinline__ bool within_bbox(const BBoxGate& g, float x, float y,
     return (g.rect[0] < u && u < g.rect[2]) && (g.rect[1] < v && v < g.rect[3]);
 }
 
+// the rectangle of frame f when the gate's rectangles come per frame (CD_BBOX_PER_FRAME / CD_BBOX_COLOR)
+__device__ __forceinline__ void frame_rect(BBoxGate& g, const FrameRects& fr, int f) {
+    if (!fr.rect) return;
+    const int32_t* r = fr.rect + (size_t)f * fr.pitch;
+    for (int i = 0; i < 4; ++i) g.rect[i] = (float)r[i];
+}
+
 __device__ __forceinline__ void extract_flags(const float4& m, int have, float thr, int negative, int crop2, float z2lo,
                                               float z2hi, const BBoxGate& g, const float4& p, bool& inl, bool& obj) {
     if (g.enable == 2) {   // cd_bbox_filter: the index output is the set of points inside the rectangle
@@ -201,12 +208,13 @@ __global__ void __launch_bounds__(BLOCK) k_plane_flag_count(const float4* __rest
                                                             const FrameState* __restrict__ fs,
                                                             const float4* __restrict__ model, const int* __restrict__ have,
                                                             float thr, int negative, int crop2, float z2lo, float z2hi, BBoxGate gate,
-                                                            int* __restrict__ cnt_plane, int* __restrict__ cnt_obj) {
+                                                            FrameRects rects, int* __restrict__ cnt_plane, int* __restrict__ cnt_obj) {
     CD_FRONT_PRIO();
     __shared__ int s_a[WAVES_PER_BLOCK], s_b[WAVES_PER_BLOCK];
     const int f = blockIdx.y, tile = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = fs[f].n_v;
     if (tile * TILE >= n) return;
+    frame_rect(gate, rects, f);
     const float4 m = model[f];
     const int hv = have[f];
     const float4* P = vox + (size_t)f * N;
@@ -234,13 +242,14 @@ __global__ void __launch_bounds__(BLOCK) k_extract_scatter(const float4* __restr
                                                            const FrameState* __restrict__ fs,
                                                            const float4* __restrict__ model, const int* __restrict__ have,
                                                            float thr, int negative, int crop2, float z2lo, float z2hi, BBoxGate gate,
-                                                           const int* __restrict__ off_plane, const int* __restrict__ off_obj,
+                                                           FrameRects rects, const int* __restrict__ off_plane, const int* __restrict__ off_obj,
                                                            int* __restrict__ plane_idx, float4* __restrict__ obj_out) {
     CD_FRONT_PRIO();
     __shared__ int s_a[WAVES_PER_BLOCK], s_b[WAVES_PER_BLOCK];
     const int f = blockIdx.y, tile = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = fs[f].n_v;
     if (tile * TILE >= n) return;
+    frame_rect(gate, rects, f);
     const size_t fbase = (size_t)f * N;
     const float4 m = model[f];
     const int hv = have[f];
@@ -289,15 +298,16 @@ void launch_plane_cov(hipStream_t s, const float4* vox, int N, int F, int Tact, 
 }
 void launch_plane_flag_count(hipStream_t s, const float4* vox, int N, int F, int T, int Tact, const FrameState* fs,
                              const float4* model, const int* have, float thr, int negative, int crop2, float z2lo,
-                             float z2hi, const BBoxGate& gate, int* cnt_plane, int* cnt_obj) {
+                             float z2hi, const BBoxGate& gate, const FrameRects& rects, int* cnt_plane, int* cnt_obj) {
     hipLaunchKernelGGL(k_plane_flag_count, dim3(Tact, F), dim3(BLOCK), 0, s, vox, N, T, fs, model, have, thr, negative,
-                       crop2, z2lo, z2hi, gate, cnt_plane, cnt_obj);
+                       crop2, z2lo, z2hi, gate, rects, cnt_plane, cnt_obj);
 }
 void launch_extract_scatter(hipStream_t s, const float4* vox, int N, int F, int T, int Tact, const FrameState* fs,
                             const float4* model, const int* have, float thr, int negative, int crop2, float z2lo,
-                            float z2hi, const BBoxGate& gate, const int* off_plane, const int* off_obj, int* plane_idx, float4* obj) {
+                            float z2hi, const BBoxGate& gate, const FrameRects& rects, const int* off_plane, const int* off_obj, int* plane_idx,
+                            float4* obj) {
     hipLaunchKernelGGL(k_extract_scatter, dim3(Tact, F), dim3(BLOCK), 0, s, vox, N, T, fs, model, have, thr, negative,
-                       crop2, z2lo, z2hi, gate, off_plane, off_obj, plane_idx, obj);
+                       crop2, z2lo, z2hi, gate, rects, off_plane, off_obj, plane_idx, obj);
 }
 
 // ---- S3 as a call of its own: pcl::ExtractIndices<PCLPointCloud2> on whole records --------------------------------------

@@ -48,6 +48,7 @@ int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* cons
                            FrameState* fs, uint32_t* ghist, int* state, int* tile_state, KeyPack kp, int* ticket);
 
 // k_plane.hip
+struct FrameRects { const int32_t* rect; int32_t pitch; };   // the gate's rectangle of frame f = rect[f * pitch + 0..3]; rect == nullptr: BBoxGate::rect
 void launch_ransac_sample(hipStream_t s, const float4* vox, int N, int F, FrameState* fs, const int* rnd_table,
                           int h_target, const int* active, float4* models, int* valid);
 void launch_ransac_count(hipStream_t s, const float4* vox, int N, int F, int Tact, const FrameState* fs,
@@ -56,10 +57,11 @@ void launch_plane_cov(hipStream_t s, const float4* vox, int N, int F, int Tact, 
                       const int* have, float thr, unsigned long long* sums);
 void launch_plane_flag_count(hipStream_t s, const float4* vox, int N, int F, int T, int Tact, const FrameState* fs,
                              const float4* model, const int* have, float thr, int negative, int crop2, float z2lo,
-                             float z2hi, const BBoxGate& gate, int* cnt_plane, int* cnt_obj);
+                             float z2hi, const BBoxGate& gate, const FrameRects& rects, int* cnt_plane, int* cnt_obj);
 void launch_extract_scatter(hipStream_t s, const float4* vox, int N, int F, int T, int Tact, const FrameState* fs,
                             const float4* model, const int* have, float thr, int negative, int crop2, float z2lo,
-                            float z2hi, const BBoxGate& gate, const int* off_plane, const int* off_obj, int* plane_idx, float4* obj);
+                            float z2hi, const BBoxGate& gate, const FrameRects& rects, const int* off_plane, const int* off_obj, int* plane_idx,
+                            float4* obj);
 
 // k_cluster.hip
 void launch_cluster_lds(hipStream_t s, const float4* obj, int N, int F, FrameState* fs, float inv_cell, float r2,
@@ -127,5 +129,17 @@ void launch_surface_load(hipStream_t s, const void* in, size_t stride, size_t fp
                          int max_count, int F, float4* out);
 void launch_surface_centroid(hipStream_t s, const float4* pts, int pitch, int F, const FrameState* fs, const float4* model,
                              const int* have, float thr, int invert, float4* out, int out_pitch);
+
+
+// k_color.hip : rule C10, one workgroup per rgb8 image -> one ColorRecord (= cd_color_bbox) per frame
+constexpr int COLOR_BLOCK = 1024;
+constexpr int COLOR_LDS_WORDS = 30720;   // both halves of a frame's packed mask, 120 KiB
+struct ColorGate { int32_t h_lo_max, h_hi_min, s_min, v_min, margin; };
+struct ColorRecord { int32_t rect[4], found, area2, n_components, n_mask; };
+bool color_fits_lds(int W, int H);
+// tables: sdiv[256] then hdiv[256]; gmask: nullptr (the mask fits LDS) or 2 * ceil(W / 32) * H words per frame; labels:
+// label_pitch >= W * H ints per frame; status: CD_OK / CD_ERR_CAPACITY per frame
+void launch_color_bbox(hipStream_t s, const uint8_t* rgb, int W, int H, int F, const ColorGate& prm, const int* tables,
+                       uint32_t* gmask, int* labels, size_t label_pitch, ColorRecord* out, int* status);
 
 }  // namespace cd
