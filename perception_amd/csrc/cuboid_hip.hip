@@ -39,7 +39,7 @@ struct cd_context {
     FrameState* h_fs = nullptr;
     // ordered-compaction tile counters
     int *d_tileA = nullptr, *d_tileB = nullptr, *d_tileK = nullptr, *d_tileC = nullptr;   // (tileC: the centroid kernel's scan state - its own array, so that one launch can zero every array of a batch up front)
-    bool batch_zeroed = false;      // a fused batch call has zeroed the scratch arrays of all its stages in one launch (zero_batch_arrays): the stages skip their own fills
+    bool batch_zeroed = false;      // a fused batch call has zeroed the scratch arrays of all its stages in one launch (zero_batch_scratch): the stages skip their own fills
     bool crop_two_pass = false;   // CUBOID_CROP_TWO_PASS=1: always the two-pass crop
     int icp_persist = 1;          // CUBOID_ICP_PERSIST=0: the sliced driver always in its multi-launch form; 2: the persistent
                                   // launch starts with its abort flag raised (tests the hand-over to the multi-launch form)
@@ -1572,246 +1572,268 @@ int check_bbox_source(cd_context* c, const cd_params* p, int F, bool color) {
     return CD_OK;
 }
 
-int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N, int F, const cd_params* p,
-                       cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, const DepthJob* dj = nullptr) {
-    int st = check_params(c, p);
-    if (st) return st;
-    st = check_bbox_source(c, p, F, dj && dj->color);
-    if (st) return st;
-    if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
-    if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
-    if (N > c->N || F > c->F) return fail(c, CD_ERR_CAPACITY, "batch larger than the context capacity");
-    invalidate_last(c);
-    std::memset(&c->timing, 0, sizeof(c->timing));
-    BatchGuard in_flight(c->device);
-    GateHold front;
-    if (c->front_concurrent > 0) front.enter(&g_front_gate[c->device & (MAX_DEVICES - 1)], c->front_concurrent);
-    const int gate_source = p->bbox_enable ? c->bbox_source : CD_BBOX_PARAMS;
-    struct RectScope {   // the gate kernels read per-frame rectangles for the duration of this call only
-        cd_context* c;
-        ~RectScope() { c->call_rects = FrameRects{nullptr, 0}; }
-    } rect_scope{c};
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+// ---- the fused batch call ---------------------------------------------------------------------------------------
+// process_batch_impl, at the end of this section, is the sequence; the functions before it are its steps in the order it calls
+// them.  Each says what it issues on the context's stream and which synchronisation it relies on.
+
+// What a fused call sets on the context for its own duration only, put back on every way out: the rectangles its gate kernels
+// read (call_rects) and the two marks of the zero launch that make the stages skip their own fills (batch_zeroed, fs_initialised).
+struct BatchScope {
+    cd_context* c;
+    ~BatchScope() { c->call_rects = FrameRects{nullptr, 0}; c->batch_zeroed = false; c->fs_initialised = false; }
+};
+
+// Every scratch array the stages want zeroed, in ONE launch (a batch had ~14 fill kernels, each a stream operation of its own
+// that queues behind the other contexts' kernels).  A scratch array that a stage expects zeroed is added to THIS list.
+// Issues that launch and sets batch_zeroed / fs_initialised (BatchScope puts them back); relies on no synchronisation.
+int zero_batch_scratch(cd_context* c, int F) {
+    ZeroRegions zr;
+    zr.n = 0;
+    zr.fs = c->mirror_writes && c->copy_kernels ? c->d_fs : nullptr;   // (the crop stage then skips its upload of the initial FrameStates)
+    zr.nfs = F;
+    c->fs_initialised = zr.fs != nullptr;
+    auto add = [&](void* ptr, size_t bytes) { zr.ptr[zr.n] = (uint32_t*)ptr; zr.words[zr.n] = bytes / 4; ++zr.n; };
+    const size_t FT = (size_t)F * c->T;
+    add(c->d_ticket, sizeof(int) * (size_t)F * TICKET_PITCH);
+    add(c->d_tileA, sizeof(int) * FT);
+    add(c->d_tileB, sizeof(int) * FT);
+    add(c->d_tileC, sizeof(int) * FT);
+    add(c->d_tile64, sizeof(unsigned long long) * FT);
+    add(c->d_ghist, sizeof(uint32_t) * (size_t)F * SORT_MAX_PASSES_HOST * RADIX);
+    add(c->d_counts, sizeof(int) * (size_t)F * MAX_HYP);
+    add(c->d_sums, sizeof(unsigned long long) * 10 * (size_t)F);
+    add(c->d_tileK, sizeof(int) * FT * KICP);
+    add(c->d_acc, sizeof(unsigned long long) * 48 * (size_t)c->cl_cap);
+    add(c->d_accf, sizeof(unsigned long long) * ((size_t)c->cl_cap + 1));
+    add(c->d_queue, sizeof(int) * 16);
+    LAUNCH(c, launch_zero_regions(c->stream, zr));
+    c->batch_zeroed = true;
+    return CD_OK;
+}
+
+// The call's stream work ahead of the crop stage, all of it after ev[0] and so inside stage [0] of the timing: the gate's
+// per-frame rectangles (an upload for CD_BBOX_PER_FRAME, the colour stage for CD_BBOX_COLOR, whose records feed the gate on
+// the device; call_rects then points at them), the deprojection of a depth call into d_frames, and the zero launch.
+// Relies on no synchronisation and makes none.
+int batch_prologue(cd_context* c, int gate_source, const void* d_frames, int F, const DepthJob* dj) {
     if (gate_source == CD_BBOX_PER_FRAME) {
         std::memcpy(c->h_rects, c->frame_rects.data(), sizeof(int32_t) * 4 * (size_t)F);
         HIPCHK(c, xfer(c, c->d_rects, c->h_rects, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyHostToDevice));
         c->call_rects = FrameRects{c->d_rects, 4};
-    } else if (gate_source == CD_BBOX_COLOR) {   // (stage [0] of the timing includes the colour stage); its records feed the gate on the device
-        st = stage_color(c, dj->color, dj->cam->width, dj->cam->height, F, &c->color_prm);
+    } else if (gate_source == CD_BBOX_COLOR) {
+        int st = stage_color(c, dj->color, dj->cam->width, dj->cam->height, F, &c->color_prm);
         if (st) return st;
         c->call_rects = FrameRects{reinterpret_cast<const int32_t*>(c->d_crec), (int32_t)(sizeof(ColorRecord) / sizeof(int32_t))};   // (rect is the record's first member)
     }
-    if (dj)   // (stage [0] of the timing includes the deprojection)
+    if (dj)
         LAUNCH(c, launch_deproject(c->stream, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, dj->cam->fx, dj->cam->fy, dj->cam->cx,
                                    dj->cam->cy, dj->cam->depth_scale, (float4*)const_cast<void*>(d_frames)));
-    struct ZeroedScope {   // the stages skip their own fills for the duration of this call only
-        cd_context* c;
-        ~ZeroedScope() { c->batch_zeroed = false; c->fs_initialised = false; }
-    } zeroed_scope{c};
-    if (c->zero_once) {
-        // every scratch array the stages want zeroed, in ONE launch (a batch had ~14 fill kernels, each a stream operation of its
-        // own that queues behind the other contexts' kernels)
-        ZeroRegions zr;
-        zr.n = 0;
-        zr.fs = c->mirror_writes && c->copy_kernels ? c->d_fs : nullptr;   // (the crop stage then skips its upload of the initial FrameStates)
-        zr.nfs = F;
-        c->fs_initialised = zr.fs != nullptr;
-        auto add = [&](void* ptr, size_t bytes) { zr.ptr[zr.n] = (uint32_t*)ptr; zr.words[zr.n] = bytes / 4; ++zr.n; };
-        const size_t FT = (size_t)F * c->T;
-        add(c->d_ticket, sizeof(int) * (size_t)F * TICKET_PITCH);
-        add(c->d_tileA, sizeof(int) * FT);
-        add(c->d_tileB, sizeof(int) * FT);
-        add(c->d_tileC, sizeof(int) * FT);
-        add(c->d_tile64, sizeof(unsigned long long) * FT);
-        add(c->d_ghist, sizeof(uint32_t) * (size_t)F * SORT_MAX_PASSES_HOST * RADIX);
-        add(c->d_counts, sizeof(int) * (size_t)F * MAX_HYP);
-        add(c->d_sums, sizeof(unsigned long long) * 10 * (size_t)F);
-        add(c->d_tileK, sizeof(int) * FT * KICP);
-        add(c->d_acc, sizeof(unsigned long long) * 48 * (size_t)c->cl_cap);
-        add(c->d_accf, sizeof(unsigned long long) * ((size_t)c->cl_cap + 1));
-        add(c->d_queue, sizeof(int) * 16);
-        LAUNCH(c, launch_zero_regions(c->stream, zr));
-        c->batch_zeroed = true;
-    }
-    int rounds = 0;
-    st = stage_crop_voxel(c, d_frames, stride, N, F, p, nullptr);
-    if (st) return st;
-    st = sync_fs(c, F);   // n_v
-    if (st) return st;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    std::vector<int> iterations;
-    st = stage_plane(c, F, p, iterations, &rounds);
-    if (st) return st;
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    st = stage_extract(c, F, p);
-    if (st) return st;
-    st = sync_fs(c, F, c->mirror_writes && c->copy_kernels);   // n_o per frame (written to the mirror by the scan): picks the clustering path and sizes the launches
-    if (st) return st;
-    int max_no = 0;
-    for (int f = 0; f < F; ++f) max_no = std::max(max_no, c->h_fs[f].n_o);
-    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff
-    if (st) return st;
-    std::vector<char> surface_flag;   // CD_GUESS_SURFACE: the frames whose guess came from their surface fit
-    if (p->icp_use_guess == CD_GUESS_SURFACE) {
-        st = surface_guesses(c, F, p, &surface_flag);
-        if (st) return st;
-    }
-    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    front.release();
-    // Every cluster of every frame gets its ICP (opd.cpp:376-413).  The device extracts the ICP sources KICP clusters per
-    // frame at a time; frames with more than KICP clusters (rare) need further rounds, and the host needs their sizes.
-    int kmax = 0, ncl = 0;
-    long long cl_points = 0;
-    std::vector<int> first_cl((size_t)F + 1, 0);
+    return c->zero_once ? zero_batch_scratch(c, F) : CD_OK;
+}
+
+struct FrontStages {   // what the front stages leave for the frame records
+    std::vector<int> iterations;     // RANSAC iterations of every frame (stage_plane)
+    int rounds = 0;                  // hypothesis rounds of the plane stage
+    std::vector<char> surface_flag;  // CD_GUESS_SURFACE: the frames whose guess came from their surface fit (empty otherwise)
+};
+
+struct BatchClusters {   // the host's table of a batch's clusters, frame-major (batch_clusters)
+    std::vector<int> first;       // index of frame f's first cluster (F + 1 entries)
+    std::vector<int> size, off;   // per cluster: its points; where its ICP source starts in the frame's segment of d_src0 / d_src
+    std::vector<int> span;        // per frame: the points of all its clusters, i.e. of one copy of its ICP sources
+    int ncl = 0, kmax = 0;        // clusters of the batch; of its fullest frame
+    int rounds_k = 1;             // extraction rounds: ceil(kmax / KICP)
+    long long points = 0;         // points of all clusters
+    int To = 1;                   // tiles of the frame with the most object points (grid of the label kernels)
+};
+
+// Every cluster of every frame gets its ICP (opd.cpp:376-413).  The device extracts the ICP sources KICP clusters per frame at a
+// time; frames with more than KICP clusters (rare) need further rounds, and the host needs their sizes.
+// Fills the table from h_fs as stage_cluster_sync's synchronisation left it.  For each frame beyond KICP it issues one D2H copy
+// of the sizes from d_sizes straight into cl->size and then synchronises the stream: cl->size is sized before the first copy and
+// neither resized nor read until that synchronisation.  Ends with ensure_clusters for one ICP problem per cluster.
+int batch_clusters(cd_context* c, int F, BatchClusters* cl) {
+    cl->first.assign((size_t)F + 1, 0);
+    int max_no = 0;   // (read again after the cluster stage's own synchronisation, not handed down from before it)
     for (int f = 0; f < F; ++f) {
-        first_cl[(size_t)f] = ncl;
-        ncl += c->h_fs[f].n_k;
-        kmax = std::max(kmax, c->h_fs[f].n_k);
+        cl->first[(size_t)f] = cl->ncl;
+        cl->ncl += c->h_fs[f].n_k;
+        cl->kmax = std::max(cl->kmax, c->h_fs[f].n_k);
+        max_no = std::max(max_no, c->h_fs[f].n_o);
     }
-    first_cl[(size_t)F] = ncl;
-    std::vector<int> csize((size_t)std::max(ncl, 1)), coff((size_t)std::max(ncl, 1));   // size / source offset of every cluster
+    cl->first[(size_t)F] = cl->ncl;
+    cl->To = std::max(1, (max_no + TILE - 1) / TILE);
+    cl->rounds_k = std::max(1, (cl->kmax + KICP - 1) / KICP);
+    cl->size.assign((size_t)std::max(cl->ncl, 1), 0);
+    cl->off.assign((size_t)std::max(cl->ncl, 1), 0);
     for (int f = 0; f < F; ++f) {
         const FrameState& s = c->h_fs[f];
-        int* sz = csize.data() + first_cl[(size_t)f];
+        int* sz = cl->size.data() + cl->first[(size_t)f];
         if (s.n_k > KICP) HIPCHK(c, hipMemcpyAsync(sz, c->d_sizes + (size_t)f * c->N, sizeof(int) * (size_t)s.n_k, hipMemcpyDeviceToHost, c->stream));
         else for (int k = 0; k < s.n_k; ++k) sz[k] = s.ksize[k];
     }
-    const int rounds_k = std::max(1, (kmax + KICP - 1) / KICP);
-    if (rounds_k > 1) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (cl->rounds_k > 1) HIPCHK(c, hipStreamSynchronize(c->stream));
+    cl->span.assign((size_t)F, 0);
     for (int f = 0; f < F; ++f) {
         int off = 0;
-        for (int k = first_cl[(size_t)f]; k < first_cl[(size_t)f + 1]; ++k) { coff[(size_t)k] = off; off += csize[(size_t)k]; cl_points += csize[(size_t)k]; }
+        for (int k = cl->first[(size_t)f]; k < cl->first[(size_t)f + 1]; ++k) { cl->off[(size_t)k] = off; off += cl->size[(size_t)k]; }
+        cl->span[(size_t)f] = off;
+        cl->points += off;
     }
-    st = ensure_clusters(c, ncl, cl_points);
+    return ensure_clusters(c, cl->ncl, cl->points);
+}
+
+// d_koffx: the offsets the label scatter writes the ICP sources to, [copy][round][F][KICP].  Cluster q of frame f starts, in
+// copy t, at off[q] + t * span[f] of the frame's segment.  copies == 1 is the table of the per-template passes; they pass
+// nullptr (packed) for round 0, so its round-0 words are never read.
+// Grows d_koffx (which synchronises the stream when it has to) and uploads the table with a blocking copy.
+int upload_koffx(cd_context* c, int F, const BatchClusters& cl, int copies) {
+    const size_t need = (size_t)copies * cl.rounds_k * F * KICP;
+    int st = grow_device(c, &c->d_koffx, &c->koffx_cap, need);
     if (st) return st;
-    int max_no2 = 0;
-    for (int f = 0; f < F; ++f) max_no2 = std::max(max_no2, c->h_fs[f].n_o);
-    const int To2 = std::max(1, (max_no2 + TILE - 1) / TILE);
-    if (rounds_k > 1) {   // offsets of the later rounds' clusters, [round][F][KICP]
-        const size_t need = (size_t)rounds_k * F * KICP;
-        st = grow_device(c, &c->d_koffx, &c->koffx_cap, need);
-        if (st) return st;
-        std::vector<int> tab(need, 0);
-        for (int r = 1; r < rounds_k; ++r)
+    std::vector<int> tab(need, 0);
+    for (int t = 0; t < copies; ++t)
+        for (int r = 0; r < cl.rounds_k; ++r)
             for (int f = 0; f < F; ++f)
                 for (int k = 0; k < KICP; ++k) {
-                    const int q = first_cl[(size_t)f] + r * KICP + k;
-                    if (q < first_cl[(size_t)f + 1]) tab[((size_t)r * F + f) * KICP + k] = coff[(size_t)q];
+                    const int q = cl.first[(size_t)f] + r * KICP + k;
+                    if (q < cl.first[(size_t)f + 1]) tab[(((size_t)t * cl.rounds_k + r) * F + f) * KICP + k] = cl.off[(size_t)q] + t * cl.span[(size_t)f];
                 }
-        HIPCHK(c, copy_sync(c, c->d_koffx, tab.data(), sizeof(int) * need, hipMemcpyHostToDevice));
+    HIPCHK(c, copy_sync(c, c->d_koffx, tab.data(), sizeof(int) * need, hipMemcpyHostToDevice));
+    return CD_OK;
+}
+const int* koffx_at(const cd_context* c, int F, const BatchClusters& cl, int t, int r) { return c->d_koffx + (((size_t)t * cl.rounds_k + r) * F) * KICP; }
+
+// Extraction round r of the ICP sources: the clusters ranked [r * KICP, (r + 1) * KICP) of every frame, to the offsets koff
+// ([F][KICP]; nullptr: packed, round 0 only).  With a single round the tile counts of stage_cluster are still in d_tileK.
+// Issues the label scatter, behind a memset, a count and a scan of d_tileK when there are several rounds; no synchronisation.
+int extract_round(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, int r, const int* koff) {
+    if (cl.rounds_k > 1) {
+        HIPCHK(c, hipMemsetAsync(c->d_tileK, 0, sizeof(int) * (size_t)F * KICP * c->T, c->stream));
+        LAUNCH(c, launch_label_count(c->stream, c->N, F, c->T, cl.To, c->d_fs, p->cluster_enable, c->d_parent, c->d_rank, c->d_label, c->d_tileK, r * KICP));
+        LAUNCH(c, launch_scan_tiles(c->stream, c->d_tileK, F * KICP, c->T, nullptr, 0));
     }
-    // extraction round r of the ICP sources: the clusters ranked [r * KICP, (r + 1) * KICP) of every frame, to the offsets
-    // koff ([F][KICP]; nullptr: packed, round 0 only).  With a single round the tile counts of stage_cluster are still in d_tileK.
-    auto extract_round = [&](int r, const int* koff) -> int {
-        if (rounds_k > 1) {
-            HIPCHK(c, hipMemsetAsync(c->d_tileK, 0, sizeof(int) * (size_t)F * KICP * c->T, c->stream));
-            LAUNCH(c, launch_label_count(c->stream, c->N, F, c->T, To2, c->d_fs, p->cluster_enable, c->d_parent, c->d_rank, c->d_label, c->d_tileK, r * KICP));
-            LAUNCH(c, launch_scan_tiles(c->stream, c->d_tileK, F * KICP, c->T, nullptr, 0));
-        }
-        LAUNCH(c, launch_label_scatter(c->stream, c->d_obj, c->N, F, c->T, To2, c->d_fs, c->d_label, c->d_tileK, c->d_src0, c->d_src, r * KICP, koff));
-        return CD_OK;
-    };
-    // (re)build the ICP sources d_src0 / d_src of every round.  Round 0 was extracted by stage_cluster; it is redone only
-    // when d_src has been consumed by a previous template pass or d_tileK by a later round.
-    auto extract_sources = [&](bool redo_round0) -> int {
-        for (int r = redo_round0 ? 0 : 1; r < rounds_k; ++r)
-            if (int e = extract_round(r, r > 0 ? c->d_koffx + (size_t)r * F * KICP : nullptr)) return e;
-        return CD_OK;
-    };
-    // ICP problems.  template_slot >= 0: every cluster against that slot.  template_slot == -1: every cluster
-    // against every loaded template, one ICP pass per slot; the result with the lowest fitness is kept
-    // (ties -> lowest slot).  The sources are re-extracted between passes (ICP transforms d_src in place).
-    std::vector<int> slots;
-    if (p->template_slot >= 0) slots.push_back(p->template_slot);
-    else for (int sidx = 0; sidx < CD_MAX_TEMPLATES; ++sidx) if (c->tpl_m[sidx] > 0) slots.push_back(sidx);
-    if (slots.empty()) slots.push_back(0);
-    // (the per-cluster results of the previous batch go away here: last_first stays empty until this batch has succeeded,
-    // so a failure in between leaves cd_get_cluster_results with "no batch" rather than old offsets into new results)
+    LAUNCH(c, launch_label_scatter(c->stream, c->d_obj, c->N, F, c->T, cl.To, c->d_fs, c->d_label, c->d_tileK, c->d_src0, c->d_src, r * KICP, koff));
+    return CD_OK;
+}
+
+// (Re)builds the ICP sources d_src0 / d_src of every round (upload_koffx with one copy has run when there are several).
+// Round 0 was extracted by stage_cluster; it is redone only when d_src has been consumed by a previous template pass or
+// d_tileK by a later round.
+int extract_sources(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, bool redo_round0) {
+    for (int r = redo_round0 ? 0 : 1; r < cl.rounds_k; ++r)
+        if (int e = extract_round(c, p, F, cl, r, r > 0 ? koffx_at(c, F, cl, 0, r) : nullptr)) return e;
+    return CD_OK;
+}
+
+struct BatchIcp {   // the ICP part of a fused call; the results themselves are kept in c->last_clusters
+    std::vector<int> slots;                    // the template slots every cluster is matched against, ascending
+    std::vector<long long> orig_off, al_off;   // per cluster, see cd_get_cluster_points (publish_last hands them to the context)
+    long long pairs = 0;                       // pair tests of all its stages
+};
+
+// The first statement of the ICP part: the per-cluster results of the previous batch go away.  last_first stays empty until
+// publish_last, so a failure in between leaves cd_get_cluster_results with "no batch" rather than old offsets into new results.
+// template_slot >= 0: every cluster against that slot; -1: against every loaded template.  Host only.
+void begin_batch_icp(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, BatchIcp* bi) {
     c->last_first.clear();
-    std::vector<cd_cluster_result>& best = c->last_clusters;
-    best.assign((size_t)std::max(ncl, 1), cd_cluster_result());
-    std::vector<long long> orig_off((size_t)std::max(ncl, 1), -1), al_off((size_t)std::max(ncl, 1), -1);   // see cd_get_cluster_points
-    {
-        int q = 0;
-        for (int f = 0; f < F; ++f)
-            for (int k = 0; k < c->h_fs[f].n_k; ++k, ++q) orig_off[(size_t)q] = (long long)f * c->N + coff[(size_t)q];
-    }
-    long long pairs = 0;
-    // Several templates: when S copies of every frame's ICP sources fit its segment of the source buffers (they do unless a
-    // frame is nearly all objects), every (cluster, template) pair becomes one ICP problem of ONE stage - the batch then
-    // fills the chip with S x ncl problems instead of running S under-filled passes one after the other.
-    const int S = (int)slots.size();
-    bool one_stage = S > 1 && ncl > 0;
-    std::vector<int> span((size_t)F, 0);
-    for (int f = 0; f < F; ++f) {
-        for (int k = first_cl[(size_t)f]; k < first_cl[(size_t)f + 1]; ++k) span[(size_t)f] += csize[(size_t)k];
-        if ((long long)S * span[(size_t)f] > (long long)c->N) one_stage = false;
-    }
-    if ((long long)S * ncl > 0x3fffffffll) one_stage = false;
-    if (one_stage) {
-        const size_t need = (size_t)S * rounds_k * F * KICP;   // source offsets of copy t, round r: [t][r][F][KICP]
-        st = grow_device(c, &c->d_koffx, &c->koffx_cap, need);
-        if (st) return st;
-        std::vector<int> tab(need, 0);
-        for (int t = 0; t < S; ++t)
-            for (int r = 0; r < rounds_k; ++r)
-                for (int f = 0; f < F; ++f)
-                    for (int k = 0; k < KICP; ++k) {
-                        const int q = first_cl[(size_t)f] + r * KICP + k;
-                        if (q < first_cl[(size_t)f + 1]) tab[(((size_t)t * rounds_k + r) * F + f) * KICP + k] = coff[(size_t)q] + t * span[(size_t)f];
-                    }
-        HIPCHK(c, copy_sync(c, c->d_koffx, tab.data(), sizeof(int) * need, hipMemcpyHostToDevice));
-        for (int t = 0; t < S; ++t)
-            for (int r = 0; r < rounds_k; ++r) {
-                st = extract_round(r, c->d_koffx + (((size_t)t * rounds_k + r) * F) * KICP);
-                if (st) return st;
-            }
-        st = ensure_clusters(c, S * ncl, (long long)S * cl_points);
-        if (st) return st;
-        for (int t = 0; t < S; ++t)
-            for (int f = 0; f < F; ++f) {
-                const int q = first_cl[(size_t)f];
-                set_icp_clusters(c, t * ncl + q, c->h_fs[f].n_k, f, csize.data() + q, coff.data() + q, f * c->N + t * span[(size_t)f], slots[(size_t)t]);
-            }
-        st = stage_icp(c, S * ncl, p, &pairs);
-        if (st) return st;
-        for (int t = 0; t < S; ++t)
-            for (int k = 0; k < ncl; ++k) {
-                cd_cluster_result r;
-                fill_cluster_result(c, t * ncl + k, p, &r);
-                r.template_slot = slots[(size_t)t];
-                if (t == 0 || r.fitness < best[(size_t)k].fitness) { best[(size_t)k] = r; al_off[(size_t)k] = c->h_cl[(size_t)t * ncl + k].src_off; }
-            }
-    }
-    for (size_t si = 0; si < slots.size() && !one_stage; ++si) {
-        const int slot = slots[si];
-        st = extract_sources(si > 0);
+    if (p->template_slot >= 0) bi->slots.push_back(p->template_slot);
+    else for (int sidx = 0; sidx < CD_MAX_TEMPLATES; ++sidx) if (c->tpl_m[sidx] > 0) bi->slots.push_back(sidx);
+    if (bi->slots.empty()) bi->slots.push_back(0);
+    c->last_clusters.assign((size_t)std::max(cl.ncl, 1), cd_cluster_result());
+    bi->orig_off.assign((size_t)std::max(cl.ncl, 1), -1);
+    bi->al_off.assign((size_t)std::max(cl.ncl, 1), -1);
+    for (int f = 0; f < F; ++f)
+        for (int q = cl.first[(size_t)f]; q < cl.first[(size_t)f + 1]; ++q) bi->orig_off[(size_t)q] = (long long)f * c->N + cl.off[(size_t)q];
+}
+
+// Several templates: when S copies of every frame's ICP sources fit its segment of the source buffers (they do unless a frame
+// is nearly all objects), every (cluster, template) pair becomes one ICP problem of ONE stage - the batch then fills the chip
+// with S x ncl problems instead of running S under-filled passes one after the other.
+bool fits_one_stage(const cd_context* c, int F, const BatchClusters& cl, int S) {
+    if (S <= 1 || cl.ncl <= 0 || (long long)S * cl.ncl > 0x3fffffffll) return false;
+    for (int f = 0; f < F; ++f)
+        if ((long long)S * cl.span[(size_t)f] > (long long)c->N) return false;
+    return true;
+}
+
+// ICP problem q of the stage just run (synchronised by stage_icp) is cluster k against slots[t].  Its result is kept when it
+// is the first (t == 0) or has the lower fitness, so ties keep the lowest slot.  `resident`: the problem's aligned points are
+// still in d_src when the call returns (al_off; -1 otherwise).
+void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, int k, int t, bool resident) {
+    cd_cluster_result r;
+    fill_cluster_result(c, q, p, &r);
+    r.template_slot = bi->slots[(size_t)t];
+    if (t > 0 && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
+    c->last_clusters[(size_t)k] = r;
+    bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
+}
+
+// All (cluster, template) pairs in one stage (fits_one_stage): problem t * ncl + k is cluster k against slots[t], on copy t of
+// the sources.  Uploads the offset table of S copies, issues every extraction round of every copy and one stage_icp, which
+// ends synchronised.  Every problem's aligned points stay resident.
+int icp_all_pairs(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, BatchIcp* bi) {
+    const int S = (int)bi->slots.size(), ncl = cl.ncl;
+    int st = upload_koffx(c, F, cl, S);
+    if (st) return st;
+    for (int t = 0; t < S; ++t)
+        for (int r = 0; r < cl.rounds_k; ++r) {
+            st = extract_round(c, p, F, cl, r, koffx_at(c, F, cl, t, r));
+            if (st) return st;
+        }
+    st = ensure_clusters(c, S * ncl, (long long)S * cl.points);
+    if (st) return st;
+    for (int t = 0; t < S; ++t)
+        for (int f = 0; f < F; ++f) {
+            const int q = cl.first[(size_t)f];
+            set_icp_clusters(c, t * ncl + q, c->h_fs[f].n_k, f, cl.size.data() + q, cl.off.data() + q, f * c->N + t * cl.span[(size_t)f], bi->slots[(size_t)t]);
+        }
+    st = stage_icp(c, S * ncl, p, &bi->pairs);
+    if (st) return st;
+    for (int t = 0; t < S; ++t)
+        for (int k = 0; k < ncl; ++k) keep_lower_fitness(c, p, bi, t * ncl + k, k, t, true);
+    return CD_OK;
+}
+
+// One ICP pass per slot, every cluster against it.  The sources are re-extracted between passes (ICP transforms d_src in
+// place), so the aligned cloud of a pass stays in d_src only until the next one: only the last slot's is resident.
+// Uploads the later rounds' offsets when there are several rounds; per pass: extract_sources, then one stage_icp, which ends
+// synchronised.
+int icp_per_template(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, BatchIcp* bi) {
+    const int S = (int)bi->slots.size();
+    if (cl.rounds_k > 1)
+        if (int e = upload_koffx(c, F, cl, 1)) return e;
+    for (int t = 0; t < S; ++t) {
+        int st = extract_sources(c, p, F, cl, t > 0);
         if (st) return st;
         for (int f = 0; f < F; ++f) {
-            const int q = first_cl[(size_t)f];
-            set_icp_clusters(c, q, c->h_fs[f].n_k, f, csize.data() + q, coff.data() + q, f * c->N, slot);
+            const int q = cl.first[(size_t)f];
+            set_icp_clusters(c, q, c->h_fs[f].n_k, f, cl.size.data() + q, cl.off.data() + q, f * c->N, bi->slots[(size_t)t]);
         }
         long long pr = 0;
-        st = stage_icp(c, ncl, p, &pr);
+        st = stage_icp(c, cl.ncl, p, &pr);
         if (st) return st;
-        pairs += pr;
-        for (int k = 0; k < ncl; ++k) {
-            cd_cluster_result r;
-            fill_cluster_result(c, k, p, &r);
-            r.template_slot = slot;
-            // (the aligned cloud of a pass stays in d_src only until the next pass re-extracts the sources)
-            if (si == 0 || r.fitness < best[(size_t)k].fitness) { best[(size_t)k] = r; al_off[(size_t)k] = si + 1 == slots.size() ? (long long)c->h_cl[k].src_off : -1; }
-        }
+        bi->pairs += pr;
+        for (int k = 0; k < cl.ncl; ++k) keep_lower_fitness(c, p, bi, k, k, t, t + 1 == S);
     }
-    c->last_first = first_cl;
-    c->last_orig_off.swap(orig_off);
-    c->last_al_off.swap(al_off);
+    return CD_OK;
+}
+
+// The state behind the read-back calls (cd_get_cluster_results, cd_get_cluster_points, cd_get_frame_cloud), published once
+// every ICP stage of the batch has succeeded: the only place last_first is assigned.  Host only.
+void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, BatchIcp* bi) {
+    c->last_first = cl.first;
+    c->last_orig_off.swap(bi->orig_off);
+    c->last_al_off.swap(bi->al_off);
     c->last_nv.resize((size_t)F); c->last_no.resize((size_t)F);
     for (int f = 0; f < F; ++f) { c->last_nv[(size_t)f] = c->h_fs[f].n_v; c->last_no[(size_t)f] = c->h_fs[f].n_o; }
     c->last_clouds = true;
     c->last_surface_ok = p->icp_use_guess == CD_GUESS_SURFACE;
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    // records
+}
+
+// The per-frame records from h_fs, the plane mirrors and c->last_clusters, and the byte counts of the timing
+// (algorithmic_bytes, icp_algorithmic_bytes).  Host only; every stage has been synchronised.
+void write_frame_records(cd_context* c, int N, int F, const BatchClusters& cl, const FrontStages& fr, cd_frame_result* results) {
     long long balg = 0;
     for (int f = 0; f < F; ++f) {
         const FrameState& s = c->h_fs[f];
@@ -1824,51 +1846,124 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
         r.n_objects = s.n_o;
         r.n_clusters = s.n_k;
         r.flags = s.n_k > KICP ? CD_FRAME_MORE_CLUSTERS : 0;
-        if (!surface_flag.empty() && surface_flag[(size_t)f]) r.flags |= CD_FRAME_SURFACE_GUESS;
-        r.ransac_iterations = iterations[f];
+        if (!fr.surface_flag.empty() && fr.surface_flag[(size_t)f]) r.flags |= CD_FRAME_SURFACE_GUESS;
+        r.ransac_iterations = fr.iterations[f];
         if (s.status == CD_OK && !c->h_have[f]) r.status = CD_ERR_NO_MODEL;
         if (c->h_have[f]) { r.plane[0] = c->h_model[f].x; r.plane[1] = c->h_model[f].y; r.plane[2] = c->h_model[f].z; r.plane[3] = c->h_model[f].w; }
-        balg += 12ll * N + 12ll * s.n_v + 12ll * s.n_v * (rounds + 3) + 4ll * s.n_v + 16ll * s.n_o + 200ll * s.n_k;
+        balg += 12ll * N + 12ll * s.n_v + 12ll * s.n_v * (fr.rounds + 3) + 4ll * s.n_v + 16ll * s.n_o + 200ll * s.n_k;
         for (int k = 0; k < s.n_k; ++k) {
-            const cd_cluster_result& cr = best[(size_t)(first_cl[(size_t)f] + k)];
+            const cd_cluster_result& cr = c->last_clusters[(size_t)(cl.first[(size_t)f] + k)];
             if (k < KICP) r.clusters[k] = cr;
             const long long b = 12ll * c->tpl_m[cr.template_slot] + 12ll * cr.size * (cr.iterations + 1);
             balg += b;
             c->timing.icp_algorithmic_bytes += b;
         }
     }
-    if (plane_inliers || labels) {
-        std::vector<int32_t> tmp((size_t)c->N);
-        for (int f = 0; f < F; ++f) {
-            const FrameState& s = c->h_fs[f];
-            if (plane_inliers) {
-                int32_t* dst = plane_inliers + (size_t)f * N;
-                std::fill(dst, dst + N, -1);
-                if (s.n_plane > 0) HIPCHK(c, copy_sync(c, dst, c->d_plane_idx + (size_t)f * c->N, sizeof(int) * s.n_plane, hipMemcpyDeviceToHost));
-            }
-            if (labels) {
-                int32_t* dst = labels + (size_t)f * N;
-                std::fill(dst, dst + N, -1);
-                if (s.n_o > 0) HIPCHK(c, copy_sync(c, dst, c->d_label + (size_t)f * c->N, sizeof(int) * s.n_o, hipMemcpyDeviceToHost));
-            }
+    c->timing.algorithmic_bytes = balg;
+}
+
+// The optional plane_inliers / labels outputs ([F][N], -1 beyond a frame's count): one blocking D2H copy per frame and output.
+int copy_frame_indices(cd_context* c, int N, int F, int32_t* plane_inliers, int32_t* labels) {
+    for (int f = 0; f < F && (plane_inliers || labels); ++f) {
+        const FrameState& s = c->h_fs[f];
+        if (plane_inliers) {
+            int32_t* dst = plane_inliers + (size_t)f * N;
+            std::fill(dst, dst + N, -1);
+            if (s.n_plane > 0) HIPCHK(c, copy_sync(c, dst, c->d_plane_idx + (size_t)f * c->N, sizeof(int) * s.n_plane, hipMemcpyDeviceToHost));
+        }
+        if (labels) {
+            int32_t* dst = labels + (size_t)f * N;
+            std::fill(dst, dst + N, -1);
+            if (s.n_o > 0) HIPCHK(c, copy_sync(c, dst, c->d_label + (size_t)f * c->N, sizeof(int) * s.n_o, hipMemcpyDeviceToHost));
         }
     }
+    return CD_OK;
+}
+
+// The stage times between the events ev[0..4] of process_batch_impl ([4]: the whole call) and the pair-test count.
+// Waits for ev[4].
+int read_stage_timing(cd_context* c, long long pairs) {
     HIPCHK(c, hipEventSynchronize(c->ev[4]));
     for (int k = 0; k < 4; ++k) hipEventElapsedTime(&c->timing.stage_ms[k], c->ev[k], c->ev[k + 1]);
     hipEventElapsedTime(&c->timing.stage_ms[4], c->ev[0], c->ev[4]);
     c->timing.icp_pair_tests_lo = (int32_t)(pairs & 0xffffffffll);
     c->timing.icp_pair_tests_hi = (int32_t)(pairs >> 32);
-    c->timing.algorithmic_bytes = balg;
-    if (gate_source != CD_BBOX_PARAMS) {   // cd_get_frame_bboxes: the rectangles this call's gate used
-        c->last_bboxes.assign((size_t)F, cd_color_bbox{});
-        for (int f = 0; f < F; ++f) {
-            if (gate_source == CD_BBOX_COLOR) std::memcpy(&c->last_bboxes[(size_t)f], &c->h_crec[f], sizeof(cd_color_bbox));
-            else { std::memcpy(c->last_bboxes[(size_t)f].rect, c->frame_rects.data() + 4 * (size_t)f, sizeof(int32_t) * 4); c->last_bboxes[(size_t)f].found = 1; }
-        }
-        if (gate_source == CD_BBOX_COLOR) { st = color_status(c, F); if (st) return st; }
-        c->last_bboxes_ok = true;
-    }
     return CD_OK;
+}
+
+// cd_get_frame_bboxes: the rectangles this call's gate used.  Host only; the colour records' mirrors (h_crec, h_cstatus) have
+// been valid since the call's first synchronisation.
+int publish_bboxes(cd_context* c, int gate_source, int F) {
+    if (gate_source == CD_BBOX_PARAMS) return CD_OK;
+    c->last_bboxes.assign((size_t)F, cd_color_bbox{});
+    for (int f = 0; f < F; ++f) {
+        if (gate_source == CD_BBOX_COLOR) std::memcpy(&c->last_bboxes[(size_t)f], &c->h_crec[f], sizeof(cd_color_bbox));
+        else { std::memcpy(c->last_bboxes[(size_t)f].rect, c->frame_rects.data() + 4 * (size_t)f, sizeof(int32_t) * 4); c->last_bboxes[(size_t)f].found = 1; }
+    }
+    if (gate_source == CD_BBOX_COLOR)
+        if (int st = color_status(c, F)) return st;
+    c->last_bboxes_ok = true;
+    return CD_OK;
+}
+
+// The fused call, in the order of DESIGN.md §5.  The event records ev[0..4] (the boundaries of cd_timing.stage_ms) and the
+// release of the front gate are all here.
+int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N, int F, const cd_params* p,
+                       cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, const DepthJob* dj = nullptr) {
+    // checks: nothing is copied or launched before they have passed
+    int st = check_params(c, p);
+    if (!st) st = check_bbox_source(c, p, F, dj && dj->color);
+    if (st) return st;
+    if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
+    if (N > c->N || F > c->F) return fail(c, CD_ERR_CAPACITY, "batch larger than the context capacity");
+    invalidate_last(c);
+    std::memset(&c->timing, 0, sizeof(c->timing));
+    BatchGuard in_flight(c->device);
+    GateHold front;
+    if (c->front_concurrent > 0) front.enter(&g_front_gate[c->device & (MAX_DEVICES - 1)], c->front_concurrent);
+    const int gate_source = p->bbox_enable ? c->bbox_source : CD_BBOX_PARAMS;
+    BatchScope scope{c};
+    // [0] gate rectangles, deprojection, zero launch, crop + voxel grid
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    st = batch_prologue(c, gate_source, d_frames, F, dj);
+    if (!st) st = stage_crop_voxel(c, d_frames, stride, N, F, p, nullptr);
+    if (!st) st = sync_fs(c, F);   // n_v
+    if (st) return st;
+    // [1] plane
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    FrontStages fr;
+    st = stage_plane(c, F, p, fr.iterations, &fr.rounds);
+    if (st) return st;
+    // [2] extract, cluster, surface guesses
+    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    st = stage_extract(c, F, p);
+    if (!st) st = sync_fs(c, F, c->mirror_writes && c->copy_kernels);   // n_o per frame (written to the mirror by the scan): picks the clustering path and sizes the launches
+    if (st) return st;
+    int max_no = 0;
+    for (int f = 0; f < F; ++f) max_no = std::max(max_no, c->h_fs[f].n_o);
+    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff
+    if (!st && p->icp_use_guess == CD_GUESS_SURFACE) st = surface_guesses(c, F, p, &fr.surface_flag);
+    if (st) return st;
+    // [3] ICP of every cluster, against one template or all of them
+    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+    front.release();
+    BatchClusters cl;
+    st = batch_clusters(c, F, &cl);
+    if (st) return st;
+    BatchIcp bi;
+    begin_batch_icp(c, p, F, cl, &bi);
+    if (fits_one_stage(c, F, cl, (int)bi.slots.size())) st = icp_all_pairs(c, p, F, cl, &bi);
+    else st = icp_per_template(c, p, F, cl, &bi);
+    if (st) return st;
+    publish_last(c, p, F, cl, &bi);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    // records and read-out
+    write_frame_records(c, N, F, cl, fr, results);
+    st = copy_frame_indices(c, N, F, plane_inliers, labels);
+    if (!st) st = read_stage_timing(c, bi.pairs);
+    if (!st) st = publish_bboxes(c, gate_source, F);
+    return st;
 }
 
 }  // namespace
