@@ -164,7 +164,7 @@ void cd_default_params(cd_params* p);
 int cd_abi_version(void);
 /* sizeof() of the ABI structs, for FFI layers to verify their mirror of this header:
  * which = 0 cd_params, 1 cd_cluster_result, 2 cd_frame_result, 3 cd_timing, 4 cd_depth_camera, 5 cd_color_gate_params,
- * 6 cd_color_bbox. */
+ * 6 cd_color_bbox, 7 cd_overlay_params, 8 cd_overlay_box. */
 int cd_struct_size(int which);
 
 /* Object lifetimes (replaces construction/destruction of the PCL objects and the node's
@@ -489,6 +489,76 @@ int cd_set_frame_bboxes(cd_context* ctx, const int32_t* rects, int n_frames);
 int cd_set_bbox_source(cd_context* ctx, int source, const cd_color_gate_params* params);
 int cd_get_bbox_source(const cd_context* ctx, int* source);
 int cd_get_frame_bboxes(const cd_context* ctx, int first, int capacity, cd_color_bbox* out);
+
+/* Overlay: the one consumer of the chain's poses that the reference has, cuboid_detection/scripts/draw_bbox.py:44-83 (the eight
+ * /icp/bbox_points corners projected with CameraInfo.P x the depth->colour extrinsics, 12 green lines of thickness 2 over the
+ * colour image), for every image of a batch on the device.  Canonical rule C11, per box = a row-major double pose
+ * (cd_cluster_result.pose) and the dimensions dims = l, w, h:
+ *   1. corners = cd_bbox_corners(pose, l, w, h): float32, the order of icp.cpp:99-106; each widened to double;
+ *   2. M = P E in double, every entry ((p0 e0 + p1 e1) + p2 e2) + p3 e3, no contraction;
+ *   3. h_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3]; u = h_0 / h_2, v = h_1 / h_2 (IEEE divide); pixel = truncation
+ *      toward zero (astype('int'), draw_bbox.py:62);
+ *   4. a box is SKIPPED (drawn = 0, corners reported as zeros) when any corner has a non-finite u or v, h_2 <= 0 or a pixel
+ *      coordinate of magnitude over 8192.  h_2 <= 0 is a deviation: the script would draw the mirrored box of a point behind
+ *      the camera;
+ *   5. edges: the 12 corner pairs of draw_bbox.py:66-77 - 01 02 04 13 15 23 26 37 45 46 57 67;
+ *   6. pixel p of the image is painted for the edge with integer end points a, b iff, with d = b - a, e = p - a, L = d.d,
+ *      s = e.d (int64):  (L == 0 or s <= 0) and 4 e.e <= t^2;  or  s >= L and 4 |p - b|^2 <= t^2;  or otherwise
+ *      4 (e x d)^2 <= t^2 L - every pixel within t / 2 of the segment, round caps, integers only;
+ *   7. painted pixels receive rgb; every other byte of the image is unchanged; nothing outside the image is touched.  All boxes
+ *      of a call share one colour, so the order of drawing cannot matter; frames are independent.
+ * Parity with a real OpenCV build's cv2.line (its fixed-point thick-line polygon) is UNPINNED, as for rule C10:
+ * perception_amd/overlay.py restates the rule on the CPU and the device equals it byte for byte. */
+typedef struct cd_overlay_params {      /* no padding holes */
+    double P[12];                       /* CameraInfo.P of the colour stream, row-major 3x4                       */
+    double E[16];                       /* depth -> colour extrinsics, row-major 4x4; identity for registered images */
+    double dims[3];                     /* l, w, h of every box of the call (iterative_closest_point.launch:39-41) */
+    int32_t thickness;                  /* 1 .. 64; draw_bbox.py: 2                                                */
+    uint8_t rgb[3];                     /* r, g, b written to painted pixels; draw_bbox.py: 0, 255, 0              */
+    uint8_t pad;
+    int32_t reserved[6];
+} cd_overlay_params;
+typedef struct cd_overlay_box {
+    int32_t corners[16];                /* u0, v0, ... u7, v7 (step 3); all zero when drawn == 0                   */
+    int32_t drawn;                      /* 0: skipped (step 4), or no box in this slot                             */
+    int32_t reserved[3];
+} cd_overlay_box;
+/* D435 P of the reference's README.md:78 (the K of cd_default_depth_camera, zero fourth column), E = identity, dims 0.2 / 0.1 /
+ * 0.03, thickness 2, green. */
+void cd_default_overlay_params(cd_overlay_params* p);
+
+/* Host-only (no context, no GPU): steps 1-4 for one box.  params == NULL: the defaults.  A skipped box is a result (CD_OK,
+ * drawn = 0); NULL pose / out, or a non-finite P, E or dims: CD_ERR_INVALID_ARG. */
+int cd_overlay_project(const double pose[16], const cd_overlay_params* params, cd_overlay_box* out);
+
+/* Rule C11 on n_frames tightly packed rgb8 images (width * height * 3 bytes each, back to back), drawn IN PLACE.  Frame f has
+ * n_boxes[f] <= boxes_per_frame boxes; the pose of its box b is poses[(f * boxes_per_frame + b) * 16 .. + 15]; out receives
+ * n_frames * boxes_per_frame records in the same order (slots at and beyond n_boxes[f]: all zero).  params == NULL: the defaults.
+ * Checked before any copy or launch, CD_ERR_INVALID_ARG: a null rgb8 / poses / n_boxes / out, width * height 0 or over
+ * max_points, width or height over 8192, n_frames outside 1 .. max_frames, boxes_per_frame outside 1 .. 1024, thickness outside
+ * 1 .. 64, a non-finite P, E or dims, a negative n_boxes[f] or one over boxes_per_frame.  A non-finite pose is no error: that
+ * box is skipped.  The host form uploads the images, draws and downloads them again.  Like every compute call
+ * these two invalidate the read-backs of the last fused call (cd_draw_last_results does not). */
+int cd_draw_boxes_batch(cd_context* ctx, uint8_t* rgb8, int width, int height, int n_frames, const double* poses,
+                        const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* params, cd_overlay_box* out);
+/* Same, images already resident in device memory of the context's GPU (ordering as cd_process_batch_device; the images are
+ * final when the call returns).  poses, n_boxes and out are host memory. */
+int cd_draw_boxes_batch_device(cd_context* ctx, uint8_t* d_rgb8, int width, int height, int n_frames, const double* poses,
+                               const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* params, cd_overlay_box* out);
+
+/* The poses of the LAST fused call of the context (cd_process_batch[_device], cd_process_frame, cd_process_depth_batch[_device])
+ * drawn into that call's n_frames images - e.g. the CD_COLOR_RGB8 images of cd_process_depth_batch_device, still resident.
+ * boxes_per_frame is CD_MAX_CLUSTERS_PER_FRAME: slot k of frame f is clusters[k] of its record; which = CD_DRAW_ACCEPTED draws
+ * the slots with accepted != 0, CD_DRAW_ALL every slot below min(n_clusters, CD_MAX_CLUSTERS_PER_FRAME); the other slots of
+ * `out` (n_frames * CD_MAX_CLUSTERS_PER_FRAME records) are zero.  Every box has params->dims.  The validity rule of
+ * cd_get_cluster_results: CD_ERR_INVALID_ARG when there is no such call or another compute call has run since; the draw calls
+ * themselves leave the fused call's read-backs as they are (both `which` can be drawn in turn).  Only the poses go to the
+ * device; in the _device form the images never visit the host.  Argument checks as cd_draw_boxes_batch. */
+enum { CD_DRAW_ACCEPTED = 0, CD_DRAW_ALL = 1 };
+int cd_draw_last_results(cd_context* ctx, uint8_t* rgb8, int width, int height, int which, const cd_overlay_params* params,
+                         cd_overlay_box* out);
+int cd_draw_last_results_device(cd_context* ctx, uint8_t* d_rgb8, int width, int height, int which, const cd_overlay_params* params,
+                                cd_overlay_box* out);
 
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */

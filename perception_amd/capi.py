@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = [
     "cd_get_surface_results",
     "cd_default_color_gate_params", "cd_color_bbox_batch", "cd_color_bbox_batch_device", "cd_set_frame_bboxes", "cd_set_bbox_source",
     "cd_get_bbox_source", "cd_get_frame_bboxes",
+    "cd_default_overlay_params", "cd_overlay_project", "cd_draw_boxes_batch", "cd_draw_boxes_batch_device", "cd_draw_last_results",
+    "cd_draw_last_results_device",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -48,6 +50,7 @@ CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE = 0, 1, 2, 
 CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
 CD_COLOR_NONE, CD_COLOR_RGB8 = 0, 1
 CD_BBOX_PARAMS, CD_BBOX_PER_FRAME, CD_BBOX_COLOR = 0, 1, 2
+CD_DRAW_ACCEPTED, CD_DRAW_ALL = 0, 1
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -130,7 +133,47 @@ class CdColorBBox(C.Structure):
                 ("n_mask", C.c_int32)]
 
 
+class CdOverlayParams(C.Structure):
+    """cd_overlay_params: the parameters of canonical rule C11 (the projected boxes of draw_bbox.py)."""
+    _fields_ = [("P", C.c_double * 12), ("E", C.c_double * 16), ("dims", C.c_double * 3), ("thickness", C.c_int32),
+                ("rgb", C.c_uint8 * 3), ("pad", C.c_uint8), ("reserved", C.c_int32 * 6)]
+
+
+class CdOverlayBox(C.Structure):
+    """cd_overlay_box: one box's projected corners u0, v0 .. u7, v7 (all zero when drawn == 0: skipped, or an empty slot)."""
+    _fields_ = [("corners", C.c_int32 * 16), ("drawn", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 FRAME_RESULT_BYTES = C.sizeof(CdFrameResult)
+
+
+def default_overlay_params():
+    """D435 P (the K of default_depth_camera, zero fourth column), E = identity, dims 0.2 / 0.1 / 0.03, thickness 2, green.
+    Pure Python mirror of cd_default_overlay_params()."""
+    from . import overlay
+    o = CdOverlayParams()
+    o.P[:] = overlay.DEFAULT_P
+    o.E[:] = overlay.DEFAULT_E
+    o.dims[:] = overlay.DEFAULT_DIMS
+    o.thickness = overlay.DEFAULT_THICKNESS
+    o.rgb[:] = overlay.DEFAULT_RGB
+    return o
+
+
+def overlay_params(P=None, E=None, dims=None, thickness=None, rgb=None):
+    """default_overlay_params() with the given fields replaced (P 3x4, E 4x4, dims l / w / h, thickness, rgb)."""
+    o = default_overlay_params()
+    if P is not None:
+        o.P[:] = [float(v) for v in np.asarray(P, np.float64).reshape(12)]
+    if E is not None:
+        o.E[:] = [float(v) for v in np.asarray(E, np.float64).reshape(16)]
+    if dims is not None:
+        o.dims[:] = [float(v) for v in dims]
+    if thickness is not None:
+        o.thickness = int(thickness)
+    if rgb is not None:
+        o.rgb[:] = [int(v) for v in rgb]
+    return o
 
 
 def default_color_gate_params():
@@ -256,6 +299,14 @@ def load_library(path=None):
     lib.cd_set_bbox_source.argtypes = [vp, C.c_int, C.POINTER(CdColorGateParams)]
     lib.cd_get_bbox_source.argtypes = [vp, ip]
     lib.cd_get_frame_bboxes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CdColorBBox)]
+    dp = C.POINTER(C.c_double)
+    lib.cd_default_overlay_params.argtypes = [C.POINTER(CdOverlayParams)]
+    lib.cd_default_overlay_params.restype = None
+    lib.cd_overlay_project.argtypes = [dp, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
+    for f in (lib.cd_draw_boxes_batch, lib.cd_draw_boxes_batch_device):
+        f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, i32p, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
+    for f in (lib.cd_draw_last_results, lib.cd_draw_last_results_device):
+        f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
     if path is None:
         _lib = lib
     return lib
@@ -512,6 +563,46 @@ class Context:
             raise CuboidError(n, "cd_get_frame_bboxes: the last fused call's gate did not read per-frame rectangles")
         return [out[i] for i in range(n)]
 
+    def draw_boxes(self, rgb, poses, n_boxes=None, params=None):
+        """Rule C11: the projected boxes of draw_bbox.py drawn IN PLACE into rgb, either a C-contiguous writable (F, H, W, 3)
+        uint8 numpy array (cd_draw_boxes_batch: uploaded, drawn, downloaded) or a contiguous torch uint8 tensor of that shape in
+        HBM (cd_draw_boxes_batch_device; the caller has synchronised the stream that wrote it).  poses (F, B, 4, 4) float64,
+        n_boxes (F,) (None: all B).  Returns an array of F * B CdOverlayBox, box b of frame f at [f * B + b]."""
+        on_device = not isinstance(rgb, np.ndarray)
+        if on_device:
+            assert rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3
+            ptr = C.c_void_p(rgb.data_ptr())
+        else:
+            assert rgb.dtype == np.uint8 and rgb.ndim == 4 and rgb.shape[3] == 3 and rgb.flags.c_contiguous and rgb.flags.writeable
+            ptr = _ptr(rgb)
+        F, H, W = (int(v) for v in rgb.shape[:3])
+        p = np.ascontiguousarray(poses, np.float64).reshape(F, -1, 16)
+        B = p.shape[1]
+        nb = np.full(F, B, np.int32) if n_boxes is None else np.ascontiguousarray(n_boxes, np.int32)
+        assert nb.shape == (F,)
+        out = (CdOverlayBox * max(F * B, 1))()
+        fn = self.lib.cd_draw_boxes_batch_device if on_device else self.lib.cd_draw_boxes_batch
+        self._check(fn(self.h, ptr, W, H, F, p.ctypes.data_as(C.POINTER(C.c_double)), nb.ctypes.data_as(C.POINTER(C.c_int32)), B,
+                       None if params is None else C.byref(params), out))
+        return out
+
+    def draw_last_results(self, rgb, which=CD_DRAW_ACCEPTED, params=None):
+        """The poses of the last fused call drawn IN PLACE into its frames' images (numpy array or torch tensor as for
+        draw_boxes; F = that call's frames).  which: CD_DRAW_ACCEPTED / CD_DRAW_ALL.  Returns F * CD_MAX_CLUSTERS_PER_FRAME
+        CdOverlayBox, slot k of frame f = clusters[k] of its record.  Leaves the fused call's read-backs as they are."""
+        on_device = not isinstance(rgb, np.ndarray)
+        if on_device:
+            assert rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3
+            ptr = C.c_void_p(rgb.data_ptr())
+        else:
+            assert rgb.dtype == np.uint8 and rgb.ndim == 4 and rgb.shape[3] == 3 and rgb.flags.c_contiguous and rgb.flags.writeable
+            ptr = _ptr(rgb)
+        F, H, W = (int(v) for v in rgb.shape[:3])
+        out = (CdOverlayBox * (max(F, 1) * CD_MAX_CLUSTERS_PER_FRAME))()
+        fn = self.lib.cd_draw_last_results_device if on_device else self.lib.cd_draw_last_results
+        self._check(fn(self.h, ptr, W, H, int(which), None if params is None else C.byref(params), out))
+        return out
+
     def surface_batch(self, clouds, table_normals, prm, invert=True):
         """cd_surface_batch: cd_surface_frame over a batch of (ragged) clouds, fitted together on the device.
         clouds: a sequence of (n_f, >=3) arrays or an (F, P, >=3) array; table_normals (F, 3).
@@ -667,6 +758,17 @@ def surface_guess(Rt):
     if st != CD_OK:
         raise CuboidError(st, "cd_surface_guess: non-finite input")
     return g.reshape(4, 4)
+
+
+def overlay_project(pose, params=None):
+    """Host-only rule C11 steps 1-4 for one box (cd_overlay_project): (16 corner ints, drawn flag)."""
+    lib = load_library()
+    a = np.ascontiguousarray(pose, np.float64).reshape(16)
+    box = CdOverlayBox()
+    st = lib.cd_overlay_project(a.ctypes.data_as(C.POINTER(C.c_double)), None if params is None else C.byref(params), C.byref(box))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_overlay_project: non-finite P, E or dims")
+    return list(box.corners), int(box.drawn)
 
 
 def results_to_array(res):

@@ -19,6 +19,7 @@
 
 #include "host_math.hpp"
 #include "kernels.hpp"
+#include "overlay_math.hpp"
 
 using namespace cd;
 
@@ -172,6 +173,11 @@ struct cd_context {
     FrameRects call_rects{nullptr, 0};
     std::vector<cd_color_bbox> last_bboxes;                       // cd_get_frame_bboxes
     bool last_bboxes_ok = false;
+    // overlay (rule C11, k_overlay.hip): poses, box counts and box records of a draw call, grown on demand (boxes: device + pinned mirror)
+    double* d_oposes = nullptr;
+    int32_t* d_onbox = nullptr;
+    OverlayBox *d_obox = nullptr, *h_obox = nullptr;
+    size_t obox_cap = 0, onbox_cap = 0;
     IcpState *d_st = nullptr, *h_st = nullptr;
     unsigned long long *d_acc = nullptr, *d_accf = nullptr, *h_accf = nullptr;
     hipEvent_t ev[8] = {nullptr};
@@ -2007,6 +2013,8 @@ int cd_struct_size(int which) {
         case 4: return (int)sizeof(cd_depth_camera);
         case 5: return (int)sizeof(cd_color_gate_params);
         case 6: return (int)sizeof(cd_color_bbox);
+        case 7: return (int)sizeof(cd_overlay_params);
+        case 8: return (int)sizeof(cd_overlay_box);
         default: return -1;
     }
 }
@@ -2035,6 +2043,11 @@ void cd_destroy(cd_context* c) {
         for (void* p : cdev) if (p) hipFree(p);
         void* chost[] = {c->h_crec, c->h_cstatus, c->h_rects};
         for (void* p : chost) if (p) hipHostFree(p);
+    }
+    {
+        void* odev[] = {c->d_oposes, c->d_onbox, c->d_obox};
+        for (void* p : odev) if (p) hipFree(p);
+        if (c->h_obox) hipHostFree(c->h_obox);
     }
     {
         void* sdev[] = {c->d_sfs, c->d_smodel, c->d_shave, c->d_sactive, c->d_spts[0], c->d_spts[1], c->d_sidx, c->d_ssum};
@@ -3127,6 +3140,127 @@ static int cd_color_bbox_batch_impl(cd_context* c, const uint8_t* rgb8, int widt
     return color_status(c, n_frames);
 }
 
+// ---- overlay (rule C11, k_overlay.hip) -----------------------------------------------------------------------------------------
+static_assert(sizeof(OverlayBox) == sizeof(cd_overlay_box) && offsetof(cd_overlay_box, drawn) == offsetof(OverlayBox, drawn), "the kernel's record is cd_overlay_box");
+static_assert(sizeof(cd_overlay_params) == 12 * 8 + 16 * 8 + 3 * 8 + 4 + 4 + 6 * 4 && offsetof(cd_overlay_params, reserved) == 256, "cd_overlay_params has no padding holes");
+constexpr int OVERLAY_MAX_BOXES = 1024;   // boxes_per_frame of a draw call
+
+// the checks on the parameters alone (shared with the host-only cd_overlay_project): nullptr = fine, else what is wrong
+static const char* overlay_params_error(const cd_overlay_params* op) {
+    for (double v : op->P) if (!std::isfinite(v)) return "P holds a non-finite value";
+    for (double v : op->E) if (!std::isfinite(v)) return "E holds a non-finite value";
+    for (double v : op->dims) if (!std::isfinite(v)) return "dims holds a non-finite value";
+    if (op->thickness < 1 || op->thickness > OVERLAY_MAX_THICKNESS) return "thickness must be in 1 .. 64";
+    return nullptr;
+}
+
+// rule C11 step 2: M = P E, every entry ((p0 e0 + p1 e1) + p2 e2) + p3 e3
+static OverlayParams overlay_kernel_params(const cd_overlay_params* op) {
+    OverlayParams k;
+    for (int r = 0; r < 3; ++r)
+        for (int col = 0; col < 4; ++col)
+            k.M[4 * r + col] = ((op->P[4 * r] * op->E[col] + op->P[4 * r + 1] * op->E[4 + col]) + op->P[4 * r + 2] * op->E[8 + col]) + op->P[4 * r + 3] * op->E[12 + col];
+    for (int i = 0; i < 3; ++i) k.dims[i] = op->dims[i];
+    return k;
+}
+
+// every check of the header's list but those on n_boxes, before anything is copied or launched
+static int check_overlay(cd_context* c, const void* rgb8, int width, int height, int n_frames, const cd_overlay_params* op, const void* out) {
+    if (!rgb8 || !out) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (width <= 0 || height <= 0 || (long long)width * height > (long long)c->N)
+        return fail(c, CD_ERR_INVALID_ARG, "width * height must be in 1 .. the context's max_points");
+    if (width > OVERLAY_COORD_MAX || height > OVERLAY_COORD_MAX) return fail(c, CD_ERR_INVALID_ARG, "width and height must not exceed 8192");
+    if (n_frames <= 0 || n_frames > c->F) return fail(c, CD_ERR_INVALID_ARG, "n_frames must be in 1 .. the context's max_frames");
+    if (const char* msg = overlay_params_error(op)) return fail(c, CD_ERR_INVALID_ARG, msg);
+    return CD_OK;
+}
+
+// poses (F * B * 16 doubles) and n_boxes (F) are HOST memory; img is device memory (on_device) or host memory that is
+// uploaded, drawn on and downloaded again.  Leaves the read-back state of the last fused call alone.
+static int stage_overlay(cd_context* c, uint8_t* img, int W, int H, int F, const double* poses, const int32_t* n_boxes, int B,
+                         const cd_overlay_params* op, cd_overlay_box* out, bool on_device) {
+    const size_t nb = (size_t)F * (size_t)B;
+    if (nb > c->obox_cap) {
+        if (c->d_oposes) hipFree(c->d_oposes);
+        if (c->d_obox) hipFree(c->d_obox);
+        if (c->h_obox) hipHostFree(c->h_obox);
+        c->d_oposes = nullptr; c->d_obox = nullptr; c->h_obox = nullptr; c->obox_cap = 0;
+        HIPCHK(c, dalloc(&c->d_oposes, nb * 16));
+        HIPCHK(c, dalloc(&c->d_obox, nb));
+        HIPCHK(c, halloc(&c->h_obox, nb));
+        c->obox_cap = nb;
+    }
+    if ((size_t)F > c->onbox_cap) {
+        if (c->d_onbox) hipFree(c->d_onbox);
+        c->d_onbox = nullptr; c->onbox_cap = 0;
+        HIPCHK(c, dalloc(&c->d_onbox, (size_t)c->F));
+        c->onbox_cap = (size_t)c->F;
+    }
+    const size_t img_bytes = (size_t)W * H * F * 3;
+    uint8_t* d_img = img;
+    if (!on_device) {
+        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        HIPCHK(c, hipMemcpyAsync(c->d_color, img, img_bytes, hipMemcpyHostToDevice, c->stream));
+        d_img = c->d_color;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_oposes, poses, sizeof(double) * 16 * nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_onbox, n_boxes, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, c->stream));
+    const OverlayParams kp = overlay_kernel_params(op);
+    LAUNCH(c, launch_overlay_project(c->stream, c->d_oposes, c->d_onbox, B, F, kp, c->d_obox));
+    LAUNCH(c, launch_overlay_raster(c->stream, d_img, W, H, B, F, op->thickness, op->rgb, c->d_obox));
+    HIPCHK(c, hipMemcpyAsync(c->h_obox, c->d_obox, sizeof(OverlayBox) * nb, hipMemcpyDeviceToHost, c->stream));
+    if (!on_device) HIPCHK(c, hipMemcpyAsync(img, d_img, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_obox, sizeof(cd_overlay_box) * nb);
+    return CD_OK;
+}
+
+static int cd_draw_boxes_batch_impl(cd_context* c, uint8_t* rgb8, int width, int height, int n_frames, const double* poses,
+                                    const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* op, cd_overlay_box* out, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    cd_overlay_params def;
+    cd_default_overlay_params(&def);
+    if (!op) op = &def;
+    int st = check_overlay(c, rgb8, width, height, n_frames, op, out);
+    if (st) return st;
+    if (!poses || !n_boxes) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (boxes_per_frame < 1 || boxes_per_frame > OVERLAY_MAX_BOXES) return fail(c, CD_ERR_INVALID_ARG, "boxes_per_frame must be in 1 .. 1024");
+    for (int f = 0; f < n_frames; ++f)
+        if (n_boxes[f] < 0 || n_boxes[f] > boxes_per_frame) return fail(c, CD_ERR_INVALID_ARG, "n_boxes[f] must be in 0 .. boxes_per_frame");
+    invalidate_last(c);
+    return stage_overlay(c, rgb8, width, height, n_frames, poses, n_boxes, boxes_per_frame, op, out, on_device);
+}
+
+static int cd_draw_last_results_impl(cd_context* c, uint8_t* rgb8, int width, int height, int which, const cd_overlay_params* op,
+                                     cd_overlay_box* out, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    cd_overlay_params def;
+    cd_default_overlay_params(&def);
+    if (!op) op = &def;
+    if (c->last_first.size() < 2) return fail(c, CD_ERR_INVALID_ARG, "no fused call to draw: none has run, or another compute call has run since");
+    const int F = (int)c->last_first.size() - 1;
+    int st = check_overlay(c, rgb8, width, height, F, op, out);
+    if (st) return st;
+    if (which != CD_DRAW_ACCEPTED && which != CD_DRAW_ALL) return fail(c, CD_ERR_INVALID_ARG, "unknown selection of boxes");
+    // slot k of frame f = cluster k of its record; a slot that is not drawn carries a NaN pose, which rule C11 skips
+    constexpr int B = CD_MAX_CLUSTERS_PER_FRAME;
+    std::vector<double> poses((size_t)F * B * 16, std::numeric_limits<double>::quiet_NaN());
+    std::vector<int32_t> n_boxes((size_t)F, 0);
+    for (int f = 0; f < F; ++f) {
+        const int lo = c->last_first[(size_t)f], hi = c->last_first[(size_t)f + 1];
+        if (lo < 0 || hi < lo || (size_t)hi > c->last_clusters.size()) return fail(c, CD_ERR_INVALID_ARG, "no fused call to draw");
+        const int n = std::min(hi - lo, B);
+        n_boxes[(size_t)f] = n;
+        for (int k = 0; k < n; ++k) {
+            const cd_cluster_result& cr = c->last_clusters[(size_t)(lo + k)];
+            if (which == CD_DRAW_ALL || cr.accepted) std::memcpy(&poses[((size_t)f * B + k) * 16], cr.pose, sizeof(cr.pose));
+        }
+    }
+    return stage_overlay(c, rgb8, width, height, F, poses.data(), n_boxes.data(), B, op, out, on_device);
+}
+
 void cd_default_depth_camera(cd_depth_camera* cam) {
     if (!cam) return;
     std::memset(cam, 0, sizeof(*cam));
@@ -3373,6 +3507,54 @@ int cd_color_bbox_batch(cd_context* c, const uint8_t* rgb8, int width, int heigh
 int cd_color_bbox_batch_device(cd_context* c, const uint8_t* d_rgb8, int width, int height, int n_frames, const cd_color_gate_params* g, cd_color_bbox* out) {
     if (!c) return CD_ERR_INVALID_ARG;
     return with_scan_retry(c, [&]() { return cd_color_bbox_batch_impl(c, d_rgb8, width, height, n_frames, g, out, true); });
+}
+
+void cd_default_overlay_params(cd_overlay_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->P[0] = p->P[5] = (double)384.0898742675781f;                       // K[0], K[4] of the reference's README.md:78
+    p->P[2] = (double)322.4656677246094f; p->P[6] = (double)240.64073181152344f;   // K[2], K[5]
+    p->P[10] = 1.0;
+    p->E[0] = p->E[5] = p->E[10] = p->E[15] = 1.0;
+    p->dims[0] = 0.2; p->dims[1] = 0.1; p->dims[2] = 0.03;               // iterative_closest_point.launch:39-41
+    p->thickness = 2;                                                    // draw_bbox.py:66
+    p->rgb[0] = 0; p->rgb[1] = 255; p->rgb[2] = 0;                       // draw_bbox.py:65
+}
+
+int cd_overlay_project(const double pose[16], const cd_overlay_params* op, cd_overlay_box* out) {
+    if (!pose || !out) return CD_ERR_INVALID_ARG;
+    cd_overlay_params def;
+    cd_default_overlay_params(&def);
+    if (!op) op = &def;
+    if (overlay_params_error(op)) return CD_ERR_INVALID_ARG;
+    const OverlayParams kp = overlay_kernel_params(op);
+    std::memset(out, 0, sizeof(*out));
+    int32_t uv[16];
+    for (int k = 0; k < 8; ++k) {
+        float cpt[3];
+        overlay_corner(pose, kp.dims, k, cpt);
+        if (!overlay_pixel(kp.M, cpt, &uv[2 * k], &uv[2 * k + 1])) return CD_OK;   // skipped: the zero record
+    }
+    std::memcpy(out->corners, uv, sizeof(uv));
+    out->drawn = 1;
+    return CD_OK;
+}
+
+int cd_draw_boxes_batch(cd_context* c, uint8_t* rgb8, int width, int height, int n_frames, const double* poses, const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* op, cd_overlay_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_draw_boxes_batch_impl(c, rgb8, width, height, n_frames, poses, n_boxes, boxes_per_frame, op, out, false); });
+}
+int cd_draw_boxes_batch_device(cd_context* c, uint8_t* d_rgb8, int width, int height, int n_frames, const double* poses, const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* op, cd_overlay_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_draw_boxes_batch_impl(c, d_rgb8, width, height, n_frames, poses, n_boxes, boxes_per_frame, op, out, true); });
+}
+int cd_draw_last_results(cd_context* c, uint8_t* rgb8, int width, int height, int which, const cd_overlay_params* op, cd_overlay_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_draw_last_results_impl(c, rgb8, width, height, which, op, out, false); });
+}
+int cd_draw_last_results_device(cd_context* c, uint8_t* d_rgb8, int width, int height, int which, const cd_overlay_params* op, cd_overlay_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_draw_last_results_impl(c, d_rgb8, width, height, which, op, out, true); });
 }
 
 int cd_set_frame_guesses(cd_context* c, const float* guesses, int n_frames) {

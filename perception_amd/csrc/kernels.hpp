@@ -142,4 +142,12 @@ bool color_fits_lds(int W, int H);
 void launch_color_bbox(hipStream_t s, const uint8_t* rgb, int W, int H, int F, const ColorGate& prm, const int* tables,
                        uint32_t* gmask, int* labels, size_t label_pitch, ColorRecord* out, int* status);
 
+// k_overlay.hip : rule C11, the projected boxes of draw_bbox.py drawn into tightly packed rgb8 images in place
+struct OverlayParams { double M[12]; double dims[3]; };   // M = P * E (row-major 3x4), the box's length / width / height
+struct OverlayBox { int32_t corners[16], drawn, reserved[3]; };   // = cd_overlay_box
+// poses: F * B row-major 4x4 doubles, box b of frame f at (f * B + b) * 16; n_boxes[f] <= B of them exist; out: F * B records
+void launch_overlay_project(hipStream_t s, const double* poses, const int32_t* n_boxes, int B, int F, const OverlayParams& op, OverlayBox* out);
+// img: F images of W * H * 3 bytes, W, H <= 8192; thickness 1 .. 64; boxes: the F * B records of launch_overlay_project
+void launch_overlay_raster(hipStream_t s, uint8_t* img, int W, int H, int B, int F, int thickness, const uint8_t rgb[3], const OverlayBox* boxes);
+
 }  // namespace cd
