@@ -104,9 +104,9 @@ class BatchPipeline:
             cx.process_batch_device(d_ptr, stride, n_points, n_frames, prm, results=res)
         return capi.results_to_array(res)[:n_frames].copy(), cx.timing()
 
-    def _run_depth(self, i, depth_ptr, color_ptr, n_frames, cam, prm):
+    def _run_depth(self, i, depth_ptr, color_ptr, n_frames, cam, prm, color_camera=None):
         cx, res = self.contexts[i], self._results[i]
-        cx.process_depth_batch_host_ptr(depth_ptr, color_ptr, n_frames, cam, prm, results=res)
+        cx.process_depth_batch_host_ptr(depth_ptr, color_ptr, n_frames, cam, prm, results=res, color_camera=color_camera)
         return capi.results_to_array(res)[:n_frames].copy(), cx.timing()
 
     def _free_context(self):
@@ -127,12 +127,13 @@ class BatchPipeline:
         self._busy[i] = fut
         return fut
 
-    def submit_depth(self, depth_ptr, color_ptr, n_frames, cam, prm):
+    def submit_depth(self, depth_ptr, color_ptr, n_frames, cam, prm, color_camera=None):
         """Queue one batch of depth images in HOST memory (depth_ptr: F x H x W uint16; color_ptr: F x H x W x 3 rgb8 registered
         to it, or None; pinned for full PCIe rate): cd_process_depth_batch, the images deprojected on the device.  Same Future
-        as submit()."""
+        as submit().  color_camera (a CdColorCamera): the pairs are UNREGISTERED, color_ptr is F x ch x cw x 3 at the colour
+        camera's size and the clouds are built by rule C12 (cd_process_depth_batch_mapped)."""
         i = self._free_context()
-        fut = self._pool.submit(self._run_depth, i, depth_ptr, color_ptr, n_frames, cam, prm)
+        fut = self._pool.submit(self._run_depth, i, depth_ptr, color_ptr, n_frames, cam, prm, color_camera)
         self._busy[i] = fut
         return fut
 

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = [
     "cd_get_bbox_source", "cd_get_frame_bboxes",
     "cd_default_overlay_params", "cd_overlay_project", "cd_draw_boxes_batch", "cd_draw_boxes_batch_device", "cd_draw_last_results",
     "cd_draw_last_results_device",
+    "cd_default_color_camera", "cd_color_camera_struct_size", "cd_texture_project", "cd_depth_to_cloud_mapped",
+    "cd_process_depth_batch_mapped", "cd_process_depth_batch_mapped_device",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -51,6 +53,7 @@ CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
 CD_COLOR_NONE, CD_COLOR_RGB8 = 0, 1
 CD_BBOX_PARAMS, CD_BBOX_PER_FRAME, CD_BBOX_COLOR = 0, 1, 2
 CD_DRAW_ACCEPTED, CD_DRAW_ALL = 0, 1
+CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -118,6 +121,17 @@ class CdDepthCamera(C.Structure):
         ("width", C.c_int32), ("height", C.c_int32),
         ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
         ("depth_scale", C.c_float), ("color", C.c_int32),
+    ]
+
+
+class CdColorCamera(C.Structure):
+    """cd_color_camera: CameraInfo of the rgb8 colour stream of an UNREGISTERED pair, the depth -> colour extrinsics
+    (p_colour = R p_depth + t, R row-major) and what becomes of a point that projects outside the colour image (rule C12)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("R", C.c_float * 9), ("t", C.c_float * 3),
+        ("no_texture", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -223,6 +237,36 @@ def default_depth_camera():
     return cam
 
 
+def default_color_camera():
+    """The D435 colour stream of the reference's README.md:48-54 (640 x 480, K of its CameraInfo), R = identity, t = 0 (the
+    reference records no extrinsic values), CD_NOTEX_DROP.  Pure Python mirror of cd_default_color_camera()."""
+    cc = CdColorCamera()
+    cc.width, cc.height = 640, 480
+    cc.fx, cc.fy = 616.8246459960938, 616.609375
+    cc.cx, cc.cy = 321.81976318359375, 239.91116333007812
+    cc.R[:] = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+    cc.no_texture = CD_NOTEX_DROP
+    return cc
+
+
+def color_camera(width=None, height=None, K=None, R=None, t=None, no_texture=None):
+    """default_color_camera() with the given fields replaced (K = fx, fy, cx, cy; R 3x3 row-major depth -> colour; t metres)."""
+    cc = default_color_camera()
+    if width is not None:
+        cc.width = int(width)
+    if height is not None:
+        cc.height = int(height)
+    if K is not None:
+        cc.fx, cc.fy, cc.cx, cc.cy = (float(v) for v in K)
+    if R is not None:
+        cc.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+    if t is not None:
+        cc.t[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+    if no_texture is not None:
+        cc.no_texture = int(no_texture)
+    return cc
+
+
 _lib = None
 
 
@@ -307,6 +351,14 @@ def load_library(path=None):
         f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, i32p, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
     for f in (lib.cd_draw_last_results, lib.cd_draw_last_results_device):
         f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
+    lib.cd_default_color_camera.argtypes = [C.POINTER(CdColorCamera)]
+    lib.cd_default_color_camera.restype = None
+    lib.cd_color_camera_struct_size.argtypes = []
+    lib.cd_texture_project.argtypes = [C.POINTER(CdDepthCamera), C.POINTER(CdColorCamera), C.c_int, C.c_int, C.c_uint16, f32p, i32p, i32p]
+    lib.cd_depth_to_cloud_mapped.argtypes = [vp, C.POINTER(CdDepthCamera), C.POINTER(CdColorCamera), vp, vp, vp, C.c_size_t, C.c_int,
+                                             C.c_int, ip]
+    for f in (lib.cd_process_depth_batch_mapped, lib.cd_process_depth_batch_mapped_device):
+        f.argtypes = [vp, C.POINTER(CdDepthCamera), C.POINTER(CdColorCamera), vp, vp, C.c_int, C.POINTER(CdParams), vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -676,22 +728,37 @@ class Context:
         self._check(self.lib.cd_template_nearest(self.h, slot, _ptr(a), stride, n, _ptr(idx), _ptr(d2)))
         return idx[:n], d2[:n]
 
-    def depth_to_cloud(self, cam, depth, color=None, stride_bytes=16, rgb_offset=12):
+    def depth_to_cloud(self, cam, depth, color=None, stride_bytes=16, rgb_offset=12, color_camera=None):
         """One depth image (H, W) uint16 (+ colour (H, W, 3) uint8 when cam.color is CD_COLOR_RGB8) -> the organized cloud as
         (W * H, stride_bytes / 4) uint32 records: x,y,z at words 0..2 (NaN where the depth is 0), the packed rgb at rgb_offset
-        (-1: none), the rest zero."""
+        (-1: none), the rest zero.  color_camera (a CdColorCamera): the pair is UNREGISTERED - colour is (ch, cw, 3) at the colour
+        camera's size and the cloud is built by rule C12 (cd_depth_to_cloud_mapped)."""
         d = np.ascontiguousarray(depth, dtype=np.uint16)
         c = None if color is None else np.ascontiguousarray(color, dtype=np.uint8)
         n = int(cam.width) * int(cam.height)
         out = np.zeros((max(n, 1), stride_bytes // 4), np.uint32)
         cnt = C.c_int()
+        if color_camera is not None:
+            self._check(self.lib.cd_depth_to_cloud_mapped(self.h, C.byref(cam), C.byref(color_camera), _ptr(d), _ptr(c), _ptr(out),
+                                                          stride_bytes, rgb_offset, n, C.byref(cnt)))
+            return out[:cnt.value]
         self._check(self.lib.cd_depth_to_cloud(self.h, C.byref(cam), _ptr(d), _ptr(c), _ptr(out), stride_bytes, rgb_offset, n,
                                                C.byref(cnt)))
         return out[:cnt.value]
 
-    def process_depth_batch(self, depth, color, cam, prm, want_indices=False):
+    def _depth_call(self, color_camera, device, cam, depth_ptr, color_ptr, n_frames, prm, res, pi, lb):
+        """cd_process_depth_batch[_device], or with a colour camera cd_process_depth_batch_mapped[_device]."""
+        tail = (depth_ptr, color_ptr, n_frames, C.byref(prm), C.cast(res, C.c_void_p), _ptr(pi), _ptr(lb))
+        if color_camera is None:
+            fn = self.lib.cd_process_depth_batch_device if device else self.lib.cd_process_depth_batch
+            return self._check(fn(self.h, C.byref(cam), *tail))
+        fn = self.lib.cd_process_depth_batch_mapped_device if device else self.lib.cd_process_depth_batch_mapped
+        return self._check(fn(self.h, C.byref(cam), C.byref(color_camera), *tail))
+
+    def process_depth_batch(self, depth, color, cam, prm, want_indices=False, color_camera=None):
         """depth (F, H, W) uint16, color (F, H, W, 3) uint8 or None (cam.color decides whether it is read): the chain on the
-        organized clouds the images deproject to.  Returns (results, plane_inliers, labels) as process_batch does."""
+        organized clouds the images deproject to.  Returns (results, plane_inliers, labels) as process_batch does.
+        color_camera: the pairs are unregistered, color is (F, ch, cw, 3) (rule C12, cd_process_depth_batch_mapped)."""
         d = np.ascontiguousarray(depth, dtype=np.uint16)
         assert d.ndim == 3
         c = None if color is None else np.ascontiguousarray(color, dtype=np.uint8)
@@ -699,26 +766,25 @@ class Context:
         res = (CdFrameResult * F)()
         pi = np.empty((F, N), np.int32) if want_indices else None
         lb = np.empty((F, N), np.int32) if want_indices else None
-        self._check(self.lib.cd_process_depth_batch(self.h, C.byref(cam), _ptr(d), _ptr(c), F, C.byref(prm),
-                                                    C.cast(res, C.c_void_p), _ptr(pi), _ptr(lb)))
+        self._depth_call(color_camera, False, cam, _ptr(d), _ptr(c), F, prm, res, pi, lb)
         return res, pi, lb
 
-    def process_depth_batch_device(self, depth, color, cam, prm, results=None, plane_inliers=None, labels=None):
+    def process_depth_batch_device(self, depth, color, cam, prm, results=None, plane_inliers=None, labels=None, color_camera=None):
         """depth: contiguous torch uint16 tensor (F, H, W) in HBM, color: uint8 tensor (F, H, W, 3) or None (data_ptr(); the
-        caller has synchronised the stream that wrote them, as for process_batch_device)."""
+        caller has synchronised the stream that wrote them, as for process_batch_device).  color_camera: as process_depth_batch."""
         assert depth.is_contiguous() and depth.dim() == 3 and (color is None or color.is_contiguous())
         F = depth.shape[0]
         res = results if results is not None else (CdFrameResult * F)()
-        self._check(self.lib.cd_process_depth_batch_device(self.h, C.byref(cam), C.c_void_p(depth.data_ptr()),
-                                                           None if color is None else C.c_void_p(color.data_ptr()), F, C.byref(prm),
-                                                           C.cast(res, C.c_void_p), _ptr(plane_inliers), _ptr(labels)))
+        self._depth_call(color_camera, True, cam, C.c_void_p(depth.data_ptr()), None if color is None else C.c_void_p(color.data_ptr()),
+                         F, prm, res, plane_inliers, labels)
         return res
 
-    def process_depth_batch_host_ptr(self, depth_ptr, color_ptr, n_frames, cam, prm, results=None):
-        """cd_process_depth_batch on raw HOST pointers (e.g. pinned torch tensors' data_ptr()): the uploads are part of the call."""
+    def process_depth_batch_host_ptr(self, depth_ptr, color_ptr, n_frames, cam, prm, results=None, color_camera=None):
+        """cd_process_depth_batch on raw HOST pointers (e.g. pinned torch tensors' data_ptr()): the uploads are part of the call.
+        color_camera: as process_depth_batch."""
         res = results if results is not None else (CdFrameResult * n_frames)()
-        self._check(self.lib.cd_process_depth_batch(self.h, C.byref(cam), C.c_void_p(depth_ptr), C.c_void_p(color_ptr) if color_ptr else None,
-                                                    n_frames, C.byref(prm), C.cast(res, C.c_void_p), None, None))
+        self._depth_call(color_camera, False, cam, C.c_void_p(depth_ptr), C.c_void_p(color_ptr) if color_ptr else None, n_frames, prm,
+                         res, None, None)
         return res
 
     def timing(self):
@@ -758,6 +824,19 @@ def surface_guess(Rt):
     if st != CD_OK:
         raise CuboidError(st, "cd_surface_guess: non-finite input")
     return g.reshape(4, 4)
+
+
+def texture_project(cam, ccam, u, v, d):
+    """Host-only rule C12 steps 1-6 for one pixel (cd_texture_project): (xyz float32[3], (iu, iv), textured)."""
+    lib = load_library()
+    xyz = np.zeros(3, np.float32)
+    pix = np.zeros(2, np.int32)
+    tex = C.c_int32()
+    st = lib.cd_texture_project(C.byref(cam), C.byref(ccam), int(u), int(v), int(d), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                pix.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(tex))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_texture_project: a camera the mapped calls refuse")
+    return xyz, (int(pix[0]), int(pix[1])), int(tex.value)
 
 
 def overlay_project(pose, params=None):

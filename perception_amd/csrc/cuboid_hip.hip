@@ -20,6 +20,7 @@
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "overlay_math.hpp"
+#include "texture_math.hpp"
 
 using namespace cd;
 
@@ -1521,7 +1522,28 @@ struct DepthJob {
     const cd_depth_camera* cam;
     const uint16_t* depth;
     const uint8_t* color;   // nullptr: no colour
+    const cd_color_camera* ccam = nullptr;   // a mapped call (rule C12, k_texture.hip): `color` is ccam->width x ccam->height per frame
 };
+
+TextureParams texture_params(const cd_depth_camera* cam, const cd_color_camera* cc) {
+    TextureParams tp;
+    tp.fx = cam->fx; tp.fy = cam->fy; tp.cx = cam->cx; tp.cy = cam->cy; tp.depth_scale = cam->depth_scale;
+    tp.cfx = cc->fx; tp.cfy = cc->fy; tp.ccx = cc->cx; tp.ccy = cc->cy;
+    for (int i = 0; i < 9; ++i) tp.R[i] = cc->R[i];
+    for (int i = 0; i < 3; ++i) tp.t[i] = cc->t[i];
+    tp.cw = cc->width; tp.ch = cc->height;
+    tp.keep = cc->no_texture == CD_NOTEX_KEEP;
+    return tp;
+}
+
+// the deprojection of a depth call into its records: rule C7 for registered images, rule C12 for a mapped call
+void launch_depth_job(hipStream_t s, const DepthJob* dj, int F, float4* out) {
+    if (dj->ccam)
+        launch_texture_map(s, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, texture_params(dj->cam, dj->ccam), out);
+    else
+        launch_deproject(s, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, dj->cam->fx, dj->cam->fy, dj->cam->cx, dj->cam->cy,
+                         dj->cam->depth_scale, out);
+}
 
 // ---- colour gate (rule C10, k_color.hip) ---------------------------------------------------------------------------------------
 static_assert(sizeof(ColorRecord) == sizeof(cd_color_bbox) && offsetof(ColorRecord, rect) == 0 && offsetof(cd_color_bbox, rect) == 0, "the kernel's record is cd_color_bbox");
@@ -1627,13 +1649,12 @@ int batch_prologue(cd_context* c, int gate_source, const void* d_frames, int F, 
         HIPCHK(c, xfer(c, c->d_rects, c->h_rects, sizeof(int32_t) * 4 * (size_t)F, hipMemcpyHostToDevice));
         c->call_rects = FrameRects{c->d_rects, 4};
     } else if (gate_source == CD_BBOX_COLOR) {
-        int st = stage_color(c, dj->color, dj->cam->width, dj->cam->height, F, &c->color_prm);
+        // (a mapped call: the raw colour images at their own size, so the rectangles are in colour pixels)
+        int st = stage_color(c, dj->color, dj->ccam ? dj->ccam->width : dj->cam->width, dj->ccam ? dj->ccam->height : dj->cam->height, F, &c->color_prm);
         if (st) return st;
         c->call_rects = FrameRects{reinterpret_cast<const int32_t*>(c->d_crec), (int32_t)(sizeof(ColorRecord) / sizeof(int32_t))};   // (rect is the record's first member)
     }
-    if (dj)
-        LAUNCH(c, launch_deproject(c->stream, dj->depth, dj->color, dj->cam->width, dj->cam->height, F, dj->cam->fx, dj->cam->fy, dj->cam->cx,
-                                   dj->cam->cy, dj->cam->depth_scale, (float4*)const_cast<void*>(d_frames)));
+    if (dj) LAUNCH(c, launch_depth_job(c->stream, dj, F, (float4*)const_cast<void*>(d_frames)));
     return c->zero_once ? zero_batch_scratch(c, F) : CD_OK;
 }
 
@@ -3044,9 +3065,39 @@ static int check_depth(cd_context* c, const cd_depth_camera* cam, const void* de
     return CD_OK;
 }
 
-// host images -> the context's depth / colour buffers (one copy each, on the context's stream)
-static int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, DepthJob* dj) {
+static_assert(sizeof(cd_color_camera) == 80 && offsetof(cd_color_camera, no_texture) == 72, "cd_color_camera has no padding holes");
+// what a mapped call (rule C12) needs besides check_depth: nullptr = fine, else what is wrong (shared with the host-only
+// cd_texture_project)
+static const char* color_camera_error(const cd_color_camera* cc) {
+    if (!cc) return "colour camera is NULL";
+    if (cc->width <= 0 || cc->height <= 0) return "the colour image's width * height must be in 1 .. the context's max_points";
+    for (float v : {cc->fx, cc->fy})
+        if (!(std::isfinite(v) && v > 0.f)) return "the colour camera's fx and fy must be finite and > 0";
+    for (float v : {cc->cx, cc->cy})
+        if (!std::isfinite(v)) return "the colour camera's cx or cy is not finite";
+    for (float v : cc->R) if (!std::isfinite(v)) return "R holds a non-finite value";
+    for (float v : cc->t) if (!std::isfinite(v)) return "t holds a non-finite value";
+    if (cc->no_texture != CD_NOTEX_DROP && cc->no_texture != CD_NOTEX_KEEP) return "unknown no_texture mode";
+    return nullptr;
+}
+
+// every check of the header's list for a mapped call, before anything is copied or launched
+static int check_mapped(cd_context* c, const cd_depth_camera* cam, const cd_color_camera* cc, const void* depth, const void* color, int n_frames) {
+    int st = check_depth(c, cam, depth, color, n_frames);
+    if (st) return st;
+    if (cam->color != CD_COLOR_RGB8) return fail(c, CD_ERR_INVALID_ARG, "a mapped call needs CD_COLOR_RGB8");
+    if (const char* msg = color_camera_error(cc)) return fail(c, CD_ERR_INVALID_ARG, msg);
+    if ((long long)cc->width * cc->height > (long long)c->N)
+        return fail(c, CD_ERR_INVALID_ARG, "the colour image's width * height must be in 1 .. the context's max_points");
+    return CD_OK;
+}
+
+// host images -> the context's depth / colour buffers (one copy each, on the context's stream); ccam: the colour images have
+// their own size
+static int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, DepthJob* dj,
+                        const cd_color_camera* ccam = nullptr) {
     const size_t px = (size_t)cam->width * cam->height * n_frames;
+    const size_t cpx = ccam ? (size_t)ccam->width * ccam->height * n_frames : px;
     if (!c->d_depth) HIPCHK(c, dalloc(&c->d_depth, (size_t)c->N * c->F));
     HIPCHK(c, hipMemcpyAsync(c->d_depth, depth, px * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     dj->cam = cam;
@@ -3054,20 +3105,23 @@ static int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_
     dj->color = nullptr;
     if (cam->color == CD_COLOR_RGB8) {
         if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
-        HIPCHK(c, hipMemcpyAsync(c->d_color, color, px * 3, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_color, color, cpx * 3, hipMemcpyHostToDevice, c->stream));
         dj->color = c->d_color;
     }
+    dj->ccam = ccam;
     return CD_OK;
 }
 
+// ccam != nullptr: the mapped call (rule C12)
 static int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames,
-                                       const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, bool on_device) {
+                                       const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels, bool on_device,
+                                       const cd_color_camera* ccam = nullptr, bool mapped = false) {
     if (!c) return CD_ERR_INVALID_ARG;
     hipSetDevice(c->device);
     int st = check_params(c, p);
     if (st) return st;
     if (!results) return fail(c, CD_ERR_INVALID_ARG, "results is NULL");
-    st = check_depth(c, cam, depth, color, n_frames);
+    st = mapped ? check_mapped(c, cam, ccam, depth, color, n_frames) : check_depth(c, cam, depth, color, n_frames);
     if (st) return st;
     st = check_bbox_source(c, p, n_frames, cam->color == CD_COLOR_RGB8);   // (before the uploads)
     if (st) return st;
@@ -3076,22 +3130,23 @@ static int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam
     const int P = cam->width * cam->height;
     st = ensure_input(c, (size_t)P * n_frames * sizeof(float4));
     if (st) return st;
-    DepthJob dj{cam, depth, cam->color == CD_COLOR_RGB8 ? color : nullptr};
+    DepthJob dj{cam, depth, cam->color == CD_COLOR_RGB8 ? color : nullptr, ccam};
     if (!on_device) {
-        st = upload_depth(c, cam, depth, color, n_frames, &dj);
+        st = upload_depth(c, cam, depth, color, n_frames, &dj, ccam);
         if (st) return st;
     }
     return process_batch_impl(c, c->d_in, sizeof(float4), P, n_frames, &q, results, plane_inliers, labels, &dj);
 }
 
 static int cd_depth_to_cloud_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, void* out_records,
-                                  size_t stride, int rgb_offset, int capacity, int* out_n) {
+                                  size_t stride, int rgb_offset, int capacity, int* out_n, const cd_color_camera* ccam = nullptr,
+                                  bool mapped = false) {
     if (!c) return CD_ERR_INVALID_ARG;
     hipSetDevice(c->device);
     if (!out_n || capacity < 0 || (capacity > 0 && !out_records) || stride < 12 || (stride & 3) ||
         (rgb_offset >= 0 && (rgb_offset < 12 || (rgb_offset & 3) || (size_t)rgb_offset + 4 > stride)))
         return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
-    int st = check_depth(c, cam, depth, color, 1);
+    int st = mapped ? check_mapped(c, cam, ccam, depth, color, 1) : check_depth(c, cam, depth, color, 1);
     if (st) return st;
     *out_n = 0;
     invalidate_last(c);
@@ -3102,10 +3157,9 @@ static int cd_depth_to_cloud_impl(cd_context* c, const cd_depth_camera* cam, con
     st = ensure_input(c, ((rec_bytes + 255) & ~(size_t)255) + (size_t)P * stride);
     if (st) return st;
     DepthJob dj;
-    st = upload_depth(c, cam, depth, color, 1, &dj);
+    st = upload_depth(c, cam, depth, color, 1, &dj, ccam);
     if (st) return st;
-    LAUNCH(c, launch_deproject(c->stream, dj.depth, dj.color, cam->width, cam->height, 1, cam->fx, cam->fy, cam->cx, cam->cy, cam->depth_scale,
-                               reinterpret_cast<float4*>(c->d_in)));
+    LAUNCH(c, launch_depth_job(c->stream, &dj, 1, reinterpret_cast<float4*>(c->d_in)));
     st = download_records(c, reinterpret_cast<const float4*>(c->d_in), P, stride, rgb_offset, 0u, out_records, rec_bytes);
     if (st) return st;
     *out_n = P;
@@ -3269,6 +3323,32 @@ void cd_default_depth_camera(cd_depth_camera* cam) {
     cam->cx = 322.4656677246094f; cam->cy = 240.64073181152344f;        // K[2], K[5]
     cam->depth_scale = 0.001f;                                           // 16UC1 in millimetres (the RealSense driver's unit)
     cam->color = CD_COLOR_NONE;
+}
+
+void cd_default_color_camera(cd_color_camera* cc) {
+    if (!cc) return;
+    std::memset(cc, 0, sizeof(*cc));
+    cc->width = 640; cc->height = 480;                                   // README.md:48-49 of the reference
+    cc->fx = 616.8246459960938f; cc->fy = 616.609375f;                  // K[0], K[4] (README.md:52)
+    cc->cx = 321.81976318359375f; cc->cy = 239.91116333007812f;         // K[2], K[5]
+    cc->R[0] = cc->R[4] = cc->R[8] = 1.f;                                // the reference records no extrinsic values
+    cc->no_texture = CD_NOTEX_DROP;
+}
+
+int cd_color_camera_struct_size(void) { return (int)sizeof(cd_color_camera); }
+
+int cd_texture_project(const cd_depth_camera* cam, const cd_color_camera* cc, int u, int v, uint16_t d, float xyz[3], int32_t pix[2],
+                       int32_t* textured) {
+    if (!cam || color_camera_error(cc) || u < 0 || v < 0) return CD_ERR_INVALID_ARG;
+    for (float f : {cam->fx, cam->fy, cam->depth_scale})
+        if (!(std::isfinite(f) && f > 0.f)) return CD_ERR_INVALID_ARG;
+    float q[3];
+    int32_t px[2];
+    const bool tex = texture_point(texture_params(cam, cc), (uint32_t)u, (uint32_t)v, d, q, px);
+    if (xyz) std::memcpy(xyz, q, sizeof(q));
+    if (pix) std::memcpy(pix, px, sizeof(px));
+    if (textured) *textured = tex ? 1 : 0;
+    return CD_OK;
 }
 
 int cd_get_frame_cloud(cd_context* c, int frame, int which, void* out_records, size_t stride, int rgb_offset, int capacity, int* out_n) {
@@ -3622,6 +3702,18 @@ int cd_depth_to_cloud(cd_context* c, const cd_depth_camera* cam, const uint16_t*
 int cd_process_depth_batch(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
     if (!c) return CD_ERR_INVALID_ARG;
     return with_scan_retry(c, [&]() { return cd_process_depth_batch_impl(c, cam, depth, color, n_frames, p, results, plane_inliers, labels, false); });
+}
+int cd_depth_to_cloud_mapped(cd_context* c, const cd_depth_camera* cam, const cd_color_camera* ccam, const uint16_t* depth, const uint8_t* color, void* out_records, size_t stride, int rgb_offset, int capacity, int* out_n) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_depth_to_cloud_impl(c, cam, depth, color, out_records, stride, rgb_offset, capacity, out_n, ccam, true); });
+}
+int cd_process_depth_batch_mapped(cd_context* c, const cd_depth_camera* cam, const cd_color_camera* ccam, const uint16_t* depth, const uint8_t* color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_process_depth_batch_impl(c, cam, depth, color, n_frames, p, results, plane_inliers, labels, false, ccam, true); });
+}
+int cd_process_depth_batch_mapped_device(cd_context* c, const cd_depth_camera* cam, const cd_color_camera* ccam, const uint16_t* d_depth, const uint8_t* d_color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_process_depth_batch_impl(c, cam, d_depth, d_color, n_frames, p, results, plane_inliers, labels, true, ccam, true); });
 }
 int cd_process_depth_batch_device(cd_context* c, const cd_depth_camera* cam, const uint16_t* d_depth, const uint8_t* d_color, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
     if (!c) return CD_ERR_INVALID_ARG;

@@ -124,6 +124,11 @@ struct DeprojectParams {
 void launch_deproject(hipStream_t s, const uint16_t* depth, const uint8_t* color, int width, int height, int n_frames, float fx,
                       float fy, float cx, float cy, float depth_scale, float4* out);
 
+// k_texture.hip : rule C12, unregistered depth + colour images -> the coloured organized cloud (texture_math.hpp: TextureParams)
+struct TextureParams;
+void launch_texture_map(hipStream_t s, const uint16_t* depth, const uint8_t* color, int width, int height, int n_frames,
+                        const TextureParams& tp, float4* out);
+
 // k_surface.hip : the batched surface-normal estimation's cloud load and plane midpoints (rule C6 sums)
 void launch_surface_load(hipStream_t s, const void* in, size_t stride, size_t fpitch, const int* count, int count_pitch, int pitch,
                          int max_count, int F, float4* out);

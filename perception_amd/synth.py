@@ -212,6 +212,54 @@ def depth_camera_params(width=WIDTH, height=HEIGHT):
     return FX * sx, FY * sy, CX * sx, CY * sy
 
 
+def render_color_camera(scene, ccam):
+    """The scene as the COLOUR camera of an unregistered pair sees it: (rgb8 uint8 (ch, cw, 3), zc float64 (ch, cw)).  ccam:
+    anything with the fields of cd_color_camera - its own size and K, its frame p_colour = R p_depth + t (R row-major), so its
+    centre sits at -R^T t of the depth frame the scene is given in.  Same table and box colours as render(); no noise, no
+    invalid pixels; zc is the depth along the colour camera's axis of what each pixel shows (inf where a ray leaves the scene:
+    such a pixel keeps the table colour, as in render())."""
+    cw, ch = int(ccam.width), int(ccam.height)
+    npx = cw * ch
+    R = np.array([float(x) for x in ccam.R]).reshape(3, 3)
+    tv = np.array([float(x) for x in ccam.t])
+    org = -(R.T @ tv)                                   # the colour camera's centre, depth frame
+    v, u = np.divmod(np.arange(npx), cw)
+    dc = np.stack([(u - float(ccam.cx)) / float(ccam.fx), (v - float(ccam.cy)) / float(ccam.fy), np.ones(npx)], axis=0)
+    dx, dy, dz = R.T @ dc                               # ray directions in the depth frame; the ray parameter is zc
+    nrm, p0 = scene["n"], scene["p0"]
+    denom = dx * nrm[0] + dy * nrm[1] + dz * nrm[2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(denom < -1e-9, ((p0 - org) @ nrm) / denom, np.inf)
+    t = np.where(t > 0, t, np.inf)
+    color = np.full(npx, _pack_rgb(150, 140, 130), dtype=np.uint32)
+    for k, bx in enumerate(scene["boxes"]):
+        Rb = bx["R"]
+        o = Rb.T @ (org - bx["c"])                      # ray origin in the box frame
+        tn = np.full(npx, -np.inf)
+        tf = np.full(npx, np.inf)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for a in range(3):                          # slab test, one box axis at a time
+                dd = dx * Rb[0, a] + dy * Rb[1, a] + dz * Rb[2, a]
+                t1 = (-bx["half"][a] - o[a]) / dd
+                t2 = (bx["half"][a] - o[a]) / dd
+                np.maximum(tn, np.minimum(t1, t2), out=tn)
+                np.minimum(tf, np.maximum(t1, t2), out=tf)
+        hit = (tn <= tf) & (tn > 0) & (tn < t)
+        t = np.where(hit, tn, t)
+        color = np.where(hit, _pack_rgb(200, 30 + 60 * k, 40), color)
+    rgb = np.stack([(color >> 16) & 255, (color >> 8) & 255, color & 255], axis=1).astype(np.uint8)
+    return rgb.reshape(ch, cw, 3), t.reshape(ch, cw)
+
+
+def unregistered_frame(index, ccam, k_obj=None, width=WIDTH, height=HEIGHT):
+    """Frame `index` as a D435 delivers it WITHOUT align_depth: (depth uint16 (height, width), rgb8 uint8 (ccam.height,
+    ccam.width, 3)).  The depth is depth_frame's; the colour image is the same scene rendered from the colour camera
+    (render_color_camera): its own size and intrinsics, its origin and axes those of the extrinsics in ccam."""
+    depth, _ = depth_frame(index, k_obj, width, height)
+    rgb, _ = render_color_camera(scene_for(index, k_obj), ccam)
+    return depth, rgb
+
+
 def truth_poses(scene):
     """4x4 template->camera pose of each cuboid (for the pose-error report)."""
     out = []
