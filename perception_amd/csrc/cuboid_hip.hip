@@ -17,6 +17,7 @@
 #include <random>
 #include <vector>
 
+#include "device_buffer.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "overlay_math.hpp"
@@ -24,60 +25,72 @@
 
 using namespace cd;
 
-struct cd_context {
+// The streams and events of a context.  A base of cd_context, so that they outlive its buffers: the members of cd_context
+// are destroyed (the buffers freed) before this destructor runs.  stream2 / stream3: the streams of the persistent ICP
+// launches: the second launch of a mixed-template batch runs beside the first (stream2); with icp_lowprio both are low-priority
+// streams, so that CUs that come free go to the short front-end kernels of the other batches in flight before the next
+// persistent workgroup
+struct cd_streams {
+    hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;
+    hipEvent_t ev[8] = {nullptr}, ev2[3] = {nullptr, nullptr, nullptr};
+    ~cd_streams() {
+        for (auto& e : ev2) if (e) hipEventDestroy(e);
+        for (auto& e : ev) if (e) hipEventDestroy(e);
+        for (hipStream_t s : {stream2, stream3, stream}) if (s) hipStreamDestroy(s);
+    }
+};
+
+// Every buffer is an owning member (device_buffer.hpp): allocated in cd_create or grown on first use (GROW), freed with the context.
+struct cd_context : cd_streams {
     int device = 0;
-    hipStream_t stream = nullptr;
     int N = 0, F = 0, T = 0;   // capacities: points per frame, frames, tiles per frame
     char err[512] = {0};
     // input staging (host-pointer API)
-    char* d_in = nullptr;
-    size_t d_in_bytes = 0;
+    DevBuf<char> d_in;   // (capacity in bytes)
     // depth-image input (cd_process_depth_batch): upload buffers of their own, allocated at the context's capacity on first use
     // (d_in is the deprojection's destination, is re-allocated by ensure_input and is the read-back staging area)
-    uint16_t* d_depth = nullptr;
-    uint8_t* d_color = nullptr;
+    DevBuf<uint16_t> d_depth;
+    DevBuf<uint8_t> d_color;
     // per-frame scalars
-    FrameState* d_fs = nullptr;
-    FrameState* h_fs = nullptr;
+    DevBuf<FrameState> d_fs;
+    PinBuf<FrameState> h_fs;
     // ordered-compaction tile counters
-    int *d_tileA = nullptr, *d_tileB = nullptr, *d_tileK = nullptr, *d_tileC = nullptr;   // (tileC: the centroid kernel's scan state - its own array, so that one launch can zero every array of a batch up front)
+    DevBuf<int> d_tileA, d_tileB, d_tileK, d_tileC;   // (tileC: the centroid kernel's scan state - its own array, so that one launch can zero every array of a batch up front)
     bool batch_zeroed = false;      // a fused batch call has zeroed the scratch arrays of all its stages in one launch (zero_batch_scratch): the stages skip their own fills
     bool crop_two_pass = false;   // CUBOID_CROP_TWO_PASS=1: always the two-pass crop
     int icp_persist = 1;          // CUBOID_ICP_PERSIST=0: the sliced driver always in its multi-launch form; 2: the persistent
                                   // launch starts with its abort flag raised (tests the hand-over to the multi-launch form)
     // point buffers (float4 = x,y,z,rgb bits)
-    float4 *d_cpt = nullptr, *d_vox = nullptr, *d_obj = nullptr, *d_src0 = nullptr, *d_src = nullptr;
-    uint32_t *d_key[2] = {nullptr, nullptr}, *d_val[2] = {nullptr, nullptr}, *d_ghist = nullptr;
-    int* d_sstate = nullptr;   // chained-scan state of the radix passes, [pass][F][tiles][256]
-    unsigned long long* d_tile64 = nullptr;   // chained-scan state of k_crop_runs: (points, runs) per tile, [F][T]
+    DevBuf<float4> d_cpt, d_vox, d_obj, d_src0, d_src;
+    DevBuf<uint32_t> d_key[2], d_val[2], d_ghist;
+    DevBuf<int> d_sstate;   // chained-scan state of the radix passes, [pass][F][tiles][256]
+    DevBuf<unsigned long long> d_tile64;   // chained-scan state of k_crop_runs: (points, runs) per tile, [F][T]
     bool crop_runs = true;      // CUBOID_CROP_RUNS=0: the crop writes per-point keys and k_voxel_runs finds the runs (rounds 2-3)
-    int* d_ticket = nullptr;   // ticket counters, one per frame (TICKET_PITCH ints apart), of the kernels that scan over tiles (take_ticket, common.hpp): zero between launches
+    DevBuf<int> d_ticket;   // ticket counters, one per frame (TICKET_PITCH ints apart), of the kernels that scan over tiles (take_ticket, common.hpp): zero between launches
     // RANSAC
-    int* d_rnd = nullptr;
-    float4* d_models = nullptr;
-    int *d_valid = nullptr, *d_counts = nullptr, *d_active = nullptr;
-    int *h_valid = nullptr, *h_counts = nullptr, *h_active = nullptr;
-    float4 *d_model = nullptr, *h_model = nullptr, *h_models = nullptr;
-    int *d_have = nullptr, *h_have = nullptr;
-    unsigned long long *d_sums = nullptr, *h_sums = nullptr;
+    DevBuf<int> d_rnd, d_valid, d_counts, d_active, d_have;
+    PinBuf<int> h_valid, h_counts, h_active, h_have;
+    DevBuf<float4> d_models, d_model;
+    PinBuf<float4> h_model, h_models;
+    DevBuf<unsigned long long> d_sums;
+    PinBuf<unsigned long long> h_sums;
     // extract / cluster
-    int *d_plane_idx = nullptr, *d_head = nullptr, *d_next = nullptr, *d_parent = nullptr, *d_csize = nullptr,
-        *d_rank = nullptr, *d_cand = nullptr, *d_sizes = nullptr, *d_label = nullptr;
+    DevBuf<int> d_plane_idx, d_head, d_next, d_parent, d_csize, d_rank, d_cand, d_sizes, d_label;
     // templates
-    float4 *d_tpl = nullptr, *d_tlo = nullptr, *d_thi = nullptr;   // points + per-64-run boxes
-    float4 *d_tplk = nullptr, *d_tlok = nullptr, *d_thik = nullptr;   // templates in k-d patch order (sliced path)
-    IcpGrid* d_grid = nullptr;                                    // per template slot
-    unsigned short* d_kdmap = nullptr;                            // k-d patch order -> cell-sorted position (resident templates)
-    unsigned short* d_tcell = nullptr;                            // cell start tables, ICP_CELL_STRIDE entries per slot
-    int* d_nn = nullptr;                                          // last NN index of every ICP source point
-    float* d_d2 = nullptr;                                        // its squared distance
-    int* d_queue = nullptr;                                       // ICP work queue heads (one per template group)
-    int* d_don = nullptr;                                         // k_icp_pipe: hand-over control block + mailbox (common.hpp DON_*)
+    DevBuf<float4> d_tpl, d_tlo, d_thi;   // points + per-64-run boxes
+    DevBuf<float4> d_tplk, d_tlok, d_thik;   // templates in k-d patch order (sliced path)
+    DevBuf<IcpGrid> d_grid;                                       // per template slot
+    DevBuf<unsigned short> d_kdmap;                               // k-d patch order -> cell-sorted position (resident templates)
+    DevBuf<unsigned short> d_tcell;                               // cell start tables, ICP_CELL_STRIDE entries per slot
+    DevBuf<int> d_nn;                                             // last NN index of every ICP source point
+    DevBuf<float> d_d2;                                           // its squared distance
+    DevBuf<int> d_queue;                                          // ICP work queue heads (one per template group)
+    DevBuf<int> d_don;                                            // k_icp_pipe: hand-over control block + mailbox (common.hpp DON_*)
     int don_idle = 0, don_fault = 0;                              // CUBOID_ICP_DON_IDLE / CUBOID_ICP_DON_FAULT: tests of the hand-over path (IcpParams::don_idle / don_fault)
     int icp_donate = -1;                                          // CUBOID_ICP_DONATE: -1 auto (a call alone on the device), 0 never, 1 always
-    int* d_wgtab = nullptr;                                       // k_icp_pipe: {first item, end item, queue} per workgroup
-    int* h_wgtab = nullptr;                                       // its pinned staging copy (3 * 1024 ints)
-    int* h_ctl = nullptr;                                         // pinned: control words of k_icp_persist going up [0..7], coming back [8]
+    DevBuf<int> d_wgtab;                                          // k_icp_pipe: {first item, end item, queue} per workgroup
+    PinBuf<int> h_wgtab;                                          // its pinned staging copy (3 * 1024 ints)
+    PinBuf<int> h_ctl;                                            // pinned: control words of k_icp_persist going up [0..7], coming back [8]
     std::vector<IcpState> st_init;                                // initial ICP states of a persistent launch (kept in case it gives up)
     int force_stall = 0;                                          // CUBOID_FORCE_SCAN_STALL=n: the next n chained-scan checks report a stall (tests the retry)
     int scan_retries = 0;                                         // calls of this context that were redone because a chained scan stalled
@@ -96,34 +109,29 @@ struct cd_context {
     bool voxel_runs = true;                                       // CUBOID_VOXEL_RUNS=0: S1 sorts the cropped points instead of their runs of equal voxel index
     int icp_slots = 0;                                            // CUBOID_ICP_SLOTS: clusters in flight per workgroup, 1 .. CD_PIPE_SLOTS (0: by regime)
     int icp_big_weight = 0;                                       // workgroup share of a template in global memory, per point (CUBOID_ICP_BIG_WEIGHT; 0 = by the launch's regime, measured on config 5)
-    int *d_order = nullptr, *h_order = nullptr;                   // clusters, largest first
+    DevBuf<int> d_order; PinBuf<int> h_order;                     // clusters, largest first
     int tpl_cap = 0, tpl_used = 0;
     std::shared_ptr<const struct PreparedTemplate> tpl_prep[CD_MAX_TEMPLATES];   // host copies (shared across contexts)
     int tpl_off[CD_MAX_TEMPLATES] = {0}, tpl_m[CD_MAX_TEMPLATES] = {0};
     bool tpl_gridded[CD_MAX_TEMPLATES] = {false};                // slot has a cell start table
     bool tpl_big[CD_MAX_TEMPLATES] = {false};                    // slot does not fit LDS but has what k_icp_pipe_big needs (cell table, k-d map, superpatches)
-    IcpSuper* d_super = nullptr;                                  // per template slot
-    IcpLattice* d_lat = nullptr;                                  // per template slot: axis tables and faces of a lattice template (nface = 0: none)
+    DevBuf<IcpSuper> d_super;                                     // per template slot
+    DevBuf<IcpLattice> d_lat;                                     // per template slot: axis tables and faces of a lattice template (nface = 0: none)
     int tpl_faces[CD_MAX_TEMPLATES] = {0};                        // faces of the slot's lattice (0: the generic searches take it)
     int icp_lattice = 1;                                          // CUBOID_ICP_LATTICE=0: lattice templates take the generic searches too (A/B, fallback tests)
     int zero_once = 1;                                            // CUBOID_ZERO_ONCE=0: every stage of a fused batch call fills its scratch arrays itself (A/B)
     int copy_kernels = 1;                                         // CUBOID_COPY_KERNELS=0: the small pinned <-> device transfers go through hipMemcpyAsync (SDMA) again
     int lat_shape[3] = {0, 0, 0};                                 // CUBOID_LAT_SHAPE=cpw,wpc[,per_slot]: clusters per workgroup, waves per cluster, clusters per slot of k_icp_lat (0: by regime)
-    hipStream_t stream2 = nullptr, stream3 = nullptr;             // streams of the persistent ICP launches: the second launch of a mixed-template batch runs beside the
-                                                                  // first (stream2); with icp_lowprio both are low-priority streams, so that CUs that come free go to the
-                                                                  // short front-end kernels of the other batches in flight before the next persistent workgroup
     int front_concurrent = 0;                                     // CUBOID_FRONT_CONCURRENT: at most that many fused batch calls of the device between crop and clusters (0 = no gate)
     int icp_concurrent = 0;                                       // CUBOID_ICP_CONCURRENT: admission gate of the whole-cluster ICP launches (0 = none)
     int icp_lowprio = 1;                                          // CUBOID_ICP_LOWPRIO: 0 never, 1 the launches of a mixed-template batch (measured: config 5 +30 %), 2 every
                                                                   // persistent ICP launch (config 3: -1 %)
-    hipEvent_t ev2[3] = {nullptr, nullptr, nullptr};
     // ICP
-    IcpCluster *d_cl = nullptr, *h_cl = nullptr;
-    IcpWork *d_work = nullptr, *h_work = nullptr, *d_work2 = nullptr, *h_work2 = nullptr;
-    int work_cap = 0;
+    DevBuf<IcpCluster> d_cl; PinBuf<IcpCluster> h_cl;
+    DevBuf<IcpWork> d_work, d_work2; PinBuf<IcpWork> h_work, h_work2;
+    int work_cap = 0;                                             // items the work lists hold
     int cl_cap = 0;                                               // ICP problems the cluster arrays hold (grown on demand)
-    int* d_koffx = nullptr;                                       // offsets of the clusters ranked >= KICP, [round][F][KICP]
-    size_t koffx_cap = 0;
+    DevBuf<int> d_koffx;                                          // offsets of the clusters ranked >= KICP, [round][F][KICP]
     std::vector<cd_cluster_result> last_clusters;                 // every cluster result of the last batch, frame-major
     std::vector<int> last_first;                                  // index of frame f's first cluster in it (F + 1 entries)
     // clouds of the last batch that stay resident for cd_get_frame_cloud / cd_get_cluster_points
@@ -132,25 +140,20 @@ struct cd_context {
     bool last_clouds = false;
     // initial guesses (cd_set_frame_guesses), and their device copy (also used for the single guess of cd_params)
     std::vector<float> frame_guess;
-    float* d_guess = nullptr;
-    size_t guess_cap = 0;
+    DevBuf<float> d_guess;
     // ICP maximum correspondence distance (cd_set_icp_max_correspondence_distance, rule C8): the distance as set, its float
     // threshold on d2 and whether it bounds anything; d_ncorr: kept-correspondence counts of the sliced / persistent drivers
     double icp_max_dist = std::numeric_limits<double>::infinity();
     float icp_d2_max = std::numeric_limits<float>::infinity();
     int icp_bounded = 0;
-    uint32_t* d_ncorr = nullptr;
-    size_t ncorr_cap = 0;
+    DevBuf<uint32_t> d_ncorr;
     // batched surface-normal estimation (cd_surface_batch, CD_GUESS_SURFACE, stage_surface): FrameStates, plane models and point
     // buffers of its own, allocated on first use, so that the S2 plane, the clouds and the plane indices of a fused call stay
     // as they are; s_pts[0..1]: the current and the next cloud of every frame, rows of s_pitch points
-    FrameState *d_sfs = nullptr, *h_sfs = nullptr;
-    float4 *d_smodel = nullptr, *h_smodel = nullptr;
-    int *d_shave = nullptr, *h_shave = nullptr, *d_sactive = nullptr, *h_sactive = nullptr;
-    float4 *d_spts[2] = {nullptr, nullptr};
-    int* d_sidx = nullptr;
-    size_t spts_cap = 0;
-    float4 *d_ssum = nullptr, *h_ssum = nullptr;                  // [F][3] midpoint sums of the three fits (x, y, z, count bits)
+    DevBuf<FrameState> d_sfs; PinBuf<FrameState> h_sfs;
+    DevBuf<float4> d_smodel, d_spts[2]; PinBuf<float4> h_smodel;
+    DevBuf<int> d_shave, d_sactive, d_sidx; PinBuf<int> h_shave, h_sactive;
+    DevBuf<float4> d_ssum; PinBuf<float4> h_ssum;                // [F][3] midpoint sums of the three fits (x, y, z, count bits)
     double surface_thr = 0.015;                                   // cd_set_surface_distance_threshold (surface_normal_estimation.launch)
     std::vector<float> surface_guess;                             // rule C9 guesses of the last CD_GUESS_SURFACE call, 16 per frame
     std::vector<cd_surface_frame_result> last_surface;            // cd_get_surface_results
@@ -158,30 +161,24 @@ struct cd_context {
     bool last_surface_ok = false;
     // colour gate (rule C10, k_color.hip): the sdiv / hdiv tables, one record and one status per frame (device + pinned mirror),
     // the union-find labels and (images whose packed mask does not fit LDS only) the mask buffers, both allocated on first use
-    int* d_ctab = nullptr;
-    ColorRecord *d_crec = nullptr, *h_crec = nullptr;
-    int *d_cstatus = nullptr, *h_cstatus = nullptr;
-    int* d_clabel = nullptr;
-    size_t clabel_cap = 0;
-    uint32_t* d_cmask = nullptr;
-    size_t cmask_cap = 0;
+    DevBuf<int> d_ctab, d_cstatus, d_clabel; PinBuf<int> h_cstatus;
+    DevBuf<ColorRecord> d_crec; PinBuf<ColorRecord> h_crec;
+    DevBuf<uint32_t> d_cmask;
     // where the fused calls' gate takes its rectangle from (cd_set_bbox_source), the rectangles cd_set_frame_bboxes stored and
     // their device copy; call_rects: what the gate kernels of the fused call in flight read (nullptr outside one, and for CD_BBOX_PARAMS)
     int bbox_source = CD_BBOX_PARAMS;
     cd_color_gate_params color_prm;
     std::vector<int32_t> frame_rects;
-    int32_t *d_rects = nullptr, *h_rects = nullptr;
+    DevBuf<int32_t> d_rects; PinBuf<int32_t> h_rects;
     FrameRects call_rects{nullptr, 0};
     std::vector<cd_color_bbox> last_bboxes;                       // cd_get_frame_bboxes
     bool last_bboxes_ok = false;
     // overlay (rule C11, k_overlay.hip): poses, box counts and box records of a draw call, grown on demand (boxes: device + pinned mirror)
-    double* d_oposes = nullptr;
-    int32_t* d_onbox = nullptr;
-    OverlayBox *d_obox = nullptr, *h_obox = nullptr;
-    size_t obox_cap = 0, onbox_cap = 0;
-    IcpState *d_st = nullptr, *h_st = nullptr;
-    unsigned long long *d_acc = nullptr, *d_accf = nullptr, *h_accf = nullptr;
-    hipEvent_t ev[8] = {nullptr};
+    DevBuf<double> d_oposes;
+    DevBuf<int32_t> d_onbox;
+    DevBuf<OverlayBox> d_obox; PinBuf<OverlayBox> h_obox;
+    DevBuf<IcpState> d_st; PinBuf<IcpState> h_st;
+    DevBuf<unsigned long long> d_acc, d_accf; PinBuf<unsigned long long> h_accf;
     cd_timing timing;
 };
 
@@ -298,53 +295,12 @@ int with_scan_retry(cd_context* c, Fn&& fn) {
     return st;
 }
 
-#ifdef CD_ALLOC_GUARD
-// Debug build (make VARIANT=guard FLAGS_EXTRA=-DCD_ALLOC_GUARD=262144): every device allocation of the library gets that many
-// bytes of 0xA5 behind it, checked when it is freed - a kernel that WRITES past the end of an array is named on stderr instead
-// of corrupting its neighbour (or faulting only when the neighbour happens to be unmapped); a kernel that only READS past the
-// end stops faulting and leaves the guards intact, which says as much.
-struct GuardEntry { void* p; size_t bytes; std::string name; };
-static std::mutex g_guard_mu;
-static std::vector<GuardEntry> g_guards;
-static hipError_t guard_malloc(void** p, size_t bytes, const char* name) {
-    const hipError_t e = hipMalloc(p, bytes + (size_t)CD_ALLOC_GUARD);
-    if (e != hipSuccess) return e;
-    (void)hipMemset((char*)*p + bytes, 0xA5, (size_t)CD_ALLOC_GUARD);
-    std::lock_guard<std::mutex> lk(g_guard_mu);
-    g_guards.push_back(GuardEntry{*p, bytes, name});
-    return hipSuccess;
-}
-static hipError_t guard_free(void* p) {
-    GuardEntry ge{nullptr, 0, ""};
-    {
-        std::lock_guard<std::mutex> lk(g_guard_mu);
-        for (size_t i = 0; i < g_guards.size(); ++i)
-            if (g_guards[i].p == p) { ge = g_guards[i]; g_guards.erase(g_guards.begin() + (long)i); break; }
-    }
-    if (ge.p) {
-        std::vector<unsigned char> h((size_t)CD_ALLOC_GUARD);
-        (void)hipDeviceSynchronize();
-        if (hipMemcpy(h.data(), (char*)p + ge.bytes, h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-            size_t first = h.size(), last = 0, bad = 0;
-            for (size_t i = 0; i < h.size(); ++i) if (h[i] != 0xA5) { if (first == h.size()) first = i; last = i; ++bad; }
-            if (bad) std::fprintf(stderr, "cuboid_hip GUARD: %s (%zu bytes) was written past its end: %zu bytes between +%zu and +%zu\n", ge.name.c_str(), ge.bytes, bad, first, last);
-        }
-    }
-    return (hipFree)(p);
-}
-#define hipFree(p) guard_free(p)
-template <class Tp>
-hipError_t dalloc_named(Tp** p, size_t n, const char* name) { return guard_malloc((void**)p, std::max<size_t>(n, 1) * sizeof(Tp), name); }
-#define dalloc(p, n) dalloc_named(p, n, #p)
-#else
-template <class Tp>
-hipError_t dalloc(Tp** p, size_t n) { return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(Tp)); }
-#endif
-template <class Tp>
-hipError_t halloc(Tp** p, size_t n) { return hipHostMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(Tp), hipHostMallocDefault); }
+// grows a buffer of the context to hold `n` elements (OwnedBuf::ensure: a no-op when it is large enough, otherwise the context's
+// stream is synchronised, the old memory freed and new allocated; contents are not kept)
+#define GROW(ctx, buf, n) HIPCHK(ctx, (ctx)->buf.ensure((ctx)->stream, (n), #buf))
 
 const int FS_PITCH = (int)(sizeof(FrameState) / sizeof(int));
-#define FS_FIELD(ctx, field) ((int*)((char*)(ctx)->d_fs + offsetof(FrameState, field)))
+#define FS_FIELD(ctx, field) ((int*)((char*)(ctx)->d_fs.get() + offsetof(FrameState, field)))
 
 // blocking copy ordered on the context's own (non-blocking) stream: the NULL stream gives no ordering against it
 static hipError_t copy_sync(cd_context* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
@@ -394,16 +350,7 @@ struct XferBatch {
 };
 
 int ensure_input(cd_context* c, size_t bytes) {
-    if (bytes <= c->d_in_bytes) return CD_OK;
-    if (c->d_in) hipFree(c->d_in);
-    c->d_in = nullptr;
-    c->d_in_bytes = 0;
-#ifdef CD_ALLOC_GUARD
-    HIPCHK(c, guard_malloc((void**)&c->d_in, bytes, "d_in"));
-#else
-    HIPCHK(c, hipMalloc((void**)&c->d_in, bytes));
-#endif
-    c->d_in_bytes = bytes;
+    GROW(c, d_in, bytes);
     return CD_OK;
 }
 
@@ -413,23 +360,16 @@ int ensure_clusters(cd_context* c, int ncl, long long points) {
     const long long work_need = points / 64 + (long long)ncl + 16;
     if (ncl <= c->cl_cap && work_need <= c->work_cap) return CD_OK;
     if (work_need > 0x7fffffffll) return fail(c, CD_ERR_CAPACITY, "ICP work list exceeds 2^31 items");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->batch_zeroed = false;   // (new arrays: stage_icp fills them itself)
-    void* dev[] = {c->d_cl, c->d_order, c->d_work, c->d_work2, c->d_st, c->d_acc, c->d_accf};
-    for (void* p : dev) if (p) hipFree(p);
-    void* host[] = {c->h_cl, c->h_order, c->h_work, c->h_work2, c->h_st, c->h_accf};
-    for (void* p : host) if (p) hipHostFree(p);
-    c->d_cl = nullptr; c->d_order = nullptr; c->d_work = nullptr; c->d_work2 = nullptr; c->d_st = nullptr; c->d_acc = nullptr; c->d_accf = nullptr;
-    c->h_cl = nullptr; c->h_order = nullptr; c->h_work = nullptr; c->h_work2 = nullptr; c->h_st = nullptr; c->h_accf = nullptr;
     // never shrink: the per-stage entry points (cd_icp) rely on the capacity cd_create gave them
     const size_t n = (size_t)std::max(std::max(ncl, c->F * KICP) + ncl / 4, c->cl_cap), w = (size_t)std::max<long long>(work_need + work_need / 4, c->work_cap);
     c->cl_cap = 0; c->work_cap = 0;
-    HIPCHK(c, dalloc(&c->d_cl, n)); HIPCHK(c, halloc(&c->h_cl, n));
-    HIPCHK(c, dalloc(&c->d_order, n)); HIPCHK(c, halloc(&c->h_order, n));
-    HIPCHK(c, dalloc(&c->d_work, w)); HIPCHK(c, halloc(&c->h_work, w));
-    HIPCHK(c, dalloc(&c->d_work2, w)); HIPCHK(c, halloc(&c->h_work2, w));
-    HIPCHK(c, dalloc(&c->d_st, n * 2)); HIPCHK(c, halloc(&c->h_st, n * 2));
-    HIPCHK(c, dalloc(&c->d_acc, n * 48)); HIPCHK(c, dalloc(&c->d_accf, n + 1)); HIPCHK(c, halloc(&c->h_accf, n + 1));   // (+ 1: k_icp_lat's wave-time word)
+    GROW(c, d_cl, n); GROW(c, h_cl, n);
+    GROW(c, d_order, n); GROW(c, h_order, n);
+    GROW(c, d_work, w); GROW(c, h_work, w);
+    GROW(c, d_work2, w); GROW(c, h_work2, w);
+    GROW(c, d_st, n * 2); GROW(c, h_st, n * 2);
+    GROW(c, d_acc, n * 48); GROW(c, d_accf, n + 1); GROW(c, h_accf, n + 1);   // (+ 1: k_icp_lat's wave-time word)
     c->cl_cap = (int)n;
     c->work_cap = (int)w;
     return CD_OK;
@@ -546,6 +486,7 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
     // on the tiles is the point count (the run count is only known on the device).  CUBOID_VOXEL_RUNS=0: sort the points.
     const bool by_runs = c->voxel_runs && npass > 0 && c->N <= (1 << 20);   // (a run's start takes 20 bits of its payload)
     int Tc_runs = Tc;
+    uint32_t* const key[2] = {c->d_key[0], c->d_key[1]}, * const val[2] = {c->d_val[0], c->d_val[1]};
     if (crop_runs) {
         // the runs and their histograms are there already; which of the packed key's four digits vary in some frame?
         int vary = 0, max_runs = 0;
@@ -557,11 +498,11 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
         for (int d = 0; d < 4; ++d) if ((vary >> d) & 1) digits[nd++] = d;
         const int Tsr = std::max(1, (max_runs + SORT_TILE - 1) / SORT_TILE);   // (the run count is known here: tighter than the point count)
         Tc_runs = std::max(1, (max_runs + TILE - 1) / TILE);
-        LAUNCH(c, cur = launch_radix_scatter_runs(c->stream, c->d_key, c->d_val, c->N, F, Tsr, digits, nd, c->d_fs, c->d_ghist, c->d_sstate, c->d_ticket));
+        LAUNCH(c, cur = launch_radix_scatter_runs(c->stream, key, val, c->N, F, Tsr, digits, nd, c->d_fs, c->d_ghist, c->d_sstate, c->d_ticket));
     } else if (by_runs)
-        LAUNCH(c, cur = launch_radix_sort_runs(c->stream, c->d_key, c->d_val, c->N, F, T, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, c->d_tileA, kp, c->d_ticket));
+        LAUNCH(c, cur = launch_radix_sort_runs(c->stream, key, val, c->N, F, T, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, c->d_tileA, kp, c->d_ticket));
     else
-        LAUNCH(c, cur = launch_radix_sort(c->stream, c->d_key, c->d_val, c->N, F, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, kp, c->d_ticket));
+        LAUNCH(c, cur = launch_radix_sort(c->stream, key, val, c->N, F, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, kp, c->d_ticket));
     if (cur < 0) return fail(c, CD_ERR_DEVICE, "radix sort: the scan state could not be zeroed");
     const uint32_t* vin = c->d_val[cur];   // zero passes (empty frames only): the permutation is never read
     // voxel heads + centroids in one kernel: n_v (0 from the FrameState init for empty frames) and every tile's output
@@ -697,8 +638,8 @@ int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode = -1) 
     LAUNCH(c, launch_plane_flag_count(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->call_rects, c->d_tileA, c->d_tileB));
     {   // both scans in one launch; the two totals also go straight into the host's FrameState mirror (nothing else of it changes here)
         const bool mirrored = c->mirror_writes && c->copy_kernels;
-        const ScanJob ja{c->d_tileA, FS_FIELD(c, n_plane), mirrored ? (int*)((char*)c->h_fs + offsetof(FrameState, n_plane)) : nullptr};
-        const ScanJob jb{c->d_tileB, FS_FIELD(c, n_o), mirrored ? (int*)((char*)c->h_fs + offsetof(FrameState, n_o)) : nullptr};
+        const ScanJob ja{c->d_tileA, FS_FIELD(c, n_plane), mirrored ? (int*)((char*)c->h_fs.get() + offsetof(FrameState, n_plane)) : nullptr};
+        const ScanJob jb{c->d_tileB, FS_FIELD(c, n_o), mirrored ? (int*)((char*)c->h_fs.get() + offsetof(FrameState, n_o)) : nullptr};
         LAUNCH(c, launch_scan_tiles2(c->stream, ja, jb, F, T, FS_PITCH));
     }
     LAUNCH(c, launch_extract_scatter(c->stream, c->d_vox, c->N, F, T, Tv, c->d_fs, model_p, have_p, thr, p->extract_negative, p->crop2_enable, z2lo, z2hi, gate, c->call_rects, c->d_tileA, c->d_tileB, c->d_plane_idx, c->d_obj));
@@ -756,19 +697,6 @@ int stage_cluster_sync(cd_context* c, int F, const cd_params* p, int max_no) {
     st = stage_cluster(c, F, p, max_no, true);
     if (st) return st;
     return sync_fs(c, F, mirrored);
-}
-
-// grows a device array to hold `need` elements (its contents are not kept); the stream is synchronised first, as work in flight
-// may still read the old array
-template <class Tp>
-int grow_device(cd_context* c, Tp** p, size_t* cap, size_t need) {
-    if (need <= *cap) return CD_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(c, dalloc(p, need));
-    *cap = need;
-    return CD_OK;
 }
 
 // IcpCluster records h_cl[first .. first + n) of the clusters 0 .. n-1 of one frame against template `slot`: sizes size[0..n),
@@ -907,7 +835,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
 int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
     const int ncl = pl->ncl;
     if (pl->guess_mode != CD_GUESS_NONE) {
-        if (int st = grow_device(c, &c->d_guess, &c->guess_cap, pl->guess_need)) return st;
+        GROW(c, d_guess, pl->guess_need);
         HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
     }
     if (!pl->lat_direct) {
@@ -925,7 +853,7 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1), c->stream));   // (+ the wave-time word of k_icp_lat)
     }
     if (c->icp_bounded) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3]
-        if (int st = grow_device(c, &c->d_ncorr, &c->ncorr_cap, 3 * (size_t)ncl)) return st;
+        GROW(c, d_ncorr, 3 * (size_t)ncl);
         HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
     }
     if (pl->guess_mode != CD_GUESS_NONE)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
@@ -989,7 +917,7 @@ int icp_run_lat(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* don
     // the clusters of the launch, largest first
     int no = 0;
     for (int k = 0; k < ncl; ++k) if (pl.in_lat[(size_t)k]) c->h_order[no++] = k;
-    std::stable_sort(c->h_order, c->h_order + no, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
+    std::stable_sort(c->h_order.get(), c->h_order + no, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
     if (!pl.lat_direct) HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * (size_t)no, hipMemcpyHostToDevice));
     // Shape of the launch (k_icp_lat.hip): clusters per workgroup x waves per cluster.  A call that has the GPU to itself wants
     // the launch short: one cluster per workgroup, four waves each when there are clusters enough to fill the chip twice that way,
@@ -1124,7 +1052,7 @@ int icp_run_whole(cd_context* c, const IcpPlan& pl, IcpParams ip, bool* done) {
     GateHold hold;   // (released on every path out of this function)
     if (c->icp_concurrent > 0) hold.enter(&g_icp_gate[c->device & (MAX_DEVICES - 1)], c->icp_concurrent);
     for (int k = 0; k < ncl; ++k) c->h_order[k] = k;
-    std::stable_sort(c->h_order, c->h_order + ncl, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
+    std::stable_sort(c->h_order.get(), c->h_order + ncl, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
     HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * ncl, hipMemcpyHostToDevice));
     const int wg_cap = pl.wg_cap;
     HIPCHK(c, hipMemsetAsync(c->d_queue, 0, sizeof(int), c->stream));   // head of the cluster queue
@@ -1205,7 +1133,7 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool*
     HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     HIPCHK(c, xfer(c, ctl + 8, c->d_queue + 5, sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
-    c->st_init.assign(c->h_st, c->h_st + 2 * (size_t)ncl);   // in case the launch gives up (no reallocation after the first call)
+    c->st_init.assign(c->h_st.get(), c->h_st + 2 * (size_t)ncl);   // in case the launch gives up (no reallocation after the first call)
     HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!ctl[8]) {   // (the abort flag: raised when the launch gave up)
@@ -1343,23 +1271,13 @@ int check_params(cd_context* c, const cd_params* p) {
 // run on the surface stage's own buffers: SurfaceBuffers swaps them in for its lifetime.
 
 int ensure_surface(cd_context* c, size_t pitch) {   // (the per-frame arrays at the context's capacity, the clouds as needed)
-    if (!c->d_sfs) {
-        const size_t F = (size_t)c->F;
-        HIPCHK(c, dalloc(&c->d_sfs, F)); HIPCHK(c, halloc(&c->h_sfs, F));
-        HIPCHK(c, dalloc(&c->d_smodel, F)); HIPCHK(c, halloc(&c->h_smodel, F));
-        HIPCHK(c, dalloc(&c->d_shave, F)); HIPCHK(c, halloc(&c->h_shave, F));
-        HIPCHK(c, dalloc(&c->d_sactive, F)); HIPCHK(c, halloc(&c->h_sactive, F));
-        HIPCHK(c, dalloc(&c->d_ssum, 3 * F)); HIPCHK(c, halloc(&c->h_ssum, 3 * F));
-    }
-    const size_t need = (size_t)c->F * std::max<size_t>(pitch, 1);
-    if (need <= c->spts_cap) return CD_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (float4*& q : c->d_spts) { if (q) hipFree(q); q = nullptr; }
-    if (c->d_sidx) hipFree(c->d_sidx);
-    c->d_sidx = nullptr;
-    c->spts_cap = 0;
-    HIPCHK(c, dalloc(&c->d_spts[0], need)); HIPCHK(c, dalloc(&c->d_spts[1], need)); HIPCHK(c, dalloc(&c->d_sidx, need));
-    c->spts_cap = need;
+    const size_t F = (size_t)c->F, need = F * std::max<size_t>(pitch, 1);
+    GROW(c, d_sfs, F); GROW(c, h_sfs, F);
+    GROW(c, d_smodel, F); GROW(c, h_smodel, F);
+    GROW(c, d_shave, F); GROW(c, h_shave, F);
+    GROW(c, d_sactive, F); GROW(c, h_sactive, F);
+    GROW(c, d_ssum, 3 * F); GROW(c, h_ssum, 3 * F);
+    GROW(c, d_spts[0], need); GROW(c, d_spts[1], need); GROW(c, d_sidx, need);
     return CD_OK;
 }
 
@@ -1558,20 +1476,10 @@ int check_color_params(cd_context* c, const cd_color_gate_params* g) {
 // (valid after the next synchronisation of the context's stream)
 int stage_color(cd_context* c, const uint8_t* d_rgb, int W, int H, int F, const cd_color_gate_params* g) {
     const size_t px = (size_t)W * H;
-    if (c->clabel_cap < px * F) {
-        if (c->d_clabel) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_clabel); c->d_clabel = nullptr; c->clabel_cap = 0; }
-        const size_t want = std::max(px * F, std::min((size_t)c->N * c->F, (size_t)640 * 480 * c->F));
-        HIPCHK(c, dalloc(&c->d_clabel, want));
-        c->clabel_cap = want;
-    }
+    if (c->d_clabel.capacity() < px * F) GROW(c, d_clabel, std::max(px * F, std::min((size_t)c->N * c->F, (size_t)640 * 480 * c->F)));
     uint32_t* gmask = nullptr;
     if (!color_fits_lds(W, H)) {
-        const size_t want = 2 * (size_t)((W + 31) / 32) * H * F;
-        if (c->cmask_cap < want) {
-            if (c->d_cmask) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_cmask); c->d_cmask = nullptr; c->cmask_cap = 0; }
-            HIPCHK(c, dalloc(&c->d_cmask, want));
-            c->cmask_cap = want;
-        }
+        GROW(c, d_cmask, 2 * (size_t)((W + 31) / 32) * H * F);
         gmask = c->d_cmask;
     }
     const ColorGate cg{g->h_lo_max, g->h_hi_min, g->s_min, g->v_min, g->margin};
@@ -1652,7 +1560,7 @@ int batch_prologue(cd_context* c, int gate_source, const void* d_frames, int F, 
         // (a mapped call: the raw colour images at their own size, so the rectangles are in colour pixels)
         int st = stage_color(c, dj->color, dj->ccam ? dj->ccam->width : dj->cam->width, dj->ccam ? dj->ccam->height : dj->cam->height, F, &c->color_prm);
         if (st) return st;
-        c->call_rects = FrameRects{reinterpret_cast<const int32_t*>(c->d_crec), (int32_t)(sizeof(ColorRecord) / sizeof(int32_t))};   // (rect is the record's first member)
+        c->call_rects = FrameRects{reinterpret_cast<const int32_t*>(c->d_crec.get()), (int32_t)(sizeof(ColorRecord) / sizeof(int32_t))};   // (rect is the record's first member)
     }
     if (dj) LAUNCH(c, launch_depth_job(c->stream, dj, F, (float4*)const_cast<void*>(d_frames)));
     return c->zero_once ? zero_batch_scratch(c, F) : CD_OK;
@@ -1716,8 +1624,7 @@ int batch_clusters(cd_context* c, int F, BatchClusters* cl) {
 // Grows d_koffx (which synchronises the stream when it has to) and uploads the table with a blocking copy.
 int upload_koffx(cd_context* c, int F, const BatchClusters& cl, int copies) {
     const size_t need = (size_t)copies * cl.rounds_k * F * KICP;
-    int st = grow_device(c, &c->d_koffx, &c->koffx_cap, need);
-    if (st) return st;
+    GROW(c, d_koffx, need);
     std::vector<int> tab(need, 0);
     for (int t = 0; t < copies; ++t)
         for (int r = 0; r < cl.rounds_k; ++r)
@@ -2045,44 +1952,8 @@ const char* cd_last_error(const cd_context* ctx) { return ctx ? ctx->err : "null
 void cd_destroy(cd_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    void* dev[] = {c->d_in, c->d_fs, c->d_tileA, c->d_tileB, c->d_tileK, c->d_cpt, c->d_vox, c->d_obj, c->d_src0, c->d_src,
-                   c->d_key[0], c->d_key[1], c->d_val[0], c->d_val[1], c->d_ghist, c->d_sstate, c->d_ticket, c->d_tile64, c->d_rnd, c->d_models, c->d_valid, c->d_counts,
-                   c->d_active, c->d_model, c->d_have, c->d_sums, c->d_plane_idx, c->d_head, c->d_next, c->d_parent, c->d_csize,
-                   c->d_rank, c->d_cand, c->d_sizes, c->d_label, c->d_tpl, c->d_tlo, c->d_thi, c->d_tplk, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_tcell, c->d_nn, c->d_d2, c->d_queue, c->d_don, c->d_wgtab, c->d_order, c->d_cl, c->d_work, c->d_work2, c->d_st, c->d_acc, c->d_accf};
-    for (void* p : dev) if (p) hipFree(p);
-    if (c->d_koffx) hipFree(c->d_koffx);
-    if (c->d_guess) hipFree(c->d_guess);
-    if (c->d_ncorr) hipFree(c->d_ncorr);
-    if (c->d_super) hipFree(c->d_super);
-    if (c->d_lat) hipFree(c->d_lat);
-    if (c->d_tileC) hipFree(c->d_tileC);
-    if (c->d_depth) hipFree(c->d_depth);
-    if (c->d_color) hipFree(c->d_color);
-    {
-        void* cdev[] = {c->d_ctab, c->d_crec, c->d_cstatus, c->d_clabel, c->d_cmask, c->d_rects};
-        for (void* p : cdev) if (p) hipFree(p);
-        void* chost[] = {c->h_crec, c->h_cstatus, c->h_rects};
-        for (void* p : chost) if (p) hipHostFree(p);
-    }
-    {
-        void* odev[] = {c->d_oposes, c->d_onbox, c->d_obox};
-        for (void* p : odev) if (p) hipFree(p);
-        if (c->h_obox) hipHostFree(c->h_obox);
-    }
-    {
-        void* sdev[] = {c->d_sfs, c->d_smodel, c->d_shave, c->d_sactive, c->d_spts[0], c->d_spts[1], c->d_sidx, c->d_ssum};
-        for (void* p : sdev) if (p) hipFree(p);
-        void* shost[] = {c->h_sfs, c->h_smodel, c->h_shave, c->h_sactive, c->h_ssum};
-        for (void* p : shost) if (p) hipHostFree(p);
-    }
-    if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); }
-    if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); }
-    for (auto& e : c->ev2) if (e) hipEventDestroy(e);
-    void* host[] = {c->h_fs, c->h_valid, c->h_counts, c->h_active, c->h_model, c->h_models, c->h_have, c->h_sums, c->h_cl, c->h_order, c->h_work, c->h_work2, c->h_st, c->h_accf, c->h_wgtab, c->h_ctl};
-    for (void* p : host) if (p) hipHostFree(p);
-    for (auto& e : c->ev) if (e) hipEventDestroy(e);
-    if (c->stream) hipStreamDestroy(c->stream);
+    for (hipStream_t q : {c->stream, c->stream2, c->stream3}) if (q) hipStreamSynchronize(q);
+    // the members free their memory, then ~cd_streams destroys the events and the (drained) streams
     delete c;
 }
 
@@ -2094,6 +1965,7 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) return CD_ERR_DEVICE;
     if (hipSetDevice(device_id) != hipSuccess) return CD_ERR_DEVICE;
     cd_context* c = new cd_context();
+#define ALLOC(buf, n) (c->buf.alloc((n), #buf) == hipSuccess)
     c->device = device_id;
     c->N = max_points;
     c->F = max_frames;
@@ -2105,41 +1977,41 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_least = prio_greatest = 0;
     bool ok = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, 0) == hipSuccess;
     for (auto& e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && dalloc(&c->d_fs, F) == hipSuccess && halloc(&c->h_fs, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_tileA, F * T) == hipSuccess && dalloc(&c->d_tileB, F * T) == hipSuccess && dalloc(&c->d_tileK, F * KICP * T) == hipSuccess && dalloc(&c->d_tileC, F * T) == hipSuccess;
-    ok = ok && dalloc(&c->d_cpt, FN) == hipSuccess && dalloc(&c->d_vox, FN) == hipSuccess && dalloc(&c->d_obj, FN) == hipSuccess;
-    ok = ok && dalloc(&c->d_src0, FN) == hipSuccess && dalloc(&c->d_src, FN) == hipSuccess;
-    for (int k = 0; k < 2; ++k) ok = ok && dalloc(&c->d_key[k], FN) == hipSuccess && dalloc(&c->d_val[k], FN) == hipSuccess;
-    ok = ok && dalloc(&c->d_ghist, F * SORT_MAX_PASSES_HOST * RADIX) == hipSuccess;
-    ok = ok && dalloc(&c->d_sstate, (size_t)SORT_MAX_PASSES_HOST * F * RADIX * ((N + SORT_TILE - 1) / SORT_TILE)) == hipSuccess;
-    ok = ok && dalloc(&c->d_tile64, F * T) == hipSuccess;
-    ok = ok && dalloc(&c->d_ticket, (size_t)F * TICKET_PITCH) == hipSuccess && hipMemset(c->d_ticket, 0, sizeof(int) * (size_t)F * TICKET_PITCH) == hipSuccess;
-    ok = ok && dalloc(&c->d_rnd, (size_t)RND_TABLE) == hipSuccess;
-    ok = ok && dalloc(&c->d_models, F * MAX_HYP) == hipSuccess && dalloc(&c->d_valid, F * MAX_HYP) == hipSuccess && dalloc(&c->d_counts, F * MAX_HYP) == hipSuccess;
-    ok = ok && halloc(&c->h_valid, F * MAX_HYP) == hipSuccess && halloc(&c->h_counts, F * MAX_HYP) == hipSuccess && halloc(&c->h_models, F * MAX_HYP) == hipSuccess;
-    ok = ok && dalloc(&c->d_active, F) == hipSuccess && halloc(&c->h_active, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_model, F) == hipSuccess && halloc(&c->h_model, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_have, F) == hipSuccess && halloc(&c->h_have, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_sums, F * 10) == hipSuccess && halloc(&c->h_sums, F * 10) == hipSuccess;
-    ok = ok && dalloc(&c->d_plane_idx, FN) == hipSuccess && dalloc(&c->d_head, F * CELL_BUCKETS) == hipSuccess;
-    ok = ok && dalloc(&c->d_next, FN) == hipSuccess && dalloc(&c->d_parent, FN) == hipSuccess && dalloc(&c->d_csize, FN) == hipSuccess;
-    ok = ok && dalloc(&c->d_rank, FN) == hipSuccess && dalloc(&c->d_cand, FN) == hipSuccess && dalloc(&c->d_sizes, FN) == hipSuccess && dalloc(&c->d_label, FN) == hipSuccess;
+    ok = ok && ALLOC(d_fs, F) && ALLOC(h_fs, F);
+    ok = ok && ALLOC(d_tileA, F * T) && ALLOC(d_tileB, F * T) && ALLOC(d_tileK, F * KICP * T) && ALLOC(d_tileC, F * T);
+    ok = ok && ALLOC(d_cpt, FN) && ALLOC(d_vox, FN) && ALLOC(d_obj, FN);
+    ok = ok && ALLOC(d_src0, FN) && ALLOC(d_src, FN);
+    for (int k = 0; k < 2; ++k) ok = ok && ALLOC(d_key[k], FN) && ALLOC(d_val[k], FN);
+    ok = ok && ALLOC(d_ghist, F * SORT_MAX_PASSES_HOST * RADIX);
+    ok = ok && ALLOC(d_sstate, (size_t)SORT_MAX_PASSES_HOST * F * RADIX * ((N + SORT_TILE - 1) / SORT_TILE));
+    ok = ok && ALLOC(d_tile64, F * T);
+    ok = ok && ALLOC(d_ticket, (size_t)F * TICKET_PITCH) && hipMemset(c->d_ticket, 0, sizeof(int) * (size_t)F * TICKET_PITCH) == hipSuccess;
+    ok = ok && ALLOC(d_rnd, (size_t)RND_TABLE);
+    ok = ok && ALLOC(d_models, F * MAX_HYP) && ALLOC(d_valid, F * MAX_HYP) && ALLOC(d_counts, F * MAX_HYP);
+    ok = ok && ALLOC(h_valid, F * MAX_HYP) && ALLOC(h_counts, F * MAX_HYP) && ALLOC(h_models, F * MAX_HYP);
+    ok = ok && ALLOC(d_active, F) && ALLOC(h_active, F);
+    ok = ok && ALLOC(d_model, F) && ALLOC(h_model, F);
+    ok = ok && ALLOC(d_have, F) && ALLOC(h_have, F);
+    ok = ok && ALLOC(d_sums, F * 10) && ALLOC(h_sums, F * 10);
+    ok = ok && ALLOC(d_plane_idx, FN) && ALLOC(d_head, F * CELL_BUCKETS);
+    ok = ok && ALLOC(d_next, FN) && ALLOC(d_parent, FN) && ALLOC(d_csize, FN);
+    ok = ok && ALLOC(d_rank, FN) && ALLOC(d_cand, FN) && ALLOC(d_sizes, FN) && ALLOC(d_label, FN);
     c->tpl_cap = 1 << 18;
-    ok = ok && dalloc(&c->d_tpl, (size_t)c->tpl_cap) == hipSuccess;
-    ok = ok && dalloc(&c->d_super, (size_t)CD_MAX_TEMPLATES) == hipSuccess;
-    ok = ok && dalloc(&c->d_lat, (size_t)CD_MAX_TEMPLATES) == hipSuccess;
+    ok = ok && ALLOC(d_tpl, (size_t)c->tpl_cap);
+    ok = ok && ALLOC(d_super, (size_t)CD_MAX_TEMPLATES);
+    ok = ok && ALLOC(d_lat, (size_t)CD_MAX_TEMPLATES);
     {
         const int prio = c->icp_lowprio ? prio_least : 0;
         ok = ok && hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio) == hipSuccess;
         ok = ok && hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio) == hipSuccess;
     }
     for (auto& e : c->ev2) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    ok = ok && dalloc(&c->d_grid, (size_t)CD_MAX_TEMPLATES) == hipSuccess && dalloc(&c->d_tcell, (size_t)CD_MAX_TEMPLATES * ICP_CELL_STRIDE) == hipSuccess;
-    ok = ok && dalloc(&c->d_tlo, (size_t)c->tpl_cap / ICP_SUB) == hipSuccess && dalloc(&c->d_thi, (size_t)c->tpl_cap / ICP_SUB) == hipSuccess;
-    ok = ok && dalloc(&c->d_kdmap, (size_t)c->tpl_cap) == hipSuccess;
-    ok = ok && dalloc(&c->d_tplk, (size_t)c->tpl_cap) == hipSuccess && dalloc(&c->d_tlok, (size_t)c->tpl_cap / ICP_SUB) == hipSuccess && dalloc(&c->d_thik, (size_t)c->tpl_cap / ICP_SUB) == hipSuccess;
-    ok = ok && dalloc(&c->d_nn, FN) == hipSuccess && dalloc(&c->d_d2, FN) == hipSuccess && dalloc(&c->d_queue, (size_t)16) == hipSuccess && dalloc(&c->d_don, (size_t)(DON_BOX + DON_CAP)) == hipSuccess && dalloc(&c->d_wgtab, (size_t)3 * 1024) == hipSuccess;
-    ok = ok && halloc(&c->h_wgtab, (size_t)3 * 1024) == hipSuccess && halloc(&c->h_ctl, (size_t)16) == hipSuccess;
+    ok = ok && ALLOC(d_grid, (size_t)CD_MAX_TEMPLATES) && ALLOC(d_tcell, (size_t)CD_MAX_TEMPLATES * ICP_CELL_STRIDE);
+    ok = ok && ALLOC(d_tlo, (size_t)c->tpl_cap / ICP_SUB) && ALLOC(d_thi, (size_t)c->tpl_cap / ICP_SUB);
+    ok = ok && ALLOC(d_kdmap, (size_t)c->tpl_cap);
+    ok = ok && ALLOC(d_tplk, (size_t)c->tpl_cap) && ALLOC(d_tlok, (size_t)c->tpl_cap / ICP_SUB) && ALLOC(d_thik, (size_t)c->tpl_cap / ICP_SUB);
+    ok = ok && ALLOC(d_nn, FN) && ALLOC(d_d2, FN) && ALLOC(d_queue, (size_t)16) && ALLOC(d_don, (size_t)(DON_BOX + DON_CAP)) && ALLOC(d_wgtab, (size_t)3 * 1024);
+    ok = ok && ALLOC(h_wgtab, (size_t)3 * 1024) && ALLOC(h_ctl, (size_t)16);
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
@@ -2147,8 +2019,8 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     const size_t ncl = F * KICP;
     c->cl_cap = (int)ncl;
     c->work_cap = (int)(F * (N / 64 + KICP + 1));
-    ok = ok && dalloc(&c->d_cl, ncl) == hipSuccess && halloc(&c->h_cl, ncl) == hipSuccess;
-    ok = ok && dalloc(&c->d_order, ncl) == hipSuccess && halloc(&c->h_order, ncl) == hipSuccess;
+    ok = ok && ALLOC(d_cl, ncl) && ALLOC(h_cl, ncl);
+    ok = ok && ALLOC(d_order, ncl) && ALLOC(h_order, ncl);
     if (const char* m = std::getenv("CUBOID_ICP_MAX_WG")) c->icp_max_wg = std::max(0, std::atoi(m));
     if (const char* m = std::getenv("CUBOID_ICP_CPW")) c->icp_cpw = std::max(0, std::atoi(m));
     if (const char* m = std::getenv("CUBOID_ICP_SLOTS")) c->icp_slots = std::max(0, std::atoi(m));
@@ -2174,13 +2046,13 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     if (const char* m = std::getenv("CUBOID_ICP_CONCURRENT")) c->icp_concurrent = std::max(0, std::atoi(m));
     if (const char* m = std::getenv("CUBOID_FRONT_CONCURRENT")) c->front_concurrent = std::max(0, std::atoi(m));
     if (const char* m = std::getenv("CUBOID_ICP_MODE")) c->icp_mode = !std::strcmp(m, "sliced") ? 1 : (!std::strcmp(m, "cluster") ? 2 : (!std::strcmp(m, "pipe") ? 3 : 0));
-    ok = ok && dalloc(&c->d_work, (size_t)c->work_cap) == hipSuccess && halloc(&c->h_work, (size_t)c->work_cap) == hipSuccess;
-    ok = ok && dalloc(&c->d_work2, (size_t)c->work_cap) == hipSuccess && halloc(&c->h_work2, (size_t)c->work_cap) == hipSuccess;
-    ok = ok && dalloc(&c->d_st, ncl * 2) == hipSuccess && halloc(&c->h_st, ncl * 2) == hipSuccess;
-    ok = ok && dalloc(&c->d_acc, ncl * 48) == hipSuccess && dalloc(&c->d_accf, ncl + 1) == hipSuccess && halloc(&c->h_accf, ncl + 1) == hipSuccess;
-    ok = ok && dalloc(&c->d_ctab, (size_t)512) == hipSuccess && dalloc(&c->d_crec, F) == hipSuccess && halloc(&c->h_crec, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_cstatus, F) == hipSuccess && halloc(&c->h_cstatus, F) == hipSuccess;
-    ok = ok && dalloc(&c->d_rects, F * 4) == hipSuccess && halloc(&c->h_rects, F * 4) == hipSuccess;
+    ok = ok && ALLOC(d_work, (size_t)c->work_cap) && ALLOC(h_work, (size_t)c->work_cap);
+    ok = ok && ALLOC(d_work2, (size_t)c->work_cap) && ALLOC(h_work2, (size_t)c->work_cap);
+    ok = ok && ALLOC(d_st, ncl * 2) && ALLOC(h_st, ncl * 2);
+    ok = ok && ALLOC(d_acc, ncl * 48) && ALLOC(d_accf, ncl + 1) && ALLOC(h_accf, ncl + 1);
+    ok = ok && ALLOC(d_ctab, (size_t)512) && ALLOC(d_crec, F) && ALLOC(h_crec, F);
+    ok = ok && ALLOC(d_cstatus, F) && ALLOC(h_cstatus, F);
+    ok = ok && ALLOC(d_rects, F * 4) && ALLOC(h_rects, F * 4);
     cd_default_color_gate_params(&c->color_prm);
     if (ok) {   // rule C10 step 1: sdiv[i] = rint((255 << 12) / i), hdiv[i] = rint((180 << 12) / (6 i)), in double, half to even
         std::vector<int> tab(512, 0);
@@ -2197,6 +2069,7 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
         for (auto& v : tab) v = (int)(gen() >> 1);
         ok = copy_sync(c, c->d_rnd, tab.data(), sizeof(int) * RND_TABLE, hipMemcpyHostToDevice) == hipSuccess;
     }
+#undef ALLOC
     if (!ok) {
         cd_destroy(c);
         return CD_ERR_DEVICE;
@@ -2821,7 +2694,7 @@ static int cd_surface_batch_impl(cd_context* c, const void* xyz, size_t stride, 
         st = ensure_input(c, std::max<size_t>(bytes, 16));
         if (st) return st;
         if (bytes > 0) HIPCHK(c, hipMemcpyAsync(c->d_in, xyz, bytes, hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, launch_surface_load(c->stream, c->d_in, stride, stride * (size_t)P, (const int*)((char*)c->d_sfs + offsetof(FrameState, n_v)),
+        LAUNCH(c, launch_surface_load(c->stream, c->d_in, stride, stride * (size_t)P, (const int*)((char*)c->d_sfs.get() + offsetof(FrameState, n_v)),
                                       FS_PITCH, pitch, max_n, F, c->d_spts[0]));
     }
     const std::vector<char> run((size_t)F, 1);
@@ -3039,7 +2912,7 @@ static int download_records(cd_context* c, const float4* d_pts, int m, size_t st
     if (m <= 0) return CD_OK;
     const size_t skip = (staging_skip + 255) & ~(size_t)255;
     int st = CD_OK;
-    if (skip + (size_t)m * stride > c->d_in_bytes) {
+    if (skip + (size_t)m * stride > c->d_in.capacity()) {
         if (skip) return fail(c, CD_ERR_CAPACITY, "record staging area too small");   // (callers that keep the input size the buffer beforehand)
         st = ensure_input(c, (size_t)m * stride);
         if (st) return st;
@@ -3098,13 +2971,13 @@ static int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_
                         const cd_color_camera* ccam = nullptr) {
     const size_t px = (size_t)cam->width * cam->height * n_frames;
     const size_t cpx = ccam ? (size_t)ccam->width * ccam->height * n_frames : px;
-    if (!c->d_depth) HIPCHK(c, dalloc(&c->d_depth, (size_t)c->N * c->F));
+    GROW(c, d_depth, (size_t)c->N * c->F);
     HIPCHK(c, hipMemcpyAsync(c->d_depth, depth, px * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     dj->cam = cam;
     dj->depth = c->d_depth;
     dj->color = nullptr;
     if (cam->color == CD_COLOR_RGB8) {
-        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        GROW(c, d_color, (size_t)c->N * c->F * 3);
         HIPCHK(c, hipMemcpyAsync(c->d_color, color, cpx * 3, hipMemcpyHostToDevice, c->stream));
         dj->color = c->d_color;
     }
@@ -3159,8 +3032,8 @@ static int cd_depth_to_cloud_impl(cd_context* c, const cd_depth_camera* cam, con
     DepthJob dj;
     st = upload_depth(c, cam, depth, color, 1, &dj, ccam);
     if (st) return st;
-    LAUNCH(c, launch_depth_job(c->stream, &dj, 1, reinterpret_cast<float4*>(c->d_in)));
-    st = download_records(c, reinterpret_cast<const float4*>(c->d_in), P, stride, rgb_offset, 0u, out_records, rec_bytes);
+    LAUNCH(c, launch_depth_job(c->stream, &dj, 1, reinterpret_cast<float4*>(c->d_in.get())));
+    st = download_records(c, reinterpret_cast<const float4*>(c->d_in.get()), P, stride, rgb_offset, 0u, out_records, rec_bytes);
     if (st) return st;
     *out_n = P;
     return CD_OK;
@@ -3183,7 +3056,7 @@ static int cd_color_bbox_batch_impl(cd_context* c, const uint8_t* rgb8, int widt
     invalidate_last(c);
     const uint8_t* d_rgb = rgb8;
     if (!on_device) {
-        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        GROW(c, d_color, (size_t)c->N * c->F * 3);
         HIPCHK(c, hipMemcpyAsync(c->d_color, rgb8, (size_t)width * height * n_frames * 3, hipMemcpyHostToDevice, c->stream));
         d_rgb = c->d_color;
     }
@@ -3234,26 +3107,12 @@ static int check_overlay(cd_context* c, const void* rgb8, int width, int height,
 static int stage_overlay(cd_context* c, uint8_t* img, int W, int H, int F, const double* poses, const int32_t* n_boxes, int B,
                          const cd_overlay_params* op, cd_overlay_box* out, bool on_device) {
     const size_t nb = (size_t)F * (size_t)B;
-    if (nb > c->obox_cap) {
-        if (c->d_oposes) hipFree(c->d_oposes);
-        if (c->d_obox) hipFree(c->d_obox);
-        if (c->h_obox) hipHostFree(c->h_obox);
-        c->d_oposes = nullptr; c->d_obox = nullptr; c->h_obox = nullptr; c->obox_cap = 0;
-        HIPCHK(c, dalloc(&c->d_oposes, nb * 16));
-        HIPCHK(c, dalloc(&c->d_obox, nb));
-        HIPCHK(c, halloc(&c->h_obox, nb));
-        c->obox_cap = nb;
-    }
-    if ((size_t)F > c->onbox_cap) {
-        if (c->d_onbox) hipFree(c->d_onbox);
-        c->d_onbox = nullptr; c->onbox_cap = 0;
-        HIPCHK(c, dalloc(&c->d_onbox, (size_t)c->F));
-        c->onbox_cap = (size_t)c->F;
-    }
+    GROW(c, d_oposes, nb * 16); GROW(c, d_obox, nb); GROW(c, h_obox, nb);
+    GROW(c, d_onbox, (size_t)c->F);
     const size_t img_bytes = (size_t)W * H * F * 3;
     uint8_t* d_img = img;
     if (!on_device) {
-        if (!c->d_color) HIPCHK(c, dalloc(&c->d_color, (size_t)c->N * c->F * 3));
+        GROW(c, d_color, (size_t)c->N * c->F * 3);
         HIPCHK(c, hipMemcpyAsync(c->d_color, img, img_bytes, hipMemcpyHostToDevice, c->stream));
         d_img = c->d_color;
     }

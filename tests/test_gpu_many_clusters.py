@@ -132,3 +132,38 @@ def test_two_templates_when_the_source_copies_do_not_fit(O, small_tpl, template)
             assert list(g.T) == list(w.T) and g.fitness == w.fitness
     finally:
         ctx.close()
+
+
+def test_small_batch_is_unchanged_by_every_growth_and_by_a_new_context(small_tpl):
+    """One context: a small batch, a batch with more clusters than cd_create sized the cluster arrays for, the first-use and
+    grow-on-demand buffers of the colour gate, the overlay (one box per frame, then three) and the surface stage, the small batch
+    again; close().  Three such contexts one after the other in one process: the small batch's records are byte-identical before
+    and after the growth and in every cycle, and so is what the other calls return."""
+    small = synth.frame(1)[None]
+    grids = np.stack([synth.render(synth.scene_grid(3)), synth.render(synth.scene_grid(3))], 0)   # 24 clusters > 2 * 8
+    rgb = np.stack([synth.depth_frame(i)[1] for i in range(2)])
+    poses = np.stack([np.stack(synth.truth_poses(synth.scene_for(i, k_obj=3))) for i in range(2)])   # (2, 3, 4, 4)
+    clouds = [synth.frame(i)[::7, :3] for i in range(2)]
+    normals = np.array([[0, 0, 1], [0, 0, 1]], np.float32)
+    prm = capi.default_params()
+    prm.cluster_min_size = 60
+    seen = []
+    for cycle in range(3):
+        ctx = capi.Context(max_points=small.shape[1], max_frames=2)
+        try:
+            ctx.set_template(0, small_tpl)
+            before = bytes(ctx.process_batch(small, prm)[0])
+            img = rgb.copy()
+            one = bytes(ctx.draw_boxes(img, poses[:, :1], None, None))
+            res = ctx.process_batch(grids, prm)[0]
+            assert res[0].n_clusters == res[1].n_clusters == 12 and len(ctx.cluster_results(1)) == 12
+            many = bytes(res) + b"".join(bytes(r) for f in range(2) for r in ctx.cluster_results(f))
+            gate = bytes(ctx.color_bbox_batch(rgb))
+            three = bytes(ctx.draw_boxes(img, poses, None, None))
+            status, out = ctx.surface_batch(clouds, normals, prm)
+            after = bytes(ctx.process_batch(small, prm)[0])
+        finally:
+            ctx.close()
+        assert after == before, cycle
+        seen.append((before, one, many, gate, three, img.tobytes(), status.tobytes(), bytes(out)))
+        assert seen[-1] == seen[0], cycle
