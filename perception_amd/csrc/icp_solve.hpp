@@ -1,6 +1,6 @@
 // icp_solve.hpp - device code shared by the ICP kernels (k_icp.hip, k_icp_lat.hip): TransformationEstimationSVD
-// (pcl::umeyama with Eigen's two-sided Jacobi SVD restated in float32) from the 16 fixed-point moment sums, and the
-// canonical 4x4 x point product.  Reference: pcl::IterativeClosestPoint as called at
+// (pcl::umeyama with Eigen's two-sided Jacobi SVD restated in float32) from the 16 fixed-point moment sums, the
+// canonical 4x4 x point product, and icp_step - one PCL iteration's state update, the same for every driver.  Reference: pcl::IterativeClosestPoint as called at
 // cuboid_detection/src/iterative_closest_point.cpp:170-178 and object_detection/src/object_pose_detection.cpp:220-228.
 #pragma once
 #include "common.hpp"
@@ -169,6 +169,62 @@ __device__ __forceinline__ void xform(const float* T, float x, float y, float z,
     ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
     oy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
     oz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+}
+// C = A * B of row-major 4x4 matrices, each entry in the association of xform; C must not overlap A or B
+__device__ __forceinline__ void mat4_mul(const float* A, const float* B, float* C) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            C[4 * i + j] = ((A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j]) + A[4 * i + 3] * B[12 + j];
+}
+
+// ONE PCL iteration's state update from the 16 moment sums A of its n correspondences - the single implementation every ICP
+// driver calls (k_icp_solve, k_icp_persist, k_icp_cluster, k_icp_pipe / k_icp_pipe_big, k_icp_lat), on one lane:
+//   TransformationEstimationSVD (umeyama_from_moments), final_transformation_ = transformation_ * final_transformation_,
+//   DefaultConvergenceCriteria::hasConverged in its order: iteration limit, rotation / translation epsilon, absolute MSE,
+//   relative MSE (prev_mse moves only when the MSE tests are reached).
+// BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
+// Returns done and leaves it in so.converged; so.done and every other bookkeeping stay with the caller.
+template <bool BOUNDED>
+__device__ __forceinline__ int icp_step(IcpState& so, const unsigned long long* A, int n, const IcpParams& prm) {
+    if (BOUNDED && n < ICP_MIN_CORR) { icp_stop_few(so); return 1; }
+    float T[16], Tf[16];
+    umeyama_from_moments(A, n, T);
+    mat4_mul(T, so.Tfinal, Tf);
+    for (int i = 0; i < 16; ++i) so.Tfinal[i] = Tf[i];
+    so.iters += 1;
+    int done = 0;
+    if (so.iters >= prm.max_iter) {
+        done = 1;
+    } else {
+        const double cos_angle = 0.5 * (double)(((T[0] + T[5]) + T[10]) - 1.0f);
+        const double translation_sqr = (double)((T[3] * T[3] + T[7] * T[7]) + T[11] * T[11]);
+        if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
+            done = 1;
+        } else {
+            const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
+            if (fabs(mse - so.prev_mse) < prm.abs_mse) done = 1;
+            else if (fabs(mse - so.prev_mse) / so.prev_mse < prm.rel_mse) done = 1;
+            so.prev_mse = mse;
+        }
+    }
+    for (int i = 0; i < 16; ++i) so.T[i] = T[i];
+    so.converged = done;
+    return done;
+}
+
+// The 16 fixed-point moment terms of ONE correspondence (rule C4): S[0..2] p, [3..5] q, [6..14] q_a p_b, [15] d2.
+// FAST: the conversion is fixq_fast (the caller has checked its range condition) instead of fixq - the same integers.
+template <bool FAST = false>
+__device__ __forceinline__ void moment_terms(const float (&pv)[3], const float (&qv)[3], float d2, unsigned long long (&S)[16]) {
+    auto fix = [](float v, int shift) { return FAST ? fixq_fast(v, shift) : (unsigned long long)fixq(v, shift); };
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        S[a] = fix(pv[a], FIX_SHIFT);
+        S[3 + a] = fix(qv[a], FIX_SHIFT);
+#pragma unroll
+        for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = fix(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
+    }
+    S[15] = fix(d2, FIX_SHIFT_D2);
 }
 
 }  // namespace cd

@@ -652,8 +652,8 @@ __device__ __forceinline__ void store_queries(const QueryRegs& q, int nk, int* n
     }
 }
 
-// One thread per cluster: TransformationEstimationSVD + final_transformation_ update +
-// DefaultConvergenceCriteria for launch `it`, from the moments launch it-1 accumulated.
+// One thread per cluster: the state update of launch `it` (icp_step: TransformationEstimationSVD + final_transformation_
+// update + DefaultConvergenceCriteria), from the moments launch it-1 accumulated.
 // Writes the state slot k_icp_iter(it) consumes, keeps the `done` flag in both parity slots and
 // clears the moment buffer launch it+1 will accumulate into.  BOUNDED (rule C8): n = the kept correspondences that launch
 // it-1 counted in bnd.ncorr; fewer than three stop the ICP before the update (icp_stop_few).
@@ -666,46 +666,13 @@ __global__ void __launch_bounds__(WAVE) k_icp_solve(int it, int ncl, const IcpCl
     if (k >= ncl) return;
     const IcpState* sin = st + (size_t)k * 2 + (it & 1);
     IcpState* sout = st + (size_t)k * 2 + ((it + 1) & 1);
-    if (sin->done) { *sout = *sin; return; }
-    IcpState so = *sin;
+    *sout = *sin;
+    if (sin->done) return;
     if (it > 0) {
-        const IcpCluster c = cl[k];
         const unsigned long long* A = acc + ((size_t)k * 3 + (it - 1) % 3) * 16;
-        const int n = BOUNDED ? (int)bnd.ncorr[(size_t)k * 3 + (it - 1) % 3] : c.n;
-        if (BOUNDED && n < ICP_MIN_CORR) {
-            so.done = 1;
-            icp_stop_few(so);
-        } else {
-            float T[16];
-            umeyama_from_moments(A, n, T);
-            // final_transformation_ = transformation_ * final_transformation_
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j)
-                    so.Tfinal[4 * i + j] = ((T[4 * i] * sin->Tfinal[j] + T[4 * i + 1] * sin->Tfinal[4 + j]) +
-                                            T[4 * i + 2] * sin->Tfinal[8 + j]) + T[4 * i + 3] * sin->Tfinal[12 + j];
-            so.iters = sin->iters + 1;
-            int done = 0;
-            // DefaultConvergenceCriteria::hasConverged
-            if (so.iters >= prm.max_iter) {
-                done = 1;
-            } else {
-                const double cos_angle = 0.5 * (double)(((T[0] + T[5]) + T[10]) - 1.0f);
-                const double translation_sqr = (double)((T[3] * T[3] + T[7] * T[7]) + T[11] * T[11]);
-                if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
-                    done = 1;
-                } else {
-                    const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
-                    if (fabs(mse - sin->prev_mse) < prm.abs_mse) done = 1;
-                    else if (fabs(mse - sin->prev_mse) / sin->prev_mse < prm.rel_mse) done = 1;
-                    so.prev_mse = mse;
-                }
-            }
-            so.done = done;
-            so.converged = done;
-            for (int i = 0; i < 16; ++i) so.T[i] = T[i];
-        }
+        const int n = BOUNDED ? (int)bnd.ncorr[(size_t)k * 3 + (it - 1) % 3] : cl[k].n;
+        sout->done = icp_step<BOUNDED>(*sout, A, n, prm);
     }
-    *sout = so;
     unsigned long long* Z = acc + ((size_t)k * 3 + (it + 1) % 3) * 16;
     for (int i = 0; i < 16; ++i) Z[i] = 0ull;
     if (BOUNDED) bnd.ncorr[(size_t)k * 3 + (it + 1) % 3] = 0u;
@@ -803,14 +770,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, c
             const float4 p = pts[i];
             const float4 qq = tp[nnq[i]];
             const float pv[3] = {p.x, p.y, p.z}, qv[3] = {qq.x, qq.y, qq.z};
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                S[a] = (unsigned long long)fixq(pv[a], FIX_SHIFT);
-                S[3 + a] = (unsigned long long)fixq(qv[a], FIX_SHIFT);
-#pragma unroll
-                for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
-            }
-            S[15] = (unsigned long long)fixq(d2q[i], FIX_SHIFT_D2);
+            moment_terms(pv, qv, d2q[i], S);
         }
         static_assert(ICP_QSLICE <= ICPT_THREADS, "one point per thread in the moment pass");
 #pragma unroll
@@ -881,39 +841,6 @@ __device__ __forceinline__ bool grid_barrier(unsigned* bar, unsigned target, int
     return *s_ok != 0;
 }
 
-// one PCL iteration's state update of a cluster from the moment sums of the previous iteration (what k_icp_solve does)
-template <bool BOUNDED>
-__device__ void persist_solve(IcpState& so, const unsigned long long* A, int n, const IcpParams& prm) {
-    if (BOUNDED && n < ICP_MIN_CORR) { so.done = 1; icp_stop_few(so); return; }
-    float T[16];
-    umeyama_from_moments(A, n, T);
-    float Tf[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            Tf[4 * i + j] = ((T[4 * i] * so.Tfinal[j] + T[4 * i + 1] * so.Tfinal[4 + j]) + T[4 * i + 2] * so.Tfinal[8 + j]) +
-                            T[4 * i + 3] * so.Tfinal[12 + j];
-    for (int i = 0; i < 16; ++i) so.Tfinal[i] = Tf[i];
-    so.iters += 1;
-    int done = 0;
-    if (so.iters >= prm.max_iter) {
-        done = 1;
-    } else {
-        const double cos_angle = 0.5 * (double)(((T[0] + T[5]) + T[10]) - 1.0f);
-        const double translation_sqr = (double)((T[3] * T[3] + T[7] * T[7]) + T[11] * T[11]);
-        if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
-            done = 1;
-        } else {
-            const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
-            if (fabs(mse - so.prev_mse) < prm.abs_mse) done = 1;
-            else if (fabs(mse - so.prev_mse) / so.prev_mse < prm.rel_mse) done = 1;
-            so.prev_mse = mse;
-        }
-    }
-    so.done = done;
-    so.converged = done;
-    for (int i = 0; i < 16; ++i) so.T[i] = T[i];
-}
-
 #ifdef CD_PERSISTDBG
 // time workgroup 0 spends per phase of an iteration (100 MHz ticks): solve, transform, fetch + search + store, moments, barrier
 __device__ unsigned long long g_persist_dbg[8];
@@ -971,7 +898,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
                 __syncthreads();
                 if (threadIdx.x == 0) {
                     IcpState so = s_st[j];
-                    persist_solve<BOUNDED>(so, s_A, BOUNDED ? (int)s_nv : c.n, prm);
+                    so.done = icp_step<BOUNDED>(so, s_A, BOUNDED ? (int)s_nv : c.n, prm);
                     s_st[j] = so;
                     // one count per cluster that closes in iteration `it`, into the slot of that iteration (see the exit test)
                     if (wk.tile == 0 && so.done) __hip_atomic_fetch_add(closed + (it & 3), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1048,14 +975,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
                 const float4 p = pts[i];
                 const float4 qq = tp[nnq[i]];
                 const float pv[3] = {p.x, p.y, p.z}, qv[3] = {qq.x, qq.y, qq.z};
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    S[a] = (unsigned long long)fixq(pv[a], FIX_SHIFT);
-                    S[3 + a] = (unsigned long long)fixq(qv[a], FIX_SHIFT);
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
-                }
-                S[15] = (unsigned long long)fixq(d2q[i], FIX_SHIFT_D2);
+                moment_terms(pv, qv, d2q[i], S);
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -1286,14 +1206,10 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     if (!BOUNDED || q.pbest <= bnd.d2_max) {
                         const float4 qq = resident ? s_tpl[q.pbi] : tp[q.pbi];
                         const float pv[3] = {q.px, q.py, q.pz}, qv[3] = {qq.x, qq.y, qq.z};
+                        unsigned long long t[16];
+                        moment_terms(pv, qv, q.pbest, t);
 #pragma unroll
-                        for (int a = 0; a < 3; ++a) {
-                            S[a] += (unsigned long long)fixq(pv[a], FIX_SHIFT);
-                            S[3 + a] += (unsigned long long)fixq(qv[a], FIX_SHIFT);
-#pragma unroll
-                            for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] += (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
-                        }
-                        S[15] += (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
+                        for (int i = 0; i < 16; ++i) S[i] += t[i];
                     }
                 }
             }
@@ -1302,39 +1218,9 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
             block_sum16(S, s_part, s_tot);
             CD_PHASE(4)
             const int n_used = BOUNDED ? (int)s_nv : c.n;
-            if (BOUNDED && threadIdx.x == 0 && n_used < ICP_MIN_CORR) {   // rule C8: too few correspondences, stop before the update
-                IcpState so = s_so;
-                icp_stop_few(so);
-                s_so = so;
-                s_flag[1] = 1;
-            } else if (threadIdx.x == 0) {   // solve for iteration it+1 (same code as k_icp_solve)
-                float Tn[16];
-                umeyama_from_moments(s_tot, n_used, Tn);
-                float Tf[16];
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j)
-                        Tf[4 * i + j] = ((Tn[4 * i] * s_so.Tfinal[j] + Tn[4 * i + 1] * s_so.Tfinal[4 + j]) +
-                                         Tn[4 * i + 2] * s_so.Tfinal[8 + j]) + Tn[4 * i + 3] * s_so.Tfinal[12 + j];
-                for (int i = 0; i < 16; ++i) s_so.Tfinal[i] = Tf[i];
-                s_so.iters += 1;
-                int done = 0;
-                if (s_so.iters >= prm.max_iter) {
-                    done = 1;
-                } else {
-                    const double cos_angle = 0.5 * (double)(((Tn[0] + Tn[5]) + Tn[10]) - 1.0f);
-                    const double translation_sqr = (double)((Tn[3] * Tn[3] + Tn[7] * Tn[7]) + Tn[11] * Tn[11]);
-                    if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
-                        done = 1;
-                    } else {
-                        const double mse = unfix(s_tot[15], FIX_SHIFT_D2) / (double)n_used;
-                        if (fabs(mse - s_so.prev_mse) < prm.abs_mse) done = 1;
-                        else if (fabs(mse - s_so.prev_mse) / s_so.prev_mse < prm.rel_mse) done = 1;
-                        s_so.prev_mse = mse;
-                    }
-                }
-                for (int i = 0; i < 16; ++i) s_so.T[i] = Tn[i];
-                if (BOUNDED) { s_so.converged = done; s_nv = 0u; }
-                s_flag[1] = done;
+            if (threadIdx.x == 0) {   // the state update for iteration it+1
+                s_flag[1] = icp_step<BOUNDED>(s_so, s_tot, n_used, prm);
+                if (BOUNDED) s_nv = 0u;
             }
             __syncthreads();
             CD_PHASE(5)
@@ -1389,7 +1275,6 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
             block_sum16(S, s_part, s_tot);
             if (threadIdx.x == 0) {
                 s_so.done = 1;
-                if (!BOUNDED) s_so.converged = 1;   // (BOUNDED: set by the solve - 0 after a stop for too few correspondences)
                 st[2 * (size_t)k] = s_so;
                 st[2 * (size_t)k + 1] = s_so;
                 accf[k] = s_tot[0];
@@ -1445,47 +1330,11 @@ struct PipeSlotN : PipeSlot {
 template <bool BOUNDED> struct PipeSlotSel { using T = PipeSlot; };
 template <> struct PipeSlotSel<true> { using T = PipeSlotN; };
 
-// Umeyama + convergence test of one iteration (lane 0 of the finishing wave); same code as k_icp_solve.
-// BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
-// (Out-of-line callees are plain overloads below, not template instances: a linkonce function has no exact definition,
+// The state update of one iteration (icp_step; lane 0 of the finishing wave).  BOUNDED (rule C8): n = the kept correspondences.
+// (Out-of-line callees are plain overloads, not template instances: a linkonce function has no exact definition,
 // so its callers could not use its register usage - k_icp_pipe would allocate more registers around the call.)
-template <bool BOUNDED>
-__device__ __forceinline__ int pipe_solve_body(typename PipeSlotSel<BOUNDED>::T* sl, const IcpParams& prm) {
-    int n = sl->n;
-    if constexpr (BOUNDED) {
-        n = (int)sl->nv;
-        if (n < ICP_MIN_CORR) { icp_stop_few(sl->so); return 1; }
-    }
-    float Tn[16];
-    umeyama_from_moments(sl->acc, n, Tn);
-    float Tf[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            Tf[4 * i + j] = ((Tn[4 * i] * sl->so.Tfinal[j] + Tn[4 * i + 1] * sl->so.Tfinal[4 + j]) +
-                             Tn[4 * i + 2] * sl->so.Tfinal[8 + j]) + Tn[4 * i + 3] * sl->so.Tfinal[12 + j];
-    for (int i = 0; i < 16; ++i) sl->so.Tfinal[i] = Tf[i];
-    sl->so.iters += 1;
-    int done = 0;
-    if (sl->so.iters >= prm.max_iter) {
-        done = 1;
-    } else {
-        const double cos_angle = 0.5 * (double)(((Tn[0] + Tn[5]) + Tn[10]) - 1.0f);
-        const double translation_sqr = (double)((Tn[3] * Tn[3] + Tn[7] * Tn[7]) + Tn[11] * Tn[11]);
-        if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
-            done = 1;
-        } else {
-            const double mse = unfix(sl->acc[15], FIX_SHIFT_D2) / (double)n;
-            if (fabs(mse - sl->so.prev_mse) < prm.abs_mse) done = 1;
-            else if (fabs(mse - sl->so.prev_mse) / sl->so.prev_mse < prm.rel_mse) done = 1;
-            sl->so.prev_mse = mse;
-        }
-    }
-    for (int i = 0; i < 16; ++i) sl->so.T[i] = Tn[i];
-    if constexpr (BOUNDED) sl->so.converged = done;
-    return done;
-}
-__device__ __noinline__ int pipe_solve(PipeSlot* sl, const IcpParams& prm) { return pipe_solve_body<false>(sl, prm); }
-__device__ __noinline__ int pipe_solve(PipeSlotN* sl, const IcpParams& prm) { return pipe_solve_body<true>(sl, prm); }
+__device__ __noinline__ int pipe_solve(PipeSlot* sl, const IcpParams& prm) { return icp_step<false>(sl->so, sl->acc, sl->n, prm); }
+__device__ __noinline__ int pipe_solve(PipeSlotN* sl, const IcpParams& prm) { return icp_step<true>(sl->so, sl->acc, (int)sl->nv, prm); }
 
 // next cluster from the global queue into the slot (lane 0 of the finishing wave)
 // (items [gbeg, gend) of `order`: the clusters that share the workgroup's template)
@@ -1881,23 +1730,9 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                             if (BOUNDED && !(q.pbest <= bnd.d2_max)) {
                                 // rejected (rule C8): adds nothing
                             } else if (fast) {
-#pragma unroll
-                                for (int a = 0; a < 3; ++a) {
-                                    S[a] = fixq_fast(pv[a], FIX_SHIFT);
-                                    S[3 + a] = fixq_fast(qv[a], FIX_SHIFT);
-#pragma unroll
-                                    for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = fixq_fast(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
-                                }
-                                S[15] = fixq_fast(q.pbest, FIX_SHIFT_D2);
+                                moment_terms<true>(pv, qv, q.pbest, S);
                             } else {
-#pragma unroll
-                                for (int a = 0; a < 3; ++a) {
-                                    S[a] = (unsigned long long)fixq(pv[a], FIX_SHIFT);
-                                    S[3 + a] = (unsigned long long)fixq(qv[a], FIX_SHIFT);
-#pragma unroll
-                                    for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT);
-                                }
-                                S[15] = (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
+                                moment_terms(pv, qv, q.pbest, S);
                             }
                         } else {
                             S[0] = fast ? fixq_fast(q.pbest, FIX_SHIFT_D2) : (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
@@ -1940,7 +1775,6 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                     } else {
                         if (phase == PH_FIT) {
                             sl->so.done = 1;
-                            if (!BOUNDED) sl->so.converged = 1;   // (BOUNDED: set by pipe_solve - 0 after a stop for too few correspondences)
                             st[2 * (size_t)sl->k] = sl->so;
                             st[2 * (size_t)sl->k + 1] = sl->so;
                             accf[sl->k] = sl->acc[0];

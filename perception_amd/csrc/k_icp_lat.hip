@@ -199,48 +199,13 @@ __device__ __forceinline__ int lat_index(const int4* s_face, const LatFaces& F, 
     return fd.z + iv * s_face[LAT_MAX_FACES + h.face].z + iu;
 }
 
-// one PCL iteration's state update from the moment sums (what k_icp_solve / pipe_solve do): TransformationEstimationSVD,
-// final_transformation_ = transformation_ * final_transformation_, DefaultConvergenceCriteria::hasConverged.  Returns done.
-// BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
-template <bool BOUNDED>
-__device__ __forceinline__ int lat_solve(IcpState* so, const unsigned long long* A, int n, const IcpParams& prm) {
-    if (BOUNDED && n < ICP_MIN_CORR) { icp_stop_few(*so); return 1; }
-    float Tn[16];
-    umeyama_from_moments(A, n, Tn);
-    float Tf[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            Tf[4 * i + j] = ((Tn[4 * i] * so->Tfinal[j] + Tn[4 * i + 1] * so->Tfinal[4 + j]) + Tn[4 * i + 2] * so->Tfinal[8 + j]) +
-                            Tn[4 * i + 3] * so->Tfinal[12 + j];
-    for (int i = 0; i < 16; ++i) so->Tfinal[i] = Tf[i];
-    so->iters += 1;
-    int done = 0;
-    if (so->iters >= prm.max_iter) {
-        done = 1;
-    } else {
-        const double cos_angle = 0.5 * (double)(((Tn[0] + Tn[5]) + Tn[10]) - 1.0f);
-        const double translation_sqr = (double)((Tn[3] * Tn[3] + Tn[7] * Tn[7]) + Tn[11] * Tn[11]);
-        if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
-            done = 1;
-        } else {
-            const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
-            if (fabs(mse - so->prev_mse) < prm.abs_mse) done = 1;
-            else if (fabs(mse - so->prev_mse) / so->prev_mse < prm.rel_mse) done = 1;
-            so->prev_mse = mse;
-        }
-    }
-    for (int i = 0; i < 16; ++i) so->T[i] = Tn[i];
-    if (BOUNDED) so->converged = done;
-    return done;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // k_icp_lat<CPW, WPC>: a workgroup keeps CPW clusters ("slots") going, WPC waves each, and works in ROUNDS of two phases:
 //   work  : the waves of a slot take the passes (64 points each) of the slot's current step - a PCL iteration (X <- T X in
 //           place, nearest neighbours, the 16 fixed-point moment sums of rule C4 kept in registers and folded into the slot's
 //           LDS accumulators) or, once converged, the final transform + getFitnessScore() pass;            -- barrier --
-//   solve : lane s of wave 0 finishes slot s's step: Umeyama + SVD + convergence tests (lat_solve: the same code as
-//           k_icp_solve), or the write-back of a finished cluster and the refill of the slot from the launch's cluster queue.
+//   solve : lane s of wave 0 finishes slot s's step: Umeyama + SVD + convergence tests (icp_step, icp_solve.hpp: what every
+//           driver calls), or the write-back of a finished cluster and the refill of the slot from the launch's cluster queue.
 //           The solves of a workgroup's slots run SIDE BY SIDE in the lanes of one wave.                     -- barrier --
 // Why this shape (measured, tools/lat_threads_serial.sh): a step of a 1 400-point cluster is ~19 us of passes for one wave
 // and ~9.6 us of single-lane solve (3 300 dependent instructions: IEEE divisions and square roots of the Jacobi sweeps).
@@ -479,13 +444,12 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
             if (sl.phase == LAT_ITER && sl.ready) {
                 for (int i = 0; i < 15; ++i) s_acc[s][i] -= off;
                 s_acc[s][15] -= off_d;
-                if (lat_solve<BOUNDED>(&s_so[s], s_acc[s], nv, prm)) sl.phase = LAT_FIT;
+                if (icp_step<BOUNDED>(s_so[s], s_acc[s], nv, prm)) sl.phase = LAT_FIT;
                 for (int i = 0; i < 16; ++i) s_acc[s][i] = 0ull;
                 if constexpr (BOUNDED) s_nv[s] = 0u;
                 sl.ready = 0;
             } else if (sl.phase == LAT_FIT) {
                 s_so[s].done = 1;
-                if (!BOUNDED) s_so[s].converged = 1;   // (BOUNDED: lat_solve set it - 0 after a stop for too few correspondences)
                 st[2 * (size_t)sl.k] = s_so[s];
                 st[2 * (size_t)sl.k + 1] = s_so[s];
                 accf[sl.k] = s_acc[s][0] - off_d;
