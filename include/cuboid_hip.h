@@ -196,6 +196,12 @@ int cd_template_nearest(cd_context* ctx, int slot, const void* queries, size_t s
  * faces, 0 = not a lattice. */
 int cd_lattice_detect(const void* xyz, size_t stride_bytes, int m, int32_t* out);
 
+/* Host-only: does the lattice cd_lattice_detect finds have at most one face per constant axis (every three-face cuboid
+ * template; not the six-face one)?  Such templates take the ICP's mask-free face code.  Returns 1 / 0 (0 also when the points
+ * are no lattice).  out_axis_face[3] (may be NULL): the face whose constant axis is x / y / z, -1 = none; out_axis_c[3] (may be
+ * NULL): that face's constant coordinate, NaN when none.  Both are all "none" when the result is 0. */
+int cd_lattice_axes(const void* xyz, size_t stride_bytes, int m, int32_t* out_axis_face, float* out_axis_c);
+
 /* S0+S1: two PassThrough filters + VoxelGrid::filter (gps.cpp:53-73).  out_xyz receives
  * N_v * 3 floats in ascending voxel-index order, out_rgb (may be NULL) N_v packed rgb. */
 int cd_crop_voxel(cd_context* ctx, const void* points, size_t stride_bytes, int n,

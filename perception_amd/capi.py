@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "cd_set_template", "cd_crop_voxel", "cd_segment_plane", "cd_extract", "cd_surface_frame", "cd_bbox_filter", "cd_cluster", "cd_icp",
     "cd_process_batch", "cd_process_frame", "cd_process_batch_device", "cd_get_cluster_results", "cd_pose_to_position_quaternion",
     "cd_bbox_corners", "cd_get_timing", "cd_get_frame_cloud", "cd_get_cluster_points", "cd_ground_plane", "cd_set_frame_guesses",
-    "cd_template_lattice_faces", "cd_template_nearest", "cd_lattice_detect", "cd_passthrough",
+    "cd_template_lattice_faces", "cd_template_nearest", "cd_lattice_detect", "cd_lattice_axes", "cd_passthrough",
     "cd_default_depth_camera", "cd_depth_to_cloud", "cd_process_depth_batch", "cd_process_depth_batch_device",
     "cd_set_icp_max_correspondence_distance", "cd_get_icp_max_correspondence_distance", "cd_icp_correspondence_threshold",
     "cd_surface_batch", "cd_surface_guess", "cd_set_surface_distance_threshold", "cd_get_surface_distance_threshold",
@@ -326,6 +326,7 @@ def load_library(path=None):
     lib.cd_template_lattice_faces.argtypes = [vp, C.c_int]
     lib.cd_template_nearest.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_lattice_detect.argtypes = [vp, C.c_size_t, C.c_int, vp]
+    lib.cd_lattice_axes.argtypes = [vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_set_icp_max_correspondence_distance.argtypes = [vp, C.c_double]
     lib.cd_get_icp_max_correspondence_distance.argtypes = [vp, C.POINTER(C.c_double)]
     lib.cd_icp_correspondence_threshold.argtypes = [C.c_double, C.POINTER(C.c_float), ip]
@@ -802,6 +803,19 @@ def lattice_detect(xyz):
     if nf < 0:
         raise CuboidError(nf, "cd_lattice_detect")
     return [tuple(int(v) for v in out[f]) for f in range(nf)]
+
+
+def lattice_axes(xyz):
+    """Host-only: (axes_distinct, axis_face[3], axis_c[3]) of the lattice cd_lattice_detect finds - at most one face per constant
+    axis (1) or not (0, also for points that are no lattice); face index per axis (-1: none) and its constant coordinate (NaN)."""
+    lib = load_library()
+    a, stride, m = _points(xyz)
+    face = np.zeros(3, np.int32)
+    c = np.zeros(3, np.float32)
+    r = lib.cd_lattice_axes(_ptr(a), stride, m, _ptr(face), _ptr(c))
+    if r < 0:
+        raise CuboidError(r, "cd_lattice_axes")
+    return int(r), [int(v) for v in face], c
 
 
 def icp_correspondence_threshold(d):

@@ -147,8 +147,36 @@ struct IcpLattice {
     float c[LAT_MAX_FACES];        // its constant coordinate
     uint32_t m0[LAT_MAX_FACES], m1[LAT_MAX_FACES], m2[LAT_MAX_FACES];   // all ones when w == 0 / 1 / 2 (the face loop's selects are v_bfi_b32 with these
                                    // words); faces beyond nface: a constant z = NaN, so that their "distance" is NaN and never compares below anything
-    float4 tab[LAT_MAX_TAB];       // entry i of a table: (T[i-1], T[i], T[i+1], unused) with T[-1] = -inf, T[n] = +inf
+    // One face per axis at the most (the three-face make_cuboid.py templates; lattice_classify_axes below): the distance to "the
+    // face of constant x" is then (fcx + fy) + fz without a select, and which face wins a tie is a matter of face order that
+    // scalar registers settle (lat_nearest_axes, k_icp_lat.hip).
+    int32_t axis_face[3];          // the face whose constant axis is x / y / z, -1 = none; valid only when axes_distinct
+    float axis_c[3];               // that face's constant coordinate, NaN when none
+    int32_t axes_distinct;         // 1: nface <= 3 and no two faces share a constant axis
+    float4 tab[LAT_MAX_TAB];      // entry i of a table: (T[i-1], T[i], T[i+1], unused) with T[-1] = -inf, T[n] = +inf
 };
+
+// Fills axis_face / axis_c / axes_distinct from nface and w[] / c[] (host: the end of lattice_detect).  A template with two
+// faces on one axis (the six-face cuboid, two parallel plates) or more than three faces keeps axes_distinct = 0 and with it
+// the general face loop.
+inline void lattice_classify_axes(IcpLattice* L) {
+    uint32_t nan_bits = 0x7fc00000u;
+    float nan;
+    static_assert(sizeof(nan) == sizeof(nan_bits), "float32");
+    __builtin_memcpy(&nan, &nan_bits, sizeof(nan));
+    for (int a = 0; a < 3; ++a) { L->axis_face[a] = -1; L->axis_c[a] = nan; }
+    L->axes_distinct = 0;
+    if (L->nface < 1 || L->nface > 3) return;
+    for (int f = 0; f < L->nface; ++f) {
+        const int w = L->w[f];
+        if (w < 0 || w > 2 || L->axis_face[w] >= 0) {   // a second face on this axis
+            for (int a = 0; a < 3; ++a) { L->axis_face[a] = -1; L->axis_c[a] = nan; }
+            return;
+        }
+        L->axis_face[w] = f; L->axis_c[w] = L->c[f];
+    }
+    L->axes_distinct = 1;
+}
 
 struct IcpState {          // dynamic ICP state, double-buffered by launch parity
     float Tfinal[16];

@@ -2170,6 +2170,7 @@ static void lattice_detect(const float* xyz, int m, IcpLattice* out) {
     }
     for (size_t f = faces.size(); f < (size_t)LAT_MAX_FACES; ++f) { out->w[f] = 2; out->m2[f] = ~0u; out->c[f] = std::numeric_limits<float>::quiet_NaN(); }   // (see IcpLattice::m0)
     out->nface = (int)faces.size();
+    lattice_classify_axes(out);
 }
 
 static std::shared_ptr<const PreparedTemplate> prepare_template(const void* xyz, size_t stride, int m) {
@@ -2484,6 +2485,18 @@ int cd_lattice_detect(const void* xyz, size_t stride, int m, int32_t* out) {
         std::memcpy(out + 5 * f, row, sizeof(row));
     }
     return L->nface;
+}
+
+int cd_lattice_axes(const void* xyz, size_t stride, int m, int32_t* out_axis_face, float* out_axis_c) {
+    if (!xyz || m <= 0 || stride < 12) return CD_ERR_INVALID_ARG;
+    std::vector<float> raw((size_t)m * 3);
+    for (int i = 0; i < m; ++i) std::memcpy(&raw[3 * (size_t)i], (const char*)xyz + (size_t)i * stride, 12);
+    auto L = std::make_unique<IcpLattice>();
+    lattice_detect(raw.data(), m, L.get());
+    if (L->nface == 0) lattice_classify_axes(L.get());   // (not a lattice: the "none" values)
+    if (out_axis_face) std::memcpy(out_axis_face, L->axis_face, sizeof(L->axis_face));
+    if (out_axis_c) std::memcpy(out_axis_c, L->axis_c, sizeof(L->axis_c));
+    return L->axes_distinct;
 }
 
 int cd_template_nearest(cd_context* c, int slot, const void* queries, size_t stride, int n, int32_t* out_index, float* out_d2) {

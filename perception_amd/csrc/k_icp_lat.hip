@@ -44,16 +44,31 @@ struct LatFaces {
     float c[LAT_MAX_FACES];
     int nx, ny, nz, tox, toy, toz;   // entries and first entry of the axis tables (separate scalars: an array indexed by a face's axis would be put into scratch memory)
     float ox, oy, oz, ivx, ivy, ivz;   // (ox = -X[0] / step, ivx = 1 / step: IcpLattice::noi, inv)
+    int axes;                          // IcpLattice::axes_distinct: one face per axis at the most - lat_nearest_axes applies
+    int afx, afy, afz;                 // the face of constant x / y / z (-1: none)
+    float cax, cay, caz;               // its constant coordinate (NaN: none)
 };
 
-// call from every thread of the workgroup; ends with a barrier
-template <int THREADS>
-__device__ __forceinline__ void lat_stage(const IcpLattice* __restrict__ L, LatFaces& F, float4* s_tab, int4* s_face) {
+// the face words of a template as wave-uniform values (scalar loads)
+__device__ __forceinline__ void lat_faces_load(const IcpLattice* __restrict__ L, LatFaces& F) {
     F.nface = L->nface;
 #pragma unroll
     for (int f = 0; f < LAT_MAX_FACES; ++f) { F.m0[f] = L->m0[f]; F.m1[f] = L->m1[f]; F.m2[f] = L->m2[f]; F.c[f] = L->c[f]; }
     F.nx = L->n[0]; F.ny = L->n[1]; F.nz = L->n[2]; F.tox = L->toff[0]; F.toy = L->toff[1]; F.toz = L->toff[2];
     F.ox = L->noi[0]; F.oy = L->noi[1]; F.oz = L->noi[2]; F.ivx = L->inv[0]; F.ivy = L->inv[1]; F.ivz = L->inv[2];
+    F.axes = L->axes_distinct;
+    F.afx = L->axis_face[0]; F.afy = L->axis_face[1]; F.afz = L->axis_face[2];
+    // (in vector registers from here on: a v_cndmask whose condition is a scalar mask has no room for a second scalar
+    // operand, and the compiler would move each constant into a register again in every pass)
+    asm("v_mov_b32 %0, %1" : "=v"(F.cax) : "s"(L->axis_c[0]));
+    asm("v_mov_b32 %0, %1" : "=v"(F.cay) : "s"(L->axis_c[1]));
+    asm("v_mov_b32 %0, %1" : "=v"(F.caz) : "s"(L->axis_c[2]));
+}
+
+// call from every thread of the workgroup; ends with a barrier
+template <int THREADS>
+__device__ __forceinline__ void lat_stage(const IcpLattice* __restrict__ L, LatFaces& F, float4* s_tab, int4* s_face) {
+    lat_faces_load(L, F);
     for (int i = threadIdx.x; i < L->ntab; i += THREADS) s_tab[i] = L->tab[i];
     if (threadIdx.x < LAT_MAX_FACES) {
         const int f = threadIdx.x, w = L->w[f], u = L->fast[f], v = 3 - w - u;
@@ -72,7 +87,7 @@ __device__ __forceinline__ float lat_pick(unsigned m, float a, float b) {
 }
 
 // one axis: the table entry nearest to q.  f = fl(fl(q - T[i])^2) at the minimum, t = T[i], gap = f(i - 1) - f(i) (+inf at
-// i = 0; 0 = not known: the exact test decides), i = ig + di with di in {-1, 0, +1} (left as two flags: only the rare tie walk
+// i = 0; negative = not known: the exact test decides), i = ig + di with di in {-1, 0, +1} (left as two flags: only the rare tie walk
 // needs the index).  Every axis has a table (one that no face varies along has the single entry 0).
 // The window's centre ig only has to be within one entry of the nearest one - all three of the window are evaluated exactly -
 // so it is taken from ONE fused multiply-add and a conversion that rounds half up (v_cvt_rpi_i32_f32): q * inv - o * inv sits
@@ -93,7 +108,11 @@ __device__ __forceinline__ void lat_axis(const float4* s_tab, int toff, int n, f
     const bool lo = f0 < f1;
     const bool hi = f2 < f1;
     f = f1; t = W.y; gap = g_mid;
-    f = lo ? f0 : f; t = lo ? W.x : t; gap = lo ? 0.f : gap;
+    // (lo - the window's centre was one entry too high, so the minimum's own lower neighbour lies outside the window - leaves
+    // gap = f0 - f1 < 0: like the 0 it used to be set to, that is below every threshold of the tie filter, and the exact walk
+    // decides.  It takes the approximate centre to disagree with the exact comparison: queries within ~1e-4 of an entry of a
+    // cell midpoint, which mostly tie and walk anyway - too rare to spend an instruction of the common path on.)
+    f = lo ? f0 : f; t = lo ? W.x : t;
     f = hi ? f2 : f; t = hi ? W.z : t; gap = hi ? g_hi : gap;
     ig_out = ig; lo_out = lo; hi_out = hi;
 }
@@ -108,9 +127,63 @@ struct LatHit {
     int ix, iy, iz;     // table indices (the constant axis' entry is not used)
 };
 
+// (3): the exact walk to the lowest original index among the points of the winning face that tie with the minimum.  Rare (a lane
+// enters when its gap is within the rounding of the sum: iteration 0, mid-cell queries): one face at a time.  ix / iy / iz = the
+// table indices of the per-axis minima; h.d and h.face are set, h.nx / ny / nz hold the neighbour found so far.
+__device__ __forceinline__ void lat_tie_walk(const float4* s_tab, const int4* s_face, const LatFaces& F, float qx, float qy, float qz, float fx, float fy, float fz,
+                                             float tx, float ty, float tz, int ix, int iy, int iz, bool maybe, LatHit& h) {
+    h.ix = ix; h.iy = iy; h.iz = iz;
+    for (int f = 0; f < F.nface; ++f) {
+        const bool mine = maybe && h.face == f;
+        if (!ballot64(mine)) continue;
+        const int4 gd = s_face[f];
+        const int w = __builtin_amdgcn_readfirstlane(gd.x), u = __builtin_amdgcn_readfirstlane(gd.y), v = 3 - w - u;   // constant, fast, slow axis
+        const float cc = __int_as_float(__builtin_amdgcn_readfirstlane(gd.w));
+        const int4 ge = s_face[LAT_MAX_FACES + f];
+        const int toff_u = __builtin_amdgcn_readfirstlane(ge.x), toff_v = __builtin_amdgcn_readfirstlane(ge.y);
+        const float qw = w == 0 ? qx : (w == 1 ? qy : qz), qu = u == 0 ? qx : (u == 1 ? qy : qz), qv = v == 0 ? qx : (v == 1 ? qy : qz);
+        const float dc = __fsub_rn(qw, cc);
+        const float fc = __fmul_rn(dc, dc);
+        float fu = u == 0 ? fx : (u == 1 ? fy : fz), fv = v == 0 ? fx : (v == 1 ? fy : fz);
+        float tu = u == 0 ? tx : (u == 1 ? ty : tz), tv = v == 0 ? tx : (v == 1 ? ty : tz);
+        int iu = u == 0 ? h.ix : (u == 1 ? h.iy : h.iz), iv = v == 0 ? h.ix : (v == 1 ? h.iy : h.iz);
+        // d2 with the terms of axes u, v, w put back on x, y, z
+        auto d_of = [&](float a_u, float a_v) {
+            const float ax = w == 0 ? fc : (u == 0 ? a_u : a_v), ay = w == 1 ? fc : (u == 1 ? a_u : a_v), az = w == 2 ? fc : (u == 2 ? a_u : a_v);
+            return lat_sum(ax, ay, az);
+        };
+        // slow axis first (its index is the high part of the original index), then the fast axis at that row
+        for (;;) {
+            const int j = max(iv - 1, 0);
+            const float t = s_tab[toff_v + j].y;
+            const float dd = __fsub_rn(qv, t);
+            const float a = __fmul_rn(dd, dd);
+            const bool go = mine && iv > 0 && d_of(fu, a) == h.d;
+            iv = go ? j : iv; fv = go ? a : fv; tv = go ? t : tv;
+            if (!ballot64(go)) break;
+        }
+        for (;;) {
+            const int i = max(iu - 1, 0);
+            const float t = s_tab[toff_u + i].y;
+            const float dd = __fsub_rn(qu, t);
+            const float a = __fmul_rn(dd, dd);
+            const bool go = mine && iu > 0 && d_of(a, fv) == h.d;
+            iu = go ? i : iu; fu = go ? a : fu; tu = go ? t : tu;
+            if (!ballot64(go)) break;
+        }
+        const bool ux = mine && u == 0, uy = mine && u == 1, uz = mine && u == 2, vx = mine && v == 0, vy = mine && v == 1, vz = mine && v == 2;
+        h.ix = ux ? iu : (vx ? iv : h.ix); h.nx = ux ? tu : (vx ? tv : h.nx);
+        h.iy = uy ? iu : (vy ? iv : h.iy); h.ny = uy ? tu : (vy ? tv : h.ny);
+        h.iz = uz ? iu : (vz ? iv : h.iz); h.nz = uz ? tu : (vz ? tv : h.nz);
+    }
+}
+
+// INDEX: the hit's table indices (and face) are wanted for every query, not only where the walk goes (k_lat_nn).  Until this
+// was added k_lat_nn had them only where SOME lane of the wave entered the tie walk - lat_index of any other wave saw zeros and
+// returned the face's first point; the existing test interleaves tie queries into every wave and never met it.
 // TIES = false: d only (getFitnessScore needs no neighbour).  NF = faces evaluated (3 or LAT_MAX_FACES; the launch's templates
 // have at most that many - entries beyond a template's own faces never win)
-template <bool TIES, int NF>
+template <bool TIES, int NF, bool INDEX = false>
 __device__ __forceinline__ LatHit lat_nearest(const float4* s_tab, const int4* s_face, const LatFaces& F, float qx, float qy, float qz) {
     float fx, fy, fz, tx, ty, tz, gx, gy, gz;
     int cx, cy, cz;
@@ -140,53 +213,81 @@ __device__ __forceinline__ LatHit lat_nearest(const float4* s_tab, const int4* s
         h.nx = fd.x == 0 ? c : tx; h.ny = fd.x == 1 ? c : ty; h.nz = fd.x == 2 ? c : tz;
         const float gsel = fd.x == 0 ? fminf(gy, gz) : (fd.x == 1 ? fminf(gx, gz) : fminf(gx, gy));
         const bool maybe = gsel <= __fmul_rn(h.d, 4.76837158203125e-07f);   // 2^-21
-        if (ballot64(maybe)) {
-            // rare (a lane enters when its gap is within the rounding of the sum: iteration 0, mid-cell queries): one face at a time
-            h.ix = cx + (hix ? 1 : 0) - (lox ? 1 : 0); h.iy = cy + (hiy ? 1 : 0) - (loy ? 1 : 0); h.iz = cz + (hiz ? 1 : 0) - (loz ? 1 : 0);
-            for (int f = 0; f < F.nface; ++f) {
-                const bool mine = maybe && h.face == f;
-                if (!ballot64(mine)) continue;
-                const int4 gd = s_face[f];
-                const int w = __builtin_amdgcn_readfirstlane(gd.x), u = __builtin_amdgcn_readfirstlane(gd.y), v = 3 - w - u;   // constant, fast, slow axis
-                const float cc = __int_as_float(__builtin_amdgcn_readfirstlane(gd.w));
-                const int4 ge = s_face[LAT_MAX_FACES + f];
-                const int toff_u = __builtin_amdgcn_readfirstlane(ge.x), toff_v = __builtin_amdgcn_readfirstlane(ge.y);
-                const float qw = w == 0 ? qx : (w == 1 ? qy : qz), qu = u == 0 ? qx : (u == 1 ? qy : qz), qv = v == 0 ? qx : (v == 1 ? qy : qz);
-                const float dc = __fsub_rn(qw, cc);
-                const float fc = __fmul_rn(dc, dc);
-                float fu = u == 0 ? fx : (u == 1 ? fy : fz), fv = v == 0 ? fx : (v == 1 ? fy : fz);
-                float tu = u == 0 ? tx : (u == 1 ? ty : tz), tv = v == 0 ? tx : (v == 1 ? ty : tz);
-                int iu = u == 0 ? h.ix : (u == 1 ? h.iy : h.iz), iv = v == 0 ? h.ix : (v == 1 ? h.iy : h.iz);
-                // d2 with the terms of axes u, v, w put back on x, y, z
-                auto d_of = [&](float a_u, float a_v) {
-                    const float ax = w == 0 ? fc : (u == 0 ? a_u : a_v), ay = w == 1 ? fc : (u == 1 ? a_u : a_v), az = w == 2 ? fc : (u == 2 ? a_u : a_v);
-                    return lat_sum(ax, ay, az);
-                };
-                // slow axis first (its index is the high part of the original index), then the fast axis at that row
-                for (;;) {
-                    const int j = max(iv - 1, 0);
-                    const float t = s_tab[toff_v + j].y;
-                    const float dd = __fsub_rn(qv, t);
-                    const float a = __fmul_rn(dd, dd);
-                    const bool go = mine && iv > 0 && d_of(fu, a) == h.d;
-                    iv = go ? j : iv; fv = go ? a : fv; tv = go ? t : tv;
-                    if (!ballot64(go)) break;
-                }
-                for (;;) {
-                    const int i = max(iu - 1, 0);
-                    const float t = s_tab[toff_u + i].y;
-                    const float dd = __fsub_rn(qu, t);
-                    const float a = __fmul_rn(dd, dd);
-                    const bool go = mine && iu > 0 && d_of(a, fv) == h.d;
-                    iu = go ? i : iu; fu = go ? a : fu; tu = go ? t : tu;
-                    if (!ballot64(go)) break;
-                }
-                const bool ux = mine && u == 0, uy = mine && u == 1, uz = mine && u == 2, vx = mine && v == 0, vy = mine && v == 1, vz = mine && v == 2;
-                h.ix = ux ? iu : (vx ? iv : h.ix); h.nx = ux ? tu : (vx ? tv : h.nx);
-                h.iy = uy ? iu : (vy ? iv : h.iy); h.ny = uy ? tu : (vy ? tv : h.ny);
-                h.iz = uz ? iu : (vz ? iv : h.iz); h.nz = uz ? tu : (vz ? tv : h.nz);
-            }
-        }
+        if (INDEX || ballot64(maybe)) lat_tie_walk(s_tab, s_face, F, qx, qy, qz, fx, fy, fz, tx, ty, tz, cx + (hix ? 1 : 0) - (lox ? 1 : 0), cy + (hiy ? 1 : 0) - (loy ? 1 : 0),
+                                          cz + (hiz ? 1 : 0) - (loz ? 1 : 0), maybe, h);
+    }
+    return h;
+}
+
+// (lane's bit of m) ? a : b for a lane mask held in scalar registers: one v_cndmask_b32 (as C++ - a uniform choice between two
+// comparison results, then a select - the compiler turns the masks into 0 / 1 vectors and compares them again: six vector
+// instructions per choice)
+__device__ __forceinline__ float lat_sel(uint64_t m, float a, float b) {
+    float r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+    return r;
+}
+// fminf of values the compiler cannot see through (results of lat_sel): v_min_f32 returns the other operand for a quiet NaN, which
+// is all fminf adds here - none of these values is a signalling NaN - without the v_max x, x the compiler puts in front.
+// ASSUMES the IEEE mode bit of compute kernels (the code object's default, .amdhsa_ieee_mode 1; without it v_min_f32 also returns
+// the non-NaN operand): tests/test_gpu_lattice_axes.py has NaN and +-inf queries.
+__device__ __forceinline__ float lat_min(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float lat_min_inf(float a) {
+    float r;
+    asm("v_min_f32 %0, 0x7f800000, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+
+// lat_nearest for a template with at most ONE FACE PER AXIS (IcpLattice::axes_distinct: the three-face cuboid templates).  The
+// same rounded operations as the face loop above, without its selects: the distance to the face of constant x is
+// (fcx + fy) + fz with fcx = fl(fl(qx - cx)^2), likewise y and z; a missing face's constant is NaN and so is its distance.
+// (4) "the first face that reaches the minimum keeps it" = the lexicographic minimum of (d, face index).  Face indices are
+// wave-uniform, so a pair (a, b) is decided by one of two comparisons, chosen by a scalar: b wins when d_b < d_a if a comes
+// first in the file, when !(d_a < d_b) if b does (or a is missing) - the second form is also true for NaN, which makes a
+// missing face lose to any present one and leaves face 0 the winner of a query nothing compares for, as in the face loop.
+// The choices are lane masks combined in scalar registers; the neighbour and the tie filter take them as v_cndmask
+// conditions - no LDS read of a face descriptor, no branch.  The walk needs the winner as a face number: made inside its branch.
+constexpr unsigned LAT_NO_FACE = 99u;   // file position of a face that is not there: after every real one (LAT_MAX_FACES of them at the most)
+static_assert(LAT_NO_FACE >= (unsigned)LAT_MAX_FACES && WAVE == 64, "lat_nearest_axes: face order and 64-bit lane masks");
+template <bool TIES, bool INDEX = false>
+__device__ __forceinline__ LatHit lat_nearest_axes(const float4* s_tab, const int4* s_face, const LatFaces& F, float qx, float qy, float qz) {
+    float fx, fy, fz, tx, ty, tz, gx, gy, gz;
+    int cx, cy, cz;
+    bool lox, hix, loy, hiy, loz, hiz;
+    LatHit h;
+    lat_axis(s_tab, F.tox, F.nx, F.ox, F.ivx, qx, fx, cx, lox, hix, tx, gx);
+    lat_axis(s_tab, F.toy, F.ny, F.oy, F.ivy, qy, fy, cy, loy, hiy, ty, gy);
+    lat_axis(s_tab, F.toz, F.nz, F.oz, F.ivz, qz, fz, cz, loz, hiz, tz, gz);
+    h.ix = h.iy = h.iz = 0; h.face = 0;
+    const float dcx = __fsub_rn(qx, F.cax), dcy = __fsub_rn(qy, F.cay), dcz = __fsub_rn(qz, F.caz);
+    const float dx = lat_sum(__fmul_rn(dcx, dcx), fy, fz), dy = lat_sum(fx, __fmul_rn(dcy, dcy), fz), dz = lat_sum(fx, fy, __fmul_rn(dcz, dcz));
+    const float inf = __uint_as_float(0x7f800000u);
+    if (!TIES) {
+        h.d = fminf(fminf(fminf(dx, dy), dz), inf);   // (NaN-ignoring: the least distance of the faces there are, +inf when nothing compares)
+        h.nx = tx; h.ny = ty; h.nz = tz;
+        return h;
+    }
+    // file order of the faces, a missing one last (uniform); the lane masks of the four comparisons, combined in scalar registers
+    const unsigned ox = F.afx < 0 ? LAT_NO_FACE : (unsigned)F.afx, oy = F.afy < 0 ? LAT_NO_FACE : (unsigned)F.afy, oz = F.afz < 0 ? LAT_NO_FACE : (unsigned)F.afz;
+    const uint64_t wy = oy < ox ? ballot64(!(dx < dy)) : ballot64(dy < dx);   // y beats x
+    const float dxy = lat_sel(wy, dy, dx);
+    const uint64_t z_first = (oz < oy ? wy : 0ull) | (oz < ox ? ~wy : 0ull);   // z comes before the better of x and y
+    const uint64_t wz = ballot64(dz < dxy) | (z_first & ballot64(!(dxy < dz)));   // z beats it
+    h.d = lat_min_inf(lat_sel(wz, dz, dxy));                                    // (NaN - a query with a NaN coordinate - becomes the loop's +inf)
+    const uint64_t win_x = ~(wy | wz);
+    h.nx = lat_sel(win_x, F.cax, tx); h.ny = lat_sel(wy & ~wz, F.cay, ty); h.nz = lat_sel(wz, F.caz, tz);
+    // (3): the lesser gap of the winning face's two in-plane axes - x wins: min(gy, gz), y: min(gx, gz), z: min(gx, gy)
+    const float gsel = lat_min(lat_sel(win_x, gy, gx), lat_sel(wz, gy, gz));
+    const bool maybe = gsel <= __fmul_rn(h.d, 4.76837158203125e-07f);   // 2^-21
+    if (INDEX || ballot64(maybe)) {
+        const int lane = (int)(threadIdx.x & (WAVE - 1));   // (bit of this lane in a mask: 64-wide waves, one-dimensional blocks - every kernel here)
+        h.face = (wz >> lane) & 1 ? F.afz : ((wy >> lane) & 1 ? F.afy : F.afx);
+        lat_tie_walk(s_tab, s_face, F, qx, qy, qz, fx, fy, fz, tx, ty, tz, cx + (hix ? 1 : 0) - (lox ? 1 : 0), cy + (hiy ? 1 : 0) - (loy ? 1 : 0),
+                     cz + (hiz ? 1 : 0) - (loz ? 1 : 0), maybe, h);
     }
     return h;
 }
@@ -335,11 +436,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
             LatFaces F;
             {
                 const IcpLattice* __restrict__ L = lats + (phase == LAT_EMPTY ? 0 : tslot);
-                F.nface = L->nface;
-#pragma unroll
-                for (int f = 0; f < LAT_MAX_FACES; ++f) { F.m0[f] = L->m0[f]; F.m1[f] = L->m1[f]; F.m2[f] = L->m2[f]; F.c[f] = L->c[f]; }
-                F.nx = L->n[0]; F.ny = L->n[1]; F.nz = L->n[2]; F.tox = L->toff[0]; F.toy = L->toff[1]; F.toz = L->toff[2];
-                F.ox = L->noi[0]; F.oy = L->noi[1]; F.oz = L->noi[2]; F.ivx = L->inv[0]; F.ivy = L->inv[1]; F.ivz = L->inv[2];
+                lat_faces_load(L, F);
             }
             const bool nf3 = F.nface <= 3;
             if (phase == LAT_ITER) {
@@ -364,7 +461,8 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                         xform(T, p.x, p.y, p.z, px, py, pz);
                         if (act) pts[myq] = make_float4(px, py, pz, p.w);
                     }
-                    const LatHit h = nf3 ? lat_nearest<true, 3>(tab, face, F, px, py, pz) : lat_nearest<true, LAT_MAX_FACES>(tab, face, F, px, py, pz);
+                    const LatHit h = F.axes ? lat_nearest_axes<true>(tab, face, F, px, py, pz)
+                                            : (nf3 ? lat_nearest<true, 3>(tab, face, F, px, py, pz) : lat_nearest<true, LAT_MAX_FACES>(tab, face, F, px, py, pz));
                     // the 16 moment terms of rule C4, accumulated as raw bits (LatFix above: the solver takes the constants off
                     // again).  Valid while every term stays below 2^50 / 2^shift; a point outside that range (coordinates beyond
                     // 256 m, a neighbour more than 128 m away) takes the general conversion - the same integers either way.  Lanes
@@ -422,7 +520,8 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                     if (act) pts[myq] = make_float4(ox, oy, oz, p.w);
                     float qx, qy, qz;
                     xform(Tf, p0.x, p0.y, p0.z, qx, qy, qz);
-                    const LatHit h = nf3 ? lat_nearest<false, 3>(tab, face, F, qx, qy, qz) : lat_nearest<false, LAT_MAX_FACES>(tab, face, F, qx, qy, qz);
+                    const LatHit h = F.axes ? lat_nearest_axes<false>(tab, face, F, qx, qy, qz)
+                                            : (nf3 ? lat_nearest<false, 3>(tab, face, F, qx, qy, qz) : lat_nearest<false, LAT_MAX_FACES>(tab, face, F, qx, qy, qz));
                     if (act) S[0] += h.d < 16384.f ? LatFix<FIX_SHIFT_D2>::bits(h.d) : (unsigned long long)fixq(h.d, FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
                 }
                 if (sub < npass) wave_fold_to_lds(S, 1, s_acc[slot]);
@@ -487,6 +586,8 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
     }
 }
 
+__device__ __forceinline__ bool lat_same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+
 // diagnostic / test entry: nearest template point of arbitrary queries (original index and canonical d2)
 __global__ void __launch_bounds__(BLOCK) k_lat_nn(const IcpLattice* __restrict__ L, const float4* __restrict__ q, int n, int* __restrict__ out_idx,
                                                   float* __restrict__ out_d2) {
@@ -497,9 +598,17 @@ __global__ void __launch_bounds__(BLOCK) k_lat_nn(const IcpLattice* __restrict__
     for (int base = blockIdx.x * BLOCK; base < n; base += gridDim.x * BLOCK) {   // (whole waves stay together: ballots inside)
         const int i = base + threadIdx.x;
         const float4 p = q[i < n ? i : n - 1];
-        const LatHit h = lat_nearest<true, LAT_MAX_FACES>(s_tab, s_face, F, p.x, p.y, p.z);
+        const LatHit h = lat_nearest<true, LAT_MAX_FACES, true>(s_tab, s_face, F, p.x, p.y, p.z);
         const LatHit g = lat_nearest<false, 3>(s_tab, s_face, F, p.x, p.y, p.z);   // (the three-face form: equal d only when nface <= 3)
-        if (i < n) { out_idx[i] = lat_index(s_face, F, h); out_d2[i] = (F.nface > 3 || h.d == g.d) ? h.d : __uint_as_float(0x7fc00000u); }
+        bool same = F.nface > 3 || h.d == g.d;
+        const int idx = lat_index(s_face, F, h);
+        if (F.axes) {   // (uniform) the one-face-per-axis forms: the same index and distance, or d2 reads NaN
+            const LatHit a = lat_nearest_axes<true, true>(s_tab, s_face, F, p.x, p.y, p.z);
+            const LatHit b = lat_nearest_axes<false>(s_tab, s_face, F, p.x, p.y, p.z);
+            same = same && a.d == h.d && b.d == h.d && lat_same_bits(a.nx, h.nx) && lat_same_bits(a.ny, h.ny) && lat_same_bits(a.nz, h.nz) &&
+                   lat_index(s_face, F, a) == idx;
+        }
+        if (i < n) { out_idx[i] = idx; out_d2[i] = same ? h.d : __uint_as_float(0x7fc00000u); }
     }
 }
 
