@@ -43,6 +43,7 @@ extern "C" {
                                      * gets an ICP for every one of them (opd.cpp:376): see cd_get_cluster_results       */
 #define CD_FRAME_MORE_CLUSTERS 1    /* cd_frame_result.flags: n_clusters > CD_MAX_CLUSTERS_PER_FRAME                    */
 #define CD_FRAME_SURFACE_GUESS 2    /* cd_frame_result.flags: the frame's ICP started from its surface guess (CD_GUESS_SURFACE) */
+#define CD_FRAME_CLUSTER_GUESS 4    /* cd_frame_result.flags: at least one cluster of the frame started from its rule-C13 guess (CD_GUESS_CLUSTER) */
 
 typedef struct cd_context cd_context;
 
@@ -110,14 +111,16 @@ typedef struct cd_params {
      * commented out / inert, and iterative_closest_point.launch:17-18 leaves the sne node out), so the guess is opt-in:
      * CD_GUESS_PARAMS uses icp_guess for every ICP of the call, CD_GUESS_PER_FRAME the matrix cd_set_frame_guesses stored
      * for the cluster's frame, CD_GUESS_SURFACE the guess the call derives from the frame's own surface fit (see
-     * cd_surface_batch; fused calls only, cd_icp refuses it).  PCL semantics: the source is first moved by the guess (input_transformed = guess * source,
+     * cd_surface_batch; fused calls only, cd_icp refuses it), CD_GUESS_CLUSTER the guess the call derives on the device for every
+     * (cluster, template) pair from the cluster's own principal frame (rule C13, below; cd_icp accepts it: its source is the
+     * cluster).  PCL semantics: the source is first moved by the guess (input_transformed = guess * source,
      * float32 4x4 * point), final_transformation_ starts as the guess, the iterations and the convergence tests run on the
      * moved cloud, getFinalTransformation() includes the guess and getFitnessScore() is that of final * source. */
     int32_t icp_use_guess;
     float icp_guess[16];                /* row-major, scene -> template */
 } cd_params;
 
-enum { CD_GUESS_NONE = 0, CD_GUESS_PARAMS = 1, CD_GUESS_PER_FRAME = 2, CD_GUESS_SURFACE = 3 };
+enum { CD_GUESS_NONE = 0, CD_GUESS_PARAMS = 1, CD_GUESS_PER_FRAME = 2, CD_GUESS_SURFACE = 3, CD_GUESS_CLUSTER = 4 };
 
 enum { CD_PLANE = 0, CD_PLANE_PERPENDICULAR = 1, CD_PLANE_PARALLEL = 2 };
 
@@ -251,6 +254,56 @@ int cd_surface_batch(cd_context* ctx, const void* xyz, size_t stride_bytes, int 
  * pose in the camera frame (the reference's commented-out line moved the template by the pose instead: equal up to rounding
  * and the choice of F).  A non-finite Rt (or result): CD_ERR_INVALID_ARG. */
 int cd_surface_guess(const float Rt[16], float guess[16]);
+
+/* Principal frame of a point set and the per-cluster ICP guess (CD_GUESS_CLUSTER).  Canonical rule C13 (DESIGN.md §2;
+ * perception_amd/cluster_frame.py restates it in plain Python and is its definition):
+ *   a set is n float32 points.  status = CD_ERR_CAPACITY for n > 2^19, else CD_ERR_INVALID_ARG when a coordinate is not finite or
+ *   |coordinate| > 64 (rule C4's range), else CD_ERR_FEW_CORRESPONDENCES for n < 3; such a record holds n, status and zeros.
+ *   1. nine order-free sums by rule C4 (fixq(v, 32), int64) of x, y, z, xx, xy, xz, yy, yz, zz, every product one float32
+ *      multiply; mean m_a = ((double)S_a 2^-32) / n, covariance c_ab = ((double)S_ab 2^-32) / n - m_a m_b, one double operation at
+ *      a time;
+ *   2. cyclic Jacobi on the 3x3 in double: 8 sweeps over the pairs (0,1), (0,2), (1,2), a rotation whose off-diagonal entry is
+ *      exactly 0 skipped, + - x / sqrt only; eigenvalues descending (ties keep their order) = var, their vectors = the columns of
+ *      axes; det < 0: the third column is negated;
+ *   3. extents: q_a = ((A_0a dx + A_1a dy) + A_2a dz), d = (double)p - m; lo_a / hi_a = min / max over the set (a zero stored as +0);
+ *   5. guess from a cluster record c and a template record t: sigma_a = sign(-(lo_t[a] + hi_t[a])), 0 when |lo_t[a] + hi_t[a]| <=
+ *      2^-20 (hi_t[a] - lo_t[a]); w_a = -((A_c[0][a] m_c0 + A_c[1][a] m_c1) + A_c[2][a] m_c2); of F = diag(1,1,1), diag(1,-1,-1),
+ *      diag(-1,1,-1), diag(-1,-1,1) the first with the strictly largest ((F_0 sigma_0) w_0 + (F_1 sigma_1) w_1) + (F_2 sigma_2) w_2;
+ *      R = A_t F A_c^T, g = m_t - R m_c in double, left to right, each element rounded once to float32, last row 0 0 0 1.  A status
+ *      != CD_OK on either side or a non-finite result: the identity.
+ * G maps the scene to the template as rule C9's does: final_transformation_ starts as G, the sources are moved by G, pose stays the
+ * object's pose in the camera frame. */
+typedef struct cd_shape_frame {
+    int32_t n, status;     /* points of the set; CD_OK or why there is no frame                      */
+    double mean[3];
+    double axes[9];        /* row-major 3x3, COLUMN a = principal axis a (largest variance first)    */
+    double var[3];         /* variances along the axes, descending                                   */
+    double lo[3], hi[3];   /* extents along the axes, relative to the mean                           */
+} cd_shape_frame;
+int cd_shape_frame_struct_size(void);   /* sizeof(cd_shape_frame) (cd_struct_size's list is closed) */
+
+/* Host-only (no context, no GPU): rule C13 steps 1-4 for one set.  Returns out->status (the record is written whenever the
+ * arguments are usable); a NULL pointer (xyz with n > 0, or out), n < 0 or a stride below 12: CD_ERR_INVALID_ARG, nothing written. */
+int cd_shape_frame_host(const void* xyz, size_t stride_bytes, int n, cd_shape_frame* out);
+
+/* The same for n_sets sets in ONE launch (k_shape.hip), from host points: set i is the records offsets[i] .. offsets[i + 1] - 1 of
+ * xyz (offsets: n_sets + 1 ascending entries, offsets[0] >= 0), out[i] its record - byte for byte what cd_shape_frame_host gives.
+ * A refused set is a result (its status), not a failure of the call.  The stage has buffers of its own (allocated on first use);
+ * like every compute call it invalidates the read-backs of the last fused call. */
+int cd_shape_frames(cd_context* ctx, const void* xyz, size_t stride_bytes, const int32_t* offsets, int n_sets, cd_shape_frame* out);
+
+/* The record cd_set_template computed for the slot's template (host, at upload).  An empty slot: CD_ERR_NO_TEMPLATE. */
+int cd_template_shape_frame(const cd_context* ctx, int slot, cd_shape_frame* out);
+
+/* Host-only: rule C13 step 5.  guess receives the row-major 4x4, *flip (may be NULL) the index 0..3 of the chosen F, or -1 when
+ * the guess is the identity fall-back (which is CD_OK).  NULL cluster / template_ / guess: CD_ERR_INVALID_ARG. */
+int cd_shape_guess(const cd_shape_frame* cluster, const cd_shape_frame* template_, float guess[16], int32_t* flip);
+
+/* The cluster records of the LAST fused call when it ran in CD_GUESS_CLUSTER mode: clusters [first, first + capacity) of `frame`
+ * (rank order, as cd_get_cluster_results) into out.  Returns the number copied; CD_ERR_INVALID_ARG when that call was not in
+ * the mode, or another compute call has run since.  They come back with the ICP stage's own result read-back: the mode adds no
+ * synchronisation. */
+int cd_get_cluster_shape_frames(const cd_context* ctx, int frame, int first, int capacity, cd_shape_frame* out);
 
 /* sne's distance threshold for CD_GUESS_SURFACE (cd_params holds the ground plane's): context state like the correspondence
  * distance.  Default 0.015, the value of surface_normal_estimation.launch.  Not finite or <= 0: CD_ERR_INVALID_ARG, the

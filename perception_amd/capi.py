@@ -14,6 +14,7 @@ CD_MAX_TEMPLATES = 8
 CD_MAX_CLUSTERS_PER_FRAME = 8
 CD_FRAME_MORE_CLUSTERS = 1
 CD_FRAME_SURFACE_GUESS = 2
+CD_FRAME_CLUSTER_GUESS = 4
 
 CD_OK = 0
 CD_ERR_INVALID_ARG = -1
@@ -43,10 +44,12 @@ EXPORTED_SYMBOLS = [
     "cd_draw_last_results_device",
     "cd_default_color_camera", "cd_color_camera_struct_size", "cd_texture_project", "cd_depth_to_cloud_mapped",
     "cd_process_depth_batch_mapped", "cd_process_depth_batch_mapped_device",
+    "cd_shape_frame_struct_size", "cd_shape_frame_host", "cd_shape_frames", "cd_template_shape_frame", "cd_shape_guess",
+    "cd_get_cluster_shape_frames",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
-CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE = 0, 1, 2, 3
+CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE, CD_GUESS_CLUSTER = 0, 1, 2, 3, 4
 
 
 CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
@@ -59,6 +62,13 @@ CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 class CdSurfaceFrameResult(C.Structure):
     _fields_ = [("Rt", C.c_float * 16), ("coeff", (C.c_float * 4) * 3), ("midpoint", (C.c_float * 4) * 3),
                 ("n_points", C.c_int32 * 3), ("iterations", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
+
+
+class CdShapeFrame(C.Structure):
+    """cd_shape_frame: the principal frame of a point set (rule C13) - axes row-major with the axes as columns, variances
+    descending, extents relative to the mean; status != CD_OK: n, status and zeros."""
+    _fields_ = [("n", C.c_int32), ("status", C.c_int32), ("mean", C.c_double * 3), ("axes", C.c_double * 9),
+                ("var", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3)]
 
 
 class CdParams(C.Structure):
@@ -360,6 +370,13 @@ def load_library(path=None):
                                              C.c_int, ip]
     for f in (lib.cd_process_depth_batch_mapped, lib.cd_process_depth_batch_mapped_device):
         f.argtypes = [vp, C.POINTER(CdDepthCamera), C.POINTER(CdColorCamera), vp, vp, C.c_int, C.POINTER(CdParams), vp, vp, vp]
+    sfp = C.POINTER(CdShapeFrame)
+    lib.cd_shape_frame_struct_size.argtypes = []
+    lib.cd_shape_frame_host.argtypes = [vp, C.c_size_t, C.c_int, sfp]
+    lib.cd_shape_frames.argtypes = [vp, vp, C.c_size_t, i32p, C.c_int, sfp]
+    lib.cd_template_shape_frame.argtypes = [vp, C.c_int, sfp]
+    lib.cd_shape_guess.argtypes = [sfp, sfp, f32p, i32p]
+    lib.cd_get_cluster_shape_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, sfp]
     if path is None:
         _lib = lib
     return lib
@@ -788,6 +805,34 @@ class Context:
                          res, None, None)
         return res
 
+    def shape_frames(self, sets):
+        """Rule C13 on the device: one CdShapeFrame per point set of `sets` (a sequence of (n_i, >= 3) float32 arrays that share
+        their number of columns, i.e. their stride), all in one launch (cd_shape_frames)."""
+        sets = [np.asarray(a, np.float32) for a in sets]
+        cols = sets[0].shape[1]
+        assert all(a.ndim == 2 and a.shape[1] == cols for a in sets)
+        pts = np.ascontiguousarray(np.concatenate(sets, axis=0))
+        off = np.zeros(len(sets) + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in sets])
+        out = (CdShapeFrame * len(sets))()
+        self._check(self.lib.cd_shape_frames(self.h, _ptr(pts), cols * 4, off.ctypes.data_as(C.POINTER(C.c_int32)), len(sets), out))
+        return out
+
+    def template_shape_frame(self, slot):
+        """The record cd_set_template computed for the slot's template (rule C13)."""
+        r = CdShapeFrame()
+        self._check(self.lib.cd_template_shape_frame(self.h, slot, C.byref(r)))
+        return r
+
+    def cluster_shape_frames(self, frame, first=0, count=None):
+        """The cluster records of `frame` of the last fused call in CD_GUESS_CLUSTER mode: a list of CdShapeFrame."""
+        cap = CD_MAX_CLUSTERS_PER_FRAME * 64 if count is None else count
+        out = (CdShapeFrame * max(cap, 1))()
+        n = self.lib.cd_get_cluster_shape_frames(self.h, frame, first, cap, out)
+        if n < 0:
+            raise CuboidError(n, "cd_get_cluster_shape_frames: the last fused call was not in CD_GUESS_CLUSTER mode")
+        return [out[i] for i in range(n)]
+
     def timing(self):
         t = CdTiming()
         self._check(self.lib.cd_get_timing(self.h, C.byref(t)))
@@ -838,6 +883,30 @@ def surface_guess(Rt):
     if st != CD_OK:
         raise CuboidError(st, "cd_surface_guess: non-finite input")
     return g.reshape(4, 4)
+
+
+def shape_frame_host(xyz):
+    """Host-only rule C13 steps 1-4 (cd_shape_frame_host): the CdShapeFrame of an (n, >= 3) float32 set; a refused or too small
+    set is a record with its status, not an exception."""
+    lib = load_library()
+    a = np.asarray(xyz, np.float32)
+    a = np.ascontiguousarray(a if a.ndim == 2 else a.reshape(-1, 3))
+    r = CdShapeFrame()
+    st = lib.cd_shape_frame_host(_ptr(a), a.shape[1] * 4, a.shape[0], C.byref(r))
+    if st != r.status:
+        raise CuboidError(st, "cd_shape_frame_host: bad arguments")
+    return r
+
+
+def shape_guess(cluster, template):
+    """Host-only rule C13 step 5 (cd_shape_guess): (4x4 float32 scene -> template, flip 0..3 or -1 = identity fall-back)."""
+    lib = load_library()
+    g = np.zeros(16, np.float32)
+    flip = C.c_int32()
+    st = lib.cd_shape_guess(C.byref(cluster), C.byref(template), g.ctypes.data_as(C.POINTER(C.c_float)), C.byref(flip))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_shape_guess")
+    return g.reshape(4, 4), int(flip.value)
 
 
 def texture_project(cam, ccam, u, v, d):

@@ -33,6 +33,7 @@
 static const char* template_filenames[] = {"", "screwdriver_ascii_tf.pcd", "eraser_ascii_tf.pcd", "clamp_ascii_tf.pcd", "marker_ascii_tf.pcd"};
 static ros::Publisher pcl_pub, icp_pub, bbox_pub, template_pub, pose_pub, marker_pub;
 static bool invert = true, ICP_SUCCESS = false;
+static bool use_cluster_guess = false;                   // not in the reference: every cluster's ICP starts from its own principal frame (CD_GUESS_CLUSTER, rule C13)
 static double voxel_size = 0.01, distance_threshold = 0.01, icp_fitness_score = 0.0004;
 static double dimensions[] = {0.02, 0.02, 0.15};           // opd.cpp:80
 static std::string template_path;
@@ -118,6 +119,7 @@ bool service_callback(object_detection::ObjectDetection::Request& req, object_de
     prm.rgb_offset = field_offset(*input_pcl, "rgb");
     prm.icp_euclidean_fitness_epsilon = icp_fitness_score;
     prm.icp_accept_fitness = icp_fitness_score;
+    if (use_cluster_guess) prm.icp_use_guess = CD_GUESS_CLUSTER;
     cd_frame_result r;
     if (cd_process_batch(ctx, input_pcl->data.data(), input_pcl->point_step, n, 1, &prm, &r, nullptr, nullptr) != CD_OK) { ROS_ERROR("%s", cd_last_error(ctx)); return false; }
     {
@@ -182,6 +184,7 @@ int main(int argc, char** argv) {
     nh.getParam("output", output_topic);
     nh.getParam("icp_fitness_score", icp_fitness_score);
     nh.getParam("template_path", template_path);
+    nh.getParam("use_cluster_guess", use_cluster_guess);   // default false: the reference's identity start
     ros::Subscriber sub = nh.subscribe(input_topic, 1, pcl_callback);
     ros::ServiceServer service = nh.advertiseService("detect_objects", service_callback);
     pcl_pub = nh.advertise<sensor_msgs::PointCloud2>(output_topic, 1);

@@ -21,6 +21,7 @@
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "overlay_math.hpp"
+#include "shape_frame_math.hpp"
 #include "texture_math.hpp"
 
 using namespace cd;
@@ -177,6 +178,17 @@ struct cd_context : cd_streams {
     DevBuf<double> d_oposes;
     DevBuf<int32_t> d_onbox;
     DevBuf<OverlayBox> d_obox; PinBuf<OverlayBox> h_obox;
+    // per-cluster principal frames (rule C13, k_shape.hip), all allocated on first use: the template records of every slot (pinned
+    // table, uploaded when a template has changed since), one record per ICP problem of a CD_GUESS_CLUSTER stage (device + pinned
+    // mirror), and the points / set list of cd_shape_frames
+    DevBuf<ShapeFrame> d_tframe; PinBuf<ShapeFrame> h_tframe;
+    ShapeFrame tpl_frame[CD_MAX_TEMPLATES] = {};                  // the slots' records (cd_set_template computes them on the host)
+    bool tframe_dirty = true;
+    DevBuf<ShapeFrame> d_shape; PinBuf<ShapeFrame> h_shape;
+    DevBuf<float4> d_shpts;
+    DevBuf<IcpCluster> d_shcl;
+    std::vector<cd_shape_frame> last_shapes;                      // cd_get_cluster_shape_frames: one per cluster of the last fused call, frame-major
+    bool last_shapes_ok = false;
     DevBuf<IcpState> d_st; PinBuf<IcpState> h_st;
     DevBuf<unsigned long long> d_acc, d_accf; PinBuf<unsigned long long> h_accf;
     cd_timing timing;
@@ -213,6 +225,7 @@ void invalidate_last(cd_context* c) {
     c->last_first.clear();
     c->last_surface_ok = false;
     c->last_bboxes_ok = false;
+    c->last_shapes_ok = false;
 }
 
 int fail(cd_context* c, int code, const char* msg) {
@@ -745,7 +758,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     if (guess_mode != CD_GUESS_NONE) {
         int max_frame = 0;
         for (int k = 0; k < ncl; ++k) { pl->max_n = std::max(pl->max_n, c->h_cl[k].n); max_frame = std::max(max_frame, c->h_cl[k].frame); }
-        pl->guess_need = guess_mode == CD_GUESS_PER_FRAME ? 16 * ((size_t)max_frame + 1) : 16;
+        pl->guess_need = guess_mode == CD_GUESS_PER_FRAME ? 16 * ((size_t)max_frame + 1) : (guess_mode == CD_GUESS_CLUSTER ? 16 * (size_t)ncl : 16);
         if (guess_mode == CD_GUESS_PER_FRAME && pl->frame_guess->size() < pl->guess_need) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_PER_FRAME but cd_set_frame_guesses holds fewer frames than the batch");
     }
     // queries per workgroup: 512 when the batch fills the chip, smaller slices (more workgroups) otherwise
@@ -800,7 +813,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
             IcpState& st = c->h_st[2 * k + s];
             std::memset(&st, 0, sizeof(st));
             for (int i = 0; i < 4; ++i) st.Tfinal[5 * i] = 1.f;
-            if (guess_mode != CD_GUESS_NONE)   // final_transformation_ = guess
+            if (guess_mode != CD_GUESS_NONE && guess_mode != CD_GUESS_CLUSTER)   // final_transformation_ = guess (CD_GUESS_CLUSTER: k_shape_frames writes it on the device)
                 std::memcpy(st.Tfinal, guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() + 16 * (size_t)cl.frame : p->icp_guess, 64);
             st.prev_mse = std::numeric_limits<double>::max();
             if (cl.tpl_m <= 0) { st.done = 1; st.status = CD_ERR_NO_TEMPLATE; }
@@ -830,13 +843,41 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     return CD_OK;
 }
 
+// which guess k_icp_apply_guess moves problem k by: the only one, its frame's, its own
+int guess_indexing(int guess_mode) { return guess_mode == CD_GUESS_PER_FRAME ? 1 : (guess_mode == CD_GUESS_CLUSTER ? 2 : 0); }
+
+// the record of a slot's template as the device table holds it: an empty slot can give no guess
+ShapeFrame template_frame(const cd_context* c, int slot) {
+    if (slot >= 0 && slot < CD_MAX_TEMPLATES && c->tpl_m[slot] > 0) return c->tpl_frame[slot];
+    ShapeFrame none;
+    shape_empty(0, CD_ERR_NO_TEMPLATE, &none);
+    return none;
+}
+
+// CD_GUESS_CLUSTER: k_shape_frames over the stage's ncl problems (d_cl, d_src0) -> d_shape, d_guess and Tfinal of d_st.  The
+// template table goes up first when a template has changed since the last time (a copy launch from its pinned mirror: no
+// synchronisation).  The buffers have been sized by icp_setup.
+int launch_cluster_guesses(cd_context* c, int ncl) {
+    if (c->tframe_dirty) {
+        for (int s = 0; s < CD_MAX_TEMPLATES; ++s) c->h_tframe[s] = template_frame(c, s);
+        HIPCHK(c, xfer(c, c->d_tframe, c->h_tframe, sizeof(ShapeFrame) * CD_MAX_TEMPLATES, hipMemcpyHostToDevice));
+        c->tframe_dirty = false;
+    }
+    LAUNCH(c, launch_shape_frames(c->stream, ncl, c->d_cl, c->d_src0, c->d_shape, c->d_tframe, c->d_guess, c->d_st));
+    return CD_OK;
+}
+
 // the stream operations every driver needs before the stage's start event: guess, cluster list, work list, initial states,
 // zeroed sums, guess applied to the sources
 int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
     const int ncl = pl->ncl;
     if (pl->guess_mode != CD_GUESS_NONE) {
         GROW(c, d_guess, pl->guess_need);
-        HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
+        if (pl->guess_mode == CD_GUESS_CLUSTER) {   // (the guesses are written on the device; the records' buffers before anything is on the stream)
+            GROW(c, d_shape, (size_t)ncl); GROW(c, h_shape, (size_t)ncl);
+            GROW(c, d_tframe, (size_t)CD_MAX_TEMPLATES); GROW(c, h_tframe, (size_t)CD_MAX_TEMPLATES);
+        } else
+            HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
     }
     if (!pl->lat_direct) {
         XferBatch xb(c);   // (one launch)
@@ -856,8 +897,12 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         GROW(c, d_ncorr, 3 * (size_t)ncl);
         HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
     }
+    if (pl->guess_mode == CD_GUESS_CLUSTER) {   // rule C13: record, guess and Tfinal of every problem, after the d_cl / d_st upload above
+        if (int e = launch_cluster_guesses(c, ncl)) return e;
+        HIPCHK(c, xfer(c, c->h_shape, c->d_shape, sizeof(ShapeFrame) * (size_t)ncl, hipMemcpyDeviceToHost));   // (on the host by the stage's final synchronisation)
+    }
     if (pl->guess_mode != CD_GUESS_NONE)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? 1 : 0, c->d_src0, c->d_src));
+        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, guess_indexing(pl->guess_mode), c->d_src0, c->d_src));
     return CD_OK;
 }
 
@@ -1153,8 +1198,10 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool*
     long long span = 0;
     for (int k = 0; k < ncl; ++k) span = std::max(span, (long long)c->h_cl[k].src_off + c->h_cl[k].n);
     HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)span, hipMemcpyDeviceToDevice, c->stream));
+    if (pl.guess_mode == CD_GUESS_CLUSTER)   // (the states just uploaded start from the identity again)
+        if (int e = launch_cluster_guesses(c, ncl)) return e;
     if (pl.guess_mode != CD_GUESS_NONE)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl.max_n, c->d_cl, c->d_guess, pl.guess_mode == CD_GUESS_PER_FRAME ? 1 : 0, c->d_src0, c->d_src));
+        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl.max_n, c->d_cl, c->d_guess, guess_indexing(pl.guess_mode), c->d_src0, c->d_src));
     return CD_OK;
 }
 
@@ -1258,7 +1305,7 @@ int check_params(cd_context* c, const cd_params* p) {
     if (p->template_slot < -1 || p->template_slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "template_slot out of range");
     if (!(p->cluster_tolerance > 0.0)) return fail(c, CD_ERR_INVALID_ARG, "cluster_tolerance must be > 0");
     if (p->plane_model < CD_PLANE || p->plane_model > CD_PLANE_PARALLEL) return fail(c, CD_ERR_INVALID_ARG, "plane_model out of range");
-    if (p->icp_use_guess < CD_GUESS_NONE || p->icp_use_guess > CD_GUESS_SURFACE) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess out of range");
+    if (p->icp_use_guess < CD_GUESS_NONE || p->icp_use_guess > CD_GUESS_CLUSTER) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess out of range");
     if (p->icp_use_guess == CD_GUESS_PARAMS)
         for (int i = 0; i < 16; ++i) if (!std::isfinite(p->icp_guess[i])) return fail(c, CD_ERR_INVALID_ARG, "icp_guess holds a non-finite value");
     return CD_OK;
@@ -1703,6 +1750,15 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
 }
 
+// CD_GUESS_CLUSTER: the records of the stage just run (h_shape, on the host since stage_icp's synchronisation) for
+// cd_get_cluster_shape_frames - problem k < ncl is cluster k.
+void keep_cluster_shapes(cd_context* c, const cd_params* p, int ncl) {
+    if (p->icp_use_guess != CD_GUESS_CLUSTER) return;
+    static_assert(sizeof(ShapeFrame) == sizeof(cd_shape_frame), "ShapeFrame mirrors cd_shape_frame");
+    c->last_shapes.resize((size_t)ncl);
+    if (ncl > 0) std::memcpy(c->last_shapes.data(), c->h_shape.get(), sizeof(ShapeFrame) * (size_t)ncl);
+}
+
 // All (cluster, template) pairs in one stage (fits_one_stage): problem t * ncl + k is cluster k against slots[t], on copy t of
 // the sources.  Uploads the offset table of S copies, issues every extraction round of every copy and one stage_icp, which
 // ends synchronised.  Every problem's aligned points stay resident.
@@ -1724,6 +1780,7 @@ int icp_all_pairs(cd_context* c, const cd_params* p, int F, const BatchClusters&
         }
     st = stage_icp(c, S * ncl, p, &bi->pairs);
     if (st) return st;
+    keep_cluster_shapes(c, p, ncl);   // (the problems of slots[0]: a cluster's record does not depend on the template)
     for (int t = 0; t < S; ++t)
         for (int k = 0; k < ncl; ++k) keep_lower_fitness(c, p, bi, t * ncl + k, k, t, true);
     return CD_OK;
@@ -1747,6 +1804,7 @@ int icp_per_template(cd_context* c, const cd_params* p, int F, const BatchCluste
         long long pr = 0;
         st = stage_icp(c, cl.ncl, p, &pr);
         if (st) return st;
+        keep_cluster_shapes(c, p, cl.ncl);
         bi->pairs += pr;
         for (int k = 0; k < cl.ncl; ++k) keep_lower_fitness(c, p, bi, k, k, t, t + 1 == S);
     }
@@ -1763,11 +1821,14 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     for (int f = 0; f < F; ++f) { c->last_nv[(size_t)f] = c->h_fs[f].n_v; c->last_no[(size_t)f] = c->h_fs[f].n_o; }
     c->last_clouds = true;
     c->last_surface_ok = p->icp_use_guess == CD_GUESS_SURFACE;
+    c->last_shapes_ok = p->icp_use_guess == CD_GUESS_CLUSTER;
+    if (c->last_shapes_ok && cl.ncl == 0) c->last_shapes.clear();
 }
 
 // The per-frame records from h_fs, the plane mirrors and c->last_clusters, and the byte counts of the timing
 // (algorithmic_bytes, icp_algorithmic_bytes).  Host only; every stage has been synchronised.
 void write_frame_records(cd_context* c, int N, int F, const BatchClusters& cl, const FrontStages& fr, cd_frame_result* results) {
+    static_assert(offsetof(ShapeFrame, mean) == offsetof(cd_shape_frame, mean) && offsetof(ShapeFrame, hi) == offsetof(cd_shape_frame, hi), "ShapeFrame mirrors cd_shape_frame");
     long long balg = 0;
     for (int f = 0; f < F; ++f) {
         const FrameState& s = c->h_fs[f];
@@ -1788,6 +1849,12 @@ void write_frame_records(cd_context* c, int N, int F, const BatchClusters& cl, c
         for (int k = 0; k < s.n_k; ++k) {
             const cd_cluster_result& cr = c->last_clusters[(size_t)(cl.first[(size_t)f] + k)];
             if (k < KICP) r.clusters[k] = cr;
+            if (c->last_shapes_ok) {   // CD_GUESS_CLUSTER: did this cluster's ICP (against the template it kept) start from a rule-C13 guess?
+                ShapeFrame rec;
+                float G[16];
+                std::memcpy(&rec, &c->last_shapes[(size_t)(cl.first[(size_t)f] + k)], sizeof(rec));
+                if (shape_guess(rec, template_frame(c, cr.template_slot), G) >= 0) r.flags |= CD_FRAME_CLUSTER_GUESS;
+            }
             const long long b = 12ll * c->tpl_m[cr.template_slot] + 12ll * cr.size * (cr.iterations + 1);
             balg += b;
             c->timing.icp_algorithmic_bytes += b;
@@ -2093,7 +2160,41 @@ struct PreparedTemplate {
     IcpSuper super;                                      // second box level of a template that does not fit LDS (n = 0: none)
     bool big_ok = false;                                 // k_icp_pipe_big can search it
     IcpLattice lat;                                      // nface > 0: the template is a union of axis-aligned lattices (k_icp_lat.hip)
+    ShapeFrame frame;                                    // rule C13: the template's principal frame (shape_frame_host)
 };
+
+// rule C13 steps 1-4 on the host: the sums as the device forms them (fixq = llrint(ldexp(v, 32)), round to nearest even), then
+// shape_frame_math.hpp
+static void shape_frame_host(const void* xyz, size_t stride, int n, ShapeFrame* out) {
+    if (n > SHAPE_N_MAX) { shape_empty(n, SHAPE_ERR_CAPACITY, out); return; }
+    auto point = [&](int i, float v[3]) { std::memcpy(v, (const char*)xyz + (size_t)i * stride, 12); };
+    uint64_t S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool bad = false;
+    for (int i = 0; i < n; ++i) {
+        float v[3];
+        point(i, v);
+        bad = bad || !shape_coord_ok(v[0], v[1], v[2]);
+        if (bad) break;
+        const float t[9] = {v[0], v[1], v[2], v[0] * v[0], v[0] * v[1], v[0] * v[2], v[1] * v[1], v[1] * v[2], v[2] * v[2]};
+        for (int k = 0; k < 9; ++k) S[k] += (uint64_t)std::llrint(std::ldexp((double)t[k], FIX_SHIFT));
+    }
+    if (bad) { shape_empty(n, SHAPE_ERR_INVALID, out); return; }
+    if (n < 3) { shape_empty(n, SHAPE_ERR_FEW, out); return; }
+    long long T[9];
+    for (int k = 0; k < 9; ++k) T[k] = (long long)S[k];
+    shape_empty(n, SHAPE_OK, out);
+    shape_solve(T, n, out);
+    const double inf = std::numeric_limits<double>::infinity();
+    double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    for (int i = 0; i < n; ++i) {
+        float v[3];
+        double q[3];
+        point(i, v);
+        shape_project(out->mean, out->axes, v[0], v[1], v[2], q);
+        for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], q[a]); hi[a] = std::fmax(hi[a], q[a]); }
+    }
+    for (int a = 0; a < 3; ++a) { out->lo[a] = lo[a] + 0.0; out->hi[a] = hi[a] + 0.0; }   // (a zero extent is stored as +0)
+}
 
 // Is the template what make_cuboid.py writes (mkc.py:38-55) - faces one after the other, each the Cartesian product of two of
 // three shared, ascending, near-uniform axis tables at a constant third coordinate, first axis fastest?  Verified bit by bit
@@ -2401,6 +2502,7 @@ static std::shared_ptr<const PreparedTemplate> prepare_template(const void* xyz,
         if (!P->big_ok) su.n = 0;
     }
     lattice_detect(raw.data(), m, &P->lat);
+    shape_frame_host(raw.data(), 12, m, &P->frame);
     P->xyz.swap(raw);
     std::lock_guard<std::mutex> lk(mu);
     if (cache.size() >= 16) cache.erase(cache.begin());
@@ -2431,6 +2533,8 @@ static int upload_template(cd_context* c, int slot, int off, const PreparedTempl
     HIPCHK(c, copy_sync(c, c->d_super + slot, &P.super, sizeof(IcpSuper), hipMemcpyHostToDevice));
     HIPCHK(c, copy_sync(c, c->d_lat + slot, &P.lat, sizeof(IcpLattice), hipMemcpyHostToDevice));
     c->tpl_faces[slot] = P.lat.nface;
+    c->tpl_frame[slot] = P.frame;
+    c->tframe_dirty = true;   // (rule C13's slot table: uploaded by the next CD_GUESS_CLUSTER stage)
     return CD_OK;
 }
 
@@ -3371,6 +3475,66 @@ int cd_get_surface_results(const cd_context* c, int first, int capacity, cd_surf
     return n;
 }
 
+// ---- rule C13: principal frames and the per-cluster guess ---------------------------------------------------
+int cd_shape_frame_struct_size(void) { return (int)sizeof(cd_shape_frame); }
+
+int cd_shape_frame_host(const void* xyz, size_t stride, int n, cd_shape_frame* out) {
+    if (!out || n < 0 || (n > 0 && !xyz) || stride < 12) return CD_ERR_INVALID_ARG;
+    ShapeFrame rec;
+    shape_frame_host(xyz, stride, n, &rec);
+    std::memcpy(out, &rec, sizeof(rec));
+    return rec.status;
+}
+
+int cd_shape_guess(const cd_shape_frame* cluster, const cd_shape_frame* template_, float guess[16], int32_t* flip) {
+    if (!cluster || !template_ || !guess) return CD_ERR_INVALID_ARG;
+    ShapeFrame cr, tr;
+    std::memcpy(&cr, cluster, sizeof(cr));
+    std::memcpy(&tr, template_, sizeof(tr));
+    const int k = shape_guess(cr, tr, guess);
+    if (flip) *flip = k;
+    return CD_OK;
+}
+
+int cd_template_shape_frame(const cd_context* c, int slot, cd_shape_frame* out) {
+    if (!c || !out || slot < 0 || slot >= CD_MAX_TEMPLATES) return CD_ERR_INVALID_ARG;
+    if (c->tpl_m[slot] <= 0) return CD_ERR_NO_TEMPLATE;
+    std::memcpy(out, &c->tpl_frame[slot], sizeof(*out));
+    return CD_OK;
+}
+
+int cd_get_cluster_shape_frames(const cd_context* c, int frame, int first, int capacity, cd_shape_frame* out) {
+    if (!c || frame < 0 || first < 0 || capacity < 0 || (capacity > 0 && !out)) return CD_ERR_INVALID_ARG;
+    if (!c->last_shapes_ok) return CD_ERR_INVALID_ARG;   // (no fused call in CD_GUESS_CLUSTER mode since the last compute call)
+    if ((size_t)frame + 1 >= c->last_first.size()) return CD_ERR_INVALID_ARG;
+    const int lo = c->last_first[(size_t)frame], hi = c->last_first[(size_t)frame + 1];
+    if (lo < 0 || hi < lo || (size_t)hi > c->last_shapes.size()) return CD_ERR_INVALID_ARG;
+    int n = 0;
+    for (int k = lo + first; k < hi && n < capacity; ++k) out[n++] = c->last_shapes[(size_t)k];
+    return n;
+}
+
+static int cd_shape_frames_impl(cd_context* c, const void* xyz, size_t stride, const int32_t* offsets, int n_sets, cd_shape_frame* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    if (!offsets || !out || n_sets <= 0 || stride < 12 || offsets[0] < 0) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    for (int i = 0; i < n_sets; ++i) if (offsets[i + 1] < offsets[i]) return fail(c, CD_ERR_INVALID_ARG, "offsets must ascend");
+    const int base = offsets[0], total = offsets[n_sets] - base;
+    if (total > 0 && !xyz) return fail(c, CD_ERR_INVALID_ARG, "null points");
+    invalidate_last(c);
+    GROW(c, d_shpts, (size_t)std::max(total, 1));
+    GROW(c, d_shcl, (size_t)n_sets);
+    GROW(c, d_shape, (size_t)n_sets);
+    std::vector<IcpCluster> sets((size_t)n_sets);
+    for (int i = 0; i < n_sets; ++i) sets[(size_t)i] = IcpCluster{offsets[i] - base, offsets[i + 1] - offsets[i], 0, i, 0, 0, 0, 0};
+    int st = upload_points(c, (const char*)xyz + (size_t)base * stride, stride, total, c->d_shpts);
+    if (st) return st;
+    HIPCHK(c, copy_sync(c, c->d_shcl, sets.data(), sizeof(IcpCluster) * (size_t)n_sets, hipMemcpyHostToDevice));
+    LAUNCH(c, launch_shape_frames(c->stream, n_sets, c->d_shcl, c->d_shpts, c->d_shape, nullptr, nullptr, nullptr));
+    HIPCHK(c, copy_sync(c, out, c->d_shape, sizeof(ShapeFrame) * (size_t)n_sets, hipMemcpyDeviceToHost));
+    return CD_OK;
+}
+
 // rule C9: sne's pose message -> poseMsgToEigen's rotation -> the symmetry variant that turns the most template
 // faces toward the camera -> the inverse, scene -> template, rounded once to float32
 int cd_surface_guess(const float Rt[16], float guess[16]) {
@@ -3554,6 +3718,10 @@ int cd_cluster(cd_context* c, const void* xyz, size_t stride, int n, const cd_pa
 int cd_icp(cd_context* c, int slot, const void* src_xyz, size_t stride, int n, const cd_params* p, cd_cluster_result* out, float* aligned) {
     if (!c) return CD_ERR_INVALID_ARG;
     return with_scan_retry(c, [&]() { return cd_icp_impl(c, slot, src_xyz, stride, n, p, out, aligned); });
+}
+int cd_shape_frames(cd_context* c, const void* xyz, size_t stride, const int32_t* offsets, int n_sets, cd_shape_frame* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_shape_frames_impl(c, xyz, stride, offsets, n_sets, out); });
 }
 int cd_process_batch_device(cd_context* c, const void* d_frames, size_t stride, int points_per_frame, int n_frames, const cd_params* p, cd_frame_result* results, int32_t* plane_inliers, int32_t* labels) {
     if (!c) return CD_ERR_INVALID_ARG;

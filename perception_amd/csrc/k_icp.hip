@@ -1924,11 +1924,12 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_fitness(const IcpWork* __r
 
 // pcl::Registration::align(output, guess): input_transformed = guess * source before the first iteration (the iterations
 // then run on d_src as they do from the identity; final_transformation_ starts as the guess - the host puts it into the
-// initial IcpState).  guesses: one row-major 4x4 per frame (per_frame != 0) or a single one.
+// initial IcpState).  guesses: one row-major 4x4 per frame (per_frame == 1), per ICP problem (per_frame == 2: CD_GUESS_CLUSTER,
+// written by k_shape_frames) or a single one (per_frame == 0).
 __global__ void __launch_bounds__(BLOCK) k_icp_apply_guess(const IcpCluster* __restrict__ cl, const float* __restrict__ guesses,
                                                            int per_frame, const float4* __restrict__ src0, float4* __restrict__ src) {
     const IcpCluster c = cl[blockIdx.x];
-    const float* G = guesses + (per_frame ? 16 * (size_t)c.frame : 0);
+    const float* G = guesses + (per_frame == 2 ? 16 * (size_t)blockIdx.x : (per_frame ? 16 * (size_t)c.frame : 0));
     float T[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) T[k] = G[k];

@@ -136,6 +136,11 @@ void launch_surface_centroid(hipStream_t s, const float4* pts, int pitch, int F,
                              const int* have, float thr, int invert, float4* out, int out_pitch);
 
 
+// k_shape.hip : rule C13, one workgroup per point set -> one ShapeFrame (= cd_shape_frame); fused form: + the ICP guess of the set
+struct ShapeFrame;
+void launch_shape_frames(hipStream_t s, int n_sets, const IcpCluster* cl, const float4* pts, ShapeFrame* rec, const ShapeFrame* tframe,
+                         float* guess, IcpState* st);
+
 // k_color.hip : rule C10, one workgroup per rgb8 image -> one ColorRecord (= cd_color_bbox) per frame
 constexpr int COLOR_BLOCK = 1024;
 constexpr int COLOR_LDS_WORDS = 30720;   // both halves of a frame's packed mask, 120 KiB
