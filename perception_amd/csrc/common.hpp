@@ -131,7 +131,7 @@ struct IcpSuper {
 
 // A template that is a union of axis-aligned LATTICES (every make_cuboid.py template: face k = the Cartesian product of two
 // of three shared axis tables X, Y, Z at a constant third coordinate, written first-axis-fastest, mkc.py:38-55).  Detected
-// and verified bit by bit against the uploaded points by cd_set_template (lattice_detect, cuboid_hip.hip); the nearest
+// and verified bit by bit against the uploaded points by cd_set_template (lattice_detect, template_prep.hpp); the nearest
 // neighbour of a query is then a closed form over the axis tables (k_icp_lat.hip) - no search structure, no template image.
 constexpr int LAT_MAX_FACES = 6;           // (a cuboid has six)
 constexpr int LAT_MAX_TAB = 512;           // axis table entries of one template, the three axes together

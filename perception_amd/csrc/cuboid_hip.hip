@@ -22,6 +22,7 @@
 #include "kernels.hpp"
 #include "overlay_math.hpp"
 #include "shape_frame_math.hpp"
+#include "template_prep.hpp"
 #include "texture_math.hpp"
 
 using namespace cd;
@@ -112,7 +113,7 @@ struct cd_context : cd_streams {
     int icp_big_weight = 0;                                       // workgroup share of a template in global memory, per point (CUBOID_ICP_BIG_WEIGHT; 0 = by the launch's regime, measured on config 5)
     DevBuf<int> d_order; PinBuf<int> h_order;                     // clusters, largest first
     int tpl_cap = 0, tpl_used = 0;
-    std::shared_ptr<const struct PreparedTemplate> tpl_prep[CD_MAX_TEMPLATES];   // host copies (shared across contexts)
+    std::shared_ptr<const cd::PreparedTemplate> tpl_prep[CD_MAX_TEMPLATES];   // host copies (shared across contexts)
     int tpl_off[CD_MAX_TEMPLATES] = {0}, tpl_m[CD_MAX_TEMPLATES] = {0};
     bool tpl_gridded[CD_MAX_TEMPLATES] = {false};                // slot has a cell start table
     bool tpl_big[CD_MAX_TEMPLATES] = {false};                    // slot does not fit LDS but has what k_icp_pipe_big needs (cell table, k-d map, superpatches)
@@ -2146,137 +2147,13 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
 }
 
 // ---- templates ------------------------------------------------------------------------------------------------------
-// Everything cd_set_template derives from the template's points is device-independent host work (two sorted layouts, run
-// boxes, the uniform grid): it is done once per distinct template and shared by every context of the process (bench.py
-// keeps three contexts per GPU; the reference re-reads and re-indexes the template for every frame, icp.cpp:159).
-struct PreparedTemplate {
-    int m = 0, m_pad = 0;
-    std::vector<float> xyz;                              // the caller's points (cache key check)
-    std::vector<float4> cell_pts, cell_lo, cell_hi;      // layout 1: sorted by grid cell; boxes of its runs of 64
-    std::vector<float4> kd_pts, kd_lo, kd_hi;            // layout 2: k-d patches of 64; their boxes
-    std::vector<unsigned short> kdmap;                   // patch order -> cell-sorted position (LDS-resident templates)
-    std::vector<unsigned short> cell_start;              // grid start table (LDS-resident templates)
-    IcpGrid grid;                                        // cell_off is set per slot at upload
-    IcpSuper super;                                      // second box level of a template that does not fit LDS (n = 0: none)
-    bool big_ok = false;                                 // k_icp_pipe_big can search it
-    IcpLattice lat;                                      // nface > 0: the template is a union of axis-aligned lattices (k_icp_lat.hip)
-    ShapeFrame frame;                                    // rule C13: the template's principal frame (shape_frame_host)
-};
-
-// rule C13 steps 1-4 on the host: the sums as the device forms them (fixq = llrint(ldexp(v, 32)), round to nearest even), then
-// shape_frame_math.hpp
-static void shape_frame_host(const void* xyz, size_t stride, int n, ShapeFrame* out) {
-    if (n > SHAPE_N_MAX) { shape_empty(n, SHAPE_ERR_CAPACITY, out); return; }
-    auto point = [&](int i, float v[3]) { std::memcpy(v, (const char*)xyz + (size_t)i * stride, 12); };
-    uint64_t S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    bool bad = false;
-    for (int i = 0; i < n; ++i) {
-        float v[3];
-        point(i, v);
-        bad = bad || !shape_coord_ok(v[0], v[1], v[2]);
-        if (bad) break;
-        const float t[9] = {v[0], v[1], v[2], v[0] * v[0], v[0] * v[1], v[0] * v[2], v[1] * v[1], v[1] * v[2], v[2] * v[2]};
-        for (int k = 0; k < 9; ++k) S[k] += (uint64_t)std::llrint(std::ldexp((double)t[k], FIX_SHIFT));
-    }
-    if (bad) { shape_empty(n, SHAPE_ERR_INVALID, out); return; }
-    if (n < 3) { shape_empty(n, SHAPE_ERR_FEW, out); return; }
-    long long T[9];
-    for (int k = 0; k < 9; ++k) T[k] = (long long)S[k];
-    shape_empty(n, SHAPE_OK, out);
-    shape_solve(T, n, out);
-    const double inf = std::numeric_limits<double>::infinity();
-    double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    for (int i = 0; i < n; ++i) {
-        float v[3];
-        double q[3];
-        point(i, v);
-        shape_project(out->mean, out->axes, v[0], v[1], v[2], q);
-        for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], q[a]); hi[a] = std::fmax(hi[a], q[a]); }
-    }
-    for (int a = 0; a < 3; ++a) { out->lo[a] = lo[a] + 0.0; out->hi[a] = hi[a] + 0.0; }   // (a zero extent is stored as +0)
-}
-
-// Is the template what make_cuboid.py writes (mkc.py:38-55) - faces one after the other, each the Cartesian product of two of
-// three shared, ascending, near-uniform axis tables at a constant third coordinate, first axis fastest?  Verified bit by bit
-// against the points; anything else (a point moved, a row missing, the object templates) leaves nface = 0.
-static void lattice_detect(const float* xyz, int m, IcpLattice* out) {
-    std::memset(out, 0, sizeof(*out));
-    struct Face { int w, u, v, base, nu, nv; float c; };
-    std::vector<Face> faces;
-    std::vector<float> tabs[3];
-    auto P = [&](int i, int a) { return xyz[3 * (size_t)i + a]; };
-    for (int i = 0; i < 3 * m; ++i) if (!std::isfinite(xyz[i])) return;
-    int pos = 0;
-    while (pos < m) {
-        if ((int)faces.size() >= LAT_MAX_FACES || pos + 1 >= m) return;
-        int u = -1;
-        for (int a = 0; a < 3; ++a)
-            if (P(pos + 1, a) != P(pos, a)) { if (u >= 0) return; u = a; }
-        if (u < 0) return;
-        int nu = 1;   // first row: only u moves, ascending
-        while (pos + nu < m && P(pos + nu, u) > P(pos + nu - 1, u) && P(pos + nu, (u + 1) % 3) == P(pos, (u + 1) % 3) &&
-               P(pos + nu, (u + 2) % 3) == P(pos, (u + 2) % 3)) ++nu;
-        if (nu < 2 || pos + nu >= m) return;
-        int v = -1;
-        for (int a = 0; a < 3; ++a)
-            if (P(pos + nu, a) != P(pos, a)) { if (v >= 0 || a == u) return; v = a; }
-        if (v < 0) return;
-        const int w = 3 - u - v;
-        int nv = 1;   // further rows: the same u values, v constant within the row and ascending from row to row, w constant
-        while (pos + (nv + 1) * nu <= m) {
-            const int r = pos + nv * nu;
-            bool ok = P(r, v) > P(r - nu, v);
-            for (int i = 0; i < nu && ok; ++i) ok = P(r + i, u) == P(pos + i, u) && P(r + i, v) == P(r, v) && P(r + i, w) == P(pos, w);
-            if (!ok) break;
-            ++nv;
-        }
-        if (nv < 2) return;
-        std::vector<float> U((size_t)nu), V((size_t)nv);
-        for (int i = 0; i < nu; ++i) U[(size_t)i] = P(pos + i, u);
-        for (int j = 0; j < nv; ++j) V[(size_t)j] = P(pos + j * nu, v);
-        const std::pair<int, std::vector<float>*> both[2] = {{u, &U}, {v, &V}};
-        for (const auto& av : both) {   // one table per axis, shared by every face that varies along it
-            if (tabs[av.first].empty()) tabs[av.first] = *av.second;
-            else if (tabs[av.first] != *av.second) return;
-        }
-        faces.push_back(Face{w, u, v, pos, nu, nv, P(pos, w)});
-        pos += nu * nv;
-    }
-    int ntab = 0;
-    for (int a = 0; a < 3; ++a) {
-        const std::vector<float>& T = tabs[a];
-        const int n = (int)T.size();
-        out->toff[a] = ntab;
-        if (n == 0) {   // no face varies along this axis: a one-entry table, so that the kernel treats every axis alike (never read by a face)
-            if (ntab + 1 > LAT_MAX_TAB) { std::memset(out, 0, sizeof(*out)); return; }
-            out->n[a] = 1; out->noi[a] = 0.f; out->inv[a] = 1.f;
-            out->tab[ntab++] = make_float4(-INFINITY, 0.f, INFINITY, 0.f);
-            continue;
-        }
-        out->n[a] = n;
-        if (ntab + n > LAT_MAX_TAB) { std::memset(out, 0, sizeof(*out)); return; }
-        const double step = ((double)T[(size_t)n - 1] - (double)T[0]) / (double)(n - 1);
-        for (int i = 0; i < n; ++i)   // uniform to 1/16 of a step: the index guess of lat_axis is then at most one entry off
-            if (!(std::fabs((double)T[(size_t)i] - ((double)T[0] + i * step)) <= step / 16.0)) { std::memset(out, 0, sizeof(*out)); return; }
-        out->noi[a] = (float)(-(double)T[0] / step);
-        out->inv[a] = (float)(1.0 / step);
-        for (int i = 0; i < n; ++i)
-            out->tab[ntab + i] = make_float4(i > 0 ? T[(size_t)i - 1] : -INFINITY, T[(size_t)i], i + 1 < n ? T[(size_t)i + 1] : INFINITY, 0.f);
-        ntab += n;
-    }
-    out->ntab = ntab;
-    for (size_t f = 0; f < faces.size(); ++f) {
-        out->w[f] = faces[f].w; out->fast[f] = faces[f].u; out->base[f] = faces[f].base; out->c[f] = faces[f].c;
-        out->m0[f] = faces[f].w == 0 ? ~0u : 0u; out->m1[f] = faces[f].w == 1 ? ~0u : 0u; out->m2[f] = faces[f].w == 2 ? ~0u : 0u;
-    }
-    for (size_t f = faces.size(); f < (size_t)LAT_MAX_FACES; ++f) { out->w[f] = 2; out->m2[f] = ~0u; out->c[f] = std::numeric_limits<float>::quiet_NaN(); }   // (see IcpLattice::m0)
-    out->nface = (int)faces.size();
-    lattice_classify_axes(out);
-}
-
-static std::shared_ptr<const PreparedTemplate> prepare_template(const void* xyz, size_t stride, int m) {
-    std::vector<float> raw((size_t)m * 3);
-    for (int i = 0; i < m; ++i) std::memcpy(&raw[3 * (size_t)i], (const char*)xyz + (size_t)i * stride, 12);
+// Everything cd_set_template derives from the template's points is device-independent host work (template_prep.hpp): it is
+// done once per distinct template and shared by every context of the process (bench.py keeps three contexts per GPU; the
+// reference re-reads and re-indexes the template for every frame, icp.cpp:159).  The cache is process-wide, keyed on m plus the
+// raw bytes, and keeps the 16 newest entries.
+// (cell_factor is tuning only and not part of the key: a cached template keeps the factor it was prepared with)
+static std::shared_ptr<const PreparedTemplate> prepared_template_cached(const void* xyz, size_t stride, int m, float cell_factor) {
+    const std::vector<float> raw = gather_xyz(xyz, stride, m);
     static std::mutex mu;
     static std::vector<std::shared_ptr<const PreparedTemplate>> cache;
     {
@@ -2284,226 +2161,7 @@ static std::shared_ptr<const PreparedTemplate> prepare_template(const void* xyz,
         for (const auto& e : cache)
             if (e->m == m && std::memcmp(e->xyz.data(), raw.data(), raw.size() * sizeof(float)) == 0) return e;
     }
-    auto P = std::make_shared<PreparedTemplate>();
-    P->m = m;
-    const int m_pad = (m + ICP_SUB - 1) / ICP_SUB * ICP_SUB;   // slots start on a 64-point run boundary
-    P->m_pad = m_pad;
-    // Sort the template by the cells of a uniform grid over its bounding box (cell edge = 2 x the point
-    // spacing, enlarged until the grid has at most ICP_MAX_CELLS cells).  The lane-per-query search of
-    // k_icp.hip scans the few cell rows a query's seed ball touches; consecutive runs of 64 stored points
-    // are still spatially compact (a strip of one cell row), which is what the run boxes of the
-    // wave-per-query search feed on.  Each stored point keeps its ORIGINAL index in .w; the
-    // nearest-neighbour tie rule (lowest original index) is evaluated on that.
-    struct TP { float x, y, z; int oi; int cid; };
-    std::vector<TP> tp((size_t)m);
-    float gmn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, gmx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int i = 0; i < m; ++i) {
-        const float* v = &raw[3 * (size_t)i];
-        tp[(size_t)i] = TP{v[0], v[1], v[2], i, 0};
-        for (int a = 0; a < 3; ++a)
-            if (std::isfinite(v[a])) { gmn[a] = std::fmin(gmn[a], v[a]); gmx[a] = std::fmax(gmx[a], v[a]); }
-    }
-    for (int a = 0; a < 3; ++a) if (!(gmn[a] <= gmx[a])) gmn[a] = gmx[a] = 0.f;
-    IcpGrid& grid = P->grid;
-    std::memset(&grid, 0, sizeof(grid));
-    std::memset(&P->super, 0, sizeof(P->super));
-    {
-        // point spacing: median nearest-neighbour distance of a sample of (at most 64 of) the points
-        std::vector<float> nn2;
-        const int step = std::max(1, m / 64);
-        for (int i = 0; i < m; i += step) {
-            float best = FLT_MAX;
-            for (int j = 0; j < m; ++j) {
-                const float dx = tp[(size_t)i].x - tp[(size_t)j].x, dy = tp[(size_t)i].y - tp[(size_t)j].y, dz = tp[(size_t)i].z - tp[(size_t)j].z;
-                const float d = dx * dx + dy * dy + dz * dz;
-                if (d > 0.f && d < best) best = d;
-            }
-            if (best < FLT_MAX) nn2.push_back(best);
-        }
-        float pitch = 0.002f;
-        if (!nn2.empty()) { std::nth_element(nn2.begin(), nn2.begin() + nn2.size() / 2, nn2.end()); pitch = std::sqrt(nn2[nn2.size() / 2]); }
-        float cell_factor = 2.0f;
-        if (const char* e = std::getenv("CUBOID_ICP_CELL_FACTOR")) cell_factor = (float)std::atof(e);   // tuning only
-        float cell = std::fmax(cell_factor * pitch, 1.0e-4f);
-        int nd[3];
-        for (;;) {
-            long long tot = 1;
-            for (int a = 0; a < 3; ++a) {
-                const double cnt = std::floor((double)(gmx[a] - gmn[a]) / cell) + 1.0;
-                nd[a] = cnt > 1.0e6 ? 1000000 : (int)cnt;
-                tot *= nd[a];
-            }
-            if (tot <= ICP_MAX_CELLS) break;
-            cell *= 1.26f;
-        }
-        grid.ox = gmn[0]; grid.oy = gmn[1]; grid.oz = gmn[2];
-        grid.cell = cell;
-        grid.inv = 1.0f / cell;
-        grid.nx = nd[0]; grid.ny = nd[1]; grid.nz = nd[2];
-        const int ncell = nd[0] * nd[1] * nd[2];
-        auto coord = [&](float v, float o, int n) {
-            const float t = std::floor((v - o) * grid.inv);
-            return t >= (float)(n - 1) ? n - 1 : (t > 0.f ? (int)t : 0);   // NaN -> 0
-        };
-        for (int i = 0; i < m; ++i) {
-            TP& t = tp[(size_t)i];
-            t.cid = (coord(t.z, grid.oz, grid.nz) * grid.ny + coord(t.y, grid.oy, grid.ny)) * grid.nx + coord(t.x, grid.ox, grid.nx);
-        }
-        std::sort(tp.begin(), tp.end(), [](const TP& a, const TP& bb) { return a.cid < bb.cid || (a.cid == bb.cid && a.oi < bb.oi); });
-        if (m <= ICP_BIG_MAX) {   // (uint16 positions: templates the persistent kernels can walk)
-            grid.ncell = ncell;
-            P->cell_start.assign((size_t)ncell + 1, 0);
-            int i = 0;
-            for (int cid = 0; cid <= ncell; ++cid) {
-                while (i < m && tp[(size_t)i].cid < cid) ++i;
-                P->cell_start[(size_t)cid] = (unsigned short)i;
-            }
-        }
-    }
-    // one layout = the points (original index in .w) and the axis-aligned box of every run of 64 consecutive STORED
-    // points (exact float min/max)
-    auto layout = [&](std::vector<float4>& pts, std::vector<float4>& lo, std::vector<float4>& hi) {
-        // (the last run is filled up with points at +inf, original index INT_MAX: kernels that read a whole run from global
-        // memory - k_icp_pipe_big - meet them as candidates that can never win)
-        const int imax = 0x7fffffff;
-        float wpad;
-        std::memcpy(&wpad, &imax, 4);
-        pts.assign((size_t)m_pad, make_float4(INFINITY, INFINITY, INFINITY, wpad));
-        for (int i = 0; i < m; ++i) {
-            float w;
-            std::memcpy(&w, &tp[(size_t)i].oi, 4);
-            pts[(size_t)i] = make_float4(tp[(size_t)i].x, tp[(size_t)i].y, tp[(size_t)i].z, w);
-        }
-        const int nrun = m_pad / ICP_SUB;
-        lo.resize((size_t)nrun);
-        hi.resize((size_t)nrun);
-        for (int r = 0; r < nrun; ++r) {
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            for (int i = r * ICP_SUB; i < std::min(m, (r + 1) * ICP_SUB); ++i) {
-                const float v[3] = {tp[(size_t)i].x, tp[(size_t)i].y, tp[(size_t)i].z};
-                for (int a = 0; a < 3; ++a) { mn[a] = std::fmin(mn[a], v[a]); mx[a] = std::fmax(mx[a], v[a]); }
-            }
-            lo[(size_t)r] = make_float4(mn[0], mn[1], mn[2], 0.f);
-            hi[(size_t)r] = make_float4(mx[0], mx[1], mx[2], 0.f);
-        }
-    };
-    layout(P->cell_pts, P->cell_lo, P->cell_hi);                      // layout 1: cell-sorted (whole-cluster kernels)
-    std::vector<int> pos_cell((size_t)m);                             // original index -> position in layout 1
-    for (int i = 0; i < m; ++i) pos_cell[(size_t)tp[(size_t)i].oi] = i;
-    std::vector<std::pair<int, int>> chunks;  // k-d subtrees of <= ICP_TPL_LDS points whose parent is larger (templates that do not fit LDS)
-    std::vector<std::pair<int, int>> supers;  // k-d subtrees of <= 64 patches whose parent is larger (same templates: IcpSuper)
-    {
-        // Layout 2, for the wave-per-query search: compact patches of 64 points from k-d median splits whose left part is
-        // a multiple of 64, so that consecutive runs of 64 stored points have the smallest boxes the run-box pruning can get.
-        std::vector<std::pair<int, int>> stack;   // [lo, hi)
-        stack.push_back({0, m});
-        while (!stack.empty()) {
-            const auto [lo, hi] = stack.back();
-            stack.pop_back();
-            const int n = hi - lo;
-            if (m > ICP_TPL_LDS && n <= ICP_TPL_LDS) {
-                bool inside = false;   // already inside a recorded chunk?
-                for (const auto& ch : chunks) inside = inside || (lo >= ch.first && hi <= ch.second);
-                if (!inside) chunks.push_back({lo, hi});
-            }
-            if (m > ICP_TPL_LDS && n <= 64 * ICP_SUB) {
-                bool inside = false;
-                for (const auto& su : supers) inside = inside || (lo >= su.first && hi <= su.second);
-                if (!inside) supers.push_back({lo, hi});
-            }
-            if (n <= ICP_SUB) {
-                std::sort(tp.begin() + lo, tp.begin() + hi, [](const TP& a, const TP& bb) { return a.oi < bb.oi; });
-                continue;
-            }
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            for (int i = lo; i < hi; ++i) {
-                const float v[3] = {tp[(size_t)i].x, tp[(size_t)i].y, tp[(size_t)i].z};
-                for (int a = 0; a < 3; ++a) { mn[a] = std::fmin(mn[a], v[a]); mx[a] = std::fmax(mx[a], v[a]); }
-            }
-            int ax = 0;
-            if (mx[1] - mn[1] > mx[ax] - mn[ax]) ax = 1;
-            if (mx[2] - mn[2] > mx[ax] - mn[ax]) ax = 2;
-            int k = ((n / 2 + ICP_SUB - 1) / ICP_SUB) * ICP_SUB;
-            if (k >= n) k -= ICP_SUB;
-            auto key = [ax](const TP& t) { return ax == 0 ? t.x : (ax == 1 ? t.y : t.z); };
-            std::nth_element(tp.begin() + lo, tp.begin() + lo + k, tp.begin() + hi,
-                             [&](const TP& a, const TP& bb) { return key(a) < key(bb) || (key(a) == key(bb) && a.oi < bb.oi); });
-            stack.push_back({lo + k, hi});
-            stack.push_back({lo, lo + k});
-        }
-    }
-    layout(P->kd_pts, P->kd_lo, P->kd_hi);
-    if (m > ICP_TPL_LDS && (int)chunks.size() <= ICP_MAX_CHUNKS) {   // chunk table of a template that does not fit LDS
-        std::sort(chunks.begin(), chunks.end());
-        grid.nchunk = (int)chunks.size();
-        for (int ci = 0; ci < grid.nchunk; ++ci) {
-            const int lo = chunks[(size_t)ci].first, hi = chunks[(size_t)ci].second;
-            grid.chunk_start[ci] = lo;
-            grid.chunk_n[ci] = hi - lo;
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            for (int r = lo / ICP_SUB; r < (hi + ICP_SUB - 1) / ICP_SUB; ++r) {
-                const float lo3[3] = {P->kd_lo[(size_t)r].x, P->kd_lo[(size_t)r].y, P->kd_lo[(size_t)r].z};
-                const float hi3[3] = {P->kd_hi[(size_t)r].x, P->kd_hi[(size_t)r].y, P->kd_hi[(size_t)r].z};
-                for (int a = 0; a < 3; ++a) { mn[a] = std::fmin(mn[a], lo3[a]); mx[a] = std::fmax(mx[a], hi3[a]); }
-            }
-            for (int a = 0; a < 3; ++a) { grid.chunk_lo[ci][a] = mn[a]; grid.chunk_hi[ci][a] = mx[a]; }
-            grid.chunk_lo[ci][3] = grid.chunk_hi[ci][3] = 0.f;
-        }
-    }
-    {   // the two halves of the root split (the stack above splits [0, m) at k0 first; patches are whole on either side)
-        int k0 = m;
-        if (m > ICP_SUB) {
-            k0 = ((m / 2 + ICP_SUB - 1) / ICP_SUB) * ICP_SUB;
-            if (k0 >= m) k0 -= ICP_SUB;
-        }
-        grid.kd_split = k0 >= m ? m_pad / ICP_SUB : k0 / ICP_SUB;
-        const int nrun = m_pad / ICP_SUB;
-        for (int h = 0; h < 2; ++h) {
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            const int r0 = h == 0 ? 0 : grid.kd_split, r1 = h == 0 ? grid.kd_split : nrun;
-            for (int r = r0; r < r1; ++r) {
-                const float lo3[3] = {P->kd_lo[(size_t)r].x, P->kd_lo[(size_t)r].y, P->kd_lo[(size_t)r].z};
-                const float hi3[3] = {P->kd_hi[(size_t)r].x, P->kd_hi[(size_t)r].y, P->kd_hi[(size_t)r].z};
-                for (int a = 0; a < 3; ++a) { mn[a] = std::fmin(mn[a], lo3[a]); mx[a] = std::fmax(mx[a], hi3[a]); }
-            }
-            for (int a = 0; a < 3; ++a) { grid.half_lo[h][a] = mn[a]; grid.half_hi[h][a] = mx[a]; }   // an empty half keeps +-FLT_MAX: never reached
-            grid.half_lo[h][3] = grid.half_hi[h][3] = 0.f;
-        }
-    }
-    if (m <= ICP_BIG_MAX) {
-        // k-d patch r = the cell-sorted positions kdmap[64 r .. 64 r + 63]: the pipelined kernel searches far queries
-        // patch by patch THROUGH this table (compact boxes) while the points themselves stay cell-sorted in LDS; for a
-        // template in global memory (k_icp_pipe_big) it turns the position of a k-d ordered point into its cell-sorted one
-        P->kdmap.assign((size_t)m_pad, (unsigned short)std::min(m_pad, 65535));   // padding -> the +inf pad run
-        for (int i = 0; i < m; ++i) P->kdmap[(size_t)i] = (unsigned short)pos_cell[(size_t)tp[(size_t)i].oi];
-    }
-    if (m > ICP_TPL_LDS && m <= ICP_BIG_MAX && m_pad / ICP_SUB <= ICP_BIG_PATCHES && !supers.empty() && supers.size() <= 64 && grid.ncell > 0) {
-        std::sort(supers.begin(), supers.end());
-        IcpSuper& su = P->super;
-        su.n = (int)supers.size();
-        bool ok = true;
-        int covered = 0;
-        for (int k = 0; k < su.n; ++k) {
-            const int lo = supers[(size_t)k].first, hi = supers[(size_t)k].second;
-            ok = ok && lo % ICP_SUB == 0 && lo == covered;   // runs of whole patches that tile the template
-            covered = hi;
-            su.first[k] = lo / ICP_SUB;
-            su.cnt[k] = (hi - lo + ICP_SUB - 1) / ICP_SUB;
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            for (int r = su.first[k]; r < su.first[k] + su.cnt[k]; ++r) {
-                const float lo3[3] = {P->kd_lo[(size_t)r].x, P->kd_lo[(size_t)r].y, P->kd_lo[(size_t)r].z};
-                const float hi3[3] = {P->kd_hi[(size_t)r].x, P->kd_hi[(size_t)r].y, P->kd_hi[(size_t)r].z};
-                for (int a = 0; a < 3; ++a) { mn[a] = std::fmin(mn[a], lo3[a]); mx[a] = std::fmax(mx[a], hi3[a]); }
-            }
-            for (int a = 0; a < 3; ++a) { su.lo[k][a] = mn[a]; su.hi[k][a] = mx[a]; }
-            su.lo[k][3] = su.hi[k][3] = 0.f;
-        }
-        P->big_ok = ok && covered == m;
-        if (!P->big_ok) su.n = 0;
-    }
-    lattice_detect(raw.data(), m, &P->lat);
-    shape_frame_host(raw.data(), 12, m, &P->frame);
-    P->xyz.swap(raw);
+    std::shared_ptr<const PreparedTemplate> P = prepare_template(raw.data(), m, cell_factor);
     std::lock_guard<std::mutex> lk(mu);
     if (cache.size() >= 16) cache.erase(cache.begin());
     cache.push_back(P);
@@ -2543,7 +2201,9 @@ int cd_set_template(cd_context* c, int slot, const void* xyz, size_t stride, int
     if (slot < 0 || slot >= CD_MAX_TEMPLATES || !xyz || m <= 0 || stride < 12) return fail(c, CD_ERR_INVALID_ARG, "bad template arguments");
     hipSetDevice(c->device);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::shared_ptr<const PreparedTemplate> P = prepare_template(xyz, stride, m);
+    float cell_factor = 2.0f;
+    if (const char* e = std::getenv("CUBOID_ICP_CELL_FACTOR")) cell_factor = (float)std::atof(e);   // tuning only
+    std::shared_ptr<const PreparedTemplate> P = prepared_template_cached(xyz, stride, m, cell_factor);
     // a slot is re-used in place when the new template fits its space, appended otherwise; when the arena is full the
     // live slots are packed again (the space of replaced templates is reclaimed) before giving up
     const int old_pad = c->tpl_prep[slot] ? c->tpl_prep[slot]->m_pad : 0;
@@ -2579,8 +2239,7 @@ int cd_template_lattice_faces(const cd_context* c, int slot) {
 
 int cd_lattice_detect(const void* xyz, size_t stride, int m, int32_t* out) {
     if (!xyz || m <= 0 || stride < 12) return CD_ERR_INVALID_ARG;
-    std::vector<float> raw((size_t)m * 3);
-    for (int i = 0; i < m; ++i) std::memcpy(&raw[3 * (size_t)i], (const char*)xyz + (size_t)i * stride, 12);
+    const std::vector<float> raw = gather_xyz(xyz, stride, m);
     auto L = std::make_unique<IcpLattice>();
     lattice_detect(raw.data(), m, L.get());
     for (int f = 0; out && f < L->nface; ++f) {
@@ -2593,8 +2252,7 @@ int cd_lattice_detect(const void* xyz, size_t stride, int m, int32_t* out) {
 
 int cd_lattice_axes(const void* xyz, size_t stride, int m, int32_t* out_axis_face, float* out_axis_c) {
     if (!xyz || m <= 0 || stride < 12) return CD_ERR_INVALID_ARG;
-    std::vector<float> raw((size_t)m * 3);
-    for (int i = 0; i < m; ++i) std::memcpy(&raw[3 * (size_t)i], (const char*)xyz + (size_t)i * stride, 12);
+    const std::vector<float> raw = gather_xyz(xyz, stride, m);
     auto L = std::make_unique<IcpLattice>();
     lattice_detect(raw.data(), m, L.get());
     if (L->nface == 0) lattice_classify_axes(L.get());   // (not a lattice: the "none" values)

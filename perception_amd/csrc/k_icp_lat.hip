@@ -4,7 +4,7 @@
 // cuboid_detection/src/iterative_closest_point.cpp:170-182, object_detection/src/object_pose_detection.cpp:220-235) for the
 // templates cuboid_detection/templates/make_cuboid.py:38-55 writes: face k = meshgrid of two of the three axis tables
 // X, Y, Z at a constant third coordinate, first axis fastest, faces one after the other.  cd_set_template verifies that
-// structure bit by bit against the uploaded points (lattice_detect, cuboid_hip.hip) and hands over IcpLattice (common.hpp);
+// structure bit by bit against the uploaded points (lattice_detect, template_prep.hpp) and hands over IcpLattice (common.hpp);
 // every other template keeps the pruned searches of k_icp.hip.
 //
 // The search.  The canonical squared distance (rule C1/C5, common.hpp dist2) to point (i, j) of a face with constant z = c is

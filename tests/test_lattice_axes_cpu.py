@@ -1,5 +1,6 @@
 """cd_lattice_axes (host only): which lattice templates have at most one face per constant axis and so take the mask-free
-face code of k_icp_lat (IcpLattice::axes_distinct, lattice_classify_axes in common.hpp)."""
+face code of k_icp_lat (IcpLattice::axes_distinct: lattice_classify_axes in common.hpp, called at the end of lattice_detect in
+template_prep.hpp)."""
 import itertools
 import os
 
