@@ -652,6 +652,125 @@ __device__ __forceinline__ void store_queries(const QueryRegs& q, int nk, int* n
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// What the sliced drivers do with one slice of queries - search, moments, fitness - is written once, here: k_icp_iter,
+// k_icp_persist and k_icp_fitness (and, for the chunk walk and the near search, both passes of k_icp_cluster) compute the same
+// thing by construction.  All of these contain barriers: call them from all threads.
+// ---------------------------------------------------------------------------------------
+// One template of the arena: its points and the boxes of its 64-point runs.
+struct TplRef { const float4 *p, *lo, *hi; };
+__device__ __forceinline__ TplRef tpl_ref(const float4* __restrict__ tpl, const float4* __restrict__ tlo,
+                                          const float4* __restrict__ thi, int off) {
+    return {tpl + off, tlo + off / ICP_SUB, thi + off / ICP_SUB};
+}
+
+// A template without a chunk table that does not fit LDS: every query against every ICPT_TPL_LDS points of it in turn.
+// The image left in LDS is a part of the template: the caller's `staged` must become -1.
+__device__ __forceinline__ void search_fixed_chunks(const TplRef& t, int m, QueryRegs& q, int nk, float4* s_tpl, RunBoxes& bx) {
+    for (int c0 = 0; c0 < m; c0 += ICPT_TPL_LDS) {
+        const int cn = min(ICPT_TPL_LDS, m - c0);
+        stage_chunk(t.p, t.lo, t.hi, c0, cn, s_tpl, bx);
+        search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
+    }
+}
+
+// Search the wave's queries against cluster c's template.  `staged` is the template offset whose whole image (and this
+// lane's boxes in bx) is resident in s_tpl, -1 for none: a template that fits LDS is staged only when another one is
+// resident, and any chunked walk leaves -1 behind, so that the next small template is staged again.
+__device__ __forceinline__ void search_slice(const TplRef& t, const IcpCluster& c, const IcpGrid* __restrict__ grids, QueryRegs& q,
+                                             int nk, float4* s_tpl, RunBoxes& bx, int& staged, int* s_flag) {
+    if (c.tpl_m <= ICPT_TPL_LDS) {
+        if (staged != c.tpl_off) { stage_chunk(t.p, t.lo, t.hi, 0, c.tpl_m, s_tpl, bx); staged = c.tpl_off; }
+        search_chunk(s_tpl, bx, 0, c.tpl_m, q, lanes_below(nk));
+        return;
+    }
+    const IcpGrid& g = grids[c.slot];
+    if (g.nchunk > 0) {
+        for (int ci = 0; ci < g.nchunk; ++ci) {
+            bool any;
+            const unsigned long long todo = chunk_needed(g, ci, q, nk, s_flag, &any);
+            if (!any) continue;
+            stage_chunk(t.p, t.lo, t.hi, g.chunk_start[ci], g.chunk_n[ci], s_tpl, bx);
+            search_chunk(s_tpl, bx, g.chunk_start[ci], g.chunk_n[ci], q, todo);
+        }
+    } else {
+        search_fixed_chunks(t, c.tpl_m, q, nk, s_tpl, bx);
+    }
+    staged = -1;
+}
+
+// X <- T * X of one slice, in place (T: 12 floats, row-major)
+__device__ __forceinline__ void transform_slice(const float* Tm, float4* pts, int nq) {
+    float T[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = Tm[k];
+    for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) {
+        const float4 p = pts[i];
+        float ox, oy, oz;
+        xform(T, p.x, p.y, p.z, ox, oy, oz);
+        pts[i] = make_float4(ox, oy, oz, p.w);
+    }
+}
+
+// The 16 fixed-point moments of a slice's correspondences (nnq, d2q: what store_queries wrote, behind a barrier), added to
+// acc[slot] with slot = cluster * 3 + it % 3: per-point terms go to LDS (term-major, conflict-free), 8 terms at a time; wave
+// k then sums term k.  BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter; bnd.ncorr[slot] counts them.
+// s_scr (8 * ICP_QSLICE words) is still being read when this returns.
+template <bool BOUNDED>
+__device__ __forceinline__ void slice_moments(const float4* pts, const float4* __restrict__ tp, const int* nnq, const float* d2q, int nq,
+                                              unsigned long long* acc, const IcpBound& bnd, size_t slot, unsigned long long* s_scr) {
+    static_assert(ICP_QSLICE <= ICPT_THREADS, "one point per thread in the moment pass");
+    const int lane = threadIdx.x & 63;
+    unsigned long long S[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) S[k] = 0ull;
+    const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
+    if constexpr (BOUNDED) {
+        const unsigned long long kb = ballot64(keep);
+        if (lane == 0 && kb) atomicAdd(&bnd.ncorr[slot], (uint32_t)__popcll(kb));
+    }
+    if (keep) {
+        const int i = threadIdx.x;
+        const float4 p = pts[i];
+        const float4 qq = tp[nnq[i]];
+        const float pv[3] = {p.x, p.y, p.z}, qv[3] = {qq.x, qq.y, qq.z};
+        moment_terms(pv, qv, d2q[i], S);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h) __syncthreads();
+        if (threadIdx.x < ICP_QSLICE) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s_scr[k * ICP_QSLICE + threadIdx.x] = S[8 * h + k];
+        }
+        __syncthreads();
+        const int k = threadIdx.x >> 6;   // waves 0..7 <-> the 8 moments of this half
+        if (k < 8) {
+            unsigned long long t = 0ull;
+#pragma unroll
+            for (int j = 0; j < ICP_QSLICE / 64; ++j) t += s_scr[k * ICP_QSLICE + j * 64 + lane];
+            t = wave_sum_u64(t);
+            if (lane == 0) atomicAdd(&acc[slot * 16 + 8 * h + k], t);
+        }
+    }
+}
+
+// getFitnessScore() of one slice: the neighbours of Tfinal * (original points), left in nnq / d2q; returns this thread's
+// share of the slice's fixed-point sum of squared distances.
+__device__ __forceinline__ unsigned long long slice_fitness(const TplRef& t, const IcpCluster& c, const IcpGrid* __restrict__ grids,
+                                                            const float* Tfinal, const float4* pts0, int nq, int* nnq, float* d2q,
+                                                            float4* s_tpl, RunBoxes& bx, int& staged, int* s_flag) {
+    QueryRegs q;
+    int nk;
+    fetch_queries(t.p, c.tpl_m, pts0, nq, true, false, true, Tfinal, nnq, q, nk);
+    search_slice(t, c, grids, q, nk, s_tpl, bx, staged, s_flag);
+    store_queries(q, nk, nnq, d2q);
+    __syncthreads();
+    unsigned long long v = 0ull;
+    for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) v += (unsigned long long)fixq(d2q[i], FIX_SHIFT_D2);
+    return v;
+}
+
 // One thread per cluster: the state update of launch `it` (icp_step: TransformationEstimationSVD + final_transformation_
 // update + DefaultConvergenceCriteria), from the moments launch it-1 accumulated.
 // Writes the state slot k_icp_iter(it) consumes, keeps the `done` flag in both parity slots and
@@ -692,9 +811,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, c
     __shared__ float4 s_tpl[ICPT_IMG];
     __shared__ unsigned long long s_scr[8 * ICP_QSLICE];   // moment scratch, 8 terms at a time (32 KiB)
     __shared__ int s_item[3];   // [0], [1]: work items (double-buffered), [2]: chunk_needed flag
-    const int lane = threadIdx.x & 63;
     RunBoxes bx;
-    int staged = -1;   // template offset whose (single-chunk) image is resident in LDS
+    int staged = -1;   // template offset whose image is resident in LDS (search_slice)
     if (threadIdx.x == 0) s_item[0] = atomicAdd(queue, 1);
     for (int ph = 0;; ph ^= 1) {
         __syncthreads();                       // one barrier per item: publishes s_item[ph], retires the previous item
@@ -712,84 +830,17 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, c
         float4* pts = src + c.src_off + q0;
         int* nnq = nn + c.src_off + q0;
         float* d2q = d2buf + c.src_off + q0;
-        if (it > 0) {   // X <- T * X, in place
-            float T[12];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) T[k] = snow->T[k];
-            for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) {
-                const float4 p = pts[i];
-                float ox, oy, oz;
-                xform(T, p.x, p.y, p.z, ox, oy, oz);
-                pts[i] = make_float4(ox, oy, oz, p.w);
-            }
-        }
+        if (it > 0) transform_slice(snow->T, pts, nq);
         if (done_now) continue;
         __syncthreads();   // the transformed points are read by other waves below
-        const float4* tp = tpl + c.tpl_off;
-        const float4* blo = tlo + c.tpl_off / ICP_SUB;
-        const float4* bhi = thi + c.tpl_off / ICP_SUB;
+        const TplRef t = tpl_ref(tpl, tlo, thi, c.tpl_off);
         QueryRegs q;
         int nk;
-        fetch_queries(tp, c.tpl_m, pts, nq, it > 0, it < 3, false, nullptr, nnq, q, nk);
-        if (c.tpl_m <= ICPT_TPL_LDS) {
-            if (staged != c.tpl_off) { stage_chunk(tp, blo, bhi, 0, c.tpl_m, s_tpl, bx); staged = c.tpl_off; }
-            search_chunk(s_tpl, bx, 0, c.tpl_m, q, lanes_below(nk));
-        } else {
-            const IcpGrid& g = grids[c.slot];
-            if (g.nchunk > 0) {
-                for (int ci = 0; ci < g.nchunk; ++ci) {
-                    bool any;
-                    const unsigned long long todo = chunk_needed(g, ci, q, nk, &s_item[2], &any);
-                    if (!any) continue;
-                    stage_chunk(tp, blo, bhi, g.chunk_start[ci], g.chunk_n[ci], s_tpl, bx);
-                    search_chunk(s_tpl, bx, g.chunk_start[ci], g.chunk_n[ci], q, todo);
-                }
-            } else {
-                for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                    const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                    stage_chunk(tp, blo, bhi, c0, cn, s_tpl, bx);
-                    search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-                }
-            }
-            staged = -1;
-        }
+        fetch_queries(t.p, c.tpl_m, pts, nq, it > 0, it < 3, false, nullptr, nnq, q, nk);
+        search_slice(t, c, grids, q, nk, s_tpl, bx, staged, &s_item[2]);
         store_queries(q, nk, nnq, d2q);
         __syncthreads();
-        // 16 fixed-point moments of the correspondences of this slice: per-point terms go to LDS
-        // (term-major, conflict-free), 8 terms at a time; wave k then sums term k.
-        unsigned long long S[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) S[k] = 0ull;
-        const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
-        if constexpr (BOUNDED) {
-            const unsigned long long kb = ballot64(keep);
-            if (lane == 0 && kb) atomicAdd(&bnd.ncorr[(size_t)wk.cluster * 3 + it % 3], (uint32_t)__popcll(kb));
-        }
-        if (keep) {
-            const int i = threadIdx.x;
-            const float4 p = pts[i];
-            const float4 qq = tp[nnq[i]];
-            const float pv[3] = {p.x, p.y, p.z}, qv[3] = {qq.x, qq.y, qq.z};
-            moment_terms(pv, qv, d2q[i], S);
-        }
-        static_assert(ICP_QSLICE <= ICPT_THREADS, "one point per thread in the moment pass");
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (h) __syncthreads();
-            if (threadIdx.x < ICP_QSLICE) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) s_scr[k * ICP_QSLICE + threadIdx.x] = S[8 * h + k];
-            }
-            __syncthreads();
-            const int k = threadIdx.x >> 6;   // waves 0..7 <-> the 8 moments of this half
-            if (k < 8) {
-                unsigned long long t = 0ull;
-#pragma unroll
-                for (int j = 0; j < ICP_QSLICE / 64; ++j) t += s_scr[k * ICP_QSLICE + j * 64 + lane];
-                t = wave_sum_u64(t);
-                if (lane == 0) atomicAdd(&acc[((size_t)wk.cluster * 3 + it % 3) * 16 + 8 * h + k], t);
-            }
-        }
+        slice_moments<BOUNDED>(pts, t.p, nnq, d2q, nq, acc, bnd, (size_t)wk.cluster * 3 + it % 3, s_scr);
     }
 }
 
@@ -808,7 +859,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_iter(int it, int n_work, c
 // All G <= n_CU workgroups must be resident together (one per CU): they are, unless other kernels hold the CUs, in which
 // case the ones already running wait at the barrier.  Every wait is bounded (2^15 polls, some tens of milliseconds): a
 // barrier that does not complete raises the abort flag, every workgroup leaves, and the host runs the multi-launch form instead.
-// Same arithmetic as k_icp_solve + k_icp_iter + k_icp_fitness (the moments are order-free integer sums): identical results.
+// The slice code is k_icp_iter's and k_icp_fitness's own (transform_slice, search_slice, slice_moments, slice_fitness), the solve
+// is icp_step, and the moments are order-free integer sums: identical results.
 // ---------------------------------------------------------------------------------------
 constexpr int PERSIST_ITEMS = 8;   // work items per workgroup at most
 
@@ -916,84 +968,19 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
             float4* pts = src + c.src_off + q0;
             int* nnq = nn + c.src_off + q0;
             float* d2q = d2buf + c.src_off + q0;
-            if (it > 0) {   // X <- T * X, in place
-                float T[12];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) T[k] = s_st[j].T[k];
-                for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) {
-                    const float4 p = pts[i];
-                    float ox, oy, oz;
-                    xform(T, p.x, p.y, p.z, ox, oy, oz);
-                    pts[i] = make_float4(ox, oy, oz, p.w);
-                }
-            }
+            if (it > 0) transform_slice(s_st[j].T, pts, nq);
             if (done_now) continue;
             __syncthreads();   // the transformed points are read by other waves below
             PERSIST_PHASE(1)
-            const float4* tp = tpl + c.tpl_off;
-            const float4* blo = tlo + c.tpl_off / ICP_SUB;
-            const float4* bhi = thi + c.tpl_off / ICP_SUB;
+            const TplRef t = tpl_ref(tpl, tlo, thi, c.tpl_off);
             QueryRegs q;
             int nk;
-            fetch_queries(tp, c.tpl_m, pts, nq, it > 0, it < 3, false, nullptr, nnq, q, nk);
-            if (c.tpl_m <= ICPT_TPL_LDS) {
-                if (staged != c.tpl_off) { stage_chunk(tp, blo, bhi, 0, c.tpl_m, s_tpl, bx); staged = c.tpl_off; }
-                search_chunk(s_tpl, bx, 0, c.tpl_m, q, lanes_below(nk));
-            } else {
-                const IcpGrid& g = grids[c.slot];
-                if (g.nchunk > 0) {
-                    for (int ci = 0; ci < g.nchunk; ++ci) {
-                        bool any;
-                        const unsigned long long todo = chunk_needed(g, ci, q, nk, &s_flag, &any);
-                        if (!any) continue;
-                        stage_chunk(tp, blo, bhi, g.chunk_start[ci], g.chunk_n[ci], s_tpl, bx);
-                        search_chunk(s_tpl, bx, g.chunk_start[ci], g.chunk_n[ci], q, todo);
-                    }
-                } else {
-                    for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                        const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                        stage_chunk(tp, blo, bhi, c0, cn, s_tpl, bx);
-                        search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-                    }
-                }
-                staged = -1;
-            }
+            fetch_queries(t.p, c.tpl_m, pts, nq, it > 0, it < 3, false, nullptr, nnq, q, nk);
+            search_slice(t, c, grids, q, nk, s_tpl, bx, staged, &s_flag);
             store_queries(q, nk, nnq, d2q);
             __syncthreads();
             PERSIST_PHASE(2)
-            unsigned long long S[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) S[k] = 0ull;
-            const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
-            if constexpr (BOUNDED) {
-                const unsigned long long kb = ballot64(keep);
-                if (lane == 0 && kb)
-                    __hip_atomic_fetch_add(bnd.ncorr + (size_t)wk.cluster * 3 + it % 3, (uint32_t)__popcll(kb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (keep) {
-                const int i = threadIdx.x;
-                const float4 p = pts[i];
-                const float4 qq = tp[nnq[i]];
-                const float pv[3] = {p.x, p.y, p.z}, qv[3] = {qq.x, qq.y, qq.z};
-                moment_terms(pv, qv, d2q[i], S);
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (h) __syncthreads();
-                if (threadIdx.x < ICP_QSLICE) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) s_scr[k * ICP_QSLICE + threadIdx.x] = S[8 * h + k];
-                }
-                __syncthreads();
-                const int k = threadIdx.x >> 6;   // waves 0..7 <-> the 8 moments of this half
-                if (k < 8) {
-                    unsigned long long t = 0ull;
-#pragma unroll
-                    for (int jj = 0; jj < ICP_QSLICE / 64; ++jj) t += s_scr[k * ICP_QSLICE + jj * 64 + lane];
-                    t = wave_sum_u64(t);
-                    if (lane == 0) atomicAdd(&acc[((size_t)wk.cluster * 3 + it % 3) * 16 + 8 * h + k], t);
-                }
-            }
+            slice_moments<BOUNDED>(pts, t.p, nnq, d2q, nq, acc, bnd, (size_t)wk.cluster * 3 + it % 3, s_scr);
             __syncthreads();   // s_scr is reused by the next item
             PERSIST_PHASE(3)
         }
@@ -1013,7 +1000,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
         if (seen0 + seen1 + seen2 + seen3 >= n_open) { ++it; break; }
     }
     if (aborted) return;
-    // fitness pass (what k_icp_fitness does) and publication of the states
+    // fitness pass and publication of the states
     for (int j = 0; j < n_items; ++j) {
         const IcpWork wk = work[blockIdx.x + j * G];
         const IcpCluster c = cl[wk.cluster];
@@ -1024,42 +1011,9 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
         for (int k = 0; k < 12; ++k) T[k] = s_st[j].Tfinal[k];
         const int q0 = wk.tile * qslice;
         const int nq = min(qslice, c.n - q0);
-        int* nnq = nn + c.src_off + q0;
-        float* d2q = d2buf + c.src_off + q0;
-        const float4* tp = tpl + c.tpl_off;
-        const float4* blo = tlo + c.tpl_off / ICP_SUB;
-        const float4* bhi = thi + c.tpl_off / ICP_SUB;
         __syncthreads();
-        QueryRegs q;
-        int nk;
-        fetch_queries(tp, c.tpl_m, src0 + c.src_off + q0, nq, true, false, true, T, nnq, q, nk);
-        if (c.tpl_m <= ICPT_TPL_LDS) {
-            if (staged != c.tpl_off) { stage_chunk(tp, blo, bhi, 0, c.tpl_m, s_tpl, bx); staged = c.tpl_off; }
-            search_chunk(s_tpl, bx, 0, c.tpl_m, q, lanes_below(nk));
-        } else {
-            const IcpGrid& g = grids[c.slot];
-            if (g.nchunk > 0) {
-                for (int ci = 0; ci < g.nchunk; ++ci) {
-                    bool any;
-                    const unsigned long long todo = chunk_needed(g, ci, q, nk, &s_flag, &any);
-                    if (!any) continue;
-                    stage_chunk(tp, blo, bhi, g.chunk_start[ci], g.chunk_n[ci], s_tpl, bx);
-                    search_chunk(s_tpl, bx, g.chunk_start[ci], g.chunk_n[ci], q, todo);
-                }
-            } else {
-                for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                    const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                    stage_chunk(tp, blo, bhi, c0, cn, s_tpl, bx);
-                    search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-                }
-            }
-            staged = -1;
-        }
-        store_queries(q, nk, nnq, d2q);
-        __syncthreads();
-        unsigned long long v = 0ull;
-        for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) v += (unsigned long long)fixq(d2q[i], FIX_SHIFT_D2);
-        v = wave_sum_u64(v);
+        const unsigned long long v = wave_sum_u64(slice_fitness(tpl_ref(tpl, tlo, thi, c.tpl_off), c, grids, T, src0 + c.src_off + q0, nq,
+                                                                nn + c.src_off + q0, d2buf + c.src_off + q0, s_tpl, bx, staged, &s_flag));
         if (lane == 0 && v) atomicAdd(&accf[wk.cluster], v);
     }
 }
@@ -1072,6 +1026,33 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_persist(int n_work, int ma
 // integer sums), so the results are bit-identical; what disappears are the ~2 launches per
 // iteration, the global moment atomics, the host completion polls and the under-filled tail.
 // ---------------------------------------------------------------------------------------
+// The search of one pass of k_icp_cluster, in two steps (the iteration pass times them apart).  First the near queries - seed
+// ball at most rmax wide, none unless the resident template has a cell table (grid_ok) -, a lane each, by the walk of the grid
+// cells the ball touches; returns whether this lane's query was one.
+__device__ __forceinline__ bool search_near(const float4* s_tpl, const unsigned short* s_cs, const IcpGrid& g, bool grid_ok, float rmax,
+                                            int gpad, QueryRegs& q, int nk) {
+    float rr = 0.f;
+    bool near = false;
+    if ((int)(threadIdx.x & 63) < nk && grid_ok) { rr = __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f); near = rr <= rmax; }
+    if (ballot64(near)) grid_search(s_tpl, s_cs, g, near, rr, q, gpad);
+    return near;
+}
+// Then the rest, a wave per query, over the run boxes of the resident image; a template of more than ICPT_TPL_LDS points has no
+// near queries and is searched ICPT_TPL_LDS points at a time.
+__device__ __forceinline__ void search_rest(const TplRef& t, int m, bool near, QueryRegs& q, int nk, float4* s_tpl, RunBoxes& bx,
+                                            int& staged) {
+    const int lane = threadIdx.x & 63;
+    if (m <= ICPT_TPL_LDS) {
+#ifdef CD_STATS
+        { const unsigned long long nb_ = ballot64(near); if (lane == 0) { atomicAdd(&g_icp_stats[0], (unsigned long long)nk); atomicAdd(&g_icp_stats[3], (unsigned long long)__popcll(nb_)); } }
+#endif
+        search_chunk(s_tpl, bx, 0, m, q, ballot64(lane < nk && !near));
+    } else {
+        search_fixed_chunks(t, m, q, nk, s_tpl, bx);
+        staged = -1;
+    }
+}
+
 __device__ __forceinline__ void block_sum16(unsigned long long (&S)[16], unsigned long long (*s_part)[16],
                                             unsigned long long* s_tot) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1121,9 +1102,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
         const int k = order[item];
         const IcpCluster c = cl[k];
         if (st[2 * (size_t)k].done) continue;            // host pre-marked (too few points / no template)
-        const float4* tp = tpl + c.tpl_off;
-        const float4* blo = tlo + c.tpl_off / ICP_SUB;
-        const float4* bhi = thi + c.tpl_off / ICP_SUB;
+        const TplRef tr = tpl_ref(tpl, tlo, thi, c.tpl_off);
+        const float4* tp = tr.p;
         const bool resident = c.tpl_m <= ICPT_TPL_LDS;
         const IcpGrid g = grids[c.slot];
         const bool grid_ok = resident && g.ncell > 0;
@@ -1132,7 +1112,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
         if (resident && staged != c.tpl_off) {
             __syncthreads();
             if (grid_ok) for (int i = threadIdx.x; i <= g.ncell; i += ICPT_THREADS) s_cs[i] = tcell[g.cell_off + i];
-            stage_chunk(tp, blo, bhi, 0, c.tpl_m, s_tpl, bx);
+            stage_chunk(tp, tr.lo, tr.hi, 0, c.tpl_m, s_tpl, bx);
             staged = c.tpl_off;
         }
         float4* pts = src + c.src_off;
@@ -1180,26 +1160,10 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     q.poi = __float_as_int(tp[q.pbi].w);
                 }
                 CD_PHASE(0)
-                if (resident) {
-                    // near queries: lane-per-query walk of the grid cells their seed ball touches; the rest: wave-per-query
-                    float rr = 0.f;
-                    bool near = false;
-                    if (lane < nk && grid_ok) { rr = __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f); near = rr <= rmax; }
-                    if (ballot64(near)) grid_search(s_tpl, s_cs, g, near, rr, q, gpad);
-                    CD_PHASE(1)
-#ifdef CD_STATS
-                    { const unsigned long long nb_ = ballot64(near); if (lane == 0) { atomicAdd(&g_icp_stats[0], (unsigned long long)nk); atomicAdd(&g_icp_stats[3], (unsigned long long)__popcll(nb_)); } }
-#endif
-                    search_chunk(s_tpl, bx, 0, c.tpl_m, q, ballot64(lane < nk && !near));
-                    CD_PHASE(2)
-                } else {
-                    for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                        const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                        stage_chunk(tp, blo, bhi, c0, cn, s_tpl, bx);
-                        search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-                    }
-                    staged = -1;
-                }
+                const bool near = search_near(s_tpl, s_cs, g, grid_ok, rmax, gpad, q, nk);
+                CD_PHASE(1)
+                search_rest(tr, c.tpl_m, near, q, nk, s_tpl, bx, staged);
+                CD_PHASE(2)
                 if constexpr (BOUNDED) nv += (uint32_t)__popcll(ballot64(lane < nk && q.pbest <= bnd.d2_max));
                 if (lane < nk) {
                     nnq[myq] = q.pbi;
@@ -1252,24 +1216,8 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     q.pbest = seed_bound(dist2(q.px, q.py, q.pz, q0p.x, q0p.y, q0p.z));
                     q.poi = __float_as_int(q0p.w);
                 }
-                if (resident) {
-                    // near queries: lane-per-query walk of the grid cells their seed ball touches; the rest: wave-per-query
-                    float rr = 0.f;
-                    bool near = false;
-                    if (lane < nk && grid_ok) { rr = __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f); near = rr <= rmax; }
-                    if (ballot64(near)) grid_search(s_tpl, s_cs, g, near, rr, q, gpad);
-#ifdef CD_STATS
-                    { const unsigned long long nb_ = ballot64(near); if (lane == 0) { atomicAdd(&g_icp_stats[0], (unsigned long long)nk); atomicAdd(&g_icp_stats[3], (unsigned long long)__popcll(nb_)); } }
-#endif
-                    search_chunk(s_tpl, bx, 0, c.tpl_m, q, ballot64(lane < nk && !near));
-                } else {
-                    for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                        const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                        stage_chunk(tp, blo, bhi, c0, cn, s_tpl, bx);
-                        search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-                    }
-                    staged = -1;
-                }
+                const bool near = search_near(s_tpl, s_cs, g, grid_ok, rmax, gpad, q, nk);
+                search_rest(tr, c.tpl_m, near, q, nk, s_tpl, bx, staged);
                 if (lane < nk) S[0] += (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
             }
             block_sum16(S, s_part, s_tot);
@@ -1885,35 +1833,10 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_fitness(const IcpWork* __r
     for (int k = 0; k < 12; ++k) T[k] = s_T[k];
     const int q0 = wk.tile * qslice;
     const int nq = min(qslice, c.n - q0);
-    int* nnq = nn + c.src_off + q0;
-    float* d2q = d2buf + c.src_off + q0;
-    {
-        const float4* tp = tpl + c.tpl_off;
-        QueryRegs q;
-        RunBoxes bx;
-        int nk;
-        fetch_queries(tp, c.tpl_m, src0 + c.src_off + q0, nq, true, false, true, T, nnq, q, nk);
-        const IcpGrid& g = grids[c.slot];
-        if (c.tpl_m > ICPT_TPL_LDS && g.nchunk > 0) {
-            for (int ci = 0; ci < g.nchunk; ++ci) {
-                bool any;
-                const unsigned long long todo = chunk_needed(g, ci, q, nk, &s_flag, &any);
-                if (!any) continue;
-                stage_chunk(tp, tlo + c.tpl_off / ICP_SUB, thi + c.tpl_off / ICP_SUB, g.chunk_start[ci], g.chunk_n[ci], s_tpl, bx);
-                search_chunk(s_tpl, bx, g.chunk_start[ci], g.chunk_n[ci], q, todo);
-            }
-        } else {
-            for (int c0 = 0; c0 < c.tpl_m; c0 += ICPT_TPL_LDS) {
-                const int cn = min(ICPT_TPL_LDS, c.tpl_m - c0);
-                stage_chunk(tp, tlo + c.tpl_off / ICP_SUB, thi + c.tpl_off / ICP_SUB, c0, cn, s_tpl, bx);
-                search_chunk(s_tpl, bx, c0, cn, q, lanes_below(nk));
-            }
-        }
-        store_queries(q, nk, nnq, d2q);
-    }
-    __syncthreads();
-    unsigned long long v = 0ull;
-    for (int i = threadIdx.x; i < nq; i += ICPT_THREADS) v += (unsigned long long)fixq(d2q[i], FIX_SHIFT_D2);
+    RunBoxes bx;
+    int staged = -1;   // one item per workgroup: nothing is resident yet
+    const unsigned long long v = slice_fitness(tpl_ref(tpl, tlo, thi, c.tpl_off), c, grids, T, src0 + c.src_off + q0, nq, nn + c.src_off + q0,
+                                               d2buf + c.src_off + q0, s_tpl, bx, staged, &s_flag);
     if ((threadIdx.x & ~63) < nq) {
         const unsigned long long t = wave_sum_u64(v);
         if ((threadIdx.x & 63) == 0) atomicAdd(&s_acc, t);

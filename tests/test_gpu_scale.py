@@ -1,5 +1,6 @@
 """GPU tests at BASELINE.json's larger sizes, through size-independent properties plus one
 oracle comparison at 1 M points (config 5's frame size)."""
+import functools
 import os
 
 import numpy as np
@@ -349,6 +350,84 @@ def test_template_sizes_at_the_kernel_limits(O, m, mode, monkeypatch):
                 assert a.iterations == b.iterations and list(a.T) == list(b.T) and a.fitness == b.fitness, (m, mode, f, k)
     finally:
         ctx.close()
+
+
+_STAGED_ENV_KEYS = ("CUBOID_ICP_LATTICE", "CUBOID_ICP_MODE", "CUBOID_ICP_PERSIST", "CUBOID_ICP_MAX_WG")
+_STAGED_MODES = [("sliced", {"CUBOID_ICP_LATTICE": "0", "CUBOID_ICP_MODE": "sliced"}),
+                 ("sliced-multi", {"CUBOID_ICP_LATTICE": "0", "CUBOID_ICP_MODE": "sliced", "CUBOID_ICP_PERSIST": "0"}),
+                 ("cluster", {"CUBOID_ICP_LATTICE": "0", "CUBOID_ICP_MODE": "cluster"}),
+                 # two workgroups for all the clusters: each one meets every template, in turn
+                 ("cluster-2wg", {"CUBOID_ICP_LATTICE": "0", "CUBOID_ICP_MODE": "cluster", "CUBOID_ICP_MAX_WG": "2"})]
+
+
+@functools.lru_cache(maxsize=None)
+def _mixed_templates_case(which, pair):
+    """(templates by slot, frames, oracle results [slot][frame]) - computed once per case, read only"""
+    from conftest import GOLDEN
+    from oracle import oracle_py as O
+    from perception_amd import pcd
+    if which == "chunk_table_10700":
+        big = templates.template_xyz32(length=0.2, width=0.1, height=0.075, density=0.002)
+        assert len(big) == 10700
+    else:
+        dense = templates.template_xyz32(length=0.2, width=0.1, height=0.03, density=0.0006)
+        big = np.ascontiguousarray(dense[np.sort(np.random.default_rng(65536).choice(len(dense), 65536, replace=False))])
+    tpls = (templates.template_xyz32(**templates.DEFAULT_TEMPLATE),
+            pcd.read_xyz(os.path.join(GOLDEN, "eraser_ascii.pcd")).astype(np.float32), big)
+    assert len(tpls[0]) <= 7552 and len(tpls[1]) <= 7552 < len(tpls[2])
+    frames = np.stack([synth.frame(i) for i in pair], 0)
+    prm = capi.default_params()
+    per = []
+    for slot, t in enumerate(tpls):
+        prm.template_slot = slot
+        per.append([O.process_frame(frames[f], prm, t)["result"] for f in range(len(frames))])
+    return tpls, frames, per
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", [(4, 5), (0, 7)], ids=["18_problems", "6_problems"])
+@pytest.mark.parametrize("which", ["chunk_table_10700", "fixed_chunks_65536"])
+def test_resident_and_chunked_templates_in_one_launch(which, pair, monkeypatch):
+    """The LDS image a workgroup keeps between work items (`staged`, k_icp.hip) across templates of different kinds in ONE
+    launch: the default template and a scanned one (both LDS-resident) and a third that is searched chunk by chunk - by its
+    chunk table (10 700 points) or, with the table empty (65 536 points: more than 12 k-d subtrees of at most 7552), in fixed
+    chunks - template_slot = -1, so every cluster meets all three.  A chunked walk must leave "nothing resident" behind, or
+    the next work item against the template that was resident before it searches the big template's last chunk.  Frames 4
+    and 5 give 18 ICP problems in ~400 slices, more than there are workgroups: the multi-launch kernels take several slices
+    each, and the whole-cluster launch capped at two workgroups takes the clusters largest first, i.e. with the templates
+    interleaved (a k_icp_cluster that forgets the reset fails here).  The sliced work list is template by template, so there
+    a workgroup goes from one resident template to the other and on to the chunked one, never back.  Frames 0 and 7 give 6
+    problems, few enough for the persistent sliced launch.  The record reports the best template per cluster: it equals the
+    oracle's result for that template (order-free integer sums: no tolerance), and every mode gives the same bytes."""
+    tpls, frames, per = _mixed_templates_case(which, pair)
+    prm = capi.default_params()
+    prm.template_slot = -1
+    recs = {}
+    for name, env in _STAGED_MODES:
+        for k in _STAGED_ENV_KEYS:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        ctx = capi.Context(max_points=frames.shape[1], max_frames=len(frames))
+        for k in _STAGED_ENV_KEYS:
+            monkeypatch.delenv(k, raising=False)
+        try:
+            for slot, t in enumerate(tpls):
+                ctx.set_template(slot, t)
+            res, _, _ = ctx.process_batch(frames, prm)
+            recs[name] = capi.results_to_array(res).copy()
+        finally:
+            ctx.close()
+        for f in range(len(frames)):
+            assert res[f].n_clusters == per[0][f].n_clusters > 0, (name, f)
+            for k in range(min(res[f].n_clusters, capi.CD_MAX_CLUSTERS_PER_FRAME)):
+                want = min(range(3), key=lambda s_: (per[s_][f].clusters[k].fitness, s_))
+                a, b = res[f].clusters[k], per[want][f].clusters[k]
+                assert a.template_slot == want, (name, f, k)
+                assert (a.size, a.iterations, a.converged, a.accepted) == (b.size, b.iterations, b.converged, b.accepted), (name, f, k)
+                assert list(a.T) == list(b.T) and a.fitness == b.fitness, (name, f, k)
+    for name in recs:
+        assert np.array_equal(recs[name], recs["sliced"]), name
 
 
 def _hard_geometry_cases(template):
