@@ -20,6 +20,8 @@ constexpr int RADIX = 1 << RADIX_BITS;
 #endif
 constexpr int SORT_BLOCK = CD_SORT_BLOCK;           // the sort's tiles are 4x larger than the ordered tiles of the other stages: a
 constexpr int SORT_TILE = SORT_BLOCK * ITEMS;   // (digit, tile) run of the scatter is then ~32 pairs = full 128-B lines
+constexpr int RUN_SHIFT = 20;              // a voxel run's record: start | length << RUN_SHIFT (k_crop_runs, k_voxel_runs); start < 2^20, length <= 64
+constexpr uint32_t RUN_START_MASK = (1u << RUN_SHIFT) - 1u;
 constexpr int KICP = CD_MAX_CLUSTERS_PER_FRAME;  // clusters per frame that get ICP
 constexpr int FIX_SHIFT = 32;              // canonical rule C4
 constexpr int FIX_SHIFT_D2 = 36;

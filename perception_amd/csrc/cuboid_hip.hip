@@ -443,7 +443,7 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
     }
     // Round 4: the single-pass crop also writes the RUNS (one record per run of equal cell key inside a row of 64 input points)
     // and their digit histograms, and the sort runs on the packed cell keys themselves (k_crop_runs, k_voxel.hip)
-    bool crop_runs = kp.enabled && c->crop_runs && c->voxel_runs && c->N <= (1 << 20);
+    bool crop_runs = kp.enabled && c->crop_runs && c->voxel_runs && c->N <= (1 << RUN_SHIFT);
     // 16-byte records x y z rgb (the D435 driver's layout): k_crop_runs leaves the kept points where they are and the centroid
     // kernel reads the input (0.5 GB less written and the same bytes read per 256-frame batch); any other layout is copied
     const bool direct_pts = c->crop_direct && stride == 16 && (rgb_off == 12 || rgb_off < 0) && (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0;
@@ -498,7 +498,7 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
     // By runs (default): the sort moves one element per run of equal voxel index among the cropped points - they are in image
     // order, 2.4 points per run on the bench frames - and the centroid kernel reads the runs' points contiguously; the bound
     // on the tiles is the point count (the run count is only known on the device).  CUBOID_VOXEL_RUNS=0: sort the points.
-    const bool by_runs = c->voxel_runs && npass > 0 && c->N <= (1 << 20);   // (a run's start takes 20 bits of its payload)
+    const bool by_runs = c->voxel_runs && npass > 0 && c->N <= (1 << RUN_SHIFT);   // (a run's start takes RUN_SHIFT bits of its payload)
     int Tc_runs = Tc;
     uint32_t* const key[2] = {c->d_key[0], c->d_key[1]}, * const val[2] = {c->d_val[0], c->d_val[1]};
     if (crop_runs) {

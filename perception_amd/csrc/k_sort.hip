@@ -252,9 +252,8 @@ int launch_radix_sort(hipStream_t s, uint32_t* const key[2], uint32_t* const val
 // elements to move; the centroid kernel then reads each run's points contiguously (k_voxel_centroid_runs).
 // k_voxel_runs: one pass over the keys of an ordered tile - voxel index (from the absolute coordinate fields of a single-pass
 // crop), run heads (a run also ends at every multiple of 64, so its length is known inside the row), (voxel index, start |
-// length << 20) written at the frame's running run count (chained scan over the tiles), n_runs, and the digit histograms of
+// length << RUN_SHIFT) written at the frame's running run count (chained scan over the tiles), n_runs, and the digit histograms of
 // all sort passes over the run keys (what k_radix_ghist does for a sort of the points).
-constexpr int RUN_SHIFT = 20;   // start < 2^20 (CD_MAX_POINTS), length <= 64
 __global__ void __launch_bounds__(SORT_BLOCK) k_voxel_runs(const uint32_t* __restrict__ kin, int N, int T, int Tact, int npass,
                                                            FrameState* __restrict__ fs, uint32_t* __restrict__ ghist,
                                                            int* __restrict__ state, uint32_t* __restrict__ kout,

@@ -46,6 +46,54 @@ __device__ __forceinline__ bool crop_keep(float x, float y, float z, const CropL
     return fin && z >= L.zlo && z <= L.zhi && x >= L.xlo && x <= L.xhi;
 }
 
+// Bounding box of the kept points (what VoxelGrid's getMinMax3D finds): per lane, then per wave (s_mn[w] / s_mx[w] of the
+// caller), then - thread 0, after the caller's barrier - per tile, merged into the frame's ordered-uint min / max.
+struct CropBox {
+    float mn[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f};
+    float mx[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+    __device__ __forceinline__ void add(float x, float y, float z) {
+        mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
+        mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
+    }
+    __device__ __forceinline__ void reduce_wave(float (&s_mn)[3], float (&s_mx)[3], int lane) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
+                mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
+            }
+        }
+        if (lane == 0) {
+            for (int a = 0; a < 3; ++a) { s_mn[a] = mn[a]; s_mx[a] = mx[a]; }
+        }
+    }
+    // tot: the tile's kept points (a tile that kept nothing leaves the frame's box alone: its waves' boxes are still +-max)
+    static __device__ __forceinline__ void commit(FrameState& s, const float (&s_mn)[WAVES_PER_BLOCK][3],
+                                                  const float (&s_mx)[WAVES_PER_BLOCK][3], int tot) {
+        if (tot <= 0) return;
+        for (int a = 0; a < 3; ++a) {
+            float lo = s_mn[0][a], hi = s_mx[0][a];
+            for (int k = 1; k < WAVES_PER_BLOCK; ++k) { lo = fminf(lo, s_mn[k][a]); hi = fmaxf(hi, s_mx[k][a]); }
+            atomicMin(&s.mn[a], f2ord(lo));
+            atomicMax(&s.mx[a], f2ord(hi));
+        }
+    }
+};
+
+// Packed cell key of a kept point: x | y << bi | z << (bi + bj), absolute cell coordinates less the field's low end.  x and z
+// are bounded by the crop; fits = the (unbounded) y cell lies in its field - where it does not, the caller flags crop_overflow
+// and the batch is redone in two passes.
+__device__ __forceinline__ uint32_t packed_cell_key(float x, float y, float z, float inv, const KeyPack& kp, bool* fits) {
+    const float jlo = (float)kp.jlo, jhi = (float)(kp.jlo + ((1 << kp.bj) - 1));
+    const float fy = floorf(__fmul_rn(y, inv));
+    *fits = fy >= jlo && fy <= jhi;
+    const uint32_t ui = (uint32_t)((int)floorf(__fmul_rn(x, inv)) - kp.ilo);
+    const uint32_t uj = *fits ? (uint32_t)((int)fy - kp.jlo) : 0u;
+    const uint32_t uk = (uint32_t)((int)floorf(__fmul_rn(z, inv)) - kp.klo);
+    return ui | (uj << kp.bi) | (uk << (kp.bi + kp.bj));
+}
+
 // ---- pass A: survivors per tile + min/max of the survivors ---------------------------
 __global__ void __launch_bounds__(BLOCK) k_crop_count(const char* __restrict__ in, size_t stride, int N, int rgb_off,
                                                       CropLimits lim, int T, FrameState* __restrict__ fs,
@@ -57,8 +105,7 @@ __global__ void __launch_bounds__(BLOCK) k_crop_count(const char* __restrict__ i
     const size_t fbase = (size_t)f * N;
     const int base = tile * TILE + w * WAVE_SPAN;
     int cnt = 0;
-    float mn[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f};
-    float mx[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+    CropBox box;
     float qx[ITEMS], qy[ITEMS], qz[ITEMS];
     uint32_t qc[ITEMS];
     load_rows<ITEMS>(in, stride, fbase, base + lane, N, rgb_off, qx, qy, qz, qc);
@@ -67,40 +114,19 @@ __global__ void __launch_bounds__(BLOCK) k_crop_count(const char* __restrict__ i
         const int e = base + j * WAVE + lane;
         bool keep = false;
         if (e < N) {
-            const float x = qx[j], y = qy[j], z = qz[j];
-            keep = crop_keep(x, y, z, lim);
-            if (keep) {
-                mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-                mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-            }
+            keep = crop_keep(qx[j], qy[j], qz[j], lim);
+            if (keep) box.add(qx[j], qy[j], qz[j]);
         }
         cnt += __popcll(__ballot(keep));
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-    }
-    if (lane == 0) {
-        s_cnt[w] = cnt;
-        for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
-    }
+    box.reduce_wave(s_mn[w], s_mx[w], lane);
+    if (lane == 0) s_cnt[w] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
         int tot = 0;
         for (int k = 0; k < WAVES_PER_BLOCK; ++k) tot += s_cnt[k];
         tile_cnt[(size_t)f * T + tile] = tot;
-        if (tot > 0) {
-            for (int a = 0; a < 3; ++a) {
-                float lo = s_mn[0][a], hi = s_mx[0][a];
-                for (int k = 1; k < WAVES_PER_BLOCK; ++k) { lo = fminf(lo, s_mn[k][a]); hi = fmaxf(hi, s_mx[k][a]); }
-                atomicMin(&fs[f].mn[a], f2ord(lo));
-                atomicMax(&fs[f].mx[a], f2ord(hi));
-            }
-        }
+        CropBox::commit(fs[f], s_mn, s_mx, tot);
     }
 }
 
@@ -267,8 +293,7 @@ __global__ void __launch_bounds__(BLOCK) k_crop_fused(const char* __restrict__ i
     uint32_t pc[ITEMS];
     uint64_t bal[ITEMS];
     int wtot = 0;
-    float mn[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f};
-    float mx[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+    CropBox box;
     load_rows<ITEMS>(in, stride, fbase, base + lane, N, rgb_off, px, py, pz, pc);
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
@@ -276,26 +301,13 @@ __global__ void __launch_bounds__(BLOCK) k_crop_fused(const char* __restrict__ i
         bool keep = false;
         if (e < N) {
             keep = crop_keep(px[j], py[j], pz[j], lim);
-            if (keep) {
-                mn[0] = fminf(mn[0], px[j]); mn[1] = fminf(mn[1], py[j]); mn[2] = fminf(mn[2], pz[j]);
-                mx[0] = fmaxf(mx[0], px[j]); mx[1] = fmaxf(mx[1], py[j]); mx[2] = fmaxf(mx[2], pz[j]);
-            }
+            if (keep) box.add(px[j], py[j], pz[j]);
         }
         bal[j] = __ballot(keep);
         wtot += __popcll(bal[j]);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-    }
-    if (lane == 0) {
-        s_cnt[w] = wtot;
-        for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
-    }
+    box.reduce_wave(s_mn[w], s_mx[w], lane);
+    if (lane == 0) s_cnt[w] = wtot;
     __syncthreads();
     if (threadIdx.x == 0) {
         int tot = 0;
@@ -303,35 +315,24 @@ __global__ void __launch_bounds__(BLOCK) k_crop_fused(const char* __restrict__ i
         const int excl = chained_scan(state + (size_t)f * T, 1, tile, tot, &fs[f].crop_overflow);
         s_excl = excl;
         if (tile == Tin - 1) fs[f].n_c = excl + tot;
-        if (tot > 0) {
-            for (int a = 0; a < 3; ++a) {
-                float lo = s_mn[0][a], hi = s_mx[0][a];
-                for (int k = 1; k < WAVES_PER_BLOCK; ++k) { lo = fminf(lo, s_mn[k][a]); hi = fmaxf(hi, s_mx[k][a]); }
-                atomicMin(&fs[f].mn[a], f2ord(lo));
-                atomicMax(&fs[f].mx[a], f2ord(hi));
-            }
-        }
+        CropBox::commit(fs[f], s_mn, s_mx, tot);
     }
     __syncthreads();
     int pos = s_excl;
     for (int k = 0; k < w; ++k) pos += s_cnt[k];
     const float inv = __fdiv_rn(1.0f, leaf);
-    const float jlo = (float)kp.jlo, jhi = (float)(kp.jlo + ((1 << kp.bj) - 1));
     const uint64_t lt = lanemask_lt();
     bool over = false;
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         if ((bal[j] >> lane) & 1ull) {
             const int r = pos + __popcll(bal[j] & lt);
-            const float fy = floorf(__fmul_rn(py[j], inv));
-            const bool fits = fy >= jlo && fy <= jhi;
+            bool fits;
+            const uint32_t key = packed_cell_key(px[j], py[j], pz[j], inv, kp, &fits);
             over = over || !fits;
-            const uint32_t ui = (uint32_t)((int)floorf(__fmul_rn(px[j], inv)) - kp.ilo);
-            const uint32_t uj = fits ? (uint32_t)((int)fy - kp.jlo) : 0u;
-            const uint32_t uk = (uint32_t)((int)floorf(__fmul_rn(pz[j], inv)) - kp.klo);
             if (r < pitch) {
                 cpt[obase + r] = make_float4(px[j], py[j], pz[j], __uint_as_float(pc[j]));
-                keys[obase + r] = ui | (uj << kp.bi) | (uk << (kp.bi + kp.bj));
+                keys[obase + r] = key;
             }
         }
         pos += __popcll(bal[j]);
@@ -346,7 +347,7 @@ __global__ void __launch_bounds__(BLOCK) k_crop_fused(const char* __restrict__ i
 // pass: two neighbouring kept points are in one voxel exactly when their packed cell keys are equal, and the packed key
 // (x | y << bi | z << (bi + bj), every field a monotone function of its coordinate) orders the voxels exactly as idx does
 // (k, then j, then i) - so the SORT can run on the packed keys themselves, whose digits are known right here.  This kernel
-// therefore writes the kept points (16 bytes each), ONE record per run - (packed key, start | length << 20), a run being
+// therefore writes the kept points (16 bytes each), ONE record per run - (packed key, start | length << RUN_SHIFT), a run being
 // consecutive kept points of one row of 64 input points with equal keys - and adds the runs' digits to the frame's four
 // histograms; which of the four digits vary at all, k_voxel_setup reads off those histograms afterwards (the y field is wide
 // because y is unbounded, but a frame's y cells span a few hundred values: digit 2 is constant unless they straddle a 512-cell
@@ -359,7 +360,6 @@ __global__ void __launch_bounds__(BLOCK) k_crop_fused(const char* __restrict__ i
 // the phases (80 registers, 6 waves); 342 with all eight loads of a wave issued together (load_rows) = 5.5 TB/s.  Fewer rows
 // per wave on more threads goes the other way (4 rows x 512 threads 427 us, 2 x 1024 966 us: half the tiles in flight each
 // time), 16 rows x 128 threads gains nothing (349), and the ticket costs 3 us.
-constexpr int RUN_SHIFT_C = 20;   // as k_sort.hip's RUN_SHIFT: start < 2^20, length <= 64
 template <bool DIRECT>
 __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in, size_t stride, int N, int pitch,
                                                      int rgb_off, CropLimits lim, int T, int Tin, float leaf, KeyPack kp,
@@ -384,13 +384,11 @@ __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in
     const size_t obase = (size_t)f * pitch;    // internal arrays
     const int base = tile * TILE + w * WAVE_SPAN;
     const float inv = __fdiv_rn(1.0f, leaf);
-    const float jlo = (float)kp.jlo, jhi = (float)(kp.jlo + ((1 << kp.bj) - 1));
     float px[ITEMS], py[ITEMS], pz[ITEMS];
     uint32_t pc[ITEMS];
     uint64_t bal[ITEMS], heads[ITEMS];
     int wtot = 0, rtot = 0;
-    float mn[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f};
-    float mx[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+    CropBox box;
     bool over = false;
     load_rows<ITEMS>(in, stride, fbase, base + lane, N, rgb_off, px, py, pz, pc);
 #pragma unroll
@@ -401,15 +399,10 @@ __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in
         if (e < N) {
             keep = crop_keep(px[j], py[j], pz[j], lim);
             if (keep) {
-                mn[0] = fminf(mn[0], px[j]); mn[1] = fminf(mn[1], py[j]); mn[2] = fminf(mn[2], pz[j]);
-                mx[0] = fmaxf(mx[0], px[j]); mx[1] = fmaxf(mx[1], py[j]); mx[2] = fmaxf(mx[2], pz[j]);
-                const float fy = floorf(__fmul_rn(py[j], inv));
-                const bool fits = fy >= jlo && fy <= jhi;
+                box.add(px[j], py[j], pz[j]);
+                bool fits;
+                key = packed_cell_key(px[j], py[j], pz[j], inv, kp, &fits);
                 over = over || !fits;
-                const uint32_t ui = (uint32_t)((int)floorf(__fmul_rn(px[j], inv)) - kp.ilo);
-                const uint32_t uj = fits ? (uint32_t)((int)fy - kp.jlo) : 0u;
-                const uint32_t uk = (uint32_t)((int)floorf(__fmul_rn(pz[j], inv)) - kp.klo);
-                key = ui | (uj << kp.bi) | (uk << (kp.bi + kp.bj));
             }
         }
         bal[j] = __ballot(keep);
@@ -421,18 +414,8 @@ __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in
         wtot += __popcll(bal[j]);
         rtot += __popcll(heads[j]);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-    }
-    if (lane == 0) {
-        s_cnt[w] = wtot; s_rcnt[w] = rtot;
-        for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
-    }
+    box.reduce_wave(s_mn[w], s_mx[w], lane);
+    if (lane == 0) { s_cnt[w] = wtot; s_rcnt[w] = rtot; }
     __syncthreads();
     if (threadIdx.x == 0) {
         int tot = 0, rt = 0;
@@ -441,14 +424,7 @@ __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in
         chained_scan2(state + (size_t)f * T, tile, tot, rt, &excl, &rexcl, &fs[f].crop_overflow);
         s_excl = excl; s_rexcl = rexcl;
         if (tile == Tin - 1) { fs[f].n_c = excl + tot; fs[f].n_runs = rexcl + rt; }
-        if (tot > 0) {
-            for (int a = 0; a < 3; ++a) {
-                float lo = s_mn[0][a], hi = s_mx[0][a];
-                for (int k = 1; k < WAVES_PER_BLOCK; ++k) { lo = fminf(lo, s_mn[k][a]); hi = fmaxf(hi, s_mx[k][a]); }
-                atomicMin(&fs[f].mn[a], f2ord(lo));
-                atomicMax(&fs[f].mx[a], f2ord(hi));
-            }
-        }
+        CropBox::commit(fs[f], s_mn, s_mx, tot);
     }
     __syncthreads();
     const int rexcl0 = s_rexcl;
@@ -470,7 +446,7 @@ __global__ void __launch_bounds__(BLOCK) k_crop_runs(const char* __restrict__ in
             s_rk[ro - rexcl0] = (unsigned short)(w * WAVE_SPAN + j * WAVE + lane);
             if (ro < pitch && CD_IN_RANGE(ro >= 0, 5u)) {
                 rkeys[obase + ro] = key;
-                rvals[obase + ro] = (uint32_t)(DIRECT ? base + j * WAVE + lane : r) | ((uint32_t)(next - lane) << RUN_SHIFT_C);
+                rvals[obase + ro] = (uint32_t)(DIRECT ? base + j * WAVE + lane : r) | ((uint32_t)(next - lane) << RUN_SHIFT);
             }
         }
         pos += __popcll(bal[j]);
@@ -543,24 +519,15 @@ __device__ __forceinline__ int quad_bcast_i(int v) {
     return __builtin_amdgcn_update_dpp(0, v, I | (I << 2) | (I << 4) | (I << 6), 0xf, 0xf, true);
 }
 
-__global__ void __launch_bounds__(BLOCK) k_voxel_centroid(const uint32_t* __restrict__ keys,
-                                                          const uint32_t* __restrict__ vals,
-                                                          const float4* __restrict__ cpt, int N, int T, int Tact, int rgb_on,
-                                                          FrameState* __restrict__ fs, int* __restrict__ state,
-                                                          float4* __restrict__ vox, int* __restrict__ ticket) {
-    CD_FRONT_PRIO();
-    __shared__ int s_cnt[WAVES_PER_BLOCK];
-    __shared__ int s_head[TILE];     // sorted positions of the voxel heads of this tile, in order
-    __shared__ int s_out0, s_ticket;
-    // workgroup b works on frame b % F and takes its tile by ticket (see k_crop_fused): the position of a tile's first voxel in
-    // the frame's output comes from a chained scan of the tiles' head counts, so the heads are found once (no count pass + scan)
-    const int F = gridDim.x / Tact;
-    const int f = blockIdx.x % F, tile = take_ticket(ticket + f * TICKET_PITCH, Tact, &s_ticket), w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = fs[f].n_c;
-    if (tile * TILE >= n) return;
-    const size_t fbase = (size_t)f * N;
-    const uint32_t* k = keys + fbase;
-    const uint32_t* v = vals + fbase;
+// ---- what the three centroid kernels share ------------------------------------------------
+// The voxel heads of a tile of the sorted keys k[0, n) (per point, or per run): their sorted positions, in order, in s_head;
+// the waves' head counts in s_cnt; the position of the tile's first voxel in the frame's output from a chained scan of the
+// tiles' head counts (state: the frame's row), so the heads are found once (no count pass + scan); the frame's n_v from the
+// last tile.  Two barriers; every thread of the workgroup calls it.
+struct TileHeads { int nheads, out0; };
+__device__ __forceinline__ TileHeads tile_voxel_heads(const uint32_t* k, int n, int tile, int* state, FrameState& s,
+                                                      int (&s_cnt)[WAVES_PER_BLOCK], int (&s_head)[TILE], int& s_out0) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int base = tile * TILE + w * WAVE_SPAN;
     uint64_t bal[ITEMS];
     int wtot = 0;
@@ -572,9 +539,9 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid(const uint32_t* __rest
     int pos = 0, nheads = 0;
     for (int q = 0; q < WAVES_PER_BLOCK; ++q) { if (q < w) pos += s_cnt[q]; nheads += s_cnt[q]; }
     if (threadIdx.x == 0) {
-        const int excl = chained_scan(state + (size_t)f * T, 1, tile, nheads, &fs[f].scan_stalled);
+        const int excl = chained_scan(state, 1, tile, nheads, &s.scan_stalled);
         s_out0 = excl;
-        if ((tile + 1) * TILE >= n) fs[f].n_v = excl + nheads;
+        if ((tile + 1) * TILE >= n) s.n_v = excl + nheads;
     }
     const uint64_t lt = lanemask_lt();
 #pragma unroll
@@ -583,7 +550,61 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid(const uint32_t* __rest
         pos += __popcll(bal[j]);
     }
     __syncthreads();
-    const int out0 = s_out0;
+    return {nheads, s_out0};
+}
+
+// Colour: exact integer channel sums (v_dot4_u32_u8: one instruction per channel) converted once - equal to PCL's float
+// sums as long as every partial sum is below 2^24, i.e. for voxels of at most 65 536 points; a larger voxel (a fifth of a
+// 640 x 480 frame in one 5 mm cell) is re-summed in float by rgb_replay.
+__device__ __forceinline__ void rgb_add(uint32_t u, uint32_t& ir, uint32_t& ig, uint32_t& ib) {
+    ir = __builtin_amdgcn_udot4(u, 0x00010000u, ir, false);
+    ig = __builtin_amdgcn_udot4(u, 0x00000100u, ig, false);
+    ib = __builtin_amdgcn_udot4(u, 0x00000001u, ib, false);
+}
+// partial sums beyond 2^24 round in PCL's float accumulation: replay it over the voxel's run records k / v [e0, ...) of key `key`
+__device__ __forceinline__ void rgb_replay(const uint32_t* k, const uint32_t* v, const float4* pts,
+                                           int e0, int n, uint32_t key, float& cr, float& cg, float& cb) {
+    cr = cg = cb = 0.f;
+    for (int e = e0; e < n && k[e] == key; ++e) {
+        const uint32_t r = v[e];
+        const int st = (int)(r & RUN_START_MASK), ln = (int)(r >> RUN_SHIFT);
+        for (int i = 0; i < ln; ++i) {
+            const uint32_t u = __float_as_uint(pts[st + i].w);
+            cr += (float)((u >> 16) & 0xff); cg += (float)((u >> 8) & 0xff); cb += (float)(u & 0xff);
+        }
+    }
+}
+// one division by the float count; rgb re-packed from the three averaged channels
+__device__ __forceinline__ void store_centroid(float4* vox_slot, float sx, float sy, float sz, float cr, float cg, float cb,
+                                               int cnt, int rgb_on) {
+    const float c = (float)cnt;
+    uint32_t packed = 0;
+    if (rgb_on) {
+        const int R = (int)__fdiv_rn(cr, c), G = (int)__fdiv_rn(cg, c), B = (int)__fdiv_rn(cb, c);
+        packed = ((uint32_t)R << 16) | ((uint32_t)G << 8) | (uint32_t)B;
+    }
+    *vox_slot = make_float4(__fdiv_rn(sx, c), __fdiv_rn(sy, c), __fdiv_rn(sz, c), __uint_as_float(packed));
+}
+
+__global__ void __launch_bounds__(BLOCK) k_voxel_centroid(const uint32_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ vals,
+                                                          const float4* __restrict__ cpt, int N, int T, int Tact, int rgb_on,
+                                                          FrameState* __restrict__ fs, int* __restrict__ state,
+                                                          float4* __restrict__ vox, int* __restrict__ ticket) {
+    CD_FRONT_PRIO();
+    __shared__ int s_cnt[WAVES_PER_BLOCK];
+    __shared__ int s_head[TILE];     // sorted positions of the voxel heads of this tile, in order
+    __shared__ int s_out0, s_ticket;
+    // workgroup b works on frame b % F and takes its tile by ticket (see k_crop_fused)
+    const int F = gridDim.x / Tact;
+    const int f = blockIdx.x % F, tile = take_ticket(ticket + f * TICKET_PITCH, Tact, &s_ticket);
+    const int n = fs[f].n_c;
+    if (tile * TILE >= n) return;
+    const size_t fbase = (size_t)f * N;
+    const uint32_t* k = keys + fbase;
+    const uint32_t* v = vals + fbase;
+    const TileHeads th = tile_voxel_heads(k, n, tile, state + (size_t)f * T, fs[f], s_cnt, s_head, s_out0);
+    const int nheads = th.nheads, out0 = th.out0;
     const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
     for (int h = quad; h < nheads; h += BLOCK / 4) {
         const int e0 = s_head[h];
@@ -613,19 +634,11 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid(const uint32_t* __rest
 #undef CD_ACC
             if (!m3) break;    // the run ended inside this group of four (runs are contiguous)
         }
-        if (ql == 0) {
-            const float c = (float)cnt;
-            uint32_t packed = 0;
-            if (rgb_on) {
-                const int R = (int)__fdiv_rn(cr, c), G = (int)__fdiv_rn(cg, c), B = (int)__fdiv_rn(cb, c);
-                packed = ((uint32_t)R << 16) | ((uint32_t)G << 8) | (uint32_t)B;
-            }
-            vox[fbase + out0 + h] = make_float4(__fdiv_rn(sx, c), __fdiv_rn(sy, c), __fdiv_rn(sz, c), __uint_as_float(packed));
-        }
+        if (ql == 0) store_centroid(&vox[fbase + out0 + h], sx, sy, sz, cr, cg, cb, cnt, rgb_on);
     }
 }
 
-// The same over SORTED RUNS (k_voxel_runs, k_sort.hip): keys = voxel index per run, vals = start | length << 20 of the run in the
+// The same over SORTED RUNS (k_voxel_runs, k_sort.hip): keys = voxel index per run, vals = start | length << RUN_SHIFT of the run in the
 // cropped points, which are in input order.  A voxel's runs are consecutive in the sorted order and, the sort being stable, in
 // ascending input order; inside a run the points are consecutive: the quad replays the same sequential sum, reading each run
 // as one contiguous piece instead of one 16-byte gather per point.
@@ -639,46 +652,22 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_runs(const uint32_t* _
     __shared__ int s_head[TILE];
     __shared__ int s_out0, s_ticket;
     const int F = gridDim.x / Tact;
-    const int f = blockIdx.x % F, tile = take_ticket(ticket + f * TICKET_PITCH, Tact, &s_ticket), w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f = blockIdx.x % F, tile = take_ticket(ticket + f * TICKET_PITCH, Tact, &s_ticket);
     const int n = fs[f].n_runs;
     if (tile * TILE >= n) return;
     const size_t fbase = (size_t)f * N;
     const uint32_t* k = keys + fbase;
     const uint32_t* v = vals + fbase;
     const float4* pts = cpt + (size_t)f * pts_pitch;   // (the cropped points, or - k_crop_runs' direct form - the input records themselves)
-    const int base = tile * TILE + w * WAVE_SPAN;
-    uint64_t bal[ITEMS];
-    int wtot = 0;
-    head_ballots<ITEMS>(k, base, n, bal);
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) wtot += __popcll(bal[j]);
-    if (lane == 0) s_cnt[w] = wtot;
-    __syncthreads();
-    int pos = 0, nheads = 0;
-    for (int q = 0; q < WAVES_PER_BLOCK; ++q) { if (q < w) pos += s_cnt[q]; nheads += s_cnt[q]; }
-    if (threadIdx.x == 0) {
-        const int excl = chained_scan(state + (size_t)f * T, 1, tile, nheads, &fs[f].scan_stalled);
-        s_out0 = excl;
-        if ((tile + 1) * TILE >= n) fs[f].n_v = excl + nheads;
-    }
-    const uint64_t lt = lanemask_lt();
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        if ((bal[j] >> lane) & 1ull) s_head[pos + __popcll(bal[j] & lt)] = base + j * WAVE + lane;
-        pos += __popcll(bal[j]);
-    }
-    __syncthreads();
-    const int out0 = s_out0;
+    const TileHeads th = tile_voxel_heads(k, n, tile, state + (size_t)f * T, fs[f], s_cnt, s_head, s_out0);
+    const int nheads = th.nheads, out0 = th.out0;
     const int quad = threadIdx.x >> 2, ql = threadIdx.x & 3;
     // Latency plan (round 4): a wave spent ~10 dependent memory round trips per group of 16 voxels - the voxel's key, its run
     // records, the first four points of four runs, then one more trip for EVERY run index that is longer than four points in
     // some quad (13 % of the runs are), and all of it again for the 20 % of voxels with more than four runs.  Now the first
     // four records of a voxel are fetched one voxel AHEAD and carry the key (record e0 is the voxel's first run), the next
     // four records are fetched while the current four are summed, and points 4..7 of every run go out together with points
-    // 0..3: ~2.6 round trips per group (one per four runs), the rest is the summation itself.
-    // Colour: exact integer channel sums (v_dot4_u32_u8: one instruction per channel) converted once - equal to PCL's float
-    // sums as long as every partial sum is below 2^24, i.e. for voxels of at most 65 536 points; a larger voxel (a fifth of a
-    // 640 x 480 frame in one 5 mm cell) is re-summed in float by the loop at the end.
+    // 0..3: ~2.6 round trips per group (one per four runs), the rest is the summation itself.  Colour: see rgb_add.
     int h = quad, e0 = 0;
     uint32_t kk = 0, rec = 0;
     bool have = false;
@@ -705,12 +694,7 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_runs(const uint32_t* _
         {                                                                                              \
             sx = __fadd_rn(sx, quad_bcast<J>(P.x)); sy = __fadd_rn(sy, quad_bcast<J>(P.y));            \
             sz = __fadd_rn(sz, quad_bcast<J>(P.z));                                                    \
-            if (rgb_on) {                                                                              \
-                const uint32_t u = __float_as_uint(quad_bcast<J>(P.w));                                \
-                ir = __builtin_amdgcn_udot4(u, 0x00010000u, ir, false);                                \
-                ig = __builtin_amdgcn_udot4(u, 0x00000100u, ig, false);                                \
-                ib = __builtin_amdgcn_udot4(u, 0x00000001u, ib, false);                                \
-            }                                                                                          \
+            if (rgb_on) rgb_add(__float_as_uint(quad_bcast<J>(P.w)), ir, ig, ib);                      \
         }
 #define CD_RUN(I, P, Q)                                                                                \
         if (len##I > 0) {                                                                              \
@@ -735,7 +719,7 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_runs(const uint32_t* _
         }
         for (int eb = e0;; eb += 4) {
             // lane ql of the quad holds record eb + ql (kk, rec, have)
-            const int mylen = (have && kk == key) ? (int)(rec >> 20) : 0, mystart = (int)(rec & ((1u << 20) - 1u));
+            const int mylen = (have && kk == key) ? (int)(rec >> RUN_SHIFT) : 0, mystart = (int)(rec & RUN_START_MASK);
             const int len0 = quad_bcast_i<0>(mylen), len1 = quad_bcast_i<1>(mylen), len2 = quad_bcast_i<2>(mylen), len3 = quad_bcast_i<3>(mylen);
             const int start0 = quad_bcast_i<0>(mystart), start1 = quad_bcast_i<1>(mystart), start2 = quad_bcast_i<2>(mystart), start3 = quad_bcast_i<3>(mystart);
             // the next four records, in case the voxel goes on (runs of a voxel are contiguous in the sorted order, so its
@@ -761,18 +745,8 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_runs(const uint32_t* _
 #undef CD_RUN
 #undef CD_ADD
         float cr = (float)ir, cg = (float)ig, cb = (float)ib;
-        if (rgb_on && cnt > 65536) {   // partial sums beyond 2^24 round in PCL's float accumulation: replay it
-            cr = cg = cb = 0.f;
-            for (int e = e0; e < n && k[e] == key; ++e) {
-                const uint32_t r = v[e];
-                const int st = (int)(r & ((1u << 20) - 1u)), ln = (int)(r >> 20);
-                for (int i = 0; i < ln; ++i) {
-                    const uint32_t u = __float_as_uint(pts[st + i].w);
-                    cr += (float)((u >> 16) & 0xff); cg += (float)((u >> 8) & 0xff); cb += (float)(u & 0xff);
-                }
-            }
-        }
-        if (ql == 0) {
+        if (rgb_on && cnt > 65536) rgb_replay(k, v, pts, e0, n, key, cr, cg, cb);
+        if (ql == 0) {   // store_centroid, written out: through the call this kernel comes out seven instructions longer
             const float c = (float)cnt;
             uint32_t packed = 0;
             if (rgb_on) {
@@ -810,30 +784,8 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_lanes(const uint32_t* 
     const uint32_t* k = keys + fbase;
     const uint32_t* v = vals + fbase;
     const float4* pts = cpt + (size_t)f * pts_pitch;   // (the cropped points, or - k_crop_runs' direct form - the input records themselves)
-    const int base = tile * TILE + w * WAVE_SPAN;
-    uint64_t bal[ITEMS];
-    int wtot = 0;
-    head_ballots<ITEMS>(k, base, n, bal);
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) wtot += __popcll(bal[j]);
-    if (lane == 0) s_cnt[w] = wtot;
-    __syncthreads();
-    int pos = 0, nheads = 0;
-    for (int q = 0; q < WAVES_PER_BLOCK; ++q) { if (q < w) pos += s_cnt[q]; nheads += s_cnt[q]; }
-    if (threadIdx.x == 0) {
-        const int excl = chained_scan(state + (size_t)f * T, 1, tile, nheads, &fs[f].scan_stalled);
-        s_out0 = excl;
-        if ((tile + 1) * TILE >= n) fs[f].n_v = excl + nheads;
-    }
-    const uint64_t lt = lanemask_lt();
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-        if ((bal[j] >> lane) & 1ull) s_head[pos + __popcll(bal[j] & lt)] = base + j * WAVE + lane;
-        pos += __popcll(bal[j]);
-    }
-    __syncthreads();
-    const int out0 = s_out0;
-    constexpr uint32_t START = (1u << 20) - 1u;
+    const TileHeads th = tile_voxel_heads(k, n, tile, state + (size_t)f * T, fs[f], s_cnt, s_head, s_out0);
+    const int nheads = th.nheads, out0 = th.out0;
     // a window of four run records (the voxel's runs are a prefix of it); a wave takes the tile's voxels 64 at a time, 256 apart
     // (fetching a lane's NEXT voxel's first window ahead was measured: nothing - nine registers for a round trip that is not
     // the bound)
@@ -856,9 +808,9 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_lanes(const uint32_t* 
         uint32_t ir = 0, ig = 0, ib = 0;
         while (ballot64(alive)) {
             const bool m0 = alive && wk0 == key, m1 = m0 && wk1 == key, m2 = m1 && wk2 == key, m3 = m2 && wk3 == key;
-            const int l0 = m0 ? (int)(wv0 >> 20) : 0, l1 = m1 ? (int)(wv1 >> 20) : 0, l2 = m2 ? (int)(wv2 >> 20) : 0, l3 = m3 ? (int)(wv3 >> 20) : 0;
+            const int l0 = m0 ? (int)(wv0 >> RUN_SHIFT) : 0, l1 = m1 ? (int)(wv1 >> RUN_SHIFT) : 0, l2 = m2 ? (int)(wv2 >> RUN_SHIFT) : 0, l3 = m3 ? (int)(wv3 >> RUN_SHIFT) : 0;
             const int c1 = l0, c2 = c1 + l1, c3 = c2 + l2, tot = c3 + l3;
-            const int s0 = (int)(wv0 & START), s1 = (int)(wv1 & START) - c1, s2 = (int)(wv2 & START) - c2, s3 = (int)(wv3 & START) - c3;   // (start - first flat index of the run)
+            const int s0 = (int)(wv0 & RUN_START_MASK), s1 = (int)(wv1 & RUN_START_MASK) - c1, s2 = (int)(wv2 & RUN_START_MASK) - c2, s3 = (int)(wv3 & RUN_START_MASK) - c3;   // (start - first flat index of the run)
             if (m3 && i == 0) {   // first trip of a full window: the voxel may go on
                 nk0 = nk1 = nk2 = nk3 = ~key;
                 if (e + 4 < n) { nk0 = k[e + 4]; nv0 = v[e + 4]; }
@@ -879,12 +831,7 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_lanes(const uint32_t* 
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 sx = __fadd_rn(sx, P[t].x); sy = __fadd_rn(sy, P[t].y); sz = __fadd_rn(sz, P[t].z);
-                if (rgb_on) {
-                    const uint32_t u = __float_as_uint(P[t].w);
-                    ir = __builtin_amdgcn_udot4(u, 0x00010000u, ir, false);
-                    ig = __builtin_amdgcn_udot4(u, 0x00000100u, ig, false);
-                    ib = __builtin_amdgcn_udot4(u, 0x00000001u, ib, false);
-                }
+                if (rgb_on) rgb_add(__float_as_uint(P[t].w), ir, ig, ib);
             }
             i += 8;
             if (alive && i >= tot) {   // the window is summed
@@ -896,24 +843,8 @@ __global__ void __launch_bounds__(BLOCK) k_voxel_centroid_lanes(const uint32_t* 
         }
         if (h < nheads) {
             float cr = (float)ir, cg = (float)ig, cb = (float)ib;
-            if (rgb_on && cnt > 65536) {   // partial sums beyond 2^24 round in PCL's float accumulation: replay it
-                cr = cg = cb = 0.f;
-                for (int ee = s_head[h]; ee < n && k[ee] == key; ++ee) {
-                    const uint32_t r = v[ee];
-                    const int s0 = (int)(r & START), ln = (int)(r >> 20);
-                    for (int i = 0; i < ln; ++i) {
-                        const uint32_t u = __float_as_uint(pts[s0 + i].w);
-                        cr += (float)((u >> 16) & 0xff); cg += (float)((u >> 8) & 0xff); cb += (float)(u & 0xff);
-                    }
-                }
-            }
-            const float c = (float)cnt;
-            uint32_t packed = 0;
-            if (rgb_on) {
-                const int R = (int)__fdiv_rn(cr, c), G = (int)__fdiv_rn(cg, c), B = (int)__fdiv_rn(cb, c);
-                packed = ((uint32_t)R << 16) | ((uint32_t)G << 8) | (uint32_t)B;
-            }
-            vox[fbase + out0 + h] = make_float4(__fdiv_rn(sx, c), __fdiv_rn(sy, c), __fdiv_rn(sz, c), __uint_as_float(packed));
+            if (rgb_on && cnt > 65536) rgb_replay(k, v, pts, s_head[h], n, key, cr, cg, cb);
+            store_centroid(&vox[fbase + out0 + h], sx, sy, sz, cr, cg, cb, cnt, rgb_on);
         }
     }
 }

@@ -122,10 +122,9 @@ def test_voxel_random_ragged_cloud(ctx, O):
     assert nc == nco and np.array_equal(vox.view(np.uint32), vo.view(np.uint32)) and np.array_equal(rgb, ro)
 
 
-def test_voxel_long_runs_and_a_voxel_of_70000_points(ctx, O):
-    """The centroid kernel's corners: runs longer than the eight points it fetches up front (64 neighbours in one voxel),
-    voxels of many runs (the same voxel visited again and again), and a voxel of more than 65 536 points, whose colour sums
-    pass 2^24 - there PCL's float accumulation rounds, and the kernel's integer channel sums are replayed in float."""
+def _long_runs_and_a_voxel_of_70000_points():
+    """120 000 xyz-rgb records: one 5 mm voxel of 70 000 points whose colours' sequential float sum differs from the exact
+    one, then stretches of 64 / 20 / 9 neighbours per voxel with the voxels revisited in a scrambled order."""
     rng = np.random.RandomState(11)
     n = 120000
     rec = np.zeros((n, 4), np.float32)
@@ -156,6 +155,15 @@ def test_voxel_long_runs_and_a_voxel_of_70000_points(ctx, O):
     rec[70000:, 2] = 0.7 + rng.uniform(0.0005, 0.0045, 50000)
     rec[70000:, 3] = rng.randint(0, 1 << 24, 50000).astype(np.uint32).view(np.float32)
     rec[70000:70200, :3] = rec[70000, :3]                 # one run of 64 + 64 + 64 + 8 identical neighbours
+    return rec
+
+
+def test_voxel_long_runs_and_a_voxel_of_70000_points(ctx, O):
+    """The centroid kernel's corners: runs longer than the eight points it fetches up front (64 neighbours in one voxel),
+    voxels of many runs (the same voxel visited again and again), and a voxel of more than 65 536 points, whose colour sums
+    pass 2^24 - there PCL's float accumulation rounds, and the kernel's integer channel sums are replayed in float."""
+    rec = _long_runs_and_a_voxel_of_70000_points()
+    n = len(rec)
     prm = capi.default_params()
     prm.rgb_offset = 12
     vox, rgb, nc = ctx.crop_voxel(rec, prm, want_rgb=True)
@@ -726,6 +734,152 @@ def test_voxel_stage_by_runs_and_by_points(O, frames4, path, monkeypatch):
             for f in range(2):
                 got = cx.frame_cloud(f, capi.CD_CLOUD_VOXELS, 16, -1)[:, :3].copy().view(np.float32)
                 assert res[f].n_voxels == len(want[f]) and np.array_equal(got.view(np.uint32), want[f].view(np.uint32))
+    finally:
+        cx.close()
+
+
+@pytest.fixture(scope="module")
+def shared_step_inputs(O, frames4):
+    """The smallest inputs on which a step that the crop and centroid kernels share can go wrong, each with the oracle's
+    crop_voxel result (computed once; nothing here is modified afterwards).  Entries: (name, records, colour, want) with
+    records (n, 4) xyz-rgb or, without colour, (n, 3); want = (points, rgb or None, n_cropped)."""
+    prm = capi.default_params()
+    rng = np.random.RandomState(31)
+
+    def kept(p):
+        with np.errstate(invalid="ignore"):
+            return (np.isfinite(p[:, :3]).all(1) & (p[:, 0] >= prm.crop_x_min) & (p[:, 0] <= prm.crop_x_max)
+                    & (p[:, 2] >= prm.crop_z_min) & (p[:, 2] <= prm.crop_z_max))
+
+    def in_cells(cells):
+        """One kept point, with a colour, in each of the listed 5 mm cells, in the order given.  Cell c is (c % 76, 0, c // 76) of a
+        76 x 1 x 160 block inside the crop, so voxel index and packed cell key both sort the cells by their number."""
+        cells = np.asarray(cells)
+        rec = np.zeros((len(cells), 4), np.float32)
+        centre = np.stack([(cells % 76 - 38 + 0.5) * 0.005, np.full(len(cells), 0.0025), (cells // 76 + 10 + 0.5) * 0.005], 1)
+        rec[:, :3] = centre + rng.uniform(-0.001, 0.001, (len(cells), 3))
+        rec[:, 3] = rng.randint(0, 1 << 24, len(cells)).astype(np.uint32).view(np.float32)
+        assert kept(rec).all()
+        return rec
+
+    cases = []
+    # ragged tile ends, in the crop's input tiles and in the centroid kernels' tiles of sorted keys alike: every point is kept and
+    # sits in a cell of its own, in scrambled order, so n_c = n_runs = n_v = n (the last-tile n_c / n_v writes, the early return
+    # of the tiles past n)
+    for n in (1, 63, 2047, 2048, 2049, 4097):
+        cases.append(("ragged_%d" % n, in_cells(rng.permutation(n)), True))
+    # the same with two points per cell, apart in the input: sorted keys 2047 and 2048 are one voxel, so the first element of the
+    # second tile takes its left neighbour from memory and is no head
+    pairs = (rng.permutation(4097) + 1) // 2
+    while (np.diff(pairs) == 0).any():     # (neighbours in one cell would be one run: 4097 runs, like the points)
+        pairs = (rng.permutation(4097) + 1) // 2
+    cases.append(("ragged_pairs_4097", in_cells(pairs), True))
+    # the tile's box needs its last wave (elements 1536 .. 2047): every cell on the x or z border of the block of cells sits
+    # there (a grid laid out without them gives other voxel indices), or nothing is kept before it (a box without them stays at
+    # its initial value: the extent check reports a leaf too small)
+    c = rng.permutation(2048)
+    border = (c % 76 == 0) | (c % 76 == 75) | (c < 76) | (c >= 1976)
+    assert border.sum() <= 512
+    cases.append(("box_corners_in_last_wave", in_cells(np.concatenate([c[~border], c[border]])), True))
+    late = in_cells(rng.permutation(2048))
+    late[:1536:2, :3] = np.nan
+    late[1:1536:2, 2] = np.float32(5.0)
+    assert not kept(late)[:1536].any()
+    cases.append(("kept_in_last_wave_only", late, True))
+    # three input tiles, nothing kept in the middle one (NaN, or outside the crop): no box to commit between two tiles that do
+    # commit, and a zero in the middle of the crop's scan chain; the 4096 kept points fill two centroid tiles
+    hole = in_cells(rng.permutation(3 * 2048))
+    hole[2048:3072, :3] = np.nan
+    hole[3072:4096, 0] = np.float32(5.0)
+    k = kept(hole)
+    assert k[:2048].all() and not k[2048:4096].any() and k[4096:].all()
+    cases.append(("empty_interior_tile", hole, True))
+    # 4001 runs of one point in two voxels: the second voxel's runs cross position 2048 of the sorted array, whose second tile
+    # then holds no voxel head
+    alt = np.zeros((4001, 4), np.float32)
+    alt[0::2, :3] = [0.1, 0.0, 0.4]
+    alt[1::2, :3] = [-0.1, 0.02, 0.6]
+    alt[:, :3] += rng.uniform(0, 0.004, (4001, 3)).astype(np.float32)
+    alt[:, 3] = rng.randint(0, 1 << 24, 4001).astype(np.uint32).view(np.float32)
+    cases.append(("tile_without_a_head", alt, True))
+    cases.append(("voxel_of_70000_points", _long_runs_and_a_voxel_of_70000_points(), True))
+    cases.append(("no_colour", np.ascontiguousarray(frames4[2][::7, :3]), False))
+    # y cells outside the packed field (as in test_crop_single_pass_equals_two_pass_and_y_overflow): the batch is redone in two passes
+    far = frames4[0].copy()
+    keep = np.flatnonzero(kept(far))
+    far[keep[::97], 1] = np.float32(400.0)
+    far[keep[5::101], 1] = np.float32(-300.0)
+    cases.append(("y_overflow", far, True))
+    # a frame with nothing kept (its box stays at the initial value) in a batch of two beside a normal frame
+    nothing = frames4[0].copy()
+    nothing[0::2, :3] = np.nan
+    nothing[1::2, 2] = np.float32(5.0)
+    assert not kept(nothing).any()
+    batch = np.stack([nothing, frames4[1]], 0)
+
+    def oracle(pts, colour):
+        p = capi.default_params()
+        p.rgb_offset = 12 if colour else -1
+        st, vo, ro, nco, _ = O.crop_voxel(pts, p, want_rgb=colour)
+        assert st == 0
+        return vo, (ro if colour else None), nco
+
+    return [(name, pts, colour, oracle(pts, colour)) for name, pts, colour in cases], batch, [oracle(f, True) for f in batch]
+
+
+SHARED_STEP_WAYS = {
+    "default": {},
+    "crop_copy": {"CUBOID_CROP_DIRECT": "0"},
+    "centroid_quads": {"CUBOID_CENTROID_LANES": "0"},
+    "runs_from_keys": {"CUBOID_CROP_RUNS": "0"},
+    "sort_points": {"CUBOID_VOXEL_RUNS": "0"},
+    "crop_two_pass": {"CUBOID_CROP_TWO_PASS": "1"},
+    "records_of_32_bytes": {},
+}
+
+
+@pytest.mark.parametrize("way", list(SHARED_STEP_WAYS))
+def test_shared_crop_and_centroid_steps_on_every_way(O, template, shared_step_inputs, way, monkeypatch):
+    """The crop and centroid kernels of k_voxel.hip share their steps (CropBox, packed_cell_key, tile_voxel_heads, rgb_add,
+    rgb_replay, store_centroid): every way through the stage - the default, the five plumbing switches, and 32-byte records
+    with rgb at offset 16 (never read in place) - on the inputs of shared_step_inputs, bit for bit against the oracle's
+    crop_voxel: points, rgb, n_cropped, voxel count.  The voxel of 70 000 points goes through the 16-byte ways only."""
+    for name, value in SHARED_STEP_WAYS[way].items():
+        monkeypatch.setenv(name, value)
+    wide = way == "records_of_32_bytes"
+    cases, batch, batch_want = shared_step_inputs
+
+    def records(pts):   # (..., 4) xyz-rgb -> this way's layout
+        if not wide:
+            return pts
+        rec = np.zeros(pts.shape[:-1] + (8,), np.float32)
+        rec[..., :3] = pts[..., :3]
+        rec[..., 4] = pts[..., 3]
+        return rec
+
+    def same(got, want, what):
+        vox, rgb, nc = got
+        vo, ro, nco = want
+        assert nc == nco and len(vox) == len(vo), what
+        assert np.array_equal(vox.view(np.uint32), vo.view(np.uint32)), what
+        assert ro is None or np.array_equal(rgb, ro), what
+
+    cx = capi.Context(max_points=synth.WIDTH * synth.HEIGHT, max_frames=2)
+    try:
+        prm = capi.default_params()
+        for name, pts, colour, want in cases:
+            if wide and name == "voxel_of_70000_points":
+                continue
+            prm.rgb_offset = (16 if wide else 12) if colour else -1
+            same(cx.crop_voxel(records(pts) if colour else pts, prm, want_rgb=colour), want, name)
+        prm.rgb_offset = 16 if wide else 12
+        cx.set_template(0, template)
+        res, _, _ = cx.process_batch(records(batch), prm)
+        for f in range(2):
+            cloud = cx.frame_cloud(f, capi.CD_CLOUD_VOXELS, 16, 12)
+            assert res[f].n_voxels == len(cloud)
+            same((cloud[:, :3].copy().view(np.float32), cloud[:, 3].copy(), res[f].n_cropped), batch_want[f], "batch frame %d" % f)
+        assert res[0].n_cropped == 0 and res[0].n_voxels == 0 and res[1].n_voxels > 0
     finally:
         cx.close()
 
