@@ -18,8 +18,17 @@ constexpr int RADIX = 1 << RADIX_BITS;
 #ifndef CD_SORT_BLOCK
 #define CD_SORT_BLOCK 1024
 #endif
-constexpr int SORT_BLOCK = CD_SORT_BLOCK;           // the sort's tiles are 4x larger than the ordered tiles of the other stages: a
-constexpr int SORT_TILE = SORT_BLOCK * ITEMS;   // (digit, tile) run of the scatter is then ~32 pairs = full 128-B lines
+constexpr int SORT_BLOCK = CD_SORT_BLOCK;           // tiles of k_radix_ghist and k_voxel_runs (the paths that do not start from k_crop_runs' run
+constexpr int SORT_TILE = SORT_BLOCK * ITEMS;   // records): 4x the ordered tiles of the other stages, fewer flushes of the digit histograms
+// The scatter kernel of the sort (k_radix_scatter) has a tile of its own: 512 threads x ITEMS rows = 4096 pairs, 38 KB of LDS, four
+// workgroups per CU.  Alone the bench batch's three passes take 0.158 ms against 0.168 with SORT_TILE; with other batches in flight
+// a 1024-thread, 76 KB workgroup waits for half a CU to drain and a 512-thread one finds room beside the other batches' kernels
+// (220 -> 191 us per launch; profiles/sort_tile_ab.txt).  -DCD_SCATTER_BLOCK=1024 (256): the A/B builds, make VARIANT=...
+#ifndef CD_SCATTER_BLOCK
+#define CD_SCATTER_BLOCK 512
+#endif
+constexpr int SCATTER_BLOCK = CD_SCATTER_BLOCK;
+constexpr int SCATTER_TILE = SCATTER_BLOCK * ITEMS;
 constexpr int RUN_SHIFT = 20;              // a voxel run's record: start | length << RUN_SHIFT (k_crop_runs, k_voxel_runs); start < 2^20, length <= 64
 constexpr uint32_t RUN_START_MASK = (1u << RUN_SHIFT) - 1u;
 constexpr int KICP = CD_MAX_CLUSTERS_PER_FRAME;  // clusters per frame that get ICP

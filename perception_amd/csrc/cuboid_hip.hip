@@ -65,7 +65,7 @@ struct cd_context : cd_streams {
     // point buffers (float4 = x,y,z,rgb bits)
     DevBuf<float4> d_cpt, d_vox, d_obj, d_src0, d_src;
     DevBuf<uint32_t> d_key[2], d_val[2], d_ghist;
-    DevBuf<int> d_sstate;   // chained-scan state of the radix passes, [pass][F][tiles][256]
+    DevBuf<int> d_sstate;   // chained-scan state of the radix passes, [pass][F][scatter tiles][256]
     DevBuf<unsigned long long> d_tile64;   // chained-scan state of k_crop_runs: (points, runs) per tile, [F][T]
     bool crop_runs = true;      // CUBOID_CROP_RUNS=0: the crop writes per-point keys and k_voxel_runs finds the runs (rounds 2-3)
     DevBuf<int> d_ticket;   // ticket counters, one per frame (TICKET_PITCH ints apart), of the kernels that scan over tiles (take_ticket, common.hpp): zero between launches
@@ -492,7 +492,8 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
     int max_nc = 0, max_bits = 0;
     for (int f = 0; f < F; ++f) { max_nc = std::max(max_nc, c->h_fs[f].n_c); max_bits = std::max(max_bits, c->h_fs[f].key_bits); }
     const int Tc = std::max(1, (max_nc + TILE - 1) / TILE);
-    const int Tsc = std::max(1, (max_nc + SORT_TILE - 1) / SORT_TILE);
+    const int Tsc = std::max(1, (max_nc + SORT_TILE - 1) / SORT_TILE);          // tiles of k_voxel_runs / k_radix_ghist
+    const int Tscat = std::max(1, (max_nc + SCATTER_TILE - 1) / SCATTER_TILE);   // tiles of the scatters (their own size: common.hpp)
     const int npass = (max_bits + RADIX_BITS - 1) / RADIX_BITS;
     int cur = 0;
     // By runs (default): the sort moves one element per run of equal voxel index among the cropped points - they are in image
@@ -510,13 +511,13 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
         }
         int digits[4], nd = 0;
         for (int d = 0; d < 4; ++d) if ((vary >> d) & 1) digits[nd++] = d;
-        const int Tsr = std::max(1, (max_runs + SORT_TILE - 1) / SORT_TILE);   // (the run count is known here: tighter than the point count)
+        const int Tsr = std::max(1, (max_runs + SCATTER_TILE - 1) / SCATTER_TILE);   // (the run count is known here: tighter than the point count)
         Tc_runs = std::max(1, (max_runs + TILE - 1) / TILE);
         LAUNCH(c, cur = launch_radix_scatter_runs(c->stream, key, val, c->N, F, Tsr, digits, nd, c->d_fs, c->d_ghist, c->d_sstate, c->d_ticket));
     } else if (by_runs)
-        LAUNCH(c, cur = launch_radix_sort_runs(c->stream, key, val, c->N, F, T, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, c->d_tileA, kp, c->d_ticket));
+        LAUNCH(c, cur = launch_radix_sort_runs(c->stream, key, val, c->N, F, T, Tsc, Tscat, npass, c->d_fs, c->d_ghist, c->d_sstate, c->d_tileA, kp, c->d_ticket));
     else
-        LAUNCH(c, cur = launch_radix_sort(c->stream, key, val, c->N, F, Tsc, npass, c->d_fs, c->d_ghist, c->d_sstate, kp, c->d_ticket));
+        LAUNCH(c, cur = launch_radix_sort(c->stream, key, val, c->N, F, Tsc, Tscat, npass, c->d_fs, c->d_ghist, c->d_sstate, kp, c->d_ticket));
     if (cur < 0) return fail(c, CD_ERR_DEVICE, "radix sort: the scan state could not be zeroed");
     const uint32_t* vin = c->d_val[cur];   // zero passes (empty frames only): the permutation is never read
     // voxel heads + centroids in one kernel: n_v (0 from the FrameState init for empty frames) and every tile's output
@@ -2051,7 +2052,7 @@ int cd_create(int device_id, int max_points, int max_frames, cd_context** out) {
     ok = ok && ALLOC(d_src0, FN) && ALLOC(d_src, FN);
     for (int k = 0; k < 2; ++k) ok = ok && ALLOC(d_key[k], FN) && ALLOC(d_val[k], FN);
     ok = ok && ALLOC(d_ghist, F * SORT_MAX_PASSES_HOST * RADIX);
-    ok = ok && ALLOC(d_sstate, (size_t)SORT_MAX_PASSES_HOST * F * RADIX * ((N + SORT_TILE - 1) / SORT_TILE));
+    ok = ok && ALLOC(d_sstate, (size_t)SORT_MAX_PASSES_HOST * F * RADIX * ((N + SCATTER_TILE - 1) / SCATTER_TILE));   // (per scatter tile: run and point counts are at most N)
     ok = ok && ALLOC(d_tile64, F * T);
     ok = ok && ALLOC(d_ticket, (size_t)F * TICKET_PITCH) && hipMemset(c->d_ticket, 0, sizeof(int) * (size_t)F * TICKET_PITCH) == hipSuccess;
     ok = ok && ALLOC(d_rnd, (size_t)RND_TABLE);

@@ -261,6 +261,21 @@ __device__ __forceinline__ void cl_join(const int* s_key, const int* s_val, int*
     }
 }
 
+// A frame the cell table cannot hold is clustered again by a later launch (stage_cluster_sync), but k_cluster_rank, k_label_count
+// and k_label_scatter of THIS launch still run over it, and k_label_count uses parent[i] as an index into rank_of_root.  The
+// frame's parent / csize / rank_of_root words are whatever the last frame that was clustered left there, and beyond that
+// frame's n_o whatever the allocation held: an index read from them can point anywhere.  So a kernel that gives a frame up
+// leaves it as n components of size 0 without a rank (what k_cluster_build starts from): every index the later kernels of the
+// launch read is then one that was written, and they find no cluster to label.  Call from every thread of the workgroup.
+__device__ __forceinline__ void cl_leave_frame(int* __restrict__ parent, int* __restrict__ csize, int* __restrict__ rank_of_root,
+                                               size_t fbase, int n) {
+    for (int i = threadIdx.x; i < n; i += CL_THREADS) {
+        parent[fbase + i] = i;
+        csize[fbase + i] = 0;
+        rank_of_root[fbase + i] = -1;
+    }
+}
+
 __global__ void __launch_bounds__(CL_THREADS) k_cluster_lds(const float4* __restrict__ obj, int N, FrameState* __restrict__ fs,
                                                             float inv_cell, float r2, int* __restrict__ parent,
                                                             int* __restrict__ csize, int* __restrict__ rank_of_root) {
@@ -324,6 +339,7 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_lds(const float4* __rest
     __syncthreads();
     const int ncell = s_ncell;
     if (s_bail || ncell > CL_MAX_CELLS) {     // uniform: leave the frame to the global-memory kernels
+        cl_leave_frame(parent, csize, rank_of_root, fbase, n);
         if (tid == 0) fs[f].cl_done = 0;
         return;
     }
@@ -493,7 +509,10 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_cells(const float4* __re
     }
     __syncthreads();
     const int ncell = s_ncell;
-    if (s_bail || ncell > CL_MAX_CELLS) return;   // (uniform) cl_done stays 0: the point-graph kernels take the frame
+    if (s_bail || ncell > CL_MAX_CELLS) {         // (uniform) cl_done stays 0: the point-graph kernels take the frame
+        cl_leave_frame(parent, csize, rank_of_root, fbase, n);   // (over the slot and ticket words above: every thread rewrites its own)
+        return;
+    }
     {   // exclusive scan of the slot counts: four consecutive slots per thread
         const int q = 4 * tid;
         const int c0 = s_val[q], c1 = s_val[q + 1], c2 = s_val[q + 2], c3 = s_val[q + 3];

@@ -4,20 +4,25 @@
 // std::sort on (idx, point) pairs; rule C2 makes it stable).  Single-histogram ("onesweep") organisation:
 //   ghist   : ONE pass over the keys builds the per-frame digit histograms of ALL passes (the histogram of a digit does
 //             not depend on the order of the elements)
-//   scatter : per pass and ordered tile of 8192 pairs - stable rank of each pair inside its tile with wave ballots
-//             ("match-any" over the 8 digit bits, 64-wide); the tile's bin counts go through a chained scan over the
+//   scatter : per pass and ordered tile of 4096 pairs (SCATTER_TILE, common.hpp) - stable rank of each pair inside its tile
+//             with wave ballots ("match-any" over the 8 digit bits, 64-wide); the tile's bin counts go through a chained scan over the
 //             frame's tiles (one thread per bin, common.hpp chained_scan) and give, with the exclusive scan of the
 //             frame's digit histogram, where the tile's part of every bin starts; the tile is put in bin order in LDS and
 //             written out as contiguous runs.
 // Element order inside a tile is (wave, row, lane), so per-wave running bin counts kept in
-// LDS plus a cross-wave prefix give the stable position.  A sort tile is 8192 pairs (1024 threads x 8 rows): with 256
-// bins a tile sends ~32 consecutive pairs to each bin.  (Rounds 1-2 ran a per-tile histogram kernel and a scan kernel before
-// every scatter: three reads of the keys more per sort.)
+// LDS plus a cross-wave prefix give the stable position.  A sort tile (k_radix_ghist, k_voxel_runs) is 8192 pairs (1024 threads x
+// 8 rows); a scatter tile is 4096 pairs (512 threads x 8 rows): with 256 bins it sends ~16 consecutive pairs to each bin.
+// (Rounds 1-2 ran a per-tile histogram kernel and a scan kernel before every scatter: three reads of the keys more per sort.)
 #include "kernels.hpp"
 
 namespace cd {
 
 constexpr int SORT_WAVES = SORT_BLOCK / WAVE;
+constexpr int SCATTER_WAVES = SCATTER_BLOCK / WAVE;
+// what k_radix_scatter assumes of its tile
+static_assert(SCATTER_BLOCK % WAVE == 0 && SCATTER_BLOCK <= 1024, "whole waves, one workgroup");
+static_assert(RADIX <= SCATTER_BLOCK && RADIX % WAVE == 0, "one thread per bin for the prefix over waves and bins; s_ws / s_gs hold one word per wave of bins");
+static_assert(WAVE_SPAN <= 0xffff && SCATTER_TILE <= 0xffff, "a wave's bin counts and their prefix over the tile's waves are kept as unsigned short");
 
 // The first pass after a single-pass crop reads absolute coordinate fields (KeyPack) and turns them into PCL's voxel index,
 // with the arithmetic of VoxelGrid::applyFilter: ijk = (int)(floor(p * inv_leaf) - min_b) in float, idx = i + j dx + k dx dy.
@@ -95,32 +100,32 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_radix_ghist(const uint32_t* __re
     }
 }
 
-__global__ void __launch_bounds__(SORT_BLOCK) k_radix_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
+__global__ void __launch_bounds__(SCATTER_BLOCK) k_radix_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                          uint32_t* __restrict__ kout, uint32_t* __restrict__ vout, int N,
                                                          int T, int Tact, int pass, int shift, FrameState* __restrict__ fs,
                                                          const uint32_t* __restrict__ ghist, int* __restrict__ state,
                                                          KeyPack kp, int use_runs, int* __restrict__ ticket) {
     CD_FRONT_PRIO();
     __shared__ int s_ticket;
-    __shared__ unsigned short s_wh[SORT_WAVES][RADIX];   // per-wave bin counts, then the wave's offset inside the bin
+    __shared__ unsigned short s_wh[SCATTER_WAVES][RADIX];   // per-wave bin counts, then the wave's offset inside the bin
     __shared__ uint32_t s_goff[RADIX];                   // where the tile's part of each bin starts in the frame
     __shared__ uint32_t s_bstart[RADIX];                 // where each bin starts inside the tile
-    __shared__ uint32_t s_k[SORT_TILE], s_v[SORT_TILE];  // the tile, ordered by bin (64 KiB)
+    __shared__ uint32_t s_k[SCATTER_TILE], s_v[SCATTER_TILE];  // the tile, ordered by bin (32 KiB)
     __shared__ uint32_t s_ws[RADIX / WAVE], s_gs[RADIX / WAVE];
     // workgroup b works on frame b % F and takes its tile by ticket (see k_crop_fused): a tile's predecessors in the chained
     // scan are long done
     const int F = gridDim.x / Tact;   // (pass: row of the frame's histogram table; shift: bit position of the digit)
     const int f = blockIdx.x % F, tile = take_ticket(ticket + f * TICKET_PITCH, Tact, &s_ticket), w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = use_runs ? fs[f].n_runs : fs[f].n_c;   // (runs: the elements are k_voxel_runs' (voxel index, start | length) pairs)
-    if (tile * SORT_TILE >= n) return;
+    if (tile * SCATTER_TILE >= n) return;
     const size_t fbase = (size_t)f * N;
 #ifdef CD_SORTDBG
     unsigned long long t0_ = wall_clock64();
     if (threadIdx.x == 0) atomicAdd(&g_sort_dbg[7], 1ull);
 #endif
-    for (int q = threadIdx.x; q < SORT_WAVES * RADIX; q += SORT_BLOCK) (&s_wh[0][0])[q] = 0;
+    for (int q = threadIdx.x; q < SCATTER_WAVES * RADIX; q += SCATTER_BLOCK) (&s_wh[0][0])[q] = 0;
     __syncthreads();
-    const int base = tile * SORT_TILE + w * WAVE_SPAN + lane;
+    const int base = tile * SCATTER_TILE + w * WAVE_SPAN + lane;
     const uint64_t lt = lanemask_lt();
     const KeyGrid g = key_grid(fs[f]);
     uint32_t key[ITEMS], rank[ITEMS], val[ITEMS];
@@ -162,7 +167,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_radix_scatter(const uint32_t* __
         const int d = threadIdx.x;
         uint32_t run = 0;
 #pragma unroll
-        for (int q = 0; q < SORT_WAVES; ++q) {
+        for (int q = 0; q < SCATTER_WAVES; ++q) {
             const uint32_t c = s_wh[q][d];
             s_wh[q][d] = (unsigned short)run;
             run += c;
@@ -198,7 +203,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_radix_scatter(const uint32_t* __
         if (e < n) {
             const uint32_t d = (key[j] >> shift) & (RADIX - 1);
             const uint32_t lp = s_bstart[d] + s_wh[w][d] + rank[j];
-            if (CD_IN_RANGE(lp < (uint32_t)SORT_TILE, 2u)) {
+            if (CD_IN_RANGE(lp < (uint32_t)SCATTER_TILE, 2u)) {
                 s_k[lp] = key[j];
                 s_v[lp] = val[j];
             }
@@ -206,10 +211,10 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_radix_scatter(const uint32_t* __
     }
     __syncthreads();
     SORT_PHASE(2)
-    const int cnt = min(SORT_TILE, n - tile * SORT_TILE);
+    const int cnt = min(SCATTER_TILE, n - tile * SCATTER_TILE);
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
-        const int lp = threadIdx.x + j * SORT_BLOCK;
+        const int lp = threadIdx.x + j * SCATTER_BLOCK;
         if (lp < cnt) {
             const uint32_t k = s_k[lp];
             const uint32_t d = (k >> shift) & (RADIX - 1);
@@ -223,22 +228,23 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_radix_scatter(const uint32_t* __
     SORT_PHASE(3)
 }
 
-// All passes of one sort.  Tact = sort tiles that hold data (max over the frames).  ghist [F][SORT_MAX_PASSES][RADIX] and
-// state [npass][F][Tact][RADIX] are zeroed here.  kp.enabled: key[0] holds the
+// All passes of one sort.  Tact = sort tiles that hold data (max over the frames), Tscat = scatter tiles that do (the histogram
+// kernel and the scatters have tiles of their own size).  ghist [F][SORT_MAX_PASSES][RADIX] and state [npass][F][Tscat][RADIX]
+// are zeroed here.  kp.enabled: key[0] holds the
 // absolute coordinate fields of k_crop_fused; the first pass writes voxel indices.  Returns the index of the buffers
 // that hold the sorted keys / the permutation, or -1 when the scan state could not be zeroed.
-int launch_radix_sort(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, int npass,
+int launch_radix_sort(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, int Tscat, int npass,
                       FrameState* fs, uint32_t* ghist, int* state, KeyPack kp, int* ticket) {
     if (npass <= 0) return 0;
     // (a failure is also left in hipGetLastError, which the caller's LAUNCH() reads; -1 makes it explicit)
     if (hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)F * SORT_MAX_PASSES * RADIX, s) != hipSuccess) return -1;
-    if (hipMemsetAsync(state, 0, sizeof(int) * (size_t)npass * F * Tact * RADIX, s) != hipSuccess) return -1;
+    if (hipMemsetAsync(state, 0, sizeof(int) * (size_t)npass * F * Tscat * RADIX, s) != hipSuccess) return -1;
     const int G = (Tact + GHIST_TILES - 1) / GHIST_TILES;
     hipLaunchKernelGGL(k_radix_ghist, dim3(G, F), dim3(SORT_BLOCK), 0, s, key[0], N, npass, fs, ghist, kp);
     int cur = 0;
     for (int pass = 0; pass < npass; ++pass) {
-        hipLaunchKernelGGL(k_radix_scatter, dim3(Tact * F), dim3(SORT_BLOCK), 0, s, key[cur], pass ? val[cur] : nullptr, key[cur ^ 1],
-                           val[cur ^ 1], N, Tact, Tact, pass, pass * RADIX_BITS, fs, ghist, state + (size_t)pass * F * Tact * RADIX, kp, 0, ticket);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(Tscat * F), dim3(SCATTER_BLOCK), 0, s, key[cur], pass ? val[cur] : nullptr, key[cur ^ 1],
+                           val[cur ^ 1], N, Tscat, Tscat, pass, pass * RADIX_BITS, fs, ghist, state + (size_t)pass * F * Tscat * RADIX, kp, 0, ticket);
         kp.enabled = 0;   // later passes read voxel indices
         cur ^= 1;
     }
@@ -334,28 +340,30 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_voxel_runs(const uint32_t* __res
 }
 
 // The sort of a batch by runs: key[0] holds the crop's keys; the runs go to key[1] / val[1] and the passes alternate from
-// there.  `tile_state` [F][T] (zeroed here) carries the chained scan of the run counts.  Returns the index of the buffers that
+// there.  `tile_state` [F][T] (zeroed here) carries the chained scan of the run counts over k_voxel_runs' Tact sort tiles; the
+// scatters take Tscat tiles of their own size and `state` [npass][F][Tscat][RADIX].  Returns the index of the buffers that
 // hold the sorted run keys / payloads, or -1 when a scan state could not be zeroed.
-int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int T, int Tact, int npass,
+int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int T, int Tact, int Tscat, int npass,
                            FrameState* fs, uint32_t* ghist, int* state, int* tile_state, KeyPack kp, int* ticket) {
     if (npass <= 0) return 0;
     if (hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)F * SORT_MAX_PASSES * RADIX, s) != hipSuccess) return -1;
-    if (hipMemsetAsync(state, 0, sizeof(int) * (size_t)npass * F * Tact * RADIX, s) != hipSuccess) return -1;
+    if (hipMemsetAsync(state, 0, sizeof(int) * (size_t)npass * F * Tscat * RADIX, s) != hipSuccess) return -1;
     if (hipMemsetAsync(tile_state, 0, sizeof(int) * (size_t)F * T, s) != hipSuccess) return -1;
     hipLaunchKernelGGL(k_voxel_runs, dim3(Tact * F), dim3(SORT_BLOCK), 0, s, key[0], N, T, Tact, npass, fs, ghist, tile_state, key[1],
                        val[1], kp, ticket);
     kp.enabled = 0;
     int cur = 1;
     for (int pass = 0; pass < npass; ++pass) {
-        hipLaunchKernelGGL(k_radix_scatter, dim3(Tact * F), dim3(SORT_BLOCK), 0, s, key[cur], val[cur], key[cur ^ 1], val[cur ^ 1], N,
-                           Tact, Tact, pass, pass * RADIX_BITS, fs, ghist, state + (size_t)pass * F * Tact * RADIX, kp, 1, ticket);
+        hipLaunchKernelGGL(k_radix_scatter, dim3(Tscat * F), dim3(SCATTER_BLOCK), 0, s, key[cur], val[cur], key[cur ^ 1], val[cur ^ 1], N,
+                           Tscat, Tscat, pass, pass * RADIX_BITS, fs, ghist, state + (size_t)pass * F * Tscat * RADIX, kp, 1, ticket);
         cur ^= 1;
     }
     return cur;
 }
 
 // The scatters of a sort whose run records and histograms k_crop_runs has already written (key[0] / val[0], ghist): one pass
-// per digit of the packed key that varies in some frame, lowest first.  `state` [ndigits][F][Tact][RADIX] is zeroed here.
+// per digit of the packed key that varies in some frame, lowest first.  Tact = scatter tiles (SCATTER_TILE pairs) that hold data;
+// `state` [ndigits][F][Tact][RADIX] is zeroed here.
 int launch_radix_scatter_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, const int* digits, int ndigits,
                               FrameState* fs, const uint32_t* ghist, int* state, int* ticket) {
     if (ndigits <= 0) return 0;
@@ -364,7 +372,7 @@ int launch_radix_scatter_runs(hipStream_t s, uint32_t* const key[2], uint32_t* c
     none.enabled = 0; none.bi = none.bj = 0; none.ilo = none.jlo = none.klo = 0;
     int cur = 0;
     for (int q = 0; q < ndigits; ++q) {
-        hipLaunchKernelGGL(k_radix_scatter, dim3(Tact * F), dim3(SORT_BLOCK), 0, s, key[cur], val[cur], key[cur ^ 1], val[cur ^ 1], N,
+        hipLaunchKernelGGL(k_radix_scatter, dim3(Tact * F), dim3(SCATTER_BLOCK), 0, s, key[cur], val[cur], key[cur ^ 1], val[cur ^ 1], N,
                            Tact, Tact, digits[q], digits[q] * RADIX_BITS, fs, ghist, state + (size_t)q * F * Tact * RADIX, none, 1, ticket);
         cur ^= 1;
     }

@@ -37,14 +37,16 @@ void launch_pack_records(hipStream_t s, const float4* pts, int m, int words, int
 
 // k_sort.hip : segmented (per frame) stable LSD radix sort of (key, value) pairs, all passes
 constexpr int SORT_MAX_PASSES_HOST = 4;
-int launch_radix_sort(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, int npass,
+// (Tact: tiles of SORT_TILE pairs that hold data - k_radix_ghist, k_voxel_runs; Tscat: tiles of SCATTER_TILE pairs - the scatters,
+// whose chained-scan state is [passes][F][Tscat][RADIX] ints)
+int launch_radix_sort(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, int Tscat, int npass,
                       FrameState* fs, uint32_t* ghist, int* state, KeyPack kp, int* ticket);
 // the same sort over RUNS of equal voxel index (k_voxel_runs: 2-3 x fewer elements on organised clouds); tile_state: [F][T] ints
 // the scatters alone, over run records whose digit histograms are already in ghist (k_crop_runs): `digits` lists the 8-bit digits
-// of the key that vary (ascending); the records are in key[0] / val[0]
+// of the key that vary (ascending); the records are in key[0] / val[0]; Tact counts scatter tiles
 int launch_radix_scatter_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int Tact, const int* digits, int ndigits,
                               FrameState* fs, const uint32_t* ghist, int* state, int* ticket);
-int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int T, int Tact, int npass,
+int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* const val[2], int N, int F, int T, int Tact, int Tscat, int npass,
                            FrameState* fs, uint32_t* ghist, int* state, int* tile_state, KeyPack kp, int* ticket);
 
 // k_plane.hip
