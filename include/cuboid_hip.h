@@ -688,6 +688,99 @@ int cd_draw_last_results(cd_context* ctx, uint8_t* rgb8, int width, int height, 
 int cd_draw_last_results_device(cd_context* ctx, uint8_t* d_rgb8, int width, int height, int which, const cd_overlay_params* params,
                                 cd_overlay_box* out);
 
+/* Pose verification: the cuboid of a pose rendered into the 16UC1 depth image the pose was found in, and every pixel it covers
+ * compared with what the sensor measured there - a machine-readable verdict beside `converged && fitness < accept`
+ * (icp.cpp:182), which accepts poses whose box the sensor saw straight through.  Canonical rule C14.  All
+ * arithmetic is double, one IEEE operation at a time, no contraction, IEEE '/'.  Per box: the row-major double pose [R t; 0 0 0 1]
+ * (box to camera, cd_cluster_result.pose), dims = l, w, h, the cd_depth_camera of the image (fx, fy, cx, cy, depth_scale
+ * widened from float32 to double) and the tolerance tau:
+ *   1. SKIP: the box is not verified (verified = 0, every count 0) when any of the 12 entries of R, t is non-finite, or any of
+ *      the 8 corners (sx, sy, sz in +-1) has zc = ((R[2][0] (sx l/2) + R[2][1] (sy w/2)) + R[2][2] (sz h/2)) + t[2] with !(zc > 0):
+ *      a box not wholly in front of the camera is not rendered;
+ *   2. ray of pixel (u, v): dx = ((double)u - cx) / fx, dy = ((double)v - cy) / fy, direction (dx, dy, 1); for each box axis a:
+ *      o_a = -((R[0][a] t[0] + R[1][a] t[1]) + R[2][a] t[2]),  dd_a = (R[0][a] dx + R[1][a] dy) + R[2][a],  half_a = dims[a] / 2;
+ *   3. slabs, written as comparisons so that a NaN behaves the same everywhere: tn = -inf, tf = +inf, miss = false; an axis with
+ *      dd_a == 0: miss |= fabs(o_a) > half_a and nothing else; any other axis: t1 = (-half_a - o_a) / dd_a, t2 = (half_a - o_a) /
+ *      dd_a, lo = t1 < t2 ? t1 : t2, hi = t1 < t2 ? t2 : t1, tn = lo > tn ? lo : tn, tf = hi < tf ? hi : tf.  The pixel is HIT
+ *      iff !miss && tn <= tf && tn > 0; the rendered depth is z_r = tn, the camera z of the entry point (a camera inside the box
+ *      hits nothing);
+ *   4. class of a hit pixel with depth value d, z_m = (double)d * depth_scale: INVALID if d == 0; THROUGH if z_m - z_r > tau (the
+ *      sensor saw past where the box should be); OCCLUDED if z_r - z_m > tau (something nearer: neutral); AGREE otherwise (both
+ *      boundaries are AGREE);
+ *   5. record: the int32 counts n_hit, n_agree, n_through, n_occluded, n_invalid; agree_abs_um = the sum over AGREE pixels of
+ *      (int64)(fabs(z_m - z_r) * 1e6 + 0.5) (an integer sum: its order cannot matter; a term of 2^63 or more counts as
+ *      2^63 - 1); score = n_agree / (double)(n_agree + n_through), 0.0 when that sum is 0; passed = verified && n_agree >=
+ *      min_agree && score >= min_score;
+ *   6. the counts are defined over every pixel of the image (the device skips pixels outside a rectangle around the projected
+ *      corners that it can prove are misses); boxes and frames are independent of each other - boxes do not occlude one another;
+ *      nothing is written to the depth image.
+ * The 180-degree flips of a cuboid are the same solid and therefore give the same record: what a grasp wants.
+ * perception_amd/verify.py restates the rule on the CPU over whole images and the device equals it in every field. */
+typedef struct cd_verify_params {       /* no padding holes */
+    double dims[3];                     /* l, w, h of every box (defaults 0.2, 0.1, 0.03)                           */
+    double slot_dims[CD_MAX_TEMPLATES][3]; /* cd_verify_last_results with use_slot_dims: dims of the record's template_slot */
+    double tolerance;                   /* tau, metres; default 0.01; finite, >= 0                                  */
+    double min_score;                   /* default 0.9; finite                                                      */
+    int32_t min_agree;                  /* default 200 (the cluster minimum); >= 0                                  */
+    int32_t use_slot_dims;              /* 0 / 1                                                                    */
+    int32_t reserved[6];
+} cd_verify_params;
+typedef struct cd_verify_box {
+    int32_t verified, passed, n_hit, n_agree, n_through, n_occluded, n_invalid, reserved;
+    int64_t agree_abs_um;
+    double score;
+} cd_verify_box;                        /* 48 bytes; all zero for an empty slot */
+enum { CD_VERIFY_ACCEPTED = 0, CD_VERIFY_ALL = 1 };
+enum { CD_VERIFY_MISS = 0, CD_VERIFY_AGREE = 1, CD_VERIFY_THROUGH = 2, CD_VERIFY_OCCLUDED = 3, CD_VERIFY_INVALID = 4 };
+/* dims 0.2 / 0.1 / 0.03 (also in every slot_dims row), tolerance 0.01, min_score 0.9, min_agree 200, use_slot_dims 0. */
+void cd_default_verify_params(cd_verify_params* p);
+/* sizeof as this library was built: which = 0 cd_verify_params, 1 cd_verify_box, anything else -1. */
+int cd_verify_struct_size(int which);
+
+/* Host-only (no context, no GPU): steps 2-4 for pixel (u, v) with depth value d of a box with params->dims.  *cls receives
+ * CD_VERIFY_MISS .. CD_VERIFY_INVALID, *z_r the rendered depth when the pixel is hit (0.0 otherwise).  Step 1 is not applied.
+ * params == NULL: the defaults.  NULL cam / pose / cls / z_r, fx / fy / depth_scale not finite or <= 0, an unknown colour mode, a
+ * non-finite or negative dims or tolerance: CD_ERR_INVALID_ARG. */
+int cd_verify_pixel(const cd_depth_camera* cam, const double pose[16], const cd_verify_params* params, int u, int v, uint16_t d,
+                    int32_t* cls, double* z_r);
+/* Host-only: the whole rule for one box over one cam->width x cam->height image, every pixel of it.  Checks as cd_verify_pixel,
+ * plus a NULL depth / out, width or height < 1, a non-finite min_score and a negative min_agree. */
+int cd_verify_box_host(const cd_depth_camera* cam, const uint16_t* depth, const double pose[16], const cd_verify_params* params,
+                       cd_verify_box* out);
+
+/* Rule C14 on n_frames tightly packed 16UC1 images (cam->width * cam->height uint16 each, back to back; no colour image is read).
+ * Layout as cd_draw_boxes_batch: frame f has n_boxes[f] <= boxes_per_frame boxes, the pose of its box b is
+ * poses[(f * boxes_per_frame + b) * 16 .. + 15], out receives n_frames * boxes_per_frame records in the same order (slots at
+ * and beyond n_boxes[f]: all zero).  box_dims == NULL: every box has params->dims; otherwise the box in slot (f, b) has
+ * box_dims[(f * boxes_per_frame + b) * 3 .. + 2].  params == NULL: the defaults.  Checked before any copy or launch,
+ * CD_ERR_INVALID_ARG: a null cam / depth / poses / n_boxes / out, the camera fields cd_process_depth_batch refuses (fx, fy or
+ * depth_scale not finite or <= 0, an unknown colour mode), width * height 0 or over max_points, n_frames outside 1 .. max_frames, boxes_per_frame outside 1 .. 1024,
+ * a non-finite or negative dims, box_dims (of an existing box) or tolerance, a non-finite min_score, a negative min_agree, a
+ * negative n_boxes[f] or one over boxes_per_frame.  A non-finite pose is no error: that box has verified = 0.  The host form
+ * uploads the images into a buffer that nothing else uses; in the _device form only poses, dims and the records cross the bus.
+ * Like every compute call these two invalidate the read-backs of the last fused call (cd_verify_last_results does not). */
+int cd_verify_boxes_batch(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* depth, int n_frames, const double* poses,
+                          const int32_t* n_boxes, int boxes_per_frame, const double* box_dims, const cd_verify_params* params,
+                          cd_verify_box* out);
+/* Same, images already resident in device memory of the context's GPU (ordering as cd_process_batch_device).  poses, n_boxes,
+ * box_dims and out are host memory. */
+int cd_verify_boxes_batch_device(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* d_depth, int n_frames, const double* poses,
+                                 const int32_t* n_boxes, int boxes_per_frame, const double* box_dims, const cd_verify_params* params,
+                                 cd_verify_box* out);
+
+/* The poses of the LAST fused call of the context verified against that call's n_frames depth images: the image that was
+ * deprojected for cd_process_depth_batch[_device]; the RAW depth image for cd_process_depth_batch_mapped[_device] (its poses are
+ * in the depth camera's frame); the caller's depth image of the same frame for the cloud-fed calls.  Slots, `which`
+ * (CD_VERIFY_ACCEPTED / CD_VERIFY_ALL), validity rule and effect on the read-backs exactly as cd_draw_last_results: out holds
+ * n_frames * CD_MAX_CLUSTERS_PER_FRAME records, slot k of frame f is clusters[k]; a slot that is not selected is all zero; the
+ * fused call's records and read-backs, and a later cd_draw_last_results, stay as they were.  Every box has params->dims, or -
+ * use_slot_dims != 0 - params->slot_dims[template_slot of its record] (then every row of slot_dims is checked like dims).
+ * Argument checks as cd_verify_boxes_batch. */
+int cd_verify_last_results(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* depth, int which, const cd_verify_params* params,
+                           cd_verify_box* out);
+int cd_verify_last_results_device(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* d_depth, int which,
+                                  const cd_verify_params* params, cd_verify_box* out);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "cd_get_bbox_source", "cd_get_frame_bboxes",
     "cd_default_overlay_params", "cd_overlay_project", "cd_draw_boxes_batch", "cd_draw_boxes_batch_device", "cd_draw_last_results",
     "cd_draw_last_results_device",
+    "cd_default_verify_params", "cd_verify_struct_size", "cd_verify_pixel", "cd_verify_box_host", "cd_verify_boxes_batch",
+    "cd_verify_boxes_batch_device", "cd_verify_last_results", "cd_verify_last_results_device",
     "cd_default_color_camera", "cd_color_camera_struct_size", "cd_texture_project", "cd_depth_to_cloud_mapped",
     "cd_process_depth_batch_mapped", "cd_process_depth_batch_mapped_device",
     "cd_shape_frame_struct_size", "cd_shape_frame_host", "cd_shape_frames", "cd_template_shape_frame", "cd_shape_guess",
@@ -56,6 +58,8 @@ CD_PLANE, CD_PLANE_PERPENDICULAR, CD_PLANE_PARALLEL = 0, 1, 2
 CD_COLOR_NONE, CD_COLOR_RGB8 = 0, 1
 CD_BBOX_PARAMS, CD_BBOX_PER_FRAME, CD_BBOX_COLOR = 0, 1, 2
 CD_DRAW_ACCEPTED, CD_DRAW_ALL = 0, 1
+CD_VERIFY_ACCEPTED, CD_VERIFY_ALL = 0, 1
+CD_VERIFY_MISS, CD_VERIFY_AGREE, CD_VERIFY_THROUGH, CD_VERIFY_OCCLUDED, CD_VERIFY_INVALID = 0, 1, 2, 3, 4
 CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 
 
@@ -168,7 +172,51 @@ class CdOverlayBox(C.Structure):
     _fields_ = [("corners", C.c_int32 * 16), ("drawn", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class CdVerifyParams(C.Structure):
+    """cd_verify_params: the parameters of canonical rule C14 (an ICP pose's box rendered into the depth image)."""
+    _fields_ = [("dims", C.c_double * 3), ("slot_dims", (C.c_double * 3) * CD_MAX_TEMPLATES), ("tolerance", C.c_double),
+                ("min_score", C.c_double), ("min_agree", C.c_int32), ("use_slot_dims", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class CdVerifyBox(C.Structure):
+    """cd_verify_box: one box's pixel counts, their verdict and score (all zero for an empty slot or a box that was not rendered)."""
+    _fields_ = [("verified", C.c_int32), ("passed", C.c_int32), ("n_hit", C.c_int32), ("n_agree", C.c_int32),
+                ("n_through", C.c_int32), ("n_occluded", C.c_int32), ("n_invalid", C.c_int32), ("reserved", C.c_int32),
+                ("agree_abs_um", C.c_int64), ("score", C.c_double)]
+
+
 FRAME_RESULT_BYTES = C.sizeof(CdFrameResult)
+
+
+def default_verify_params():
+    """dims 0.2 / 0.1 / 0.03 (also in every slot_dims row), tolerance 0.01, min_score 0.9, min_agree 200.  Pure Python mirror of
+    cd_default_verify_params()."""
+    from . import verify
+    p = CdVerifyParams()
+    p.dims[:] = verify.DEFAULT_DIMS
+    for row in p.slot_dims:
+        row[:] = verify.DEFAULT_DIMS
+    p.tolerance, p.min_score, p.min_agree = verify.DEFAULT_TOLERANCE, verify.DEFAULT_MIN_SCORE, verify.DEFAULT_MIN_AGREE
+    return p
+
+
+def verify_params(dims=None, slot_dims=None, tolerance=None, min_score=None, min_agree=None, use_slot_dims=None):
+    """default_verify_params() with the given fields replaced (slot_dims: {slot: (l, w, h)} or a sequence of rows)."""
+    p = default_verify_params()
+    if dims is not None:
+        p.dims[:] = [float(v) for v in dims]
+    if slot_dims is not None:
+        for k, row in (slot_dims.items() if isinstance(slot_dims, dict) else enumerate(slot_dims)):
+            p.slot_dims[k][:] = [float(v) for v in row]
+    if tolerance is not None:
+        p.tolerance = float(tolerance)
+    if min_score is not None:
+        p.min_score = float(min_score)
+    if min_agree is not None:
+        p.min_agree = int(min_agree)
+    if use_slot_dims is not None:
+        p.use_slot_dims = int(use_slot_dims)
+    return p
 
 
 def default_overlay_params():
@@ -362,6 +410,16 @@ def load_library(path=None):
         f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dp, i32p, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
     for f in (lib.cd_draw_last_results, lib.cd_draw_last_results_device):
         f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(CdOverlayParams), C.POINTER(CdOverlayBox)]
+    vpp, vbp, dcp = C.POINTER(CdVerifyParams), C.POINTER(CdVerifyBox), C.POINTER(CdDepthCamera)
+    lib.cd_default_verify_params.argtypes = [vpp]
+    lib.cd_default_verify_params.restype = None
+    lib.cd_verify_struct_size.argtypes = [C.c_int]
+    lib.cd_verify_pixel.argtypes = [dcp, dp, vpp, C.c_int, C.c_int, C.c_uint16, i32p, dp]
+    lib.cd_verify_box_host.argtypes = [dcp, vp, dp, vpp, vbp]
+    for f in (lib.cd_verify_boxes_batch, lib.cd_verify_boxes_batch_device):
+        f.argtypes = [vp, dcp, vp, C.c_int, dp, i32p, C.c_int, dp, vpp, vbp]
+    for f in (lib.cd_verify_last_results, lib.cd_verify_last_results_device):
+        f.argtypes = [vp, dcp, vp, C.c_int, vpp, vbp]
     lib.cd_default_color_camera.argtypes = [C.POINTER(CdColorCamera)]
     lib.cd_default_color_camera.restype = None
     lib.cd_color_camera_struct_size.argtypes = []
@@ -673,6 +731,50 @@ class Context:
         self._check(fn(self.h, ptr, W, H, int(which), None if params is None else C.byref(params), out))
         return out
 
+    @staticmethod
+    def _depth_images(depth):
+        """(pointer, on_device, F, H, W) of a C-contiguous (F, H, W) uint16 numpy array or a contiguous 16-bit torch tensor in HBM."""
+        on_device = not isinstance(depth, np.ndarray)
+        if on_device:
+            assert depth.is_contiguous() and depth.dim() == 3 and depth.element_size() == 2
+            ptr = C.c_void_p(depth.data_ptr())
+        else:
+            assert depth.dtype == np.uint16 and depth.ndim == 3 and depth.flags.c_contiguous
+            ptr = _ptr(depth)
+        F, H, W = (int(v) for v in depth.shape)
+        return ptr, on_device, F, H, W
+
+    def verify_boxes(self, depth, poses, n_boxes, cam, params=None, box_dims=None):
+        """Rule C14: the boxes of `poses` rendered into `depth` and compared with it, either a C-contiguous (F, H, W) uint16 numpy
+        array (cd_verify_boxes_batch: uploaded) or a contiguous 16-bit torch tensor of that shape in HBM
+        (cd_verify_boxes_batch_device; the caller has synchronised the stream that wrote it).  poses (F, B, 4, 4) float64, n_boxes
+        (F,) (None: all B), cam a CdDepthCamera of that width and height, box_dims None or (F, B, 3).  Returns an array of F * B
+        CdVerifyBox, box b of frame f at [f * B + b].  The images are only read."""
+        ptr, on_device, F, H, W = self._depth_images(depth)
+        assert (cam.width, cam.height) == (W, H)
+        p = np.ascontiguousarray(poses, np.float64).reshape(F, -1, 16)
+        B = p.shape[1]
+        nb = np.full(F, B, np.int32) if n_boxes is None else np.ascontiguousarray(n_boxes, np.int32)
+        assert nb.shape == (F,)
+        dp = C.POINTER(C.c_double)
+        bd = None if box_dims is None else np.ascontiguousarray(box_dims, np.float64).reshape(F, B, 3)
+        out = (CdVerifyBox * max(F * B, 1))()
+        fn = self.lib.cd_verify_boxes_batch_device if on_device else self.lib.cd_verify_boxes_batch
+        self._check(fn(self.h, C.byref(cam), ptr, F, p.ctypes.data_as(dp), nb.ctypes.data_as(C.POINTER(C.c_int32)), B,
+                       None if bd is None else bd.ctypes.data_as(dp), None if params is None else C.byref(params), out))
+        return out
+
+    def verify_last_results(self, depth, cam, which=CD_VERIFY_ACCEPTED, params=None):
+        """The poses of the last fused call verified against its frames' depth images (numpy array or torch tensor as for
+        verify_boxes; F = that call's frames).  which: CD_VERIFY_ACCEPTED / CD_VERIFY_ALL.  Returns F * CD_MAX_CLUSTERS_PER_FRAME
+        CdVerifyBox, slot k of frame f = clusters[k] of its record.  Leaves the fused call's read-backs as they are."""
+        ptr, on_device, F, H, W = self._depth_images(depth)
+        assert (cam.width, cam.height) == (W, H)
+        out = (CdVerifyBox * (max(F, 1) * CD_MAX_CLUSTERS_PER_FRAME))()
+        fn = self.lib.cd_verify_last_results_device if on_device else self.lib.cd_verify_last_results
+        self._check(fn(self.h, C.byref(cam), ptr, int(which), None if params is None else C.byref(params), out))
+        return out
+
     def surface_batch(self, clouds, table_normals, prm, invert=True):
         """cd_surface_batch: cd_surface_frame over a batch of (ragged) clouds, fitted together on the device.
         clouds: a sequence of (n_f, >=3) arrays or an (F, P, >=3) array; table_normals (F, 3).
@@ -931,6 +1033,39 @@ def overlay_project(pose, params=None):
     if st != CD_OK:
         raise CuboidError(st, "cd_overlay_project: non-finite P, E or dims")
     return list(box.corners), int(box.drawn)
+
+
+def verify_pixel(cam, pose, u, v, d, params=None):
+    """Host-only rule C14 steps 2-4 for one pixel (cd_verify_pixel): (class CD_VERIFY_MISS .. CD_VERIFY_INVALID, z_r)."""
+    lib = load_library()
+    a = np.ascontiguousarray(pose, np.float64).reshape(16)
+    cls, z = C.c_int32(-1), C.c_double(0.0)
+    st = lib.cd_verify_pixel(C.byref(cam), a.ctypes.data_as(C.POINTER(C.c_double)), None if params is None else C.byref(params),
+                             int(u), int(v), int(d), C.byref(cls), C.byref(z))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_verify_pixel: bad camera, dims or tolerance")
+    return cls.value, z.value
+
+
+def verify_box_host(cam, depth, pose, params=None):
+    """Host-only rule C14 for one box over one whole (H, W) uint16 image (cd_verify_box_host): a CdVerifyBox."""
+    lib = load_library()
+    depth = np.ascontiguousarray(depth, np.uint16)
+    assert depth.shape == (cam.height, cam.width)
+    a = np.ascontiguousarray(pose, np.float64).reshape(16)
+    box = CdVerifyBox()
+    st = lib.cd_verify_box_host(C.byref(cam), _ptr(depth), a.ctypes.data_as(C.POINTER(C.c_double)),
+                                None if params is None else C.byref(params), C.byref(box))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_verify_box_host: bad camera or parameters")
+    return box
+
+
+def verify_records(boxes, F=None, B=None):
+    """An array of CdVerifyBox as a numpy array of verify.RECORD ((F, B) when both are given)."""
+    from . import verify
+    a = np.frombuffer(bytes(boxes), verify.RECORD)
+    return a if F is None else a[:F * B].reshape(F, B)
 
 
 def results_to_array(res):

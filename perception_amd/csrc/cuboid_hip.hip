@@ -21,6 +21,7 @@
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "overlay_math.hpp"
+#include "verify_math.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
 #include "texture_math.hpp"
@@ -179,6 +180,12 @@ struct cd_context : cd_streams {
     DevBuf<double> d_oposes;
     DevBuf<int32_t> d_onbox;
     DevBuf<OverlayBox> d_obox; PinBuf<OverlayBox> h_obox;
+    // pose verification (rule C14, k_verify.hip), all grown on demand: the depth images of the host forms (a buffer nothing else
+    // reads or stages through), and per (frame, slot) the pose + dims going up and the record coming back (device + pinned mirror)
+    DevBuf<uint16_t> d_vdepth;
+    DevBuf<VerifyJob> d_vjob; PinBuf<VerifyJob> h_vjob;
+    DevBuf<int32_t> d_vnbox; PinBuf<int32_t> h_vnbox;
+    DevBuf<VerifyRecord> d_vrec; PinBuf<VerifyRecord> h_vrec;
     // per-cluster principal frames (rule C13, k_shape.hip), all allocated on first use: the template records of every slot (pinned
     // table, uploaded when a template has changed since), one record per ICP problem of a CD_GUESS_CLUSTER stage (device + pinned
     // mirror), and the points / set list of cd_shape_frames
@@ -2950,6 +2957,157 @@ static int cd_draw_last_results_impl(cd_context* c, uint8_t* rgb8, int width, in
     return stage_overlay(c, rgb8, width, height, F, poses.data(), n_boxes.data(), B, op, out, on_device);
 }
 
+// ---- pose verification (rule C14, k_verify.hip) -----------------------------------------------------------------------------------
+static_assert(sizeof(VerifyRecord) == sizeof(cd_verify_box) && sizeof(cd_verify_box) == 48 && offsetof(cd_verify_box, agree_abs_um) == offsetof(VerifyRecord, agree_abs_um) &&
+              offsetof(cd_verify_box, score) == 40, "the kernel's record is cd_verify_box");
+static_assert(sizeof(cd_verify_params) == (3 + 3 * CD_MAX_TEMPLATES + 2) * 8 + 8 * 4 && offsetof(cd_verify_params, reserved) == sizeof(cd_verify_params) - 24, "cd_verify_params has no padding holes");
+static_assert(sizeof(VerifyJob) == 152, "152 bytes per box cross the bus");
+
+static bool verify_dim_ok(double v) { return std::isfinite(v) && v >= 0.0; }
+// the checks on the camera and the parameters alone (shared with the host-only entries): nullptr = fine, else what is wrong
+static const char* verify_camera_error(const cd_depth_camera* cam) {
+    if (!cam) return "depth camera is NULL";
+    if (cam->color != CD_COLOR_NONE && cam->color != CD_COLOR_RGB8) return "unknown colour mode";
+    for (float v : {cam->fx, cam->fy, cam->depth_scale})
+        if (!(std::isfinite(v) && v > 0.f)) return "fx, fy and depth_scale must be finite and > 0";
+    return nullptr;
+}
+static const char* verify_params_error(const cd_verify_params* vp) {
+    for (double v : vp->dims) if (!verify_dim_ok(v)) return "dims must be finite and >= 0";
+    if (vp->use_slot_dims)
+        for (int s = 0; s < CD_MAX_TEMPLATES; ++s)
+            for (double v : vp->slot_dims[s]) if (!verify_dim_ok(v)) return "slot_dims must be finite and >= 0";
+    if (!verify_dim_ok(vp->tolerance)) return "tolerance must be finite and >= 0";
+    if (!std::isfinite(vp->min_score)) return "min_score must be finite";
+    if (vp->min_agree < 0) return "min_agree must be >= 0";
+    return nullptr;
+}
+static VerifyCam verify_kernel_camera(const cd_depth_camera* cam) {
+    VerifyCam k;
+    k.fx = (double)cam->fx; k.fy = (double)cam->fy; k.cx = (double)cam->cx; k.cy = (double)cam->cy; k.depth_scale = (double)cam->depth_scale;
+    k.width = cam->width; k.height = cam->height;
+    return k;
+}
+// rule C14 step 5: what the host adds to the counts
+static void verify_finish(const cd_verify_params* vp, cd_verify_box* r) {
+    const long long den = (long long)r->n_agree + (long long)r->n_through;
+    r->score = den != 0 ? (double)r->n_agree / (double)den : 0.0;
+    r->passed = (r->verified && r->n_agree >= vp->min_agree && r->score >= vp->min_score) ? 1 : 0;
+    r->reserved = 0;
+}
+
+// every check of the header's list but those on the boxes, before anything is copied or launched
+static int check_verify(cd_context* c, const cd_depth_camera* cam, const void* depth, int n_frames, const cd_verify_params* vp, const void* out) {
+    if (!depth || !out) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (const char* msg = verify_camera_error(cam)) return fail(c, CD_ERR_INVALID_ARG, msg);
+    if (cam->width <= 0 || cam->height <= 0 || (long long)cam->width * cam->height > (long long)c->N)
+        return fail(c, CD_ERR_INVALID_ARG, "width * height must be in 1 .. the context's max_points");
+    if (n_frames <= 0 || n_frames > c->F) return fail(c, CD_ERR_INVALID_ARG, "n_frames must be in 1 .. the context's max_frames");
+    if (const char* msg = verify_params_error(vp)) return fail(c, CD_ERR_INVALID_ARG, msg);
+    return CD_OK;
+}
+
+// poses (F * B * 16 doubles), n_boxes (F) and dims (F * B * 3 doubles) are HOST memory; depth is device memory (on_device) or host
+// memory that is uploaded into d_vdepth.  Reads the images only, and leaves the read-back state of the last fused call alone.
+static int stage_verify(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, int F, const double* poses, const int32_t* n_boxes,
+                        int B, const double* dims, const cd_verify_params* vp, cd_verify_box* out, bool on_device) {
+    const size_t nb = (size_t)F * (size_t)B;
+    GROW(c, d_vjob, nb); GROW(c, h_vjob, nb); GROW(c, d_vrec, nb); GROW(c, h_vrec, nb);
+    GROW(c, d_vnbox, (size_t)c->F); GROW(c, h_vnbox, (size_t)c->F);
+    const uint16_t* d_img = depth;
+    if (!on_device) {
+        const size_t px = (size_t)cam->width * cam->height * F;
+        GROW(c, d_vdepth, px);
+        HIPCHK(c, hipMemcpyAsync(c->d_vdepth, depth, px * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        d_img = c->d_vdepth;
+    }
+    for (int f = 0; f < F; ++f) {
+        c->h_vnbox[f] = n_boxes[f];
+        for (int b = 0; b < B; ++b) {
+            const size_t i = (size_t)f * B + b;
+            VerifyJob& j = c->h_vjob[i];
+            std::memcpy(j.pose, poses + i * 16, sizeof(j.pose));
+            std::memcpy(j.dims, dims + i * 3, sizeof(j.dims));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_vjob, c->h_vjob, sizeof(VerifyJob) * nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_vnbox, c->h_vnbox, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(c, launch_verify_boxes(c->stream, d_img, verify_kernel_camera(cam), vp->tolerance, c->d_vjob, c->d_vnbox, B, F, c->d_vrec));
+    HIPCHK(c, hipMemcpyAsync(c->h_vrec, c->d_vrec, sizeof(VerifyRecord) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out, c->h_vrec, sizeof(cd_verify_box) * nb);
+    for (int f = 0; f < F; ++f)
+        for (int b = 0; b < n_boxes[f]; ++b) verify_finish(vp, out + (size_t)f * B + b);
+    return CD_OK;
+}
+
+static int cd_verify_boxes_batch_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, int n_frames, const double* poses,
+                                      const int32_t* n_boxes, int boxes_per_frame, const double* box_dims, const cd_verify_params* vp,
+                                      cd_verify_box* out, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    cd_verify_params def;
+    cd_default_verify_params(&def);
+    if (!vp) vp = &def;
+    int st = check_verify(c, cam, depth, n_frames, vp, out);
+    if (st) return st;
+    if (!poses || !n_boxes) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
+    if (boxes_per_frame < 1 || boxes_per_frame > OVERLAY_MAX_BOXES) return fail(c, CD_ERR_INVALID_ARG, "boxes_per_frame must be in 1 .. 1024");
+    const int B = boxes_per_frame;
+    for (int f = 0; f < n_frames; ++f)
+        if (n_boxes[f] < 0 || n_boxes[f] > B) return fail(c, CD_ERR_INVALID_ARG, "n_boxes[f] must be in 0 .. boxes_per_frame");
+    std::vector<double> dims((size_t)n_frames * B * 3);
+    for (size_t i = 0; i < (size_t)n_frames * B; ++i)
+        for (int k = 0; k < 3; ++k) dims[i * 3 + k] = vp->dims[k];
+    if (box_dims)
+        for (int f = 0; f < n_frames; ++f)
+            for (int b = 0; b < n_boxes[f]; ++b)
+                for (int k = 0; k < 3; ++k) {
+                    const size_t i = ((size_t)f * B + b) * 3 + k;
+                    if (!verify_dim_ok(box_dims[i])) return fail(c, CD_ERR_INVALID_ARG, "box_dims must be finite and >= 0");
+                    dims[i] = box_dims[i];
+                }
+    invalidate_last(c);
+    return stage_verify(c, cam, depth, n_frames, poses, n_boxes, B, dims.data(), vp, out, on_device);
+}
+
+static int cd_verify_last_results_impl(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, int which, const cd_verify_params* vp,
+                                       cd_verify_box* out, bool on_device) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    cd_verify_params def;
+    cd_default_verify_params(&def);
+    if (!vp) vp = &def;
+    if (c->last_first.size() < 2) return fail(c, CD_ERR_INVALID_ARG, "no fused call to verify: none has run, or another compute call has run since");
+    const int F = (int)c->last_first.size() - 1;
+    int st = check_verify(c, cam, depth, F, vp, out);
+    if (st) return st;
+    if (which != CD_VERIFY_ACCEPTED && which != CD_VERIFY_ALL) return fail(c, CD_ERR_INVALID_ARG, "unknown selection of boxes");
+    // slot k of frame f = cluster k of its record; a slot that is not selected carries a NaN pose (verified = 0, every count 0:
+    // the zero record)
+    constexpr int B = CD_MAX_CLUSTERS_PER_FRAME;
+    std::vector<double> poses((size_t)F * B * 16, std::numeric_limits<double>::quiet_NaN());
+    std::vector<double> dims((size_t)F * B * 3);
+    std::vector<int32_t> n_boxes((size_t)F, 0);
+    for (size_t i = 0; i < (size_t)F * B; ++i)
+        for (int k = 0; k < 3; ++k) dims[i * 3 + k] = vp->dims[k];
+    for (int f = 0; f < F; ++f) {
+        const int lo = c->last_first[(size_t)f], hi = c->last_first[(size_t)f + 1];
+        if (lo < 0 || hi < lo || (size_t)hi > c->last_clusters.size()) return fail(c, CD_ERR_INVALID_ARG, "no fused call to verify");
+        const int n = std::min(hi - lo, B);
+        n_boxes[(size_t)f] = n;
+        for (int k = 0; k < n; ++k) {
+            const cd_cluster_result& cr = c->last_clusters[(size_t)(lo + k)];
+            if (which != CD_VERIFY_ALL && !cr.accepted) continue;
+            const size_t i = (size_t)f * B + k;
+            std::memcpy(&poses[i * 16], cr.pose, sizeof(cr.pose));
+            if (vp->use_slot_dims && cr.template_slot >= 0 && cr.template_slot < CD_MAX_TEMPLATES)
+                std::memcpy(&dims[i * 3], vp->slot_dims[cr.template_slot], 3 * sizeof(double));
+        }
+    }
+    return stage_verify(c, cam, depth, F, poses.data(), n_boxes.data(), B, dims.data(), vp, out, on_device);
+}
+
 void cd_default_depth_camera(cd_depth_camera* cam) {
     if (!cam) return;
     std::memset(cam, 0, sizeof(*cam));
@@ -3313,6 +3471,81 @@ int cd_overlay_project(const double pose[16], const cd_overlay_params* op, cd_ov
     std::memcpy(out->corners, uv, sizeof(uv));
     out->drawn = 1;
     return CD_OK;
+}
+
+void cd_default_verify_params(cd_verify_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->dims[0] = 0.2; p->dims[1] = 0.1; p->dims[2] = 0.03;               // iterative_closest_point.launch:39-41
+    for (auto& row : p->slot_dims) { row[0] = 0.2; row[1] = 0.1; row[2] = 0.03; }
+    p->tolerance = 0.01;
+    p->min_score = 0.9;
+    p->min_agree = 200;                                                  // object_pose_detection.cpp:356 (the cluster minimum)
+}
+
+int cd_verify_struct_size(int which) {
+    switch (which) {
+        case 0: return (int)sizeof(cd_verify_params);
+        case 1: return (int)sizeof(cd_verify_box);
+        default: return -1;
+    }
+}
+
+int cd_verify_pixel(const cd_depth_camera* cam, const double pose[16], const cd_verify_params* vp, int u, int v, uint16_t d, int32_t* cls, double* z_r) {
+    if (!pose || !cls || !z_r || verify_camera_error(cam)) return CD_ERR_INVALID_ARG;
+    cd_verify_params def;
+    cd_default_verify_params(&def);
+    if (!vp) vp = &def;
+    for (double x : vp->dims) if (!verify_dim_ok(x)) return CD_ERR_INVALID_ARG;
+    if (!verify_dim_ok(vp->tolerance)) return CD_ERR_INVALID_ARG;
+    VerifySetup s;
+    verify_setup(pose, vp->dims, &s);
+    VerifyCounts acc = {0, 0, 0, 0, 0, 0ull};
+    double z = 0.0;
+    *cls = verify_pixel(s, verify_kernel_camera(cam), vp->tolerance, u, v, d, &z, &acc);
+    *z_r = *cls == VERIFY_MISS ? 0.0 : z;
+    return CD_OK;
+}
+
+int cd_verify_box_host(const cd_depth_camera* cam, const uint16_t* depth, const double pose[16], const cd_verify_params* vp, cd_verify_box* out) {
+    if (!depth || !pose || !out || verify_camera_error(cam) || cam->width < 1 || cam->height < 1) return CD_ERR_INVALID_ARG;
+    cd_verify_params def;
+    cd_default_verify_params(&def);
+    if (!vp) vp = &def;
+    if (verify_params_error(vp)) return CD_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof(*out));
+    VerifySetup s;
+    verify_setup(pose, vp->dims, &s);
+    if (!s.verified) return CD_OK;   // the zero record
+    const VerifyCam kc = verify_kernel_camera(cam);
+    VerifyCounts acc = {0, 0, 0, 0, 0, 0ull};
+    for (int v = 0; v < cam->height; ++v)
+        for (int u = 0; u < cam->width; ++u) {
+            double z;
+            verify_pixel(s, kc, vp->tolerance, u, v, depth[(size_t)v * (size_t)cam->width + (size_t)u], &z, &acc);
+        }
+    out->verified = 1;
+    out->n_hit = acc.n_hit; out->n_agree = acc.n_agree; out->n_through = acc.n_through; out->n_occluded = acc.n_occluded; out->n_invalid = acc.n_invalid;
+    out->agree_abs_um = (int64_t)acc.agree_abs_um;
+    verify_finish(vp, out);
+    return CD_OK;
+}
+
+int cd_verify_boxes_batch(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, int n_frames, const double* poses, const int32_t* n_boxes, int boxes_per_frame, const double* box_dims, const cd_verify_params* vp, cd_verify_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_verify_boxes_batch_impl(c, cam, depth, n_frames, poses, n_boxes, boxes_per_frame, box_dims, vp, out, false); });
+}
+int cd_verify_boxes_batch_device(cd_context* c, const cd_depth_camera* cam, const uint16_t* d_depth, int n_frames, const double* poses, const int32_t* n_boxes, int boxes_per_frame, const double* box_dims, const cd_verify_params* vp, cd_verify_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_verify_boxes_batch_impl(c, cam, d_depth, n_frames, poses, n_boxes, boxes_per_frame, box_dims, vp, out, true); });
+}
+int cd_verify_last_results(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, int which, const cd_verify_params* vp, cd_verify_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_verify_last_results_impl(c, cam, depth, which, vp, out, false); });
+}
+int cd_verify_last_results_device(cd_context* c, const cd_depth_camera* cam, const uint16_t* d_depth, int which, const cd_verify_params* vp, cd_verify_box* out) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    return with_scan_retry(c, [&]() { return cd_verify_last_results_impl(c, cam, d_depth, which, vp, out, true); });
 }
 
 int cd_draw_boxes_batch(cd_context* c, uint8_t* rgb8, int width, int height, int n_frames, const double* poses, const int32_t* n_boxes, int boxes_per_frame, const cd_overlay_params* op, cd_overlay_box* out) {

@@ -162,4 +162,13 @@ void launch_overlay_project(hipStream_t s, const double* poses, const int32_t* n
 // img: F images of W * H * 3 bytes, W, H <= 8192; thickness 1 .. 64; boxes: the F * B records of launch_overlay_project
 void launch_overlay_raster(hipStream_t s, uint8_t* img, int W, int H, int B, int F, int thickness, const uint8_t rgb[3], const OverlayBox* boxes);
 
+// k_verify.hip : rule C14, one workgroup per (frame, slot) -> one VerifyRecord (= cd_verify_box without score and passed)
+struct VerifyCam;
+struct VerifyJob { double pose[16]; double dims[3]; };   // what crosses the bus per box: 152 bytes
+struct VerifyRecord { int32_t verified, passed, n_hit, n_agree, n_through, n_occluded, n_invalid, reserved; long long agree_abs_um; double score; };
+// depth: F images of cam.width * cam.height uint16; jobs: F * B, box b of frame f at f * B + b; n_boxes[f] <= B of them exist;
+// out: F * B records (all zero for the slots that do not exist)
+void launch_verify_boxes(hipStream_t s, const uint16_t* depth, const VerifyCam& cam, double tau, const VerifyJob* jobs, const int32_t* n_boxes,
+                         int B, int F, VerifyRecord* out);
+
 }  // namespace cd
