@@ -1,0 +1,403 @@
+// context.hpp - what the host units of the library share: the context, the error and launch macros, the per-device locks and
+// gates, the small-transfer batch and the declarations of every function that more than one unit calls.  Internal: only the
+// units that make up the library driver include it (DESIGN.md lists them).
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+#include <vector>
+
+#include "device_buffer.hpp"
+#include "kernels.hpp"
+#include "shape_frame_math.hpp"
+#include "template_prep.hpp"
+
+using namespace cd;
+
+// What the CUBOID_* environment variables set, read once per context (read_tunables, context.hip).  CUBOID_DEBUG,
+// CUBOID_ICP_GRID_RC and CUBOID_ICP_CELL_FACTOR are read where they are used.
+struct Tunables {
+    bool crop_two_pass = false;   // CUBOID_CROP_TWO_PASS=1: always the two-pass crop
+    int icp_persist = 1;          // CUBOID_ICP_PERSIST=0: the sliced driver always in its multi-launch form; 2: the persistent
+                                  // launch starts with its abort flag raised (tests the hand-over to the multi-launch form)
+    bool crop_runs = true;        // CUBOID_CROP_RUNS=0: the crop writes per-point keys and k_voxel_runs finds the runs (rounds 2-3)
+    int don_idle = 0, don_fault = 0;   // CUBOID_ICP_DON_IDLE / CUBOID_ICP_DON_FAULT: tests of the hand-over path (IcpParams::don_idle / don_fault)
+    int icp_donate = -1;          // CUBOID_ICP_DONATE: -1 auto (a call alone on the device), 0 never, 1 always
+    int force_stall = 0;          // CUBOID_FORCE_SCAN_STALL=n: the next n chained-scan checks report a stall (tests the retry)
+    int icp_mode = 0;             // CUBOID_ICP_MODE: 0 auto, 1 sliced multi-launch, 2 whole-cluster kernel, 3 grouped pipe
+    int icp_max_wg = 0;           // > 0: cap on the persistent ICP grid (CUBOID_ICP_MAX_WG; tests force slot refills with it)
+    int icp_cpw = 0;              // CUBOID_ICP_CPW: clusters per workgroup a persistent ICP launch is sized for (0: by regime, icp_run_whole)
+    int icp_direct = 1;           // CUBOID_ICP_DIRECT=0: an all-lattice ICP stage uploads its lists and reads its results back by copy launches
+    int mirror_reads = 1;         // CUBOID_MIRROR_READS=0: active flags and chosen plane models are uploaded before the kernels that read them
+    int mirror_writes = 1;        // CUBOID_MIRROR_WRITES=0: every host read-back of the FrameState array is a copy launch again
+    int cluster_cells = 1;        // CUBOID_CLUSTER_CELLS=0: frames above 8192 object points straight to the point-graph kernels (rounds 1-5)
+    int crop_direct = 1;          // CUBOID_CROP_DIRECT=0: the crop always copies the kept points (rounds 1-5)
+    int centroid_lanes = 1;       // CUBOID_CENTROID_LANES=0: the quad-per-voxel centroid kernel (rounds 3-5) instead of a lane per voxel
+    bool voxel_runs = true;       // CUBOID_VOXEL_RUNS=0: S1 sorts the cropped points instead of their runs of equal voxel index
+    int icp_slots = 0;            // CUBOID_ICP_SLOTS: clusters in flight per workgroup, 1 .. CD_PIPE_SLOTS (0: by regime)
+    int icp_big_weight = 0;       // workgroup share of a template in global memory, per point (CUBOID_ICP_BIG_WEIGHT; 0 = by the launch's regime, measured on config 5)
+    int icp_lattice = 1;          // CUBOID_ICP_LATTICE=0: lattice templates take the generic searches too (A/B, fallback tests)
+    int zero_once = 1;            // CUBOID_ZERO_ONCE=0: every stage of a fused batch call fills its scratch arrays itself (A/B)
+    int copy_kernels = 1;         // CUBOID_COPY_KERNELS=0: the small pinned <-> device transfers go through hipMemcpyAsync (SDMA) again
+    int lat_shape[3] = {0, 0, 0};   // CUBOID_LAT_SHAPE=cpw,wpc[,per_slot]: clusters per workgroup, waves per cluster, clusters per slot of k_icp_lat (0: by regime)
+    int front_concurrent = 0;     // CUBOID_FRONT_CONCURRENT: at most that many fused batch calls of the device between crop and clusters (0 = no gate)
+    int icp_concurrent = 0;       // CUBOID_ICP_CONCURRENT: admission gate of the whole-cluster ICP launches (0 = none)
+    int icp_lowprio = 1;          // CUBOID_ICP_LOWPRIO: 0 never, 1 the launches of a mixed-template batch (measured: config 5 +30 %), 2 every
+                                  // persistent ICP launch (config 3: -1 %)
+};
+
+// The streams and events of a context.  A base of cd_context, so that they outlive its buffers: the members of cd_context
+// are destroyed (the buffers freed) before this destructor runs.  stream2 / stream3: the streams of the persistent ICP
+// launches: the second launch of a mixed-template batch runs beside the first (stream2); with icp_lowprio both are low-priority
+// streams, so that CUs that come free go to the short front-end kernels of the other batches in flight before the next
+// persistent workgroup
+struct cd_streams {
+    hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;
+    hipEvent_t ev[8] = {nullptr}, ev2[3] = {nullptr, nullptr, nullptr};
+    ~cd_streams() {
+        for (auto& e : ev2) if (e) hipEventDestroy(e);
+        for (auto& e : ev) if (e) hipEventDestroy(e);
+        for (hipStream_t s : {stream2, stream3, stream}) if (s) hipStreamDestroy(s);
+    }
+};
+
+// Every buffer is an owning member (device_buffer.hpp): allocated in cd_create or grown on first use (GROW), freed with the context.
+struct cd_context : cd_streams {
+    int device = 0;
+    int N = 0, F = 0, T = 0;   // capacities: points per frame, frames, tiles per frame
+    char err[512] = {0};
+    Tunables tun;
+    // input staging (host-pointer API)
+    DevBuf<char> d_in;   // (capacity in bytes)
+    // depth-image input (cd_process_depth_batch): upload buffers of their own, allocated at the context's capacity on first use
+    // (d_in is the deprojection's destination, is re-allocated by ensure_input and is the read-back staging area)
+    DevBuf<uint16_t> d_depth;
+    DevBuf<uint8_t> d_color;
+    // per-frame scalars
+    DevBuf<FrameState> d_fs;
+    PinBuf<FrameState> h_fs;
+    // ordered-compaction tile counters
+    DevBuf<int> d_tileA, d_tileB, d_tileK, d_tileC;   // (tileC: the centroid kernel's scan state - its own array, so that one launch can zero every array of a batch up front)
+    bool batch_zeroed = false;      // a fused batch call has zeroed the scratch arrays of all its stages in one launch (zero_batch_scratch): the stages skip their own fills
+    // point buffers (float4 = x,y,z,rgb bits)
+    DevBuf<float4> d_cpt, d_vox, d_obj, d_src0, d_src;
+    DevBuf<uint32_t> d_key[2], d_val[2], d_ghist;
+    DevBuf<int> d_sstate;   // chained-scan state of the radix passes, [pass][F][scatter tiles][256]
+    DevBuf<unsigned long long> d_tile64;   // chained-scan state of k_crop_runs: (points, runs) per tile, [F][T]
+    DevBuf<int> d_ticket;   // ticket counters, one per frame (TICKET_PITCH ints apart), of the kernels that scan over tiles (take_ticket, common.hpp): zero between launches
+    // RANSAC
+    DevBuf<int> d_rnd, d_valid, d_counts, d_active, d_have;
+    PinBuf<int> h_valid, h_counts, h_active, h_have;
+    DevBuf<float4> d_models, d_model;
+    PinBuf<float4> h_model, h_models;
+    DevBuf<unsigned long long> d_sums;
+    PinBuf<unsigned long long> h_sums;
+    // extract / cluster
+    DevBuf<int> d_plane_idx, d_head, d_next, d_parent, d_csize, d_rank, d_cand, d_sizes, d_label;
+    // templates
+    DevBuf<float4> d_tpl, d_tlo, d_thi;   // points + per-64-run boxes
+    DevBuf<float4> d_tplk, d_tlok, d_thik;   // templates in k-d patch order (sliced path)
+    DevBuf<IcpGrid> d_grid;                                       // per template slot
+    DevBuf<unsigned short> d_kdmap;                               // k-d patch order -> cell-sorted position (resident templates)
+    DevBuf<unsigned short> d_tcell;                               // cell start tables, ICP_CELL_STRIDE entries per slot
+    DevBuf<int> d_nn;                                             // last NN index of every ICP source point
+    DevBuf<float> d_d2;                                           // its squared distance
+    DevBuf<int> d_queue;                                          // ICP work queue heads (one per template group)
+    DevBuf<int> d_don;                                            // k_icp_pipe: hand-over control block + mailbox (common.hpp DON_*)
+    DevBuf<int> d_wgtab;                                          // k_icp_pipe: {first item, end item, queue} per workgroup
+    PinBuf<int> h_wgtab;                                          // its pinned staging copy (3 * 1024 ints)
+    PinBuf<int> h_ctl;                                            // pinned: control words of k_icp_persist going up [0..7], coming back [8]
+    std::vector<IcpState> st_init;                                // initial ICP states of a persistent launch (kept in case it gives up)
+    int scan_retries = 0;                                         // calls of this context that were redone because a chained scan stalled
+    int persist_gave_up = 0;                                      // persistent launches of this context that handed over to the multi-launch loop
+    int n_cu = 256;
+    bool fs_initialised = false;                                  // the device FrameStates hold their initial value (set by the zero launch of a fused batch call)
+    DevBuf<int> d_order; PinBuf<int> h_order;                     // clusters, largest first
+    int tpl_cap = 0, tpl_used = 0;
+    std::shared_ptr<const cd::PreparedTemplate> tpl_prep[CD_MAX_TEMPLATES];   // host copies (shared across contexts)
+    int tpl_off[CD_MAX_TEMPLATES] = {0}, tpl_m[CD_MAX_TEMPLATES] = {0};
+    bool tpl_gridded[CD_MAX_TEMPLATES] = {false};                // slot has a cell start table
+    bool tpl_big[CD_MAX_TEMPLATES] = {false};                    // slot does not fit LDS but has what k_icp_pipe_big needs (cell table, k-d map, superpatches)
+    DevBuf<IcpSuper> d_super;                                     // per template slot
+    DevBuf<IcpLattice> d_lat;                                     // per template slot: axis tables and faces of a lattice template (nface = 0: none)
+    int tpl_faces[CD_MAX_TEMPLATES] = {0};                        // faces of the slot's lattice (0: the generic searches take it)
+    // ICP
+    DevBuf<IcpCluster> d_cl; PinBuf<IcpCluster> h_cl;
+    DevBuf<IcpWork> d_work, d_work2; PinBuf<IcpWork> h_work, h_work2;
+    int work_cap = 0;                                             // items the work lists hold
+    int cl_cap = 0;                                               // ICP problems the cluster arrays hold (grown on demand)
+    DevBuf<int> d_koffx;                                          // offsets of the clusters ranked >= KICP, [round][F][KICP]
+    std::vector<cd_cluster_result> last_clusters;                 // every cluster result of the last batch, frame-major
+    std::vector<int> last_first;                                  // index of frame f's first cluster in it (F + 1 entries)
+    // clouds of the last batch that stay resident for cd_get_frame_cloud / cd_get_cluster_points
+    std::vector<int> last_nv, last_no;                            // voxels / object points per frame
+    std::vector<long long> last_orig_off, last_al_off;            // per cluster: offset of its points in d_src0; of its aligned points in d_src (-1: not resident)
+    bool last_clouds = false;
+    // initial guesses (cd_set_frame_guesses), and their device copy (also used for the single guess of cd_params)
+    std::vector<float> frame_guess;
+    DevBuf<float> d_guess;
+    // ICP maximum correspondence distance (cd_set_icp_max_correspondence_distance, rule C8): the distance as set, its float
+    // threshold on d2 and whether it bounds anything; d_ncorr: kept-correspondence counts of the sliced / persistent drivers
+    double icp_max_dist = std::numeric_limits<double>::infinity();
+    float icp_d2_max = std::numeric_limits<float>::infinity();
+    int icp_bounded = 0;
+    DevBuf<uint32_t> d_ncorr;
+    // batched surface-normal estimation (cd_surface_batch, CD_GUESS_SURFACE, stage_surface): FrameStates, plane models and point
+    // buffers of its own, allocated on first use, so that the S2 plane, the clouds and the plane indices of a fused call stay
+    // as they are; s_pts[0..1]: the current and the next cloud of every frame, rows of s_pitch points
+    DevBuf<FrameState> d_sfs; PinBuf<FrameState> h_sfs;
+    DevBuf<float4> d_smodel, d_spts[2]; PinBuf<float4> h_smodel;
+    DevBuf<int> d_shave, d_sactive, d_sidx; PinBuf<int> h_shave, h_sactive;
+    DevBuf<float4> d_ssum; PinBuf<float4> h_ssum;                // [F][3] midpoint sums of the three fits (x, y, z, count bits)
+    double surface_thr = 0.015;                                   // cd_set_surface_distance_threshold (surface_normal_estimation.launch)
+    std::vector<float> surface_guess;                             // rule C9 guesses of the last CD_GUESS_SURFACE call, 16 per frame
+    std::vector<cd_surface_frame_result> last_surface;            // cd_get_surface_results
+    std::vector<int32_t> last_surface_status;
+    bool last_surface_ok = false;
+    // colour gate (rule C10, k_color.hip): the sdiv / hdiv tables, one record and one status per frame (device + pinned mirror),
+    // the union-find labels and (images whose packed mask does not fit LDS only) the mask buffers, both allocated on first use
+    DevBuf<int> d_ctab, d_cstatus, d_clabel; PinBuf<int> h_cstatus;
+    DevBuf<ColorRecord> d_crec; PinBuf<ColorRecord> h_crec;
+    DevBuf<uint32_t> d_cmask;
+    // where the fused calls' gate takes its rectangle from (cd_set_bbox_source), the rectangles cd_set_frame_bboxes stored and
+    // their device copy; call_rects: what the gate kernels of the fused call in flight read (nullptr outside one, and for CD_BBOX_PARAMS)
+    int bbox_source = CD_BBOX_PARAMS;
+    cd_color_gate_params color_prm;
+    std::vector<int32_t> frame_rects;
+    DevBuf<int32_t> d_rects; PinBuf<int32_t> h_rects;
+    FrameRects call_rects{nullptr, 0};
+    std::vector<cd_color_bbox> last_bboxes;                       // cd_get_frame_bboxes
+    bool last_bboxes_ok = false;
+    // overlay (rule C11, k_overlay.hip): poses, box counts and box records of a draw call, grown on demand (boxes: device + pinned mirror)
+    DevBuf<double> d_oposes;
+    DevBuf<int32_t> d_onbox;
+    DevBuf<OverlayBox> d_obox; PinBuf<OverlayBox> h_obox;
+    // pose verification (rule C14, k_verify.hip), all grown on demand: the depth images of the host forms (a buffer nothing else
+    // reads or stages through), and per (frame, slot) the pose + dims going up and the record coming back (device + pinned mirror)
+    DevBuf<uint16_t> d_vdepth;
+    DevBuf<VerifyJob> d_vjob; PinBuf<VerifyJob> h_vjob;
+    DevBuf<int32_t> d_vnbox; PinBuf<int32_t> h_vnbox;
+    DevBuf<VerifyRecord> d_vrec; PinBuf<VerifyRecord> h_vrec;
+    // per-cluster principal frames (rule C13, k_shape.hip), all allocated on first use: the template records of every slot (pinned
+    // table, uploaded when a template has changed since), one record per ICP problem of a CD_GUESS_CLUSTER stage (device + pinned
+    // mirror), and the points / set list of cd_shape_frames
+    DevBuf<ShapeFrame> d_tframe; PinBuf<ShapeFrame> h_tframe;
+    ShapeFrame tpl_frame[CD_MAX_TEMPLATES] = {};                  // the slots' records (cd_set_template computes them on the host)
+    bool tframe_dirty = true;
+    DevBuf<ShapeFrame> d_shape; PinBuf<ShapeFrame> h_shape;
+    DevBuf<float4> d_shpts;
+    DevBuf<IcpCluster> d_shcl;
+    std::vector<cd_shape_frame> last_shapes;                      // cd_get_cluster_shape_frames: one per cluster of the last fused call, frame-major
+    bool last_shapes_ok = false;
+    DevBuf<IcpState> d_st; PinBuf<IcpState> h_st;
+    DevBuf<unsigned long long> d_acc, d_accf; PinBuf<unsigned long long> h_accf;
+    cd_timing timing;
+};
+
+#define HIPCHK(ctx, expr)                                                                                   \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) {                                                                             \
+            snprintf((ctx)->err, sizeof((ctx)->err), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                     __FILE__, __LINE__);                                                                   \
+            return CD_ERR_DEVICE;                                                                           \
+        }                                                                                                   \
+    } while (0)
+
+// kernel launches report a bad configuration (grid, LDS size, arguments) through hipGetLastError only: name the kernel
+#define LAUNCH(ctx, call)                                                                                     \
+    do {                                                                                                      \
+        call;                                                                                                 \
+        hipError_t e_ = hipGetLastError();                                                                    \
+        if (e_ != hipSuccess) {                                                                               \
+            snprintf((ctx)->err, sizeof((ctx)->err), "launch failed: %s: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                     __FILE__, __LINE__);                                                                     \
+            return CD_ERR_DEVICE;                                                                             \
+        }                                                                                                     \
+    } while (0)
+
+namespace cd {
+// the per-batch read-backs (cd_get_cluster_results, cd_get_frame_cloud, cd_get_cluster_points) describe the last fused call;
+// every other compute call reuses the same device buffers
+inline void invalidate_last(cd_context* c) {
+    c->last_clouds = false;
+    c->last_first.clear();
+    c->last_surface_ok = false;
+    c->last_bboxes_ok = false;
+    c->last_shapes_ok = false;
+}
+
+inline int fail(cd_context* c, int code, const char* msg) {
+    snprintf(c->err, sizeof(c->err), "%s", msg);
+    return code;
+}
+
+// ---- chained scans and several contexts on one GPU ---------------------------------------------------------------------------
+// A chained scan (crop, radix scatters, voxel heads, cd_extract) waits for tiles with smaller ids.  Since round 4 the ids are
+// atomic tickets (take_ticket, common.hpp): the holder of a ticket has started, so a wait can only be for a workgroup that is
+// running or done - finite by construction, whatever else shares the GPU.  (Rounds 1-3 took the ids from blockIdx and relied
+// on the order in which an XCD starts a grid's workgroups; with several contexts in flight that argument had a hole.)  What is
+// left of the old answer to that hole is a safety net that cannot trigger on its own: the waits are still bounded
+// (common.hpp), a kernel that gives up reports scan_stalled, and the call is REDONE ALONE - every compute call holds this
+// per-device lock shared, the redo exclusively.  CUBOID_FORCE_SCAN_STALL exercises the path.
+// The redo must not starve: libstdc++'s shared_mutex is a reader-preferring pthread_rwlock, and with five contexts calling
+// back to back some reader nearly always holds it.  So every call first passes a turnstile (a plain mutex, taken and
+// released at once); a redo holds the turnstile while it waits for the exclusive lock - new calls queue behind it, the
+// calls in flight drain, the redo runs, the queue moves on (tests/test_gpu_readback_guess.py, saturated pipeline).
+constexpr int CD_INTERNAL_STALL = -100;   // never leaves the library
+constexpr int MAX_DEVICES = 16;
+
+// Admission gate of the whole-cluster ICP launches (CUBOID_ICP_CONCURRENT = K; 0 = none): at most K contexts of a device are
+// between the launch of their persistent ICP kernel and its completion.  The launches of several batches otherwise share the
+// CUs workgroup by workgroup (processor sharing: five batches submitted together all finish late, together); through the gate
+// they run K at a time, first come first served, so the first batches of a burst come back early and their contexts refill
+// the pipeline.
+struct IcpGate {
+    std::mutex mu;
+    std::condition_variable cv;
+    int inside = 0;
+    void enter(int k) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return inside < k; }); ++inside; }
+    void leave() { { std::lock_guard<std::mutex> lk(mu); --inside; } cv.notify_one(); }
+};
+struct GateHold {   // (released on every path out of its scope)
+    IcpGate* g = nullptr;
+    void enter(IcpGate* gate, int k) { g = gate; g->enter(k); }
+    void release() { if (g) { g->leave(); g = nullptr; } }
+    ~GateHold() { release(); }
+};
+
+// What the contexts of one device share.  ONE object per device and process: the table is defined in context.hip and reached
+// through device_shared only - a copy per unit would give each unit locks of its own.
+struct DeviceShared {
+    std::shared_mutex scan_mu;
+    std::mutex turnstile;
+    std::atomic<int> calls_in_flight{0};     // one per compute call: counts the contexts at work on the device (k_icp_persist wants the chip to itself)
+    std::atomic<int> batches_in_flight{0};   // fused batch calls only: what the launch regime of the whole-cluster ICP kernel looks at
+                                             // (a cd_bbox_filter or cd_extract beside a batch must not change the shape of its ICP launch)
+    IcpGate icp_gate;
+    IcpGate front_gate;   // the same for the front end (crop .. clusters) of the fused batch calls: CUBOID_FRONT_CONCURRENT
+};
+DeviceShared& device_shared(const cd_context* c);
+
+struct InFlight {   // counts its holder in for its lifetime
+    std::atomic<int>& n;
+    explicit InFlight(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+    ~InFlight() { n.fetch_sub(1); }
+};
+
+// An entry point that runs under the per-device scan lock is `return with_scan_retry(c, [&] { return X_impl(c, ...); });`: the
+// null check, the device selection (once: a redo runs on the same thread), then the call under the lock.  The host-only entries,
+// the setters and getters, the read-backs, cd_set_template and cd_template_nearest take no lock, as before, and do their own.
+template <class Fn>
+int with_scan_retry(cd_context* c, Fn&& fn) {
+    if (!c) return CD_ERR_INVALID_ARG;
+    hipSetDevice(c->device);
+    DeviceShared& ds = device_shared(c);
+    int st;
+    {
+        { std::lock_guard<std::mutex> pass(ds.turnstile); }   // held by a pending redo: wait behind it
+        std::shared_lock<std::shared_mutex> lk(ds.scan_mu);
+        InFlight g(ds.calls_in_flight);
+        st = fn();
+    }
+    if (st != CD_INTERNAL_STALL) return st;
+    if (std::getenv("CUBOID_DEBUG")) std::fprintf(stderr, "cuboid_hip: %s - redoing the call with the device to itself\n", c->err);
+    c->scan_retries += 1;
+    hipStreamSynchronize(c->stream);
+    {
+        std::lock_guard<std::mutex> hold(ds.turnstile);          // no new call starts until this redo is done
+        std::unique_lock<std::shared_mutex> lk(ds.scan_mu);      // ... and the calls in flight have drained
+        InFlight g(ds.calls_in_flight);
+        st = fn();
+    }
+    c->timing.scan_retries = 1;
+    if (st == CD_INTERNAL_STALL) return fail(c, CD_ERR_DEVICE, "a chained scan stalled twice, the second time with the device to itself");
+    return st;
+}
+}  // namespace cd
+
+// grows a buffer of the context to hold `n` elements (OwnedBuf::ensure: a no-op when it is large enough, otherwise the context's
+// stream is synchronised, the old memory freed and new allocated; contents are not kept)
+#define GROW(ctx, buf, n) HIPCHK(ctx, (ctx)->buf.ensure((ctx)->stream, (n), #buf))
+
+const int FS_PITCH = (int)(sizeof(FrameState) / sizeof(int));
+#define FS_FIELD(ctx, field) ((int*)((char*)(ctx)->d_fs.get() + offsetof(FrameState, field)))
+
+// a stage's zero-fill of one of its scratch arrays - skipped when the fused batch call has zeroed them all in one launch
+#define ZERO_FILL(ctx, ptr, bytes)                                                            \
+    do {                                                                                      \
+        if (!(ctx)->batch_zeroed) HIPCHK(ctx, hipMemsetAsync((ptr), 0, (bytes), (ctx)->stream)); \
+    } while (0)
+
+namespace cd {
+// consecutive small transfers of a stage collected into one launch (xfer's fallback applies: without copy kernels, or for a
+// width that is no multiple of 4, each goes through the runtime's copy as before)
+struct XferBatch {
+    cd_context* c;
+    CopyList L;
+    hipError_t err = hipSuccess;
+    explicit XferBatch(cd_context* ctx) : c(ctx) { L.n = 0; }
+    void add2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, int rows, hipMemcpyKind kind) {
+        if (err != hipSuccess || width == 0 || rows <= 0) return;
+        if (!c->tun.copy_kernels || (width & 3) || (dpitch & 3) || (spitch & 3)) { err = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, c->stream); return; }
+        if (L.n == 8) flush();
+        L.seg[L.n++] = CopySeg{(uint32_t*)dst, (const uint32_t*)src, dpitch / 4, spitch / 4, (int)(width / 4), rows};
+    }
+    void add(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { add2d(dst, bytes, src, bytes, bytes, 1, kind); }
+    hipError_t flush() {
+        if (L.n > 0 && err == hipSuccess) { launch_copy_list(c->stream, L); err = hipGetLastError(); }
+        L.n = 0;
+        return err;
+    }
+};
+
+// depth images of a batch on the device, deprojected into the records d_frames of the fused call (k_depth.hip)
+struct DepthJob {
+    const cd_depth_camera* cam;
+    const uint16_t* depth;
+    const uint8_t* color;   // nullptr: no colour
+    const cd_color_camera* ccam = nullptr;   // a mapped call (rule C12, k_texture.hip): `color` is ccam->width x ccam->height per frame
+};
+
+// ---- context.hip
+hipError_t copy_sync(cd_context* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+hipError_t xfer(cd_context* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+int ensure_input(cd_context* c, size_t bytes);
+int ensure_clusters(cd_context* c, int ncl, long long points);
+int sync_fs(cd_context* c, int F, bool copied = false);   // copied: the caller has put the FrameState read-back on the stream already
+int upload_points(cd_context* c, const void* pts, size_t stride, int n, float4* dst);
+int check_params(cd_context* c, const cd_params* p);
+int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, int rgb_offset, uint32_t pad3, void* out, size_t staging_skip = 0);
+// ---- cuboid_hip.hip
+int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int F, const cd_params* p, int* rounds_out);
+int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iterations, int* rounds_out, const float* axes = nullptr);
+int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode = -1);
+int stage_cluster_sync(cd_context* c, int F, const cd_params* p, int max_no);
+void set_icp_clusters(cd_context* c, int first, int n, int frame, const int* size, const int* off, int base, int slot);
+ShapeFrame template_frame(const cd_context* c, int slot);
+int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests);
+void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_cluster_result* r);
+// ---- surface.hip
+int ensure_surface(cd_context* c, size_t pitch);
+int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,
+                  int invert, const cd_params* p, cd_surface_frame_result* res, int32_t* status);
+void surface_record(int counts[3], float normals[3][4], float mids[3][4], cd_surface_frame_result* r);
+int surface_guesses(cd_context* c, int F, const cd_params* p, std::vector<char>* flagged);
+int check_color_params(cd_context* c, const cd_color_gate_params* g);
+int stage_color(cd_context* c, const uint8_t* d_rgb, int W, int H, int F, const cd_color_gate_params* g);
+int color_status(cd_context* c, int F);
+// ---- images.hip
+void launch_depth_job(hipStream_t s, const DepthJob* dj, int F, float4* out);
+int check_depth(cd_context* c, const cd_depth_camera* cam, const void* depth, const void* color, int n_frames);
+int check_mapped(cd_context* c, const cd_depth_camera* cam, const cd_color_camera* cc, const void* depth, const void* color, int n_frames);
+int upload_depth(cd_context* c, const cd_depth_camera* cam, const uint16_t* depth, const uint8_t* color, int n_frames, DepthJob* dj,
+                 const cd_color_camera* ccam = nullptr);
+}  // namespace cd
