@@ -128,6 +128,7 @@ static void read_tunables(Tunables* t) {
     flag("CUBOID_CENTROID_LANES", &t->centroid_lanes);
     flag("CUBOID_CROP_DIRECT", &t->crop_direct);
     flag("CUBOID_CLUSTER_CELLS", &t->cluster_cells);
+    flag("CUBOID_CLUSTER_TIERS", &t->cluster_tiers);
     flag("CUBOID_MIRROR_WRITES", &t->mirror_writes);
     flag("CUBOID_MIRROR_READS", &t->mirror_reads);
     flag("CUBOID_ICP_DIRECT", &t->icp_direct);

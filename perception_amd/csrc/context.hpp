@@ -39,6 +39,8 @@ struct Tunables {
     int mirror_reads = 1;         // CUBOID_MIRROR_READS=0: active flags and chosen plane models are uploaded before the kernels that read them
     int mirror_writes = 1;        // CUBOID_MIRROR_WRITES=0: every host read-back of the FrameState array is a copy launch again
     int cluster_cells = 1;        // CUBOID_CLUSTER_CELLS=0: frames above 8192 object points straight to the point-graph kernels (rounds 1-5)
+    int cluster_tiers = 1;        // CUBOID_CLUSTER_TIERS=0: k_cluster_lds (150 KiB of LDS, 1024 threads) for every frame up to 8192 object points, and
+                                  // the 64 KiB sampler map for every RANSAC round, as before the small tiers
     int crop_direct = 1;          // CUBOID_CROP_DIRECT=0: the crop always copies the kept points (rounds 1-5)
     int centroid_lanes = 1;       // CUBOID_CENTROID_LANES=0: the quad-per-voxel centroid kernel (rounds 3-5) instead of a lane per voxel
     bool voxel_runs = true;       // CUBOID_VOXEL_RUNS=0: S1 sorts the cropped points instead of their runs of equal voxel index
@@ -202,7 +204,15 @@ struct cd_context : cd_streams {
     cd_timing timing;
 };
 
-#define HIPCHK(ctx, expr)                                                                                   \
+// Where k_ransac_sample's small shuffle map goes when it fills up: SAMPLER_SPILL_PITCH ints per frame, of which the kernel uses
+// 2 * SAMPLER_MAP (k_plane.hip asserts that they fit).  The area IS d_head, the bucket heads of the point-graph clustering: the
+// plane stage ends before the clustering starts on the context's one stream, stage_cluster fills d_head with 0xff before
+// k_cluster_build reads it, and every batch in flight has a context of its own.  Whoever gives d_head another user between the
+// plane stage and the clustering has to give the sampler a buffer of its own here.
+constexpr int SAMPLER_SPILL_PITCH = CELL_BUCKETS;
+inline int* sampler_spill_area(const cd_context* c) { return c->d_head.get(); }
+
+#define HIPCHK(ctx, expr)                                                                                  \
     do {                                                                                                    \
         hipError_t e_ = (expr);                                                                             \
         if (e_ != hipSuccess) {                                                                             \

@@ -162,7 +162,10 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
         // the pinned host arrays, which the device sees; CUBOID_MIRROR_READS=0 uploads them first as rounds 1-5 did)
         if (!mr) HIPCHK(c, xfer(c, c->d_active, c->h_active, sizeof(int) * F, hipMemcpyHostToDevice));
         const int* active_p = mr ? c->h_active : c->d_active;
-        LAUNCH(c, launch_ransac_sample(c->stream, c->d_vox, c->N, F, c->d_fs, c->d_rnd, h_target, active_p, c->d_models, c->d_valid));
+        // (the rounds of 16 and 64 hypotheses with the sampler's 8 KiB map; should a frame's map fill up it moves to the frame's
+        // part of the spill area: context.hpp)
+        LAUNCH(c, launch_ransac_sample(c->stream, c->d_vox, c->N, F, c->d_fs, c->d_rnd, h_target, active_p, c->d_models, c->d_valid,
+                                       c->tun.cluster_tiers ? sampler_spill_area(c) : nullptr, SAMPLER_SPILL_PITCH));
         LAUNCH(c, launch_ransac_count(c->stream, c->d_vox, c->N, F, Tv, c->d_fs, c->d_models, c->d_valid, active_p, h_prev, h_target, thr, c->d_counts));
         // only the first h_target columns of the [F][MAX_HYP] tables are live: one strided copy each
         {   // (one launch: the three tables and - sync_fs below finds it done - nothing else; the FrameState read-back follows)
@@ -268,14 +271,23 @@ int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode) {
 }
 
 // S5.  in: d_obj + fs.n_o (device).  out: d_label, d_sizes, fs.n_k/ksize/koff, d_src0/d_src
-static int stage_cluster(cd_context* c, int F, const cd_params* p, int max_no_hint, bool force_global = false) {
+// level: which kernels cluster the frames.  CL_LEVEL_TIER: the small tier alone (every frame has at most CL_TIER_CAP points);
+// CL_LEVEL_TOP: k_cluster_lds, and k_cluster_cells behind it when a frame has more than 8192 points; CL_LEVEL_GLOBAL: the same
+// with the point-graph kernels behind them.  A frame that a level gives up (fs.cl_done == 0) is taken by the next one.
+enum { CL_LEVEL_TIER = 0, CL_LEVEL_TOP = 1, CL_LEVEL_GLOBAL = 2 };
+static int stage_cluster(cd_context* c, int F, const cd_params* p, int max_no_hint, int level) {
     const int T = c->T;
     const int To = std::max(1, (max_no_hint + TILE - 1) / TILE);
     const float cell = (float)(p->cluster_tolerance * (1.0 + 1.0 / 1024.0));
     const float inv_cell = 1.0f / cell;
     const float r2 = (float)(p->cluster_tolerance * p->cluster_tolerance);
     const float small_cell = (float)(p->cluster_tolerance / std::sqrt(3.0) * (1.0 - 1.0 / 1024.0));
-    if (p->cluster_enable) {
+    const bool force_global = level == CL_LEVEL_GLOBAL;
+    if (p->cluster_enable && level == CL_LEVEL_TIER) {
+        // the same cell graph as below with the cell table in 27 KiB of LDS and the points in cell order in d_src (free until the
+        // labels are scattered; 70 KB per frame: it stays in L2): a workgroup that finds room beside the other batches' kernels
+        LAUNCH(c, launch_cluster_tier(c->stream, c->d_obj, c->N, F, c->d_fs, 1.0f / small_cell, r2, c->d_parent, c->d_csize, c->d_rank, c->d_src));
+    } else if (p->cluster_enable) {
         // frames with <= 8192 object points (the usual case) are clustered by one workgroup in LDS, over cells small
         // enough (edge just under tol / sqrt(3)) that the points of one cell are connected by construction ...
         LAUNCH(c, launch_cluster_lds(c->stream, c->d_obj, c->N, F, c->d_fs, 1.0f / small_cell, r2, c->d_parent, c->d_csize, c->d_rank));
@@ -302,21 +314,25 @@ static int stage_cluster(cd_context* c, int F, const cd_params* p, int max_no_hi
 }
 
 // stage_cluster + sync; when the LDS kernel gave a frame up (too many cells / too wide a cloud for its table) and the
-// global-memory kernels were not part of the launch, the stage is run again with them.
+// global-memory kernels were not part of the launch, the stage is run again with them.  The first launch is the small tier's
+// when the largest frame fits it (CUBOID_CLUSTER_TIERS=0: never); what that gives up goes to k_cluster_lds first.
 int stage_cluster_sync(cd_context* c, int F, const cd_params* p, int max_no) {
     const bool mirrored = c->tun.mirror_writes && c->tun.copy_kernels;   // (k_cluster_rank wrote the FrameState mirror)
-    int st = stage_cluster(c, F, p, max_no);
-    if (st) return st;
-    st = sync_fs(c, F, mirrored);
-    if (st || !p->cluster_enable || (max_no > 8192 && !c->tun.cluster_cells)) return st;   // (the point-graph kernels were part of the launch)
-    bool left = false;
-    for (int f = 0; f < F; ++f) left = left || (c->h_fs[f].n_o > 0 && !c->h_fs[f].cl_done);
-    if (!left) return CD_OK;
-    if (std::getenv("CUBOID_DEBUG")) std::fprintf(stderr, "cuboid_hip: LDS clustering gave frames up, running the global-memory path\n");
-    c->batch_zeroed = false;   // (d_tileK has been used: the redo fills it again)
-    st = stage_cluster(c, F, p, max_no, true);
-    if (st) return st;
-    return sync_fs(c, F, mirrored);
+    int level = c->tun.cluster_tiers && max_no <= CL_TIER_CAP ? CL_LEVEL_TIER : CL_LEVEL_TOP;
+    for (;;) {
+        int st = stage_cluster(c, F, p, max_no, level);
+        if (st) return st;
+        st = sync_fs(c, F, mirrored);
+        if (st || !p->cluster_enable || level == CL_LEVEL_GLOBAL) return st;
+        if (level == CL_LEVEL_TOP && max_no > CL_TOP_CAP && !c->tun.cluster_cells) return st;   // (the point-graph kernels were part of the launch)
+        bool left = false;
+        for (int f = 0; f < F; ++f) left = left || (c->h_fs[f].n_o > 0 && !c->h_fs[f].cl_done);
+        if (!left) return CD_OK;
+        ++level;
+        if (std::getenv("CUBOID_DEBUG"))
+            std::fprintf(stderr, "cuboid_hip: LDS clustering gave frames up, running %s\n", level == CL_LEVEL_TOP ? "the top tier" : "the global-memory path");
+        c->batch_zeroed = false;   // (d_tileK has been used: the redo fills it again)
+    }
 }
 
 // IcpCluster records h_cl[first .. first + n) of the clusters 0 .. n-1 of one frame against template `slot`: sizes size[0..n),

@@ -178,7 +178,7 @@ extern "C" int cd_debug_cluster(unsigned long long* out, int reset) {
 #else
 #define CL_PHASE(k)
 #endif
-constexpr int CL_LDS_CAP = 8192;
+constexpr int CL_LDS_CAP = CL_TOP_CAP;
 constexpr int CL_SLOTS = 4096;          // cell table (power of two)
 constexpr int CL_MAX_CELLS = 3072;      // load factor <= 3/4
 constexpr int CL_COORD_MIN = -1;        // a centroid may round one ulp below the cloud's minimum
@@ -205,9 +205,11 @@ struct ClOffsets {
 };
 __constant__ ClOffsets cl_offsets = ClOffsets();
 
+template <int SLOTS>
 __device__ __forceinline__ uint32_t cl_slot_hash(int key) {
+    static_assert(SLOTS > 0 && (SLOTS & (SLOTS - 1)) == 0 && SLOTS <= (1 << 15), "a power of two within the hash's 15 bits");
     uint32_t h = (uint32_t)key * 2654435761u;
-    return (h >> 17) & (CL_SLOTS - 1);
+    return (h >> 17) & (SLOTS - 1);
 }
 // find with path halving; parents live in LDS (coherent within the workgroup).  A halving store
 // only ever re-points a NON-root at one of its ancestors, so it cannot disturb the root CAS.
@@ -221,20 +223,21 @@ __device__ __forceinline__ int lds_find(int* par, int x) {
     }
     return x;
 }
-// slot of a cell key, or -1 (the table always keeps empty slots: CL_MAX_CELLS < CL_SLOTS)
+// slot of a cell key, or -1 (the table always keeps empty slots: at most 3/4 of its SLOTS hold a cell)
+template <int SLOTS>
 __device__ __forceinline__ int cl_lookup(const int* s_key, int key) {
-    int h = (int)cl_slot_hash(key);
+    int h = (int)cl_slot_hash<SLOTS>(key);
     for (;;) {
         const int k = s_key[h];
         if (k == key) return h;
         if (k == -1) return -1;
-        h = (h + 1) & (CL_SLOTS - 1);
+        h = (h + 1) & (SLOTS - 1);
     }
 }
 // cell `ha` against the cell at packed offset `delta`: union the two when one pair of points is closer than tol
 __device__ __forceinline__ void cl_join(const int* s_key, const int* s_val, int* s_par, const float* s_x, const float* s_y,
                                         const float* s_z, int ha, int key, int delta, float r2, int& ra) {
-    const int hb = cl_lookup(s_key, key + delta);
+    const int hb = cl_lookup<CL_SLOTS>(s_key, key + delta);
     if (hb < 0) return;
     int rb = lds_find(s_par, hb);
     if (rb == ra) return;
@@ -268,8 +271,8 @@ __device__ __forceinline__ void cl_join(const int* s_key, const int* s_val, int*
 // leaves it as n components of size 0 without a rank (what k_cluster_build starts from): every index the later kernels of the
 // launch read is then one that was written, and they find no cluster to label.  Call from every thread of the workgroup.
 __device__ __forceinline__ void cl_leave_frame(int* __restrict__ parent, int* __restrict__ csize, int* __restrict__ rank_of_root,
-                                               size_t fbase, int n) {
-    for (int i = threadIdx.x; i < n; i += CL_THREADS) {
+                                               size_t fbase, int n, int threads) {
+    for (int i = threadIdx.x; i < n; i += threads) {
         parent[fbase + i] = i;
         csize[fbase + i] = 0;
         rank_of_root[fbase + i] = -1;
@@ -317,7 +320,7 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_lds(const float4* __rest
             bool ok = cx >= CL_COORD_MIN && cy >= CL_COORD_MIN && cz >= CL_COORD_MIN && cx <= CL_COORD_MAX && cy <= CL_COORD_MAX && cz <= CL_COORD_MAX;
             if (ok) {
                 const int key = (cx + 3) | ((cy + 3) << 10) | ((cz + 3) << 20);
-                int h = (int)cl_slot_hash(key);
+                int h = (int)cl_slot_hash<CL_SLOTS>(key);
                 ok = false;
                 for (int probe = 0; probe < CL_SLOTS; ++probe) {
                     const int old = atomicCAS(&s_key[h], -1, key);
@@ -339,7 +342,7 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_lds(const float4* __rest
     __syncthreads();
     const int ncell = s_ncell;
     if (s_bail || ncell > CL_MAX_CELLS) {     // uniform: leave the frame to the global-memory kernels
-        cl_leave_frame(parent, csize, rank_of_root, fbase, n);
+        cl_leave_frame(parent, csize, rank_of_root, fbase, n, CL_THREADS);
         if (tid == 0) fs[f].cl_done = 0;
         return;
     }
@@ -428,9 +431,20 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_lds(const float4* __rest
 // put in cell order into `sorted` (a per-frame scratch array: the ICP source buffer, which is written after this stage), each
 // point's (slot, ticket) waits in parent / csize, which receive their final values at the end.  Same cells, same predicate,
 // same components as k_cluster_lds.  Frames the table cannot hold keep cl_done = 0 for the point-graph kernels.
+//
+// The kernel is a template on (point capacity, table slots, threads).  CAP = 0 is the kernel described above: any number of
+// points, CL_SLOTS slots, CL_THREADS threads, and it follows k_cluster_lds in the launch (frames with cl_done set are skipped).
+// CAP > 0 is a TIER for frames of at most CAP points, launched INSTEAD of k_cluster_lds when no frame of the launch has more
+// (stage_cluster): a thread keeps the (slot, ticket) of its CAP / THREADS points in registers, a frame that does not fit (more
+// than CAP points, more cells than 3/4 of SLOTS, too wide a cloud) is given up through cl_leave_frame with cl_done = 0, and the
+// host redoes the stage with the next tier.  What a tier is for is its footprint: k_cluster_lds needs 150 KiB of LDS and 1024
+// threads, i.e. a CU that is empty of everything else, and with other batches in flight such a CU is rare (a launch of 256
+// workgroups took 0.8 ms instead of 0.06 ms); k_cluster_cells_t<CL_TIER_CAP, CL_TIER_SLOTS, CL_TIER_THREADS> takes 27 KiB and
+// 512 threads, which fit beside the crop's, the sort's and the ICP's workgroups.
+template <int SLOTS>
 __device__ __forceinline__ void cl_join_g(const int* s_key, const int* s_val, int* s_par, const float4* __restrict__ S, int ha, int key, int delta,
                                           float r2, int& ra) {
-    const int hb = cl_lookup(s_key, key + delta);
+    const int hb = cl_lookup<SLOTS>(s_key, key + delta);
     if (hb < 0) return;
     int rb = lds_find(s_par, hb);
     if (rb == ra) return;
@@ -457,60 +471,90 @@ __device__ __forceinline__ void cl_join_g(const int* s_key, const int* s_val, in
     }
 }
 
-__global__ void __launch_bounds__(CL_THREADS) k_cluster_cells(const float4* __restrict__ obj, int N, FrameState* __restrict__ fs,
-                                                              float inv_cell, float r2, int* __restrict__ parent,
-                                                              int* __restrict__ csize, int* __restrict__ rank_of_root,
-                                                              float4* __restrict__ sorted) {
+// a point's cell -> its slot in the table (opened if need be) and its ticket among the cell's points; false: the frame does
+// not fit (cell coordinate out of range, or no free slot)
+template <int SLOTS>
+__device__ __forceinline__ bool cl_insert(const float4& p, const float* org, float inv_cell, int* s_key, int* s_val, unsigned short* s_cells,
+                                          int* s_ncell, int& h, int& tk) {
+    constexpr int MAX_CELLS = SLOTS / 4 * 3;
+    int cx, cy, cz;
+    cell_of(p, org, inv_cell, cx, cy, cz);
+    h = 0; tk = 0;
+    if (!(cx >= CL_COORD_MIN && cy >= CL_COORD_MIN && cz >= CL_COORD_MIN && cx <= CL_COORD_MAX && cy <= CL_COORD_MAX && cz <= CL_COORD_MAX)) return false;
+    const int key = (cx + 3) | ((cy + 3) << 10) | ((cz + 3) << 20);
+    h = (int)cl_slot_hash<SLOTS>(key);
+    for (int probe = 0; probe < SLOTS; ++probe) {
+        const int old = atomicCAS(&s_key[h], -1, key);
+        if (old == -1) {
+            const int ci = atomicAdd(s_ncell, 1);
+            if (ci < MAX_CELLS) s_cells[ci] = (unsigned short)h;
+            tk = atomicAdd(&s_val[h], 1);
+            return true;
+        }
+        if (old == key) { tk = atomicAdd(&s_val[h], 1); return true; }
+        h = (h + 1) & (SLOTS - 1);
+    }
+    return false;
+}
+
+template <int CAP, int SLOTS, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_cluster_cells_t(const float4* __restrict__ obj, int N, FrameState* __restrict__ fs,
+                                                             float inv_cell, float r2, int* __restrict__ parent,
+                                                             int* __restrict__ csize, int* __restrict__ rank_of_root,
+                                                             float4* __restrict__ sorted) {
+    constexpr int MAX_CELLS = SLOTS / 4 * 3;            // load factor <= 3/4
+    constexpr int PER = CAP > 0 ? CAP / THREADS : 1;    // points per thread of a tier
+    static_assert(SLOTS == 4 * THREADS, "the scan below takes four consecutive slots per thread");
+    static_assert(THREADS % WAVE == 0 && CAP % THREADS == 0 && SLOTS <= 65536, "whole waves, whole rows of points, 16-bit slot numbers");
     CD_FRONT_PRIO();
-    __shared__ int s_key[CL_SLOTS];        // packed cell of the slot, -1 = empty; after the hook: per-component smallest member
-    __shared__ int s_val[CL_SLOTS + 1];    // points in the slot's cell, then their start; after the hook: per-component size
-    __shared__ int s_par[CL_SLOTS];        // union-find over slots
-    __shared__ unsigned short s_cells[CL_MAX_CELLS];
-    __shared__ int s_w[CL_WAVES];
+    __shared__ int s_key[SLOTS];        // packed cell of the slot, -1 = empty; after the hook: per-component smallest member
+    __shared__ int s_val[SLOTS + 1];    // points in the slot's cell, then their start; after the hook: per-component size
+    __shared__ int s_par[SLOTS];        // union-find over slots
+    __shared__ unsigned short s_cells[MAX_CELLS];
+    __shared__ int s_w[THREADS / WAVE];
     __shared__ int s_ncell, s_bail;
     const int f = blockIdx.x;
     const int n = fs[f].n_o;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    if (n <= 0 || fs[f].cl_done) return;       // (uniform) empty, or finished by k_cluster_lds
     const size_t fbase = (size_t)f * N;
+    if (CAP > 0) {
+        if (n <= 0 || n > CAP) {                   // (uniform) empty: nothing to do; too many points: the next tier's
+            if (n > CAP) cl_leave_frame(parent, csize, rank_of_root, fbase, n, THREADS);
+            if (tid == 0) fs[f].cl_done = n <= 0 ? 1 : 0;
+            return;
+        }
+    } else if (n <= 0 || fs[f].cl_done) return;    // (uniform) empty, or finished by k_cluster_lds
     const float4* __restrict__ P = obj + fbase;
     float4* __restrict__ S = sorted + fbase;
-    int* slot_of = parent + fbase;             // scratch until the end
+    int* slot_of = parent + fbase;             // CAP = 0: scratch until the end
     int* ticket_of = csize + fbase;
     const float org[3] = {fs[f].origin[0], fs[f].origin[1], fs[f].origin[2]};
-    for (int i = tid; i < CL_SLOTS; i += CL_THREADS) { s_key[i] = -1; s_val[i] = 0; s_par[i] = i; }
+    for (int i = tid; i < SLOTS; i += THREADS) { s_key[i] = -1; s_val[i] = 0; s_par[i] = i; }
     if (tid == 0) { s_ncell = 0; s_bail = 0; }
     __syncthreads();
-    for (int i = tid; i < n; i += CL_THREADS) {
-        int cx, cy, cz;
-        cell_of(P[i], org, inv_cell, cx, cy, cz);
-        bool ok = cx >= CL_COORD_MIN && cy >= CL_COORD_MIN && cz >= CL_COORD_MIN && cx <= CL_COORD_MAX && cy <= CL_COORD_MAX && cz <= CL_COORD_MAX;
-        int h = 0, tk = 0;
-        if (ok) {
-            const int key = (cx + 3) | ((cy + 3) << 10) | ((cz + 3) << 20);
-            h = (int)cl_slot_hash(key);
-            ok = false;
-            for (int probe = 0; probe < CL_SLOTS; ++probe) {
-                const int old = atomicCAS(&s_key[h], -1, key);
-                if (old == -1) {
-                    const int ci = atomicAdd(&s_ncell, 1);
-                    if (ci < CL_MAX_CELLS) s_cells[ci] = (unsigned short)h;
-                    ok = true;
-                    break;
-                }
-                if (old == key) { ok = true; break; }
-                h = (h + 1) & (CL_SLOTS - 1);
-            }
-            if (ok) tk = atomicAdd(&s_val[h], 1);
+    float4 pt[PER];
+    int sl[PER], tk[PER];                      // CAP > 0: slot and ticket (later: root slot) of the thread's points
+    if (CAP > 0) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) pt[k] = P[min(tid + k * THREADS, n - 1)];   // (all loads first: see load_rows_clamped)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            sl[k] = 0; tk[k] = 0;
+            if (tid + k * THREADS < n && !cl_insert<SLOTS>(pt[k], org, inv_cell, s_key, s_val, s_cells, &s_ncell, sl[k], tk[k])) s_bail = 1;
         }
-        if (!ok) s_bail = 1;
-        slot_of[i] = h;
-        ticket_of[i] = tk;
+    } else {
+        for (int i = tid; i < n; i += THREADS) {
+            int h, t;
+            if (!cl_insert<SLOTS>(P[i], org, inv_cell, s_key, s_val, s_cells, &s_ncell, h, t)) s_bail = 1;
+            slot_of[i] = h;
+            ticket_of[i] = t;
+        }
     }
     __syncthreads();
     const int ncell = s_ncell;
-    if (s_bail || ncell > CL_MAX_CELLS) {         // (uniform) cl_done stays 0: the point-graph kernels take the frame
-        cl_leave_frame(parent, csize, rank_of_root, fbase, n);   // (over the slot and ticket words above: every thread rewrites its own)
+    if (s_bail || ncell > MAX_CELLS) {            // (uniform) cl_done = 0: the next tier or the point-graph kernels take the frame
+        cl_leave_frame(parent, csize, rank_of_root, fbase, n, THREADS);   // (CAP = 0: over the slot and ticket words above - every thread rewrites its own)
+        if (CAP > 0 && tid == 0) fs[f].cl_done = 0;
         return;
     }
     {   // exclusive scan of the slot counts: four consecutive slots per thread
@@ -531,40 +575,69 @@ __global__ void __launch_bounds__(CL_THREADS) k_cluster_cells(const float4* __re
         s_val[q + 1] = base + c0;
         s_val[q + 2] = base + c0 + c1;
         s_val[q + 3] = base + c0 + c1 + c2;
-        if (tid == 0) s_val[CL_SLOTS] = n;
+        if (tid == 0) s_val[SLOTS] = n;
     }
     __syncthreads();
-    for (int i = tid; i < n; i += CL_THREADS) S[s_val[slot_of[i]] + ticket_of[i]] = P[i];   // (every thread reads back its own words)
+    if (CAP > 0) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k)
+            if (tid + k * THREADS < n) S[s_val[sl[k]] + tk[k]] = pt[k];   // (a position below n: the tickets of a cell are 0 .. count-1)
+    } else {
+        for (int i = tid; i < n; i += THREADS) S[s_val[slot_of[i]] + ticket_of[i]] = P[i];   // (every thread reads back its own words)
+    }
     __syncthreads();   // (workgroup-scope release / acquire: the points are read by other waves of this workgroup below)
     const int items = ncell * CL_LANES_PER_CELL;
     for (int ring = 0; ring < 2; ++ring) {
         const int j0 = ring == 0 ? 0 : CL_RING1, j1 = ring == 0 ? CL_RING1 : CL_FORWARD;
-        for (int it = tid; it < items; it += CL_THREADS) {
+        for (int it = tid; it < items; it += THREADS) {
             const int ha = (int)s_cells[it / CL_LANES_PER_CELL], g = it % CL_LANES_PER_CELL;
             const int key = s_key[ha];
             int ra = lds_find(s_par, ha);
 #pragma unroll 1
-            for (int j = j0 + g; j < j1; j += CL_LANES_PER_CELL) cl_join_g(s_key, s_val, s_par, S, ha, key, cl_offsets.d[j], r2, ra);
+            for (int j = j0 + g; j < j1; j += CL_LANES_PER_CELL) cl_join_g<SLOTS>(s_key, s_val, s_par, S, ha, key, cl_offsets.d[j], r2, ra);
         }
         __syncthreads();
     }
     int* s_min = s_key;   // (the keys and the cell starts are dead from here on)
     int* s_cnt = s_val;
-    for (int q = tid; q < CL_SLOTS; q += CL_THREADS) { s_min[q] = 0x7fffffff; s_cnt[q] = 0; }
+    for (int q = tid; q < SLOTS; q += THREADS) { s_min[q] = 0x7fffffff; s_cnt[q] = 0; }
     __syncthreads();
-    for (int i = tid; i < n; i += CL_THREADS) {
-        const int r = lds_find(s_par, slot_of[i]);
-        slot_of[i] = r;
-        atomicMin(&s_min[r], i);
-        atomicAdd(&s_cnt[r], 1);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += CL_THREADS) {
-        const int root = slot_of[i];
-        const int r = s_min[root];
-        parent[fbase + i] = r;
-        csize[fbase + i] = r == i ? s_cnt[root] : 0;
-        rank_of_root[fbase + i] = -1;
+    if (CAP > 0) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid + k * THREADS;
+            if (i < n) {
+                sl[k] = lds_find(s_par, sl[k]);
+                atomicMin(&s_min[sl[k]], i);
+                atomicAdd(&s_cnt[sl[k]], 1);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = tid + k * THREADS;
+            if (i < n) {
+                const int r = s_min[sl[k]];
+                parent[fbase + i] = r;
+                csize[fbase + i] = r == i ? s_cnt[sl[k]] : 0;
+                rank_of_root[fbase + i] = -1;
+            }
+        }
+    } else {
+        for (int i = tid; i < n; i += THREADS) {
+            const int r = lds_find(s_par, slot_of[i]);
+            slot_of[i] = r;
+            atomicMin(&s_min[r], i);
+            atomicAdd(&s_cnt[r], 1);
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += THREADS) {
+            const int root = slot_of[i];
+            const int r = s_min[root];
+            parent[fbase + i] = r;
+            csize[fbase + i] = r == i ? s_cnt[root] : 0;
+            rank_of_root[fbase + i] = -1;
+        }
     }
     if (tid == 0) fs[f].cl_done = 1;
 }
@@ -753,7 +826,15 @@ void launch_cluster_lds(hipStream_t s, const float4* obj, int N, int F, FrameSta
 }
 void launch_cluster_cells(hipStream_t s, const float4* obj, int N, int F, FrameState* fs, float inv_cell, float r2,
                           int* parent, int* csize, int* rank_of_root, float4* sorted) {
-    hipLaunchKernelGGL(k_cluster_cells, dim3(F), dim3(CL_THREADS), 0, s, obj, N, fs, inv_cell, r2, parent, csize, rank_of_root, sorted);
+    hipLaunchKernelGGL((k_cluster_cells_t<0, CL_SLOTS, CL_THREADS>), dim3(F), dim3(CL_THREADS), 0, s, obj, N, fs, inv_cell, r2, parent, csize, rank_of_root, sorted);
+}
+// the footprint a tier exists for (see k_cluster_cells_t): three int tables of CL_TIER_SLOTS, the 16-bit cell list, a few words
+static_assert(CL_TIER_CAP <= CL_LDS_CAP && CL_TIER_THREADS <= 512 &&
+              13 * CL_TIER_SLOTS + CL_TIER_SLOTS / 2 + 4 * (CL_TIER_THREADS / WAVE) + 16 <= 48 * 1024, "the small tier: at most 48 KiB of LDS and 512 threads");
+void launch_cluster_tier(hipStream_t s, const float4* obj, int N, int F, FrameState* fs, float inv_cell, float r2,
+                         int* parent, int* csize, int* rank_of_root, float4* sorted) {
+    hipLaunchKernelGGL((k_cluster_cells_t<CL_TIER_CAP, CL_TIER_SLOTS, CL_TIER_THREADS>), dim3(F), dim3(CL_TIER_THREADS), 0, s, obj, N, fs, inv_cell, r2, parent, csize,
+                       rank_of_root, sorted);
 }
 void launch_cluster_build(hipStream_t s, const float4* obj, int N, int F, int Tact, const FrameState* fs, float inv_cell,
                           int* head, int* next, int* parent, int* csize, int* rank_of_root) {

@@ -20,36 +20,49 @@
 namespace cd {
 
 // ---- sampler: PCL SampleConsensusModel::getSamples + plane model -------------------------
-__global__ void __launch_bounds__(WAVE) k_ransac_sample(const float4* __restrict__ vox, int N,
-                                                        FrameState* __restrict__ fs, const int* __restrict__ rnd,
-                                                        int h_target, const int* __restrict__ active,
-                                                        float4* __restrict__ models, int* __restrict__ valid) {
-    CD_FRONT_PRIO();
-    __shared__ int s_key[SAMPLER_MAP];
-    __shared__ int s_val[SAMPLER_MAP];
-    const int f = blockIdx.x;
-    if (active && !active[f]) return;
-    for (int i = threadIdx.x; i < SAMPLER_MAP; i += WAVE) s_key[i] = -1;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int n = fs[f].n_v;
-    const float4* P = vox + (size_t)f * N;
-    float4* M = models + (size_t)f * MAX_HYP;
-    int* V = valid + (size_t)f * MAX_HYP;
-    if (n < 3) { fs[f].n_hyp = 0; fs[f].sampler_exhausted = 1; return; }
+//
+// The shuffle map holds the positions of PCL's shuffled index vector that differ from the identity.  A draw (drawIndexSample:
+// three swaps of position i = 0, 1, 2 with a position j >= i) touches positions 0, 1, 2 and at most three others, so after d
+// draws at most 3 + 3 d slots are in use; every hypothesis - kept or skipped as collinear by computeModelCoefficients - takes
+// one draw plus one per sample that isSampleGood rejects (exact equality of three float ratios: none on sensor data).  The
+// first h hypotheses therefore need 3 h + 3 slots and three per rejected sample; the sampler gives a frame up (exhausted) when
+// used + 6 > 3/4 SAMPLER_MAP before a draw - that rule is part of the result and does not depend on the map's size here:
+//   MAP = SAMPLER_MAP        64 KiB of LDS, one wave: a workgroup that needs 40 % of a CU's LDS free (the rounds of 256
+//                            hypotheses and more)
+//   MAP = SAMPLER_MAP_SMALL  8 KiB for the rounds of at most SAMPLER_SMALL_HYP hypotheses, which is room for them and 188
+//                            rejected samples; a frame that needs more MOVES its map to `spill` (2 SAMPLER_MAP ints of the
+//                            frame in global memory) and goes on there under the same rule, so the models, n_hyp and
+//                            sampler_exhausted are those of the large map in every case.
+constexpr int SAMPLER_MAP_SMALL = 1024;
+constexpr int SAMPLER_SMALL_HYP = 64;
+static_assert(3 * (SAMPLER_SMALL_HYP - 1) + 3 + 6 <= (SAMPLER_MAP_SMALL * 3) / 4,
+              "the small map holds the slots of SAMPLER_SMALL_HYP hypotheses without a rejected sample: 3 + 3 (h - 1) before the last draw, which asks for 6 more");
+static_assert(2 * SAMPLER_MAP_SMALL * sizeof(int) <= 8 * 1024 && 2 * SAMPLER_MAP <= CELL_BUCKETS, "8 KiB of LDS; the spill area is the frame's part of the cluster hash heads");
+
+struct SamplerState {
+    int rp, h, used, it, exhausted;   // random numbers consumed, hypotheses emitted, slots in use, sample checks of the open hypothesis
+};
+
+// Runs the sampler on the map (key, val) of MAP slots until h_target hypotheses are out or the frame is exhausted (returns
+// true), or - MAP < SAMPLER_MAP only - until the map is as full as it may get (returns false: the caller moves the map and
+// calls again; `st` is where the next draw starts).
+template <int MAP>
+__device__ __forceinline__ bool sampler_run(int* key, int* val, SamplerState& st, const float4* __restrict__ P, int n,
+                                            const int* __restrict__ rnd, int h_target, float4* __restrict__ M, int* __restrict__ V) {
     auto slot = [&](int pos) {
-        uint32_t h = ((uint32_t)pos * 2654435761u) & (SAMPLER_MAP - 1);
-        while (s_key[h] != -1 && s_key[h] != pos) h = (h + 1) & (SAMPLER_MAP - 1);
+        uint32_t h = ((uint32_t)pos * 2654435761u) & (MAP - 1);
+        while (key[h] != -1 && key[h] != pos) h = (h + 1) & (MAP - 1);
         return (int)h;
     };
-    int rp = 0, h = 0, used = 0, exhausted = 0;
-    auto get = [&](int pos) { const int h = slot(pos); return s_key[h] == pos ? s_val[h] : pos; };
-    auto set = [&](int pos, int v) { const int h = slot(pos); if (s_key[h] == -1) ++used; s_key[h] = pos; s_val[h] = v; };
+    int rp = st.rp, h = st.h, used = st.used, it0 = st.it, exhausted = 0;
+    auto get = [&](int pos) { const int h = slot(pos); return key[h] == pos ? val[h] : pos; };
+    auto set = [&](int pos, int v) { const int h = slot(pos); if (key[h] == -1) ++used; key[h] = pos; val[h] = v; };
     while (h < h_target) {
         bool good = false;
         int s0 = 0, s1 = 0, s2 = 0;
-        for (int it = 0; it < 1000; ++it) {            // max_sample_checks_
+        for (int it = it0; it < 1000; ++it) {          // max_sample_checks_
             if (rp + 3 > RND_TABLE || used + 6 > (SAMPLER_MAP * 3) / 4) { exhausted = 1; break; }
+            if (MAP < SAMPLER_MAP && used + 6 > (MAP * 3) / 4) { st.rp = rp; st.h = h; st.used = used; st.it = it; return false; }
             for (int i = 0; i < 3; ++i) {               // drawIndexSample
                 const uint32_t r = (uint32_t)rnd[rp++];
                 const int j = i + (int)(r % (uint32_t)(n - i));
@@ -64,6 +77,7 @@ __global__ void __launch_bounds__(WAVE) k_ransac_sample(const float4* __restrict
             const float q2 = __fdiv_rn(p1.z - p0.z, p2.z - p0.z);
             if ((q0 != q1) || (q2 != q1)) { good = true; break; }
         }
+        it0 = 0;
         if (!good) { exhausted = 1; break; }
         // computeModelCoefficients
         const float4 p0 = P[s0], p1 = P[s1], p2 = P[s2];
@@ -87,8 +101,48 @@ __global__ void __launch_bounds__(WAVE) k_ransac_sample(const float4* __restrict
         V[h] = ok;
         ++h;
     }
-    fs[f].n_hyp = h;
-    fs[f].sampler_exhausted = exhausted;
+    st.rp = rp; st.h = h; st.used = used; st.it = 0; st.exhausted = exhausted;
+    return true;
+}
+
+template <int MAP>
+__global__ void __launch_bounds__(WAVE) k_ransac_sample(const float4* __restrict__ vox, int N,
+                                                        FrameState* __restrict__ fs, const int* __restrict__ rnd,
+                                                        int h_target, const int* __restrict__ active,
+                                                        float4* __restrict__ models, int* __restrict__ valid,
+                                                        int* __restrict__ spill, int spill_pitch) {
+    CD_FRONT_PRIO();
+    __shared__ int s_key[MAP];
+    __shared__ int s_val[MAP];
+    const int f = blockIdx.x;
+    if (active && !active[f]) return;
+    for (int i = threadIdx.x; i < MAP; i += WAVE) s_key[i] = -1;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int n = fs[f].n_v;
+    const float4* P = vox + (size_t)f * N;
+    float4* M = models + (size_t)f * MAX_HYP;
+    int* V = valid + (size_t)f * MAX_HYP;
+    if (n < 3) { fs[f].n_hyp = 0; fs[f].sampler_exhausted = 1; return; }
+    SamplerState st = {0, 0, 0, 0, 0};
+    const bool finished = sampler_run<MAP>(s_key, s_val, st, P, n, rnd, h_target, M, V);
+    if (MAP < SAMPLER_MAP && !finished) {
+        // the small map is full: every entry moves to a map of SAMPLER_MAP slots in global memory
+        int* g_key = spill + (size_t)f * spill_pitch;
+        int* g_val = g_key + SAMPLER_MAP;
+        for (int i = 0; i < SAMPLER_MAP; ++i) g_key[i] = -1;
+        for (int i = 0; i < MAP; ++i) {
+            const int pos = s_key[i];
+            if (pos == -1) continue;
+            uint32_t h = ((uint32_t)pos * 2654435761u) & (SAMPLER_MAP - 1);
+            while (g_key[h] != -1) h = (h + 1) & (SAMPLER_MAP - 1);
+            g_key[h] = pos;
+            g_val[h] = s_val[i];
+        }
+        sampler_run<SAMPLER_MAP>(g_key, g_val, st, P, n, rnd, h_target, M, V);
+    }
+    fs[f].n_hyp = st.h;
+    fs[f].sampler_exhausted = st.exhausted;
 }
 
 // ---- batched per-hypothesis inlier count --------------------------------------------------
@@ -285,8 +339,12 @@ __global__ void __launch_bounds__(BLOCK) k_extract_scatter(const float4* __restr
 }
 
 void launch_ransac_sample(hipStream_t s, const float4* vox, int N, int F, FrameState* fs, const int* rnd_table,
-                          int h_target, const int* active, float4* models, int* valid) {
-    hipLaunchKernelGGL(k_ransac_sample, dim3(F), dim3(WAVE), 0, s, vox, N, fs, rnd_table, h_target, active, models, valid);
+                          int h_target, const int* active, float4* models, int* valid, int* spill, int spill_pitch) {
+    // spill: 2 * SAMPLER_MAP ints per frame, spill_pitch ints apart, for the small map's overflow; nullptr: always the large map
+    if (spill && spill_pitch >= 2 * SAMPLER_MAP && h_target <= SAMPLER_SMALL_HYP)
+        hipLaunchKernelGGL(k_ransac_sample<SAMPLER_MAP_SMALL>, dim3(F), dim3(WAVE), 0, s, vox, N, fs, rnd_table, h_target, active, models, valid, spill, spill_pitch);
+    else
+        hipLaunchKernelGGL(k_ransac_sample<SAMPLER_MAP>, dim3(F), dim3(WAVE), 0, s, vox, N, fs, rnd_table, h_target, active, models, valid, spill, spill_pitch);
 }
 void launch_ransac_count(hipStream_t s, const float4* vox, int N, int F, int Tact, const FrameState* fs,
                          const float4* models, const int* valid, const int* active, int h0, int h1, float thr, int* counts) {

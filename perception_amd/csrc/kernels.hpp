@@ -52,7 +52,7 @@ int launch_radix_sort_runs(hipStream_t s, uint32_t* const key[2], uint32_t* cons
 // k_plane.hip
 struct FrameRects { const int32_t* rect; int32_t pitch; };   // the gate's rectangle of frame f = rect[f * pitch + 0..3]; rect == nullptr: BBoxGate::rect
 void launch_ransac_sample(hipStream_t s, const float4* vox, int N, int F, FrameState* fs, const int* rnd_table,
-                          int h_target, const int* active, float4* models, int* valid);
+                          int h_target, const int* active, float4* models, int* valid, int* spill, int spill_pitch);
 void launch_ransac_count(hipStream_t s, const float4* vox, int N, int F, int Tact, const FrameState* fs,
                          const float4* models, const int* valid, const int* active, int h0, int h1, float thr, int* counts);
 void launch_plane_cov(hipStream_t s, const float4* vox, int N, int F, int Tact, const FrameState* fs, const float4* model,
@@ -70,6 +70,15 @@ void launch_cluster_lds(hipStream_t s, const float4* obj, int N, int F, FrameSta
                         int* parent, int* csize, int* rank_of_root);
 void launch_cluster_cells(hipStream_t s, const float4* obj, int N, int F, FrameState* fs, float inv_cell, float r2,
                           int* parent, int* csize, int* rank_of_root, float4* sorted);
+// The small clustering tier (k_cluster_cells_t, k_cluster.hip): launched instead of k_cluster_lds when no frame of the launch
+// has more than CL_TIER_CAP object points.  The bench frames have at most 4306 object points in at most ~800 occupied cells
+// (cell edge tol / sqrt(3); 2855 points in 512 cells on average); the table holds 3/4 of its slots.
+constexpr int CL_TIER_CAP = 4608;      // object points (nine per thread)
+constexpr int CL_TIER_SLOTS = 2048;    // cell table: at most 1536 occupied cells
+constexpr int CL_TIER_THREADS = 512;
+constexpr int CL_TOP_CAP = 8192;       // k_cluster_lds, the top tier of the one-workgroup kernels with the points in LDS
+void launch_cluster_tier(hipStream_t s, const float4* obj, int N, int F, FrameState* fs, float inv_cell, float r2,
+                         int* parent, int* csize, int* rank_of_root, float4* sorted);
 void launch_cluster_build(hipStream_t s, const float4* obj, int N, int F, int Tact, const FrameState* fs, float inv_cell,
                           int* head, int* next, int* parent, int* csize, int* rank_of_root);
 void launch_cluster_hook(hipStream_t s, const float4* obj, int N, int F, int Tact, const FrameState* fs, float inv_cell,
