@@ -194,6 +194,22 @@ int cd_template_lattice_faces(const cd_context* ctx, int slot);
 int cd_template_nearest(cd_context* ctx, int slot, const void* queries, size_t stride_bytes, int n, int32_t* out_index,
                         float* out_d2);
 
+/* Diagnostic: ONE ICP iteration's state update on its own, for k records at once (no context; the current device).  The lattice
+ * ICP finishes an iteration on a row of 16 lanes; this entry runs that code and the single-lane code every other ICP driver
+ * uses side by side in one launch, four records per wave, and returns both results - they must be the same bytes.
+ *   sums       k x 16 fixed-point moment sums (rule C4: [0..2] sum p, [3..5] sum q, [6..14] sum q_a p_b at 2^32, [15] sum d2 at 2^36)
+ *   n          k correspondence counts
+ *   states_in  k records of 152 bytes: float Tfinal[16], float T[16], double prev_mse, int32 iters, done, converged, status
+ *   max_iter .. abs_mse  the convergence criteria (rot_thr = 1 - transformation epsilon as the library derives it)
+ *   bounded    != 0: the variant with a maximum correspondence distance (fewer than three correspondences stop the ICP)
+ *   states_row, states_lane  k outgoing records each;  done  k x 2 return values (row, single lane)
+ *   unary      NULL, or 6 words: the row code's two short forms (square root of x in [1, +inf], reciprocal of 1 <= |x| < 2^126)
+ *              compared with the IEEE operations for every float of those domains - [0] differing square roots, [1] the first
+ *              such input's bits, [2], [3] the same for reciprocals, [4], [5] whether the library uses each short form */
+int cd_icp_solve_batch(int k, const uint64_t* sums, const int32_t* n, const void* states_in, int max_iter, double trans_eps,
+                       double rel_mse, double rot_thr, double abs_mse, int bounded, void* states_row, void* states_lane,
+                       int32_t* done, uint64_t* unary);
+
 /* Host-only (no context, no GPU): the lattice test of cd_set_template.  out (may be NULL) receives up to 8 faces x
  * {constant axis, fast axis, first index, points along the fast axis, points along the slow axis}.  Returns the number of
  * faces, 0 = not a lattice. */

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "cd_process_depth_batch_mapped", "cd_process_depth_batch_mapped_device",
     "cd_shape_frame_struct_size", "cd_shape_frame_host", "cd_shape_frames", "cd_template_shape_frame", "cd_shape_guess",
     "cd_get_cluster_shape_frames",
+    "cd_icp_solve_batch",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -383,6 +384,7 @@ def load_library(path=None):
     lib.cd_get_surface_results.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CdSurfaceFrameResult), i32p]
     lib.cd_template_lattice_faces.argtypes = [vp, C.c_int]
     lib.cd_template_nearest.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, vp]
+    lib.cd_icp_solve_batch.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp]
     lib.cd_lattice_detect.argtypes = [vp, C.c_size_t, C.c_int, vp]
     lib.cd_lattice_axes.argtypes = [vp, C.c_size_t, C.c_int, vp, vp]
     lib.cd_set_icp_max_correspondence_distance.argtypes = [vp, C.c_double]
@@ -963,6 +965,29 @@ def lattice_axes(xyz):
     if r < 0:
         raise CuboidError(r, "cd_lattice_axes")
     return int(r), [int(v) for v in face], c
+
+
+ICP_STATE = np.dtype([("Tfinal", np.float32, 16), ("T", np.float32, 16), ("prev_mse", np.float64), ("iters", np.int32),
+                      ("done", np.int32), ("converged", np.int32), ("status", np.int32)])
+
+
+def icp_solve_batch(sums, n, states, max_iter=50, trans_eps=1e-8, rel_mse=1e-6, rot_thr=None, abs_mse=1e-12, bounded=False, unary=False):
+    """cd_icp_solve_batch: one ICP step for k records (sums uint64 [k, 16], n int32 [k], states ICP_STATE [k]) by the row code
+    and by the single-lane code in one launch.  Returns (states_row, states_lane, done int32 [k, 2], unary uint64 [6] or None)."""
+    lib = load_library()
+    sums = np.ascontiguousarray(sums, np.uint64).reshape(-1, 16)
+    k = sums.shape[0]
+    n = np.ascontiguousarray(n, np.int32).reshape(k)
+    states = np.ascontiguousarray(states, ICP_STATE).reshape(k)
+    out_row, out_lane = np.zeros(k, ICP_STATE), np.zeros(k, ICP_STATE)
+    done = np.zeros((k, 2), np.int32)
+    un = np.zeros(6, np.uint64) if unary else None
+    st = lib.cd_icp_solve_batch(k, _ptr(sums), _ptr(n), _ptr(states), int(max_iter), float(trans_eps), float(rel_mse),
+                                float(1.0 - trans_eps if rot_thr is None else rot_thr), float(abs_mse), int(bool(bounded)),
+                                _ptr(out_row), _ptr(out_lane), _ptr(done), None if un is None else _ptr(un))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_icp_solve_batch")
+    return out_row, out_lane, done, un
 
 
 def icp_correspondence_threshold(d):

@@ -2,6 +2,7 @@
 // cluster, ICP, ground plane and shape frames.  Each `X_impl` runs under with_scan_retry (context.hpp).
 #include "context.hpp"
 #include "host_math.hpp"
+#include "icp_solve_row.hpp"
 
 namespace {
 int cd_crop_voxel_impl(cd_context* c, const void* points, size_t stride, int n, const cd_params* p, float* out_xyz,
@@ -473,3 +474,95 @@ int cd_ground_plane(cd_context* c, const void* points, size_t stride, int n, con
     return with_scan_retry(c, [&] { return cd_ground_plane_impl(c, points, stride, n, p, coeff, out_records, capacity, out_n, out_n_inliers); });
 }
 }  // extern "C"
+
+// ---- cd_icp_solve_batch: the ICP step on its own (diagnostic; what cd_template_nearest is for the search) ----
+// one wave = four records, one per row of 16 lanes: icp_step_row on a copy of the record's state, then icp_step on another
+// copy by the row's first lane - the two solvers of one launch side by side, rows free to diverge
+template <bool BOUNDED>
+__global__ void __launch_bounds__(WAVE) k_icp_solve_batch(int k, const unsigned long long* __restrict__ sums, const int* __restrict__ n,
+                                                           const IcpState* __restrict__ in, IcpParams prm, IcpState* __restrict__ out_row,
+                                                           IcpState* __restrict__ out_lane, int* __restrict__ done) {
+    __shared__ IcpState s_row[4], s_one[4];
+    __shared__ unsigned long long s_sums[4][16];
+    const int tid = (int)threadIdx.x, r = tid >> 4, l = tid & 15;
+    const int rec = (int)blockIdx.x * 4 + r;
+    if (rec >= k) return;   // (whole rows; no barrier below)
+    if (l == 0) { s_row[r] = in[rec]; s_one[r] = in[rec]; }
+    s_sums[r][l] = sums[(size_t)rec * 16 + l];
+    const int nn = n[rec];
+    RowLanes row(tid);
+    RowLanes::V<unsigned long long> a;
+    a.v = s_sums[r][l];
+    const int d_row = icp_step_row<BOUNDED>(row, s_row[r], a, nn, prm);
+    if (l == 0) {
+        const int d_one = icp_step<BOUNDED>(s_one[r], s_sums[r], nn, prm);
+        out_row[rec] = s_row[r];
+        out_lane[rec] = s_one[r];
+        done[2 * rec] = d_row;
+        done[2 * rec + 1] = d_one;
+    }
+}
+// sqrt_ge1 / rcp_ge1 against the compiler's IEEE sqrtf / division for EVERY float of their domains: x in [1, +inf] for the
+// square root, |x| in [1, 2^126) for the reciprocal.  res: [0] square roots that differ, [1] the smallest such input's bits,
+// [2], [3] the same for reciprocals
+__global__ void __launch_bounds__(BLOCK) k_unary_exhaustive(unsigned long long* __restrict__ res) {
+    unsigned long long bad_s = 0, bad_r = 0, first_s = ~0ull, first_r = ~0ull;
+    const unsigned lo = 0x3f800000u, hi = 0x7f800000u, rcp_end = 0x7e800000u;   // 1.0f, +inf, 2^126
+    for (unsigned long long b = lo + (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; b <= hi; b += (unsigned long long)gridDim.x * BLOCK) {
+        const float x = __uint_as_float((unsigned)b);
+        if (__float_as_uint(sqrt_ge1(x)) != __float_as_uint(sqrtf(x))) { bad_s += 1; first_s = first_s < b ? first_s : b; }
+        if (b < rcp_end) {
+            if (__float_as_uint(rcp_ge1(x)) != __float_as_uint(1.0f / x)) { bad_r += 1; first_r = first_r < b ? first_r : b; }
+            const unsigned long long bn = b | 0x80000000ull;
+            if (__float_as_uint(rcp_ge1(-x)) != __float_as_uint(1.0f / -x)) { bad_r += 1; first_r = first_r < bn ? first_r : bn; }
+        }
+    }
+    if (bad_s) { atomicAdd(&res[0], bad_s); atomicMin(&res[1], first_s); }
+    if (bad_r) { atomicAdd(&res[2], bad_r); atomicMin(&res[3], first_r); }
+}
+
+extern "C" int cd_icp_solve_batch(int k, const uint64_t* sums, const int32_t* n, const void* states_in, int max_iter, double trans_eps,
+                                  double rel_mse, double rot_thr, double abs_mse, int bounded, void* states_row, void* states_lane,
+                                  int32_t* done, uint64_t* unary) {
+    static_assert(sizeof(IcpState) == 152, "the record layout cuboid_hip.h documents");
+    if (k < 0 || (k > 0 && (!sums || !n || !states_in || !states_row || !states_lane || !done))) return CD_ERR_INVALID_ARG;
+    unsigned long long *d_sums = nullptr, *d_res = nullptr;
+    int *d_n = nullptr, *d_done = nullptr;
+    IcpState *d_in = nullptr, *d_row = nullptr, *d_lane = nullptr;
+    bool ok = true;
+    auto chk = [&](hipError_t e) { ok = ok && e == hipSuccess; return ok; };
+    if (k > 0) {
+        const size_t kk = (size_t)k;
+        if (chk(hipMalloc(&d_sums, kk * 128)) && chk(hipMalloc(&d_n, kk * 4)) && chk(hipMalloc(&d_done, kk * 8)) && chk(hipMalloc(&d_in, kk * sizeof(IcpState))) &&
+            chk(hipMalloc(&d_row, kk * sizeof(IcpState))) && chk(hipMalloc(&d_lane, kk * sizeof(IcpState))) &&
+            chk(hipMemcpy(d_sums, sums, kk * 128, hipMemcpyHostToDevice)) && chk(hipMemcpy(d_n, n, kk * 4, hipMemcpyHostToDevice)) &&
+            chk(hipMemcpy(d_in, states_in, kk * sizeof(IcpState), hipMemcpyHostToDevice))) {
+            IcpParams prm;
+            std::memset(&prm, 0, sizeof(prm));
+            prm.max_iter = max_iter; prm.trans_eps = trans_eps; prm.rel_mse = rel_mse; prm.rot_thr = rot_thr; prm.abs_mse = abs_mse;
+            const int grid = (k + 3) / 4;
+            if (bounded) hipLaunchKernelGGL(k_icp_solve_batch<true>, dim3(grid), dim3(WAVE), 0, 0, k, d_sums, d_n, d_in, prm, d_row, d_lane, d_done);
+            else hipLaunchKernelGGL(k_icp_solve_batch<false>, dim3(grid), dim3(WAVE), 0, 0, k, d_sums, d_n, d_in, prm, d_row, d_lane, d_done);
+            chk(hipGetLastError());
+            chk(hipDeviceSynchronize());
+            chk(hipMemcpy(states_row, d_row, kk * sizeof(IcpState), hipMemcpyDeviceToHost));
+            chk(hipMemcpy(states_lane, d_lane, kk * sizeof(IcpState), hipMemcpyDeviceToHost));
+            chk(hipMemcpy(done, d_done, kk * 8, hipMemcpyDeviceToHost));
+        }
+    }
+    if (ok && unary) {
+        const unsigned long long init[4] = {0ull, ~0ull, 0ull, ~0ull};
+        if (chk(hipMalloc(&d_res, sizeof(init))) && chk(hipMemcpy(d_res, init, sizeof(init), hipMemcpyHostToDevice))) {
+            hipLaunchKernelGGL(k_unary_exhaustive, dim3(4096), dim3(BLOCK), 0, 0, d_res);
+            chk(hipGetLastError());
+            chk(hipDeviceSynchronize());
+            chk(hipMemcpy(unary, d_res, sizeof(init), hipMemcpyDeviceToHost));
+        }
+        if (ok) {
+            unary[4] = CD_ROW_SQRT_GE1;   // does the library's icp_step_row use the short form (1) or the plain operation (0)
+            unary[5] = CD_ROW_RCP_GE1;
+        }
+    }
+    (void)hipFree(d_sums); (void)hipFree(d_n); (void)hipFree(d_done); (void)hipFree(d_in); (void)hipFree(d_row); (void)hipFree(d_lane); (void)hipFree(d_res);
+    return ok ? CD_OK : CD_ERR_DEVICE;
+}

@@ -31,7 +31,7 @@
 // Launch shape: a workgroup keeps one or several clusters going, every cluster's whole ICP inside it (k_icp_lat<CPW, WPC> below).
 // No MFMA: there is no dense contraction here (3x3 matrices only).
 #include "kernels.hpp"
-#include "icp_solve.hpp"
+#include "icp_solve_row.hpp"
 
 namespace cd {
 
@@ -305,13 +305,17 @@ __device__ __forceinline__ int lat_index(const int4* s_face, const LatFaces& F, 
 //   work  : the waves of a slot take the passes (64 points each) of the slot's current step - a PCL iteration (X <- T X in
 //           place, nearest neighbours, the 16 fixed-point moment sums of rule C4 kept in registers and folded into the slot's
 //           LDS accumulators) or, once converged, the final transform + getFitnessScore() pass;            -- barrier --
-//   solve : lane s of wave 0 finishes slot s's step: Umeyama + SVD + convergence tests (icp_step, icp_solve.hpp: what every
-//           driver calls), or the write-back of a finished cluster and the refill of the slot from the launch's cluster queue.
-//           The solves of a workgroup's slots run SIDE BY SIDE in the lanes of one wave.                     -- barrier --
-// Why this shape (measured, tools/lat_threads_serial.sh): a step of a 1 400-point cluster is ~19 us of passes for one wave
-// and ~9.6 us of single-lane solve (3 300 dependent instructions: IEEE divisions and square roots of the Jacobi sweeps).
-// One cluster per workgroup of four waves spends two thirds of its life with three waves parked behind one lane; CPW
-// clusters per workgroup pay that solve once per round for all of them.  <1, 4> / <1, 16> (one cluster, many waves) remain the
+//   solve : a row of 16 lanes per slot (row s % 4 of wave s / 4) finishes the slot's step: Umeyama + SVD + convergence tests
+//           (icp_step_row, icp_solve_row.hpp: icp_step - what every other driver calls on one lane - spread over the row, the
+//           same bits), or the row's first lane writes a finished cluster back and refills the slot from the launch's cluster
+//           queue.  The solves of a workgroup's slots run SIDE BY SIDE in the rows of one or two waves.      -- barrier --
+// Why this shape (measured, tools/lat_threads_serial.sh, tools/probe_lat_phases.py): a step of a 1 400-point cluster is ~19 us
+// of passes for one wave, and its solve was ~13 k cycles on a single lane (3 300 dependent instructions: IEEE divisions and
+// square roots of the Jacobi sweeps, 17 double divisions before them, two 4x4 products after).  The row does the elementwise
+// parts once per lane instead of once per entry and the sweeps' square roots and reciprocals in exact shorter forms; the
+// rotation parameters remain a serial chain that every lane of the row repeats (profiles/EXPERIMENTS.md A11 for the cycles).
+// One cluster per workgroup of four waves still spends close to half of its life with its waves parked behind that chain; CPW
+// clusters per workgroup pay it once per round for all of them.  <1, 4> / <1, 16> (one cluster, many waves) remain the
 // latency shapes: a launch that has the GPU to itself, a single frame.
 // Each slot has its own copy of its template's tables (a launch may mix templates: BASELINE config 5), restaged when a refill
 // brings a cluster of another template.
@@ -356,8 +360,11 @@ struct LatSlot {
 };
 enum { LAT_ITER = 0, LAT_FIT = 1, LAT_EMPTY = 2 };
 
+#ifndef CD_LAT_SOLVE_ROW
+#define CD_LAT_SOLVE_ROW 1   // 0: the single-lane icp_step in the solve phase (variant builds, A/B)
+#endif
 #ifndef CD_LAT_WAVES_PER_EU
-#define CD_LAT_WAVES_PER_EU 4   // four waves per SIMD: 128 registers - the single-lane solve is what needs them
+#define CD_LAT_WAVES_PER_EU 4   // four waves per SIMD: 128 registers (the pass loop and the solve both need more than 96)
 #endif
 // BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; s_nv counts them per slot (one popcount of a
 // ballot per pass and wave, one LDS add per wave and round) and takes the place of n in the solve and in the constants' offset
@@ -375,7 +382,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
     __shared__ unsigned long long s_acc[CPW][16];
     __shared__ IcpState s_so[CPW];
     __shared__ LatSlot s_slot[CPW];
-    __shared__ int s_flags[2];   // [0] every slot is empty, [1] some slot was refilled in this round
+    __shared__ int s_flags[2];   // [0] always 0 (see the solve phase), [1] some slot was refilled in this round
     __shared__ unsigned s_nv[BOUNDED ? CPW : 1];   // (BOUNDED) kept correspondences of the slot's current step
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slot = wave / WPC, sub = wave % WPC;
@@ -528,16 +535,53 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
             }
         }
         LAT_T(0)
+        // (every thread has read s_flags[1] for this round - those that found it set have also passed the staging barrier - and
+        // nobody raises it before the barrier below)
+        if (threadIdx.x == 0) s_flags[1] = 0;
         __syncthreads();
         LAT_T(1)
-        // ---- solve phase: lane s of wave 0 <-> slot s (everything below happens in wave 0, whose LDS operations execute in
-        // program order: the flag is cleared before a refill raises it, and thread 0 sees the other lanes' phases) ----
-        if (threadIdx.x == 0) s_flags[1] = 0;
+#if CD_LAT_SOLVE_ROW
+        // ---- solve phase: slot s <-> the row of 16 lanes 16 * (s % 4) .. + 15 of wave s / 4 (CPW <= 4: wave 0; CPW = 8: waves 0
+        // and 1).  The row solves the slot's step together (icp_step_row); write-back, refill and the slot's words stay with the
+        // row's first lane.  (s_flags[1] was cleared before the barrier above: two waves may raise it here) ----
+        // tid: the thread index through a zero read from LDS in every round.  The compiler cannot move what the row derives from
+        // it (lane numbers, the addresses of the slot's state and sums) out of the round loop, where a dozen such values would
+        // stay in registers across the pass loop and push it into scratch.  Nothing but the compiler's ignorance of that zero keeps
+        // it so: tests/test_lat_loop_count.py (no spill, no scratch, <= 128 VGPRs in all 26 instantiations) is what holds it.
+        const int tid = (int)threadIdx.x | s_flags[0];
+        if (tid < CPW * 16) {
+            const int s = tid >> 4, l = tid & 15;
+            LatSlot& sl = s_slot[s];
+            const int phase = sl.phase, ready = sl.ready;
+            // (every point added the constant of its scale to each sum it touched: see LatFix; BOUNDED: every KEPT point, and
+            // the fitness pass below keeps them all)
+            const int nv = BOUNDED && phase == LAT_ITER ? (int)s_nv[s] : sl.n;
+            const unsigned long long off = (unsigned long long)nv * LatFix<FIX_SHIFT>::C, off_d = (unsigned long long)nv * LatFix<FIX_SHIFT_D2>::C;
+            if (phase == LAT_ITER && ready) {
+                RowLanes row(tid);
+                RowLanes::V<unsigned long long> a;
+                a.v = s_acc[s][l] - (l == 15 ? off_d : off);   // the lane that owns a sum takes the constants off it
+                const int done = icp_step_row<BOUNDED>(row, s_so[s], a, nv, prm);
+                s_acc[s][l] = 0ull;
+                if (l == 0) {
+                    if (done) sl.phase = LAT_FIT;
+                    if constexpr (BOUNDED) s_nv[s] = 0u;
+                    sl.ready = 0;
+                }
+            } else if (phase == LAT_FIT && l == 0) {
+                s_so[s].done = 1;
+                st[2 * (size_t)sl.k] = s_so[s];
+                st[2 * (size_t)sl.k + 1] = s_so[s];
+                accf[sl.k] = s_acc[s][0] - off_d;
+                refill(s);
+                if (sl.phase != LAT_EMPTY) s_flags[1] = 1;
+            }
+        }
+#else
+        // ---- solve phase, single-lane variant (-DCD_LAT_SOLVE_ROW=0, A/B runs): lane s of wave 0 <-> slot s ----
         if (threadIdx.x < CPW) {
             const int s = threadIdx.x;
             LatSlot& sl = s_slot[s];
-            // (every point added the constant of its scale to each sum it touched: see LatFix; BOUNDED: every KEPT point, and
-            // the fitness pass below keeps them all)
             const int nv = BOUNDED && sl.phase == LAT_ITER ? (int)s_nv[s] : sl.n;
             const unsigned long long off = (unsigned long long)nv * LatFix<FIX_SHIFT>::C, off_d = (unsigned long long)nv * LatFix<FIX_SHIFT_D2>::C;
             if (sl.phase == LAT_ITER && sl.ready) {
@@ -556,18 +600,18 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                 if (sl.phase != LAT_EMPTY) s_flags[1] = 1;
             }
         }
-        if (threadIdx.x == 0) {
-            int all_empty = 1;
-            for (int s = 0; s < CPW; ++s) all_empty &= s_slot[s].phase == LAT_EMPTY ? 1 : 0;
-            s_flags[0] = all_empty;
-        }
+#endif
         LAT_T(2)
         __syncthreads();
         LAT_T(3)
 #ifdef CD_LAT_TIMERS
         tph[4] += 1;
 #endif
-        if (s_flags[0]) break;
+        // (behind the barrier: the slots of both solving waves are settled, and nobody changes one before the next barrier)
+        int all_empty = 1;
+#pragma unroll
+        for (int s = 0; s < CPW; ++s) all_empty &= s_slot[s].phase == LAT_EMPTY ? 1 : 0;
+        if (all_empty) break;
     }
 #ifdef CD_LAT_TIMERS
     if (threadIdx.x == 0) for (int i = 0; i < 6; ++i) atomicAdd(&g_lat_stats[i], (unsigned long long)tph[i]);

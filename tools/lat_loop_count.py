@@ -22,7 +22,18 @@ loop of the LAT_ITER branch along the path a flagship batch takes:
    if / else, the out-of-range form of the moment sums, which no lane of a flagship batch takes.
 
 A vector instruction is a line whose mnemonic starts with "v_" (VALU incl. compares, moves, lane reads); ds_ / global_ / s_ are
-listed separately.  --csrc DIR counts another checkout's perception_amd/csrc (the parent commit's, for a before / after)."""
+listed separately.  --csrc DIR counts another checkout's perception_amd/csrc (the parent commit's, for a before / after).
+
+--solve reports the SOLVE instead (nothing else is compiled): a stand-alone probe with one kernel that calls the single-lane
+icp_step and, where the checkout has icp_solve_row.hpp, one that calls icp_step_row on a row, compiled with the same command.
+Per kernel, in layout order: the vector instructions before the sweep loop (the only loop that holds a v_sqrt_f32), inside it
+and after it.  The sweep loop holds the three (p, q) pair bodies, so "rotation" = loop / 3: threshold test, rotation parameters,
+the updates of W, U and V, a third of the loop control.  Every conditionally executed region is counted (both arms of t == 0 and
+y == 0, the rank-2 branch after the loop) EXCEPT, in the row kernel, the plain form of row_rotation: the forward branch after the
+validity test whose skipped region holds exactly the six IEEE divisions (v_div_fixup_f32) and three square roots of
+jacobi_svd3's own statements - the largest such region of each pair.  Three are expected; anything else ends the tool with a
+message.  The short form's own IEEE divisions (d / t and the one of tau) and square roots are listed, so that a build which lost
+the short forms (-DCD_ROW_RCP_GE1=0, a compiler that expands them differently) shows as six divisions per rotation."""
 import argparse
 import heapq
 import json
@@ -159,6 +170,103 @@ def hot_path(asm_lines, mangled):
             "other_nearest_blocks_v_bfi": [c[0] for c in cands[1:]]}
 
 
+SOLVE_PROBE = r"""
+#include "icp_solve.hpp"
+#if __has_include("icp_solve_row.hpp")
+#include "icp_solve_row.hpp"
+#define HAVE_ROW 1
+#endif
+using namespace cd;
+extern "C" __global__ void __launch_bounds__(64) probe_lane(IcpState* st, const unsigned long long* A, const int* n, IcpParams prm, int* done) {
+    __shared__ IcpState so;
+    __shared__ unsigned long long a[16];
+    if (threadIdx.x < 16) a[threadIdx.x] = A[blockIdx.x * 16 + threadIdx.x];
+    if (threadIdx.x == 0) {
+        so = st[blockIdx.x];
+        done[blockIdx.x] = icp_step<false>(so, a, n[blockIdx.x], prm);
+        st[blockIdx.x] = so;
+    }
+}
+#ifdef HAVE_ROW
+extern "C" __global__ void __launch_bounds__(64) probe_row(IcpState* st, const unsigned long long* A, const int* n, IcpParams prm, int* done) {
+    __shared__ IcpState so;
+    const int tid = (int)threadIdx.x;
+    if (tid >= 16) return;
+    if (tid == 0) so = st[blockIdx.x];
+    RowLanes row(tid);
+    RowLanes::V<unsigned long long> a;
+    a.v = A[blockIdx.x * 16 + tid];
+    const int d = icp_step_row<false>(row, so, a, n[blockIdx.x], prm);
+    if (tid == 0) { done[blockIdx.x] = d; st[blockIdx.x] = so; }
+}
+#endif
+"""
+
+
+def compile_probe(csrc, src, out):
+    """The Makefile's compile line for k_icp_lat.o with the probe as the source, device-only -S."""
+    dry = subprocess.run(["make", "-C", csrc, "-n", "-B", "build/k_icp_lat.o"], check=True, capture_output=True, text=True).stdout
+    line = next(l for l in dry.splitlines() if "k_icp_lat.hip" in l and " -c " in l)
+    argv = shlex.split(line)
+    argv[argv.index("-o") + 1] = out
+    argv[argv.index("-c")] = "-S"
+    argv[argv.index("k_icp_lat.hip")] = src
+    argv[1:1] = ["--cuda-device-only", "-I", csrc]
+    subprocess.run(argv, check=True, cwd=csrc, stderr=subprocess.DEVNULL)
+
+
+def solve_counts(asm_lines, kernel, skip_plain):
+    i = next((k for k, l in enumerate(asm_lines) if l.startswith(kernel + ":")), None)
+    if i is None:
+        return None
+    j = next(k for k in range(i, len(asm_lines)) if asm_lines[k].strip().startswith("s_endpgm"))
+    blocks = parse_blocks(asm_lines[i + 1:j + 1])
+    pos = {b["name"]: k for k, b in enumerate(blocks)}
+    hdrs = {b["loop"][0] for b in blocks if b["loop"] and b["loop"][1] and count(b["insts"], "v_sqrt_f32")}
+    if len(hdrs) != 1:
+        raise SystemExit("%s: expected ONE loop with square roots (the sweeps), found %s: look at the assembly" % (kernel, sorted(hdrs)))
+    hdr = hdrs.pop()
+    inside = [k for k, b in enumerate(blocks) if (b["loop"] and b["loop"][0] == hdr) or b["name"].split("+")[0] == hdr]
+    first, last = min(inside), max(inside)
+    n = lambda ks, pre: sum(count(blocks[k]["insts"], pre) for k in ks)
+    skipped = set()
+    if skip_plain:
+        regions = []
+        for k in range(first, last + 1):
+            for t in blocks[k]["insts"]:
+                m = BRANCH.match(t)
+                if m and m.group(1) != "s_branch" and pos.get(m.group(2), -1) > k + 1:
+                    r = range(k + 1, pos[m.group(2)])
+                    if n(r, "v_div_fixup_f32") == 6 and n(r, "v_sqrt_f32") == 3:
+                        regions.append(r)
+        regions = [r for r in regions if not any(o is not r and o.start <= r.start and r.stop <= o.stop for o in regions)]
+        if len(regions) != 3:
+            raise SystemExit("%s: expected the plain form of row_rotation three times, found %d regions: look at the assembly" % (kernel, len(regions)))
+        for r in regions:
+            skipped.update(r)
+    loop = [k for k in range(first, last + 1) if k not in skipped]
+    part = lambda ks: {"valu": n(ks, "v_"), "v_div_fixup_f32": n(ks, "v_div_fixup_f32"), "v_div_fixup_f64": n(ks, "v_div_fixup_f64"),
+                       "v_sqrt_f32": n(ks, "v_sqrt_f32"), "v_rcp_f32": n(ks, "v_rcp_f32"), "ds_bpermute": n(ks, "ds_bpermute"),
+                       "salu": n(ks, "s_") - n(ks, "s_waitcnt") - n(ks, "s_nop")}
+    out = {"before": part(range(0, first)), "loop": part(loop), "after": part(range(last + 1, len(blocks))), "plain_form_skipped": part(sorted(skipped))}
+    out["rotation"] = {k: v / 3.0 for k, v in out["loop"].items()}
+    return out
+
+
+def solve_report(csrc, keep):
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(tmp, "solve_probe.hip")
+        open(src, "w").write(SOLVE_PROBE)
+        out = os.path.abspath(keep) if keep else os.path.join(tmp, "solve_probe.s")
+        compile_probe(csrc, src, out)
+        lines = open(out).read().split("\n")
+    res = {"lane": solve_counts(lines, "probe_lane", False)}
+    row = solve_counts(lines, "probe_row", True)
+    if row is not None:
+        res["row"] = row
+    return res
+
+
 def resources(asm_lines):
     """vgprs / sgprs / spills / scratch / LDS of every k_icp_lat instantiation, from the .amdhsa metadata."""
     out, cur = {}, None
@@ -181,7 +289,19 @@ def main():
     ap.add_argument("--csrc", default=os.path.join(ROOT, "perception_amd", "csrc"))
     ap.add_argument("--keep", help="write the assembly here")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--solve", action="store_true", help="report the solve (icp_step / icp_step_row) instead of the pass loop")
     a = ap.parse_args()
+    if a.solve:
+        res = {"solve": solve_report(os.path.abspath(a.csrc), a.keep)}
+        if a.json:
+            print(json.dumps(res))
+            return 0
+        for k, r in res["solve"].items():
+            for part in ("before", "rotation", "after"):
+                p = r[part]
+                print("%-4s %-8s vector instructions %6.1f (IEEE f32 divisions %.1f, f64 %.1f, v_sqrt_f32 %.1f, v_rcp_f32 %.1f), ds_bpermute %.1f, scalar %.1f" % (
+                    k, part, p["valu"], p["v_div_fixup_f32"], p["v_div_fixup_f64"], p["v_sqrt_f32"], p["v_rcp_f32"], p["ds_bpermute"], p["salu"]))
+        return 0
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.abspath(a.keep) if a.keep else os.path.join(tmp, "k_icp_lat.s")
         compile_to_asm(os.path.abspath(a.csrc), out)
