@@ -797,6 +797,59 @@ int cd_verify_last_results(cd_context* ctx, const cd_depth_camera* cam, const ui
 int cd_verify_last_results_device(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* d_depth, int which,
                                   const cd_verify_params* params, cd_verify_box* out);
 
+/* Point labels: for every INPUT record (pixel) of the last fused call of the context, what the chain made of it.  Canonical rule
+ * C15; the rule is by provenance - a point takes the class of the voxel VoxelGrid put it in, and the voxel's class
+ * is read off the call's own plane_inliers, object cloud and labels, so a label can never disagree with the call's records.
+ * One uint8 per record:
+ *   CD_LABEL_INVALID  x, y or z is not finite (a depth value of 0 under rule C7);
+ *   CD_LABEL_CROPPED  finite, but outside the S0 limits (the z limits, then the x limits; double limits, inclusive);
+ *   CD_LABEL_PLANE    kept by S0, its voxel is in the call's refined inlier list and not in its object cloud;
+ *   CD_LABEL_OBJECT   its voxel is in the object cloud with cluster label -1 or a cluster rank >= 248;
+ *   CD_LABEL_GATED    kept by S0, its voxel is in neither set (removed by S3b or the bbox gate; a non-inlier with
+ *                     extract_negative = 0; the frame's status ended the chain before S3);
+ *   5 .. 7            reserved, never written;
+ *   CD_LABEL_CLUSTER0 + r   its voxel is in the object cloud with cluster label r, 0 <= r < 248 (the rank order of
+ *                     cd_get_cluster_results; with cluster_enable = 0 every object voxel has rank 0).
+ * A point's voxel is the cell floor(p * inv_leaf) - min_b in float32, inv_leaf = 1.0f / leaf; a voxel's number is the rank of its
+ * idx = i + j dx + k dx dy among the frame's occupied cells: the order of CD_CLOUD_VOXELS.  perception_amd/point_labels.py
+ * restates the rule in numpy and the device equals it byte for byte. */
+enum { CD_LABEL_INVALID = 0, CD_LABEL_CROPPED = 1, CD_LABEL_PLANE = 2, CD_LABEL_OBJECT = 3, CD_LABEL_GATED = 4, CD_LABEL_CLUSTER0 = 8 };
+/* The caller passes the frames of the fused call AGAIN (as cd_verify_last_results takes the depth images again: the library does
+ * not keep its input).  out receives n_frames * points_per_frame bytes in record order - for an organized cloud it is the label
+ * image.  CD_ERR_INVALID_ARG: a null pointer; no fused call, or another compute call has run since (the validity rule of
+ * cd_get_cluster_results); n_frames, points_per_frame or stride_bytes differing from that call's (a depth-fed call has 16-byte
+ * records).  Data that is not that call's input has a defined result: the rule evaluated on that data against the call's grid -
+ * a cell that holds no voxel reads CD_LABEL_GATED, and a cell outside the grid is a miss that is never used as an index.
+ * The fused call's records and read-backs stay valid, and draw, verify and label calls can follow each other in any order.
+ * _device: frames and out are device memory of the context's GPU (ordering as cd_process_batch_device). */
+int cd_label_points_last(cd_context* ctx, const void* frames, size_t stride_bytes, int points_per_frame, int n_frames, uint8_t* out);
+int cd_label_points_last_device(cd_context* ctx, const void* d_frames, size_t stride_bytes, int points_per_frame, int n_frames,
+                                uint8_t* d_out);
+/* The same from the n_frames tightly packed 16UC1 depth images of the call, deprojected by rule C7 (no colour image is read):
+ * out is the label image, cam->width * cam->height bytes per frame.  Serves cd_process_depth_batch[_device], a cloud-fed call
+ * whose records were the rule-C7 cloud of these images, and cd_process_depth_batch_mapped[_device] with CD_NOTEX_KEEP.  A
+ * mapped call with CD_NOTEX_DROP is REFUSED with CD_ERR_INVALID_ARG: rule C12 gives its untextured pixels NaN coordinates, which
+ * rule C7 does not, so the depth image alone does not say what that call's records were - label such a call through
+ * cd_label_points_last with the records of cd_depth_to_cloud_mapped.  Further CD_ERR_INVALID_ARG: a null pointer, fx, fy or
+ * depth_scale not finite or <= 0, width * height or n_frames differing from that call's. */
+int cd_label_depth_last(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* depth, int n_frames, uint8_t* out);
+int cd_label_depth_last_device(cd_context* ctx, const cd_depth_camera* cam, const uint16_t* d_depth, int n_frames, uint8_t* d_out);
+
+/* Tint: labels drawn over tightly packed rgb8 images in place.  For each pixel and channel c' = (c (255 - a) + p a + 127) / 255
+ * in integers, (p, a) = palette->rgba[label][channel], [3].  palette == NULL: the default palette - alpha 0 for CD_LABEL_INVALID
+ * and CD_LABEL_CROPPED (the pixel stays as it is), a grey for the plane, orange for CD_LABEL_OBJECT, a dark red for
+ * CD_LABEL_GATED, and eight cluster colours that repeat with the rank.  A host-side utility of the image domain: it reads no
+ * state of a fused call and invalidates none.  CD_ERR_INVALID_ARG: a null image or labels, width * height 0 or over max_points,
+ * n_frames outside 1 .. max_frames. */
+typedef struct cd_label_palette { uint8_t rgba[256][4]; } cd_label_palette;
+void cd_default_label_palette(cd_label_palette* palette);
+/* sizeof as this library was built: which = 0 cd_label_palette, anything else -1 (cd_struct_size's list is closed). */
+int cd_label_struct_size(int which);
+int cd_tint_labels_batch(cd_context* ctx, uint8_t* rgb8, const uint8_t* labels, int width, int height, int n_frames,
+                         const cd_label_palette* palette);
+int cd_tint_labels_batch_device(cd_context* ctx, uint8_t* d_rgb8, const uint8_t* d_labels, int width, int height, int n_frames,
+                                const cd_label_palette* palette);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "cd_shape_frame_struct_size", "cd_shape_frame_host", "cd_shape_frames", "cd_template_shape_frame", "cd_shape_guess",
     "cd_get_cluster_shape_frames",
     "cd_icp_solve_batch",
+    "cd_label_points_last", "cd_label_points_last_device", "cd_label_depth_last", "cd_label_depth_last_device",
+    "cd_default_label_palette", "cd_label_struct_size", "cd_tint_labels_batch", "cd_tint_labels_batch_device",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -62,6 +64,7 @@ CD_DRAW_ACCEPTED, CD_DRAW_ALL = 0, 1
 CD_VERIFY_ACCEPTED, CD_VERIFY_ALL = 0, 1
 CD_VERIFY_MISS, CD_VERIFY_AGREE, CD_VERIFY_THROUGH, CD_VERIFY_OCCLUDED, CD_VERIFY_INVALID = 0, 1, 2, 3, 4
 CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
+CD_LABEL_INVALID, CD_LABEL_CROPPED, CD_LABEL_PLANE, CD_LABEL_OBJECT, CD_LABEL_GATED, CD_LABEL_CLUSTER0 = 0, 1, 2, 3, 4, 8
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -187,6 +190,17 @@ class CdVerifyBox(C.Structure):
 
 
 FRAME_RESULT_BYTES = C.sizeof(CdFrameResult)
+
+
+class CdLabelPalette(C.Structure):
+    _fields_ = [("rgba", (C.c_uint8 * 4) * 256)]
+
+
+def default_label_palette():
+    """The default palette of cd_tint_labels_batch as a (256, 4) uint8 array: r g b alpha per label."""
+    p = CdLabelPalette()
+    load_library().cd_default_label_palette(C.byref(p))
+    return np.frombuffer(bytes(p), np.uint8).reshape(256, 4).copy()
 
 
 def default_verify_params():
@@ -437,6 +451,16 @@ def load_library(path=None):
     lib.cd_template_shape_frame.argtypes = [vp, C.c_int, sfp]
     lib.cd_shape_guess.argtypes = [sfp, sfp, f32p, i32p]
     lib.cd_get_cluster_shape_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, sfp]
+    lpp, u8p = C.POINTER(CdLabelPalette), C.c_void_p
+    for f in (lib.cd_label_points_last, lib.cd_label_points_last_device):
+        f.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, u8p]
+    for f in (lib.cd_label_depth_last, lib.cd_label_depth_last_device):
+        f.argtypes = [vp, dcp, vp, C.c_int, u8p]
+    lib.cd_default_label_palette.argtypes = [lpp]
+    lib.cd_default_label_palette.restype = None
+    lib.cd_label_struct_size.argtypes = [C.c_int]
+    for f in (lib.cd_tint_labels_batch, lib.cd_tint_labels_batch_device):
+        f.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_int, lpp]
     if path is None:
         _lib = lib
     return lib
@@ -776,6 +800,56 @@ class Context:
         fn = self.lib.cd_verify_last_results_device if on_device else self.lib.cd_verify_last_results
         self._check(fn(self.h, C.byref(cam), ptr, int(which), None if params is None else C.byref(params), out))
         return out
+
+    def label_points_last(self, frames, out=None):
+        """Rule C15: one uint8 label per input record of the LAST fused call, whose frames are passed again: a C-contiguous
+        (F, P, k) float32 numpy array (cd_label_points_last; returns an (F, P) uint8 array) or a contiguous float32 torch tensor
+        of that shape in HBM (cd_label_points_last_device; `out`, an (F, P) uint8 tensor on the same device, is filled and
+        returned).  Leaves the fused call's read-backs as they are."""
+        if isinstance(frames, np.ndarray):
+            assert frames.dtype == np.float32 and frames.ndim == 3 and frames.shape[2] >= 3 and frames.flags.c_contiguous
+            F, P = frames.shape[:2]
+            res = np.empty((F, P), np.uint8)
+            self._check(self.lib.cd_label_points_last(self.h, _ptr(frames), frames.strides[1], P, F, _ptr(res)))
+            return res
+        assert frames.is_contiguous() and frames.dim() == 3 and frames.element_size() == 4
+        F, P = (int(v) for v in frames.shape[:2])
+        assert out is not None and out.is_contiguous() and out.numel() == F * P and out.element_size() == 1
+        self._check(self.lib.cd_label_points_last_device(self.h, C.c_void_p(frames.data_ptr()), 4 * int(frames.shape[2]), P, F, C.c_void_p(out.data_ptr())))
+        return out
+
+    def label_depth_last(self, depth, cam, out=None):
+        """Rule C15 from the depth images of the last fused call (deprojected by rule C7): an (F, H, W) uint16 numpy array
+        (cd_label_depth_last; returns the (F, H, W) uint8 label images) or a 16-bit torch tensor of that shape in HBM
+        (cd_label_depth_last_device; `out`, an (F, H, W) uint8 tensor on the same device, is filled and returned)."""
+        ptr, on_device, F, H, W = self._depth_images(depth)
+        assert (cam.width, cam.height) == (W, H)
+        if not on_device:
+            res = np.empty((F, H, W), np.uint8)
+            self._check(self.lib.cd_label_depth_last(self.h, C.byref(cam), ptr, F, _ptr(res)))
+            return res
+        assert out is not None and out.is_contiguous() and out.numel() == F * H * W and out.element_size() == 1
+        self._check(self.lib.cd_label_depth_last_device(self.h, C.byref(cam), ptr, F, C.c_void_p(out.data_ptr())))
+        return out
+
+    def tint_labels(self, rgb, labels, palette=None):
+        """cd_tint_labels_batch[_device]: the labels drawn IN PLACE over rgb, an (F, H, W, 3) uint8 numpy array with (F, H, W)
+        uint8 numpy labels, or torch tensors of those shapes in HBM.  palette: None (the default) or a (256, 4) uint8 array."""
+        pal = None
+        if palette is not None:
+            pal = CdLabelPalette.from_buffer_copy(np.ascontiguousarray(palette, np.uint8).reshape(256, 4).tobytes())
+        on_device = not isinstance(rgb, np.ndarray)
+        F, H, W = (int(v) for v in rgb.shape[:3])
+        if on_device:
+            assert rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3 and labels.is_contiguous() and labels.numel() == F * H * W
+            a, b = C.c_void_p(rgb.data_ptr()), C.c_void_p(labels.data_ptr())
+        else:
+            assert rgb.dtype == np.uint8 and rgb.ndim == 4 and rgb.shape[3] == 3 and rgb.flags.c_contiguous and rgb.flags.writeable
+            assert labels.dtype == np.uint8 and labels.size == F * H * W and labels.flags.c_contiguous
+            a, b = _ptr(rgb), _ptr(labels)
+        fn = self.lib.cd_tint_labels_batch_device if on_device else self.lib.cd_tint_labels_batch
+        self._check(fn(self.h, a, b, W, H, F, None if pal is None else C.byref(pal)))
+        return rgb
 
     def surface_batch(self, clouds, table_normals, prm, invert=True):
         """cd_surface_batch: cd_surface_frame over a batch of (ragged) clouds, fitted together on the device.

@@ -418,6 +418,14 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     else st = icp_per_template(c, p, F, cl, &bi);
     if (st) return st;
     publish_last(c, p, F, cl, &bi);
+    {   // what the label calls (rule C15, labels.hip) need of this call; host fields only
+        LastCall& lc = c->last_call;
+        lc.stride = stride; lc.N = N; lc.F = F;
+        lc.prm = *p;
+        lc.rects = c->call_rects;
+        lc.depth_is_c7 = !(dj && dj->ccam && dj->ccam->no_texture != CD_NOTEX_KEEP);
+        lc.keys = c->voxel_keys;
+    }
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     // records and read-out
     write_frame_records(c, N, F, cl, fr, results);

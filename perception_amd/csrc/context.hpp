@@ -56,6 +56,24 @@ struct Tunables {
                                   // persistent ICP launch (config 3: -1 %)
 };
 
+// Rule C15: the sorted keys of the voxel stage are still in d_key[cur] when a fused call returns (nothing after the centroid kernel
+// writes d_key / d_val).  Frame f's keys are its first n_runs (by_runs) or n_c entries; `packed`: the bit fields of k_crop_runs
+// with their KeyPack, otherwise PCL's idx.  `path` names the crop / voxel path for messages.
+struct VoxelKeys {
+    int cur = 0, by_runs = 0, packed = 0;
+    KeyPack kp = {0, 0, 0, 0, 0, 0};
+    const char* path = "none";
+};
+// What a label call needs of the last fused call besides the device buffers (valid while last_first is not empty)
+struct LastCall {
+    size_t stride = 0;
+    int N = 0, F = 0;
+    cd_params prm = {};
+    FrameRects rects{nullptr, 0};   // the per-frame rectangles its gate read (device memory that stays until the next fused call)
+    bool depth_is_c7 = true;        // false: a mapped call that dropped its untextured points (rule C12's xyz is not rule C7's)
+    VoxelKeys keys;
+};
+
 // The streams and events of a context.  A base of cd_context, so that they outlive its buffers: the members of cd_context
 // are destroyed (the buffers freed) before this destructor runs.  stream2 / stream3: the streams of the persistent ICP
 // launches: the second launch of a mixed-template batch runs beside the first (stream2); with icp_lowprio both are low-priority
@@ -201,6 +219,14 @@ struct cd_context : cd_streams {
     bool last_shapes_ok = false;
     DevBuf<IcpState> d_st; PinBuf<IcpState> h_st;
     DevBuf<unsigned long long> d_acc, d_accf; PinBuf<unsigned long long> h_accf;
+    // point labels (rule C15, k_labels.hip): where the voxel stage left its sorted keys (host fields, set at the end of
+    // stage_crop_voxel), what the last fused call ran with (set when it publishes its read-backs), and the buffers of the label
+    // calls, all grown on demand: the voxel keys and classes of every frame (rows of one pitch), the labels and the label images
+    // of the host forms
+    VoxelKeys voxel_keys;
+    LastCall last_call;
+    DevBuf<uint32_t> d_vkey;
+    DevBuf<uint8_t> d_vclass, d_plabel, d_tlabel;
     cd_timing timing;
 };
 
@@ -390,6 +416,8 @@ int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, i
 int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int F, const cd_params* p, int* rounds_out);
 int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iterations, int* rounds_out, const float* axes = nullptr);
 int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode = -1);
+struct ExtractArgs { float thr, z2lo, z2hi; BBoxGate gate; };   // what the S3 kernels take of cd_params (also rule C15's voxel classes)
+ExtractArgs extract_args(const cd_params* p, int gate_mode);
 int stage_cluster_sync(cd_context* c, int F, const cd_params* p, int max_no);
 void set_icp_clusters(cd_context* c, int first, int n, int frame, const int* size, const int* off, int base, int slot);
 ShapeFrame template_frame(const cd_context* c, int slot);

@@ -134,6 +134,12 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
                                              rgb_off >= 0 ? 1 : 0, c->d_fs, c->d_tileC, c->d_vox, c->d_ticket, c->tun.centroid_lanes, crop_runs && direct_pts ? N : c->N));
     else
         LAUNCH(c, launch_voxel_centroid(c->stream, c->d_key[cur], vin, c->d_cpt, c->N, F, T, Tc, rgb_off >= 0 ? 1 : 0, c->d_fs, c->d_tileC, c->d_vox, c->d_ticket));
+    // (rule C15: where the sorted keys are and what they are)
+    c->voxel_keys.cur = cur;
+    c->voxel_keys.by_runs = (crop_runs || by_runs) ? 1 : 0;
+    c->voxel_keys.packed = crop_runs ? 1 : 0;
+    c->voxel_keys.kp = kp;
+    c->voxel_keys.path = crop_runs ? (direct_pts ? "runs direct" : "runs compacted") : (by_runs ? (kp.enabled ? "fused single pass" : "two-pass") : "sort by points");
     if (rounds_out) *rounds_out = 0;
     return CD_OK;
 }
@@ -242,19 +248,27 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
     return CD_OK;
 }
 
+ExtractArgs extract_args(const cd_params* p, int gate_mode) {
+    ExtractArgs ea;
+    ea.thr = hm::fold_ge(p->plane_distance_threshold);
+    ea.z2lo = hm::fold_ge(p->crop2_z_min);
+    ea.z2hi = hm::fold_le(p->crop2_z_max);
+    std::memset(&ea.gate, 0, sizeof(ea.gate));
+    ea.gate.enable = gate_mode >= 0 ? gate_mode : (p->bbox_enable ? 1 : 0);
+    for (int i = 0; i < 12; ++i) ea.gate.P[i] = p->bbox_P[i];
+    for (int i = 0; i < 4; ++i) ea.gate.rect[i] = (float)p->bbox_rect[i];
+    return ea;
+}
+
 // S3 (+S3b).  out: d_plane_idx, d_obj, fs.n_plane, fs.n_o
 int stage_extract(cd_context* c, int F, const cd_params* p, int gate_mode) {
     const int T = c->T;
-    const float thr = hm::fold_ge(p->plane_distance_threshold);
     int max_nv = 0;
     for (int f = 0; f < F; ++f) max_nv = std::max(max_nv, c->h_fs[f].n_v);
     const int Tv = std::max(1, (max_nv + TILE - 1) / TILE);
-    const float z2lo = hm::fold_ge(p->crop2_z_min), z2hi = hm::fold_le(p->crop2_z_max);
-    BBoxGate gate;
-    std::memset(&gate, 0, sizeof(gate));
-    gate.enable = gate_mode >= 0 ? gate_mode : (p->bbox_enable ? 1 : 0);
-    for (int i = 0; i < 12; ++i) gate.P[i] = p->bbox_P[i];
-    for (int i = 0; i < 4; ++i) gate.rect[i] = (float)p->bbox_rect[i];
+    const ExtractArgs ea = extract_args(p, gate_mode);
+    const float thr = ea.thr, z2lo = ea.z2lo, z2hi = ea.z2hi;
+    const BBoxGate& gate = ea.gate;
     const float4* model_p = c->tun.mirror_reads ? c->h_model : c->d_model;   // (see stage_plane)
     const int* have_p = c->tun.mirror_reads ? c->h_active : c->d_have;
     ZERO_FILL(c, c->d_tileA, sizeof(int) * (size_t)F * T);

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "label_math.hpp"
 
 namespace cd {
 
@@ -61,14 +62,7 @@ __global__ void __launch_bounds__(BLOCK) k_deproject(const uint16_t* __restrict_
                 uint32_t rgb = 0u;
                 if (color) rgb = ((uint32_t)sc[3 * j] << 16) | ((uint32_t)sc[3 * j + 1] << 8) | (uint32_t)sc[3 * j + 2];
                 float4 r;
-                if (d == 0u) {
-                    r.x = r.y = r.z = __uint_as_float(0x7FC00000u);
-                } else {
-                    const float z = (float)d * dp.depth_scale;
-                    r.x = (((float)u - dp.cx) / dp.fx) * z;
-                    r.y = (((float)v - dp.cy) / dp.fy) * z;
-                    r.z = z;
-                }
+                deproject_c7(u, v, d, dp.fx, dp.fy, dp.cx, dp.cy, dp.depth_scale, &r.x, &r.y, &r.z);   // (label_math.hpp: rule C15 deprojects the same way)
                 r.w = __uint_as_float(rgb);
                 out[g0 + j] = r;
             }

@@ -180,4 +180,28 @@ struct VerifyRecord { int32_t verified, passed, n_hit, n_agree, n_through, n_occ
 void launch_verify_boxes(hipStream_t s, const uint16_t* depth, const VerifyCam& cam, double tau, const VerifyJob* jobs, const int32_t* n_boxes,
                          int B, int F, VerifyRecord* out);
 
+// k_labels.hip : rule C15, the label of every input record of the last fused call, and the tint of label images
+// step 1: voxel v's key, in the order of d_vox, from the frame's sorted keys (rows of N; n_runs of them when by_runs, else n_c) -> vkey[f * vpitch + v]
+void launch_label_voxel_keys(hipStream_t s, const uint32_t* keys, int N, int F, const FrameState* fs, int by_runs, uint32_t* vkey, int vpitch);
+// step 2: voxel v's class (CD_LABEL_PLANE / OBJECT / GATED / CLUSTER0 + r) from the call's plane index list, the S3 predicate and
+// the cluster labels -> vclass[f * vpitch + v]
+void launch_label_voxel_classes(hipStream_t s, const float4* vox, int N, int F, const FrameState* fs, const float4* model, const int* have,
+                                float thr, int negative, int crop2, float z2lo, float z2hi, const BBoxGate& gate, const FrameRects& rects,
+                                const int* plane_idx, const int* label, uint8_t* vclass, int vpitch);
+// step 3: the batch as one linear stream of F * P records (depth == nullptr: `stride` bytes each, x y z first) or pixels (rule C7)
+struct LabelPointsParams {
+    CropLimits lim;
+    float inv_leaf;
+    int32_t packed;          // the keys are k_crop_runs' bit fields (kp), else PCL's idx
+    KeyPack kp;
+    uint32_t P;              // records / pixels per frame
+    int32_t F, vpitch;
+    uint32_t width;          // depth form
+    float fx, fy, cx, cy, depth_scale;
+};
+void launch_label_points(hipStream_t s, const void* records, size_t stride, const uint16_t* depth, const LabelPointsParams& lp,
+                         const FrameState* fs, const uint32_t* vkey, const uint8_t* vclass, uint8_t* out);
+struct LabelPalette { uint32_t rgba[256]; };   // = cd_label_palette: byte 0 r, 1 g, 2 b, 3 alpha
+void launch_tint_labels(hipStream_t s, uint8_t* rgb, const uint8_t* labels, size_t pixels, const LabelPalette& pal);
+
 }  // namespace cd
