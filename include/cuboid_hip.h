@@ -850,6 +850,47 @@ int cd_tint_labels_batch(cd_context* ctx, uint8_t* rgb8, const uint8_t* labels, 
 int cd_tint_labels_batch_device(cd_context* ctx, uint8_t* d_rgb8, const uint8_t* d_labels, int width, int height, int n_frames,
                                 const cd_label_palette* palette);
 
+/* Statistical outlier removal on the object cloud (pcl::StatisticalOutlierRemoval in front of EuclideanClusterExtraction).
+ * Canonical rule C16; perception_amd/outlier_filter.py restates it in numpy and the device equals it bit for
+ * bit - every dist_i, the statistics and the kept set.  Parity with a real PCL is unpinned, as for every other rule (its k-d
+ * tree's order among equidistant neighbours and its summation order are its own).  For a cloud of n points, mean_k in
+ * 1 .. CD_OUTLIER_MAX_MEAN_K, std_mul and negative:
+ *   1. points with a non-finite coordinate are dropped first: never a neighbour, not counted, never in the output; m finite points;
+ *   2. m <= mean_k: every finite point is kept (negative or not), nothing is computed, the statistics are reported as 0;
+ *   3. for finite point i the float32 squared distances (dx*dx + dy*dy) + dz*dz to ALL finite points, itself included; of these
+ *      the mean_k + 1 smallest as a multiset less exactly one, the smallest (itself; a coincident twin's 0 stays and counts);
+ *   4. their float32 square roots added into a double in ascending order; dist_i = (float)(sum / mean_k);
+ *   5. over the finite points in cloud order, sequentially in double: sum += d, sq += d * d; mean = sum / m,
+ *      var = (sq - sum * sum / m) / (m - 1), stddev = sqrt(var), threshold = mean + std_mul * stddev;
+ *   6. kept iff (double)dist_i <= threshold (negative: iff not); the output keeps the cloud's order.
+ *
+ * cd_set_outlier_filter: context state, as the ICP correspondence distance is.  mean_k = 0 turns the filter off (the default:
+ * no kernel of the fused calls changes and every output is byte for byte what it was); otherwise 1 <= mean_k <= 63 and std_mul
+ * finite, else CD_ERR_INVALID_ARG and the setting stays.  With the filter on, every fused call (cd_process_batch[_device],
+ * cd_process_frame, cd_process_depth_batch[_device], cd_process_depth_batch_mapped[_device]) filters each frame's object cloud
+ * between S3 and S5, and everything behind it takes the filtered cloud: clustering, the surface and cluster guesses, ICP,
+ * n_objects of the frame record, the `labels` output, cd_get_frame_cloud(CD_CLOUD_OBJECTS) (whole records: the colour travels
+ * with the point) and cd_get_cluster_points.  The label calls (rule C15) give a voxel that S3 moved into the object cloud and
+ * the filter removed CD_LABEL_GATED.  cd_ground_plane, cd_cluster, cd_icp and every other call of a single stage are unaffected.
+ * CD_OUTLIER_LDS_TILE: the candidates the kernel stages in LDS at a time (the sizes around it are where its loop turns). */
+#define CD_OUTLIER_MAX_MEAN_K 63
+#define CD_OUTLIER_LDS_TILE 1024
+int cd_set_outlier_filter(cd_context* ctx, int mean_k, double std_mul, int negative);
+int cd_get_outlier_filter(const cd_context* ctx, int* mean_k, double* std_mul, int* negative);
+/* What the filter did to `frame` of the last fused call: the object points before it, how many it removed, and the statistics
+ * of step 5 (0 when step 2 applied).  Any pointer may be NULL.  CD_ERR_INVALID_ARG when that call ran without the filter, has
+ * been invalidated (the validity rule of cd_get_cluster_results) or had no such frame. */
+int cd_get_outlier_stats(const cd_context* ctx, int frame, int* n_before, int* n_removed, double* mean, double* stddev,
+                         double* threshold);
+/* The filter as a call of its own (pcl::StatisticalOutlierRemoval::filter(indices)): the kept indices ascending, like
+ * cd_bbox_filter.  out_dist (may be NULL) receives n floats, dist_i, 0 for a dropped non-finite point; stats (may be NULL)
+ * mean, stddev, threshold.  Out-of-range arguments (mean_k outside 1 .. 63, a non-finite std_mul, n < 0, a stride below 12 or
+ * no multiple of 4, a null pointer) give CD_ERR_INVALID_ARG before anything is launched; n above the context's max_points
+ * CD_ERR_CAPACITY; capacity < kept CD_ERR_CAPACITY with *out_n = kept.  The context's own setting is neither read nor
+ * changed; like every compute call it invalidates the read-backs of the last fused call. */
+int cd_outlier_filter(cd_context* ctx, const void* xyz, size_t stride_bytes, int n, int mean_k, double std_mul, int negative,
+                      int32_t* out_indices, int capacity, int* out_n, float* out_dist, double stats[3]);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "cd_icp_solve_batch",
     "cd_label_points_last", "cd_label_points_last_device", "cd_label_depth_last", "cd_label_depth_last_device",
     "cd_default_label_palette", "cd_label_struct_size", "cd_tint_labels_batch", "cd_tint_labels_batch_device",
+    "cd_set_outlier_filter", "cd_get_outlier_filter", "cd_get_outlier_stats", "cd_outlier_filter",
 ]
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
@@ -65,6 +66,7 @@ CD_VERIFY_ACCEPTED, CD_VERIFY_ALL = 0, 1
 CD_VERIFY_MISS, CD_VERIFY_AGREE, CD_VERIFY_THROUGH, CD_VERIFY_OCCLUDED, CD_VERIFY_INVALID = 0, 1, 2, 3, 4
 CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 CD_LABEL_INVALID, CD_LABEL_CROPPED, CD_LABEL_PLANE, CD_LABEL_OBJECT, CD_LABEL_GATED, CD_LABEL_CLUSTER0 = 0, 1, 2, 3, 4, 8
+CD_OUTLIER_MAX_MEAN_K, CD_OUTLIER_LDS_TILE = 63, 1024
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -461,6 +463,10 @@ def load_library(path=None):
     lib.cd_label_struct_size.argtypes = [C.c_int]
     for f in (lib.cd_tint_labels_batch, lib.cd_tint_labels_batch_device):
         f.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_int, lpp]
+    lib.cd_set_outlier_filter.argtypes = [vp, C.c_int, C.c_double, C.c_int]
+    lib.cd_get_outlier_filter.argtypes = [vp, ip, dp, ip]
+    lib.cd_get_outlier_stats.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp]
+    lib.cd_outlier_filter.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.c_int, ip, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -900,6 +906,37 @@ class Context:
         v = C.c_double()
         self._check(self.lib.cd_get_icp_max_correspondence_distance(self.h, C.byref(v)))
         return v.value
+
+    def set_outlier_filter(self, mean_k, std_mul=1.0, negative=False):
+        """Rule C16 (pcl::StatisticalOutlierRemoval) on the object cloud of the following fused calls; mean_k = 0 (or None): off."""
+        self._check(self.lib.cd_set_outlier_filter(self.h, int(mean_k or 0), float(std_mul), 1 if negative else 0))
+
+    def outlier_filter_setting(self):
+        """(mean_k, std_mul, negative) as cd_set_outlier_filter left them; mean_k = 0: off."""
+        k, neg, mul = C.c_int(), C.c_int(), C.c_double()
+        self._check(self.lib.cd_get_outlier_filter(self.h, C.byref(k), C.byref(mul), C.byref(neg)))
+        return k.value, mul.value, bool(neg.value)
+
+    def outlier_stats(self, frame):
+        """What the filter did to `frame` of the last fused call: dict(n_before, n_removed, mean, stddev, threshold)."""
+        nb, nr = C.c_int(), C.c_int()
+        mean, sd, thr = C.c_double(), C.c_double(), C.c_double()
+        st = self.lib.cd_get_outlier_stats(self.h, frame, C.byref(nb), C.byref(nr), C.byref(mean), C.byref(sd), C.byref(thr))
+        if st != CD_OK:
+            raise CuboidError(st, "no filtered fused call to read: the last one ran without the filter, has been invalidated, or had no such frame")
+        return dict(n_before=nb.value, n_removed=nr.value, mean=mean.value, stddev=sd.value, threshold=thr.value)
+
+    def outlier_filter(self, xyz, mean_k, std_mul=1.0, negative=False, capacity=None):
+        """The filter as a call of its own.  Returns (kept indices int32 ascending, dist float32 (n), (mean, stddev, threshold))."""
+        a, stride, n = _points(xyz)
+        cap = max(n, 1) if capacity is None else int(capacity)
+        idx = np.empty(max(cap, 1), np.int32)
+        dist = np.zeros(max(n, 1), np.float32)
+        stats = np.zeros(3, np.float64)
+        cnt = C.c_int()
+        self._check(self.lib.cd_outlier_filter(self.h, _ptr(a), stride, n, int(mean_k), float(std_mul), 1 if negative else 0, _ptr(idx), cap,
+                                               C.byref(cnt), _ptr(dist), _ptr(stats)))
+        return idx[:cnt.value].copy(), dist[:n].copy(), tuple(float(v) for v in stats)
 
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""

@@ -403,7 +403,10 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     if (st) return st;
     int max_no = 0;
     for (int f = 0; f < F; ++f) max_no = std::max(max_no, c->h_fs[f].n_o);
-    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff
+    int omap_pitch = 0;   // rule C16 (cd_set_outlier_filter): d_obj and n_o become the filtered clouds; max_no stays an upper bound
+    if (c->outlier_k > 0) st = stage_outlier(c, F, max_no, &omap_pitch);
+    if (st) return st;
+    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff (and, filtered, the outlier records)
     if (!st && p->icp_use_guess == CD_GUESS_SURFACE) st = surface_guesses(c, F, p, &fr.surface_flag);
     if (st) return st;
     // [3] ICP of every cluster, against one template or all of them
@@ -425,6 +428,12 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
         lc.rects = c->call_rects;
         lc.depth_is_c7 = !(dj && dj->ccam && dj->ccam->no_texture != CD_NOTEX_KEEP);
         lc.keys = c->voxel_keys;
+        lc.filtered = c->outlier_k > 0;
+        lc.omap_pitch = omap_pitch;
+        if (lc.filtered) {   // cd_get_outlier_stats (the records' mirror has been valid since the cluster stage's synchronisation)
+            c->last_outlier.assign(c->h_orec.get(), c->h_orec.get() + F);
+            c->last_outlier_ok = true;
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     // records and read-out

@@ -291,6 +291,22 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
     const uint32_t lane = threadIdx.x & 63;
     return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 }
+// One workgroup walking a row tile by tile (k_labels.hip, k_outlier.hip): exclusive prefix of the ballots of the workgroup's rows
+// in (wave, row, lane) order; returns the tile's total through *total
+template <int R>
+__device__ __forceinline__ int tile_prefix(const uint64_t (&bal)[R], int (&s_cnt)[WAVES_PER_BLOCK], int* total) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int wtot = 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) wtot += __popcll(bal[j]);
+    __syncthreads();   // (the previous tile's readers of s_cnt are done)
+    if (lane == 0) s_cnt[w] = wtot;
+    __syncthreads();
+    int pos = 0, tot = 0;
+    for (int q = 0; q < WAVES_PER_BLOCK; ++q) { if (q < w) pos += s_cnt[q]; tot += s_cnt[q]; }
+    *total = tot;
+    return pos;
+}
 __device__ __forceinline__ long long fixq(float v, int shift) {
     // float->double exact, power-of-two scale exact, round to nearest even (C4)
     return __double2ll_rn(ldexp((double)v, shift));

@@ -17,6 +17,7 @@
 
 #include "device_buffer.hpp"
 #include "kernels.hpp"
+#include "outlier_math.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
 
@@ -72,6 +73,8 @@ struct LastCall {
     FrameRects rects{nullptr, 0};   // the per-frame rectangles its gate read (device memory that stays until the next fused call)
     bool depth_is_c7 = true;        // false: a mapped call that dropped its untextured points (rule C12's xyz is not rule C7's)
     VoxelKeys keys;
+    bool filtered = false;          // rule C16: the call filtered its object clouds (d_omap / d_orec describe them, rows of omap_pitch)
+    int omap_pitch = 0;
 };
 
 // The streams and events of a context.  A base of cd_context, so that they outlive its buffers: the members of cd_context
@@ -227,6 +230,15 @@ struct cd_context : cd_streams {
     LastCall last_call;
     DevBuf<uint32_t> d_vkey;
     DevBuf<uint8_t> d_vclass, d_plabel, d_tlabel;
+    // statistical outlier removal (rule C16, k_outlier.hip): the setting (cd_set_outlier_filter; mean_k = 0: off), and - grown on
+    // demand - the map of the last filtered call (one int per point of the unfiltered object cloud, rows of one pitch) and one
+    // record per frame (device + pinned mirror); last_outlier: the records behind cd_get_outlier_stats
+    int outlier_k = 0, outlier_neg = 0;
+    double outlier_mul = 1.0;
+    DevBuf<int> d_omap;
+    DevBuf<OutlierRecord> d_orec; PinBuf<OutlierRecord> h_orec;
+    std::vector<OutlierRecord> last_outlier;
+    bool last_outlier_ok = false;
     cd_timing timing;
 };
 
@@ -269,6 +281,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_surface_ok = false;
     c->last_bboxes_ok = false;
     c->last_shapes_ok = false;
+    c->last_outlier_ok = false;
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -423,6 +436,8 @@ void set_icp_clusters(cd_context* c, int first, int n, int frame, const int* siz
 ShapeFrame template_frame(const cd_context* c, int slot);
 int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests);
 void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_cluster_result* r);
+// ---- outlier.hip
+int stage_outlier(cd_context* c, int F, int max_no, int* map_pitch);
 // ---- surface.hip
 int ensure_surface(cd_context* c, size_t pitch);
 int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,

@@ -6,7 +6,9 @@
 //   2. k_label_voxel_classes  voxel v's class: CD_LABEL_GATED, then CD_LABEL_PLANE for every entry of the call's plane index list,
 //                             then - for the voxels that the S3 predicate (extract_flags.hpp, what k_extract_scatter applied)
 //                             moved into the object cloud, numbered by an order-preserving scan - CD_LABEL_OBJECT or
-//                             CD_LABEL_CLUSTER0 + r from the call's cluster labels;
+//                             CD_LABEL_CLUSTER0 + r from the call's cluster labels; after a call that filtered its object
+//                             clouds (rule C16) that number goes through the filter's map first: a voxel the filter removed
+//                             stays CD_LABEL_GATED;
 //   3. k_label_points         the batch as ONE linear stream of records or pixels (as k_deproject takes it): the S0 predicate, the
 //                             point's key in the form step 1 found, a binary search among the frame's voxel keys (at most 32
 //                             probes, ~15 on a 640 x 480 frame: the table of a frame is ~70 KB and stays in L2; neighbouring
@@ -20,24 +22,9 @@
 #include "extract_flags.hpp"
 #include "kernels.hpp"
 #include "label_math.hpp"
+#include "outlier_math.hpp"
 
 namespace cd {
-
-// exclusive prefix of the ballots of the workgroup's rows in (wave, row, lane) order; returns the tile's total through *total
-template <int R>
-__device__ __forceinline__ int tile_prefix(const uint64_t (&bal)[R], int (&s_cnt)[WAVES_PER_BLOCK], int* total) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int wtot = 0;
-#pragma unroll
-    for (int j = 0; j < R; ++j) wtot += __popcll(bal[j]);
-    __syncthreads();   // (the previous tile's readers of s_cnt are done)
-    if (lane == 0) s_cnt[w] = wtot;
-    __syncthreads();
-    int pos = 0, tot = 0;
-    for (int q = 0; q < WAVES_PER_BLOCK; ++q) { if (q < w) pos += s_cnt[q]; tot += s_cnt[q]; }
-    *total = tot;
-    return pos;
-}
 
 // ---- step 1 ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLOCK) k_label_voxel_keys(const uint32_t* __restrict__ keys, int N, const FrameState* __restrict__ fs,
@@ -82,11 +69,14 @@ __global__ void __launch_bounds__(BLOCK) k_label_voxel_classes(const float4* __r
                                                                const float4* __restrict__ model, const int* __restrict__ have, float thr,
                                                                int negative, int crop2, float z2lo, float z2hi, BBoxGate gate, FrameRects rects,
                                                                const int* __restrict__ plane_idx, const int* __restrict__ label,
-                                                               uint8_t* __restrict__ vclass, int vpitch) {
+                                                               uint8_t* __restrict__ vclass, int vpitch, OutlierMap omap) {
     __shared__ int s_cnt[WAVES_PER_BLOCK];
     const int f = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nv = min(min(max(fs[f].n_v, 0), vpitch), N);
     const int n_plane = min(max(fs[f].n_plane, 0), N), n_o = min(max(fs[f].n_o, 0), N);
+    // what S3 moved: the object cloud itself, or - a filtered call - the cloud the filter read, whose row of the map holds one entry each
+    const int n_s3 = omap.map ? min(min(max(omap.rec[f].n_before, 0), omap.pitch), N) : n_o;
+    const int* omap_row = omap.map ? omap.map + (size_t)f * omap.pitch : nullptr;
     const size_t fbase = (size_t)f * N;
     uint8_t* cls = vclass + (size_t)f * vpitch;
     for (int v = threadIdx.x; v < nv; v += BLOCK) cls[v] = (uint8_t)LABEL_GATED;
@@ -96,7 +86,7 @@ __global__ void __launch_bounds__(BLOCK) k_label_voxel_classes(const float4* __r
         if (v >= 0 && v < nv) cls[v] = (uint8_t)LABEL_PLANE;
     }
     __syncthreads();
-    if (n_o <= 0) return;   // (the frame's chain ended before S3, or S3 kept nothing)
+    if (n_s3 <= 0 || n_o <= 0) return;   // (the frame's chain ended before S3, or S3 - or the filter - kept nothing)
     frame_rect(gate, rects, f);
     const float4 m = model[f];
     const int hv = have[f];
@@ -118,8 +108,11 @@ __global__ void __launch_bounds__(BLOCK) k_label_voxel_classes(const float4* __r
         int pos = out0 + tile_prefix<ITEMS>(bal, s_cnt, &tot);
 #pragma unroll
         for (int j = 0; j < ITEMS; ++j) {
-            const int v = base + j * WAVE, r = pos + __popcll(bal[j] & lt);   // (r: the voxel's place in the object cloud)
-            if (((bal[j] >> lane) & 1ull) && r < n_o) cls[v] = label_of_rank(label[fbase + r]);
+            const int v = base + j * WAVE;
+            int r = pos + __popcll(bal[j] & lt);   // (r: the voxel's place among what S3 moved)
+            const bool moved = ((bal[j] >> lane) & 1ull) && r < n_s3;
+            if (moved && omap_row) r = omap_row[r];   // (its place in the object cloud, -1: the filter removed it)
+            if (moved && r >= 0 && r < n_o) cls[v] = label_of_rank(label[fbase + r]);
             pos += __popcll(bal[j]);
         }
         out0 += tot;
@@ -263,9 +256,9 @@ void launch_label_voxel_keys(hipStream_t s, const uint32_t* keys, int N, int F, 
 }
 void launch_label_voxel_classes(hipStream_t s, const float4* vox, int N, int F, const FrameState* fs, const float4* model, const int* have,
                                 float thr, int negative, int crop2, float z2lo, float z2hi, const BBoxGate& gate, const FrameRects& rects,
-                                const int* plane_idx, const int* label, uint8_t* vclass, int vpitch) {
+                                const int* plane_idx, const int* label, uint8_t* vclass, int vpitch, const OutlierMap& omap) {
     hipLaunchKernelGGL(k_label_voxel_classes, dim3(F), dim3(BLOCK), 0, s, vox, N, fs, model, have, thr, negative, crop2, z2lo, z2hi, gate, rects,
-                       plane_idx, label, vclass, vpitch);
+                       plane_idx, label, vclass, vpitch, omap);
 }
 static unsigned stream_grid(size_t elements) {
     const size_t groups = (elements + (size_t)BLOCK * 4 - 1) / ((size_t)BLOCK * 4);

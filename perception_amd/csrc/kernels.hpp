@@ -184,10 +184,13 @@ void launch_verify_boxes(hipStream_t s, const uint16_t* depth, const VerifyCam& 
 // step 1: voxel v's key, in the order of d_vox, from the frame's sorted keys (rows of N; n_runs of them when by_runs, else n_c) -> vkey[f * vpitch + v]
 void launch_label_voxel_keys(hipStream_t s, const uint32_t* keys, int N, int F, const FrameState* fs, int by_runs, uint32_t* vkey, int vpitch);
 // step 2: voxel v's class (CD_LABEL_PLANE / OBJECT / GATED / CLUSTER0 + r) from the call's plane index list, the S3 predicate and
-// the cluster labels -> vclass[f * vpitch + v]
+// the cluster labels -> vclass[f * vpitch + v].  omap.map != nullptr: the call filtered its object clouds (rule C16) - a voxel
+// that S3 moved and the filter removed stays CD_LABEL_GATED, the others index the labels through the map
+struct OutlierRecord;
+struct OutlierMap { const int* map; const OutlierRecord* rec; int pitch; };   // map[f * pitch + r]: index in the filtered cloud, or -1
 void launch_label_voxel_classes(hipStream_t s, const float4* vox, int N, int F, const FrameState* fs, const float4* model, const int* have,
                                 float thr, int negative, int crop2, float z2lo, float z2hi, const BBoxGate& gate, const FrameRects& rects,
-                                const int* plane_idx, const int* label, uint8_t* vclass, int vpitch);
+                                const int* plane_idx, const int* label, uint8_t* vclass, int vpitch, const OutlierMap& omap);
 // step 3: the batch as one linear stream of F * P records (depth == nullptr: `stride` bytes each, x y z first) or pixels (rule C7)
 struct LabelPointsParams {
     CropLimits lim;
@@ -203,5 +206,14 @@ void launch_label_points(hipStream_t s, const void* records, size_t stride, cons
                          const FrameState* fs, const uint32_t* vkey, const uint8_t* vclass, uint8_t* out);
 struct LabelPalette { uint32_t rgba[256]; };   // = cd_label_palette: byte 0 r, 1 g, 2 b, 3 alpha
 void launch_tint_labels(hipStream_t s, uint8_t* rgb, const uint8_t* labels, size_t pixels, const LabelPalette& pal);
+
+// k_outlier.hip : rule C16, statistical outlier removal on F rows of N points (row f holds fs[f].n_o of them, max_n at the most)
+// step 1: dist_i of every point -> dist[f * dpitch + i] (0 for a non-finite point and in a row of no more than mean_k finite points)
+void launch_outlier_knn(hipStream_t s, const float4* pts, int N, int F, int max_n, const FrameState* fs, int mean_k, float* dist, int dpitch);
+// step 2: the row's statistics -> rec[f]; the kept points in order -> out[f * N ..] (nullptr: none), their indices ->
+// kept_idx[f * N ..] (nullptr: none), every point's index in the filtered row or -1 -> map[f * mpitch + i]; fs[f].n_o (and the
+// mirror's, when given) becomes the kept count
+void launch_outlier_select(hipStream_t s, const float4* pts, int N, int F, FrameState* fs, FrameState* mirror, const float* dist, int dpitch,
+                           int mean_k, double std_mul, int negative, float4* out, int* map, int mpitch, int* kept_idx, OutlierRecord* rec);
 
 }  // namespace cd

@@ -269,3 +269,33 @@ def truth_poses(scene):
         Tm[:3, 3] = bx["c"]
         out.append(Tm)
     return out
+
+
+def flying_pixels(records, width, height, seed, frac):
+    """Edge outliers as a depth camera makes them: a copy of the (height*width, 4) records in which a fraction `frac` of the
+    pixels on a depth jump get a depth between the jump's two sides.  A pixel is on a jump when a 4-neighbour (left, right, up,
+    down, the first that qualifies) has a finite depth more than 1 cm from its own; its new depth is z + t (z_neighbour - z)
+    with t uniform in [0, 1), and the point moves along its ray (x and y scale with z).  Colours stay.  A pure function of its
+    arguments (the counter-based streams of render())."""
+    rec = np.asarray(records, np.float32)
+    assert rec.shape == (width * height, 4)
+    z = rec[:, 2].astype(np.float64).reshape(height, width)
+    other = np.full((height, width), np.nan)
+    for dv, du in ((0, -1), (0, 1), (-1, 0), (1, 0)):
+        nb = np.full((height, width), np.nan)
+        nb[max(0, -dv):height - max(0, dv), max(0, -du):width - max(0, du)] = z[max(0, dv):height - max(0, -dv), max(0, du):width - max(0, -du)]
+        with np.errstate(invalid="ignore"):
+            jump = np.isnan(other) & np.isfinite(z) & np.isfinite(nb) & (np.abs(nb - z) > 0.01)
+        other = np.where(jump, nb, other)
+    npx = width * height
+    pick = np.isfinite(other).reshape(npx) & (_uniform(seed, 300, npx) < frac)
+    t = _uniform(seed, 301, npx)
+    zf, of = z.reshape(npx), other.reshape(npx)
+    out = rec.copy()
+    i = np.flatnonzero(pick)
+    znew = zf[i] + t[i] * (of[i] - zf[i])
+    scale = znew / zf[i]
+    out[i, 0] = (rec[i, 0].astype(np.float64) * scale).astype(np.float32)
+    out[i, 1] = (rec[i, 1].astype(np.float64) * scale).astype(np.float32)
+    out[i, 2] = znew.astype(np.float32)
+    return out
