@@ -891,6 +891,60 @@ int cd_get_outlier_stats(const cd_context* ctx, int frame, int* n_before, int* n
 int cd_outlier_filter(cd_context* ctx, const void* xyz, size_t stride_bytes, int n, int mean_k, double std_mul, int negative,
                       int32_t* out_indices, int capacity, int* out_n, float* out_dist, double stats[3]);
 
+/* Plane-weighted ICP for lattice templates: an opt-in transformation estimate, off by default.  Canonical rule C17 (DESIGN.md
+ * §2); perception_amd/icp_plane.py restates it in numpy and the device equals it bit for bit.  It is NOT
+ * pcl::registration::TransformationEstimationPointToPlaneLLS: that estimator is the case lambda = 0 below, which is singular
+ * whenever a cluster touches two faces only; parity with any PCL estimator is neither claimed nor pinned.
+ * Within an iteration, in getFitnessScore(), `accepted` and the records it is the library's ICP: correspondences by rule C5
+ * (bounded by C8), step, X <- T X, Tfinal <- T Tfinal, DefaultConvergenceCriteria in its order.  Only the step differs.
+ * State of a (cluster, template) pair: X, Tfinal, prev_mse, iters and `latched`, initially true iff switch_distance is +inf.
+ *   1. q, d2 and q's face come from rule C5; n = the correspondences kept (C8); n < 3 stops the ICP as under C8.  w = the
+ *      constant axis of q's face (a lattice face's normal is a coordinate axis).
+ *   2. lambda_it = latched ? (float)tangent_weight : 1.0f.  For each axis a with b, c the next two cyclically:
+ *      r = q_a - s_a, g = (a == w) ? 1.0f : lambda_it, u = g s_c, v = g s_b, h = g r; the nine terms of the axis are
+ *      g, u, v, u s_c, v s_b, u s_b, h, h s_c, h s_b - single float32 operations, no FMA.  The 27 terms and d2 go into 64-bit
+ *      integer sums by rule C4 (2^32; 2^36 for d2): nothing depends on how points are divided among lanes, waves or passes.
+ *   3. In double, on the sums divided by their scale, unknowns (omega_x, omega_y, omega_z, t_x, t_y, t_z); component a's row has
+ *      +s_c at omega_b, -s_b at omega_c, 1 at t_a.  Axis a (x, y, z in turn) adds S3 to M[ob][ob], S4 to M[oc][oc], -S5 to
+ *      M[ob][oc], S1 to M[ob][ta], -S2 to M[oc][ta], S0 to M[ta][ta], and S7, -S8, S6 to the right-hand side at ob, oc, ta.
+ *      M = L D L^T (the lower Cholesky factorisation without its square roots), column by column, inner sums ascending, every
+ *      operation rounded; column j is singular iff !(d_j > M_jj * 2^-40).  A singular solve stops the ICP before the update,
+ *      as too few correspondences do: converged = accepted = 0, T = identity, Tfinal and iterations as they were.  Forward
+ *      substitution ascending, back substitution descending (the module's docstring has every association).
+ *   4. R = the rotation of the quaternion (1, omega / 2): with k = omega / 2 and m = ((1 + kx^2) + ky^2) + kz^2, each entry its
+ *      polynomial divided by m in double (R00 = (((1 + kx^2) - ky^2) - kz^2) / m, R01 = (2 (kx ky - kz)) / m, ...), cast to
+ *      float32, as is t.  No sqrt, no library function.
+ *   5. mse = sum d2 / n; latched |= (mse <= switch_distance^2), in double, after the solve of every iteration that reaches it
+ *      (a one-way latch: a switch that can reopen cycles).  Then icp_step's tail unchanged.
+ *
+ * cd_set_icp_plane_weight: context state, as the correspondence distance is; applies to every ICP of the following cd_icp and
+ * fused calls.  tangent_weight == 0 turns the mode off (the default: every record, launch and kernel is what it was);
+ * otherwise tangent_weight in [1/1024, 1] and switch_distance >= 0 or +inf (plane weights from the first iteration).  Anything
+ * else, NaN included: CD_ERR_INVALID_ARG and the setting stays.  CD_ICP_PLANE_WEIGHT_DEFAULT / CD_ICP_PLANE_SWITCH_DEFAULT are
+ * the recommended pair (a switch at 0.02 m is too early, weights from 0.55 m away diverge: INTEGRATION.md §3).
+ * With the mode on every live cluster goes to the mode's own driver (k_icp_plane); CUBOID_ICP_LATTICE / CUBOID_ICP_MODE do not
+ * apply and no generic driver implements it.  A call that would use a loaded template that is not a lattice
+ * (cd_template_lattice_faces == 0) returns CD_ERR_INVALID_ARG before anything is launched.  In cd_icp a singular stop returns
+ * CD_ERR_FEW_CORRESPONDENCES (the message says "singular") with out filled; in a batch it is a result, the frame stays CD_OK. */
+#define CD_ICP_PLANE_WEIGHT_DEFAULT (1.0 / 32.0)
+#define CD_ICP_PLANE_SWITCH_DEFAULT 0.01
+#define CD_ICP_PLANE_WEIGHT_MIN (1.0 / 1024.0)
+typedef struct cd_icp_plane_stats {
+    int32_t plane_iterations;        /* iterations run with `latched` true                      */
+    int32_t first_plane_iteration;   /* the first of them, 1-based; 0: never latched            */
+    int32_t stopped_singular;        /* 1: the ICP stopped on a singular step                   */
+    int32_t reserved;
+} cd_icp_plane_stats;
+int cd_set_icp_plane_weight(cd_context* ctx, double tangent_weight, double switch_distance);
+int cd_get_icp_plane_weight(const cd_context* ctx, double* tangent_weight, double* switch_distance);
+/* Indexed like cd_get_cluster_results (the stats of the template whose result the cluster kept); after a stand-alone cd_icp
+ * the result is at frame 0, index 0.  Returns the number copied; CD_ERR_INVALID_ARG when the call ran with the mode off, has
+ * been invalidated by another compute call, or had no such frame. */
+int cd_get_cluster_plane_stats(const cd_context* ctx, int frame, int first, int count, cd_icp_plane_stats* out);
+/* Host only (no context, no GPU): steps 3 and 4 on the 28 sums of n correspondences (sum 9 a + j: term j of axis a; sum 27:
+ * d2, unused here).  T row-major; *singular = 1 and T = identity for a singular system or n < 1. */
+int cd_icp_plane_solve_host(const int64_t sums[28], int n, float T[16], int32_t* singular);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -78,10 +78,12 @@ class BatchPipeline:
     icp_max_correspondence_distance: IterativeClosestPoint::setMaxCorrespondenceDistance for every context (None:
     unbounded, the default; rule C8).
     surface_distance_threshold: sne's distance threshold for prm.icp_use_guess = CD_GUESS_SURFACE on every context (None:
-    the default, 0.015)."""
+    the default, 0.015).
+    icp_plane_weight: (tangent_weight, switch_distance) of the plane-weighted ICP step for lattice templates on every context
+    (None: off, the default; rule C17)."""
 
     def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2, icp_max_correspondence_distance=None,
-                 surface_distance_threshold=None):
+                 surface_distance_threshold=None, icp_plane_weight=None):
         from concurrent.futures import ThreadPoolExecutor
         self.inflight = max(1, int(inflight))
         self.contexts = [capi.Context(max_points=max_points, max_frames=max_frames, device_id=device_id) for _ in range(self.inflight)]
@@ -92,6 +94,8 @@ class BatchPipeline:
                 cx.set_icp_max_correspondence_distance(icp_max_correspondence_distance)
             if surface_distance_threshold is not None:
                 cx.set_surface_distance_threshold(surface_distance_threshold)
+            if icp_plane_weight is not None:
+                cx.set_icp_plane_weight(*icp_plane_weight)
         self._results = [(capi.CdFrameResult * max_frames)() for _ in range(self.inflight)]
         self._busy = [None] * self.inflight
         self._pool = ThreadPoolExecutor(self.inflight)

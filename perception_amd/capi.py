@@ -52,7 +52,11 @@ EXPORTED_SYMBOLS = [
     "cd_label_points_last", "cd_label_points_last_device", "cd_label_depth_last", "cd_label_depth_last_device",
     "cd_default_label_palette", "cd_label_struct_size", "cd_tint_labels_batch", "cd_tint_labels_batch_device",
     "cd_set_outlier_filter", "cd_get_outlier_filter", "cd_get_outlier_stats", "cd_outlier_filter",
+    "cd_set_icp_plane_weight", "cd_get_icp_plane_weight", "cd_get_cluster_plane_stats", "cd_icp_plane_solve_host",
 ]
+
+# rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
+CD_ICP_PLANE_WEIGHT_DEFAULT, CD_ICP_PLANE_SWITCH_DEFAULT, CD_ICP_PLANE_WEIGHT_MIN = 1.0 / 32.0, 0.01, 1.0 / 1024.0
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
 CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE, CD_GUESS_CLUSTER = 0, 1, 2, 3, 4
@@ -467,6 +471,10 @@ def load_library(path=None):
     lib.cd_get_outlier_filter.argtypes = [vp, ip, dp, ip]
     lib.cd_get_outlier_stats.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp]
     lib.cd_outlier_filter.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_int, vp, C.c_int, ip, vp, vp]
+    lib.cd_set_icp_plane_weight.argtypes = [vp, C.c_double, C.c_double]
+    lib.cd_get_icp_plane_weight.argtypes = [vp, dp, dp]
+    lib.cd_get_cluster_plane_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_icp_plane_solve_host.argtypes = [vp, C.c_int, vp, ip]
     if path is None:
         _lib = lib
     return lib
@@ -938,6 +946,27 @@ class Context:
                                                C.byref(cnt), _ptr(dist), _ptr(stats)))
         return idx[:cnt.value].copy(), dist[:n].copy(), tuple(float(v) for v in stats)
 
+    def set_icp_plane_weight(self, tangent_weight, switch_distance=CD_ICP_PLANE_SWITCH_DEFAULT):
+        """Rule C17, the plane-weighted ICP step for lattice templates, for every later ICP of this context; tangent_weight = 0
+        (or None): off, the default.  The recommended pair is (CD_ICP_PLANE_WEIGHT_DEFAULT, CD_ICP_PLANE_SWITCH_DEFAULT)."""
+        self._check(self.lib.cd_set_icp_plane_weight(self.h, float(tangent_weight or 0.0), float(switch_distance)))
+
+    def icp_plane_weight(self):
+        """(tangent_weight, switch_distance) as cd_set_icp_plane_weight left them; tangent_weight = 0: off."""
+        w, d = C.c_double(), C.c_double()
+        self._check(self.lib.cd_get_icp_plane_weight(self.h, C.byref(w), C.byref(d)))
+        return w.value, d.value
+
+    def cluster_plane_stats(self, frame, first=0, count=None):
+        """Rule C17's counters of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
+        cluster_results: an (n, 4) int32 array of plane_iterations, first_plane_iteration, stopped_singular, reserved."""
+        cap = 4096 if count is None else int(count)
+        out = np.zeros((max(cap, 1), 4), np.int32)
+        got = self.lib.cd_get_cluster_plane_stats(self.h, frame, first, cap, _ptr(out))
+        if got < 0:
+            raise CuboidError(got, "no plane-weighted call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
+        return out[:got].copy()
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1099,6 +1128,18 @@ def icp_solve_batch(sums, n, states, max_iter=50, trans_eps=1e-8, rel_mse=1e-6, 
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_solve_batch")
     return out_row, out_lane, done, un
+
+
+def icp_plane_solve_host(sums, n):
+    """Host-only rule C17, steps 3 and 4: (T float32 4x4, singular) from the 28 int64 sums of n correspondences."""
+    lib = load_library()
+    a = np.ascontiguousarray(sums, np.int64).reshape(28)
+    T = np.zeros(16, np.float32)
+    sg = C.c_int()
+    st = lib.cd_icp_plane_solve_host(_ptr(a), int(n), _ptr(T), C.byref(sg))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_icp_plane_solve_host")
+    return T.reshape(4, 4), int(sg.value)
 
 
 def icp_correspondence_threshold(d):

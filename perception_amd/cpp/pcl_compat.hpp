@@ -345,6 +345,10 @@ public:
     // object shares the device's context, so align() hands the context this object's value before each ICP.
     void setMaxCorrespondenceDistance(double d) { max_corr_ = d; }
     double getMaxCorrespondenceDistance() const { return max_corr_; }
+    // Not PCL: the library's plane-weighted step for lattice templates (rule C17, cd_set_icp_plane_weight); 0 = off, the
+    // default.  It is no PCL estimator - TransformationEstimationPointToPlaneLLS is its singular case - and handed to the shared
+    // context before each ICP like the distance above.
+    void setPlaneWeight(double tangent_weight, double switch_distance = CD_ICP_PLANE_SWITCH_DEFAULT) { plane_w_ = tangent_weight; plane_d_ = switch_distance; }
     // align(output, guess): pcl::Registration's second overload (row-major 4x4, scene -> template)
     void align(PointCloud<PointSource>& output, const Matrix4& guess) {
         prm_.icp_use_guess = CD_GUESS_PARAMS;
@@ -360,7 +364,8 @@ public:
         const int n = (int)src_->points.size();
         std::vector<float> al((size_t)std::max(n, 1) * 3);
         cd_cluster_result r;
-        if (cd_set_icp_max_correspondence_distance(Device::instance().ctx(), max_corr_) != CD_OK) {
+        if (cd_set_icp_max_correspondence_distance(Device::instance().ctx(), max_corr_) != CD_OK ||
+            cd_set_icp_plane_weight(Device::instance().ctx(), plane_w_, plane_d_) != CD_OK) {
             std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx()));
             return;
         }
@@ -386,6 +391,7 @@ private:
     cd_params prm_;
     int slot_ = 0, iterations_ = 0;
     double max_corr_ = std::sqrt(std::numeric_limits<double>::max());
+    double plane_w_ = 0.0, plane_d_ = CD_ICP_PLANE_SWITCH_DEFAULT;
     typename PointCloud<PointSource>::ConstPtr src_;
     typename PointCloud<PointTarget>::ConstPtr tgt_;
     Matrix4 final_;

@@ -184,6 +184,7 @@ void begin_batch_icp(cd_context* c, const cd_params* p, int F, const BatchCluste
     c->last_clusters.assign((size_t)std::max(cl.ncl, 1), cd_cluster_result());
     bi->orig_off.assign((size_t)std::max(cl.ncl, 1), -1);
     bi->al_off.assign((size_t)std::max(cl.ncl, 1), -1);
+    if (c->plane_weight != 0.0) c->last_plane.assign((size_t)std::max(cl.ncl, 1), cd_icp_plane_stats());   // rule C17: the kept result's counters
     for (int f = 0; f < F; ++f)
         for (int q = cl.first[(size_t)f]; q < cl.first[(size_t)f + 1]; ++q) bi->orig_off[(size_t)q] = (long long)f * c->N + cl.off[(size_t)q];
 }
@@ -207,6 +208,7 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
     r.template_slot = bi->slots[(size_t)t];
     if (t > 0 && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
     c->last_clusters[(size_t)k] = r;
+    if (c->plane_weight != 0.0) std::memcpy(&c->last_plane[(size_t)k], &c->h_pstat[q], sizeof(cd_icp_plane_stats));
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
 }
 
@@ -282,6 +284,8 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     c->last_clouds = true;
     c->last_surface_ok = p->icp_use_guess == CD_GUESS_SURFACE;
     c->last_shapes_ok = p->icp_use_guess == CD_GUESS_CLUSTER;
+    c->last_plane_ok = c->plane_weight != 0.0;
+    if (c->last_plane_ok) c->last_plane_first = cl.first;
     if (c->last_shapes_ok && cl.ncl == 0) c->last_shapes.clear();
 }
 
@@ -374,6 +378,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     // checks: nothing is copied or launched before they have passed
     int st = check_params(c, p);
     if (!st) st = check_bbox_source(c, p, F, dj && dj->color);
+    if (!st) st = check_plane_templates(c, p->template_slot);   // rule C17: lattice templates only
     if (st) return st;
     if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
     if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
@@ -449,6 +454,7 @@ int cd_process_batch_impl(cd_context* c, const void* frames, size_t stride, int 
     if (!frames || points_per_frame <= 0 || n_frames <= 0) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
     const size_t bytes = (size_t)points_per_frame * n_frames * stride;
     int st = check_bbox_source(c, p, n_frames, false);   // (before the upload)
+    if (!st && p) st = check_plane_templates(c, p->template_slot);
     if (st) return st;
     st = ensure_input(c, bytes);
     if (st) return st;
@@ -466,6 +472,7 @@ int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam, const
     st = mapped ? check_mapped(c, cam, ccam, depth, color, n_frames) : check_depth(c, cam, depth, color, n_frames);
     if (st) return st;
     st = check_bbox_source(c, p, n_frames, cam->color == CD_COLOR_RGB8);   // (before the uploads)
+    if (!st) st = check_plane_templates(c, p->template_slot);
     if (st) return st;
     cd_params q = *p;
     q.rgb_offset = cam->color == CD_COLOR_RGB8 ? 12 : -1;   // the canonical records: x y z rgb, 16 bytes

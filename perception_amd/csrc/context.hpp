@@ -18,6 +18,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "outlier_math.hpp"
+#include "icp_plane_math.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
 
@@ -239,6 +240,14 @@ struct cd_context : cd_streams {
     DevBuf<OutlierRecord> d_orec; PinBuf<OutlierRecord> h_orec;
     std::vector<OutlierRecord> last_outlier;
     bool last_outlier_ok = false;
+    // plane-weighted ICP (rule C17, k_icp_plane.hip): the setting (cd_set_icp_plane_weight; plane_weight = 0: off), one record per
+    // ICP problem of a stage (device + pinned mirror, grown on demand), and what cd_get_cluster_plane_stats reads: one record per
+    // cluster of the last fused call, frame-major with last_plane_first as its index (a stand-alone cd_icp: one frame, one record)
+    double plane_weight = 0.0, plane_switch = CD_ICP_PLANE_SWITCH_DEFAULT;
+    DevBuf<PlaneStats> d_pstat; PinBuf<PlaneStats> h_pstat;
+    std::vector<cd_icp_plane_stats> last_plane;
+    std::vector<int> last_plane_first;
+    bool last_plane_ok = false;
     cd_timing timing;
 };
 
@@ -282,6 +291,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_bboxes_ok = false;
     c->last_shapes_ok = false;
     c->last_outlier_ok = false;
+    c->last_plane_ok = false;
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -424,6 +434,9 @@ int ensure_clusters(cd_context* c, int ncl, long long points);
 int sync_fs(cd_context* c, int F, bool copied = false);   // copied: the caller has put the FrameState read-back on the stream already
 int upload_points(cd_context* c, const void* pts, size_t stride, int n, float4* dst);
 int check_params(cd_context* c, const cd_params* p);
+// ---- icp_plane.hip (rule C17): with the mode on, a loaded template the call would use (slot >= 0: that one; -1: every loaded one)
+// that is not a lattice fails the call - to be asked before anything is launched
+int check_plane_templates(cd_context* c, int slot);
 int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, int rgb_offset, uint32_t pad3, void* out, size_t staging_skip = 0);
 // ---- cuboid_hip.hip
 int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int F, const cd_params* p, int* rounds_out);

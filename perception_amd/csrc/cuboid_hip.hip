@@ -366,7 +366,8 @@ ShapeFrame template_frame(const cd_context* c, int slot) {
 // ---- S6: ICP ------------------------------------------------------------------------------------------------------------------
 // stage_icp plans the stage on the host (plan_icp), issues what every driver needs (icp_setup), then hands the clusters to the
 // drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe launches for several templates, the whole-cluster
-// launch, the persistent launch for a few clusters, and the sliced multi-launch loop for whatever is left.  A driver sets
+// launch, the persistent launch for a few clusters, and the sliced multi-launch loop for whatever is left (rule C17 on:
+// k_icp_plane takes every live cluster and finishes the stage; none of the others runs).  A driver sets
 // *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after it take
 // the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
 }  // namespace cd
@@ -393,6 +394,7 @@ struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
     bool grouped_pipe = false, lat_direct = false, pipe_ok = false, big_ok = false, whole_cluster = false;
     bool pre_zeroed = false;                     // (icp_setup) d_acc / d_accf / d_queue were zeroed by the fused call
     bool crowded = false;                        // (icp_params) four or more batches in flight on the device
+    bool plane = false;                          // rule C17 (cd_set_icp_plane_weight): every live cluster takes k_icp_plane
 };
 
 // Clusters h_cl[0..ncl) -> plan; fills the work list h_work, tile0 of every cluster and the initial states h_st.
@@ -419,15 +421,18 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     // Clusters whose template is a lattice (every make_cuboid.py template; IcpLattice, common.hpp) go to k_icp_lat - closed-form
     // nearest neighbour, one workgroup per cluster - and take no part in the grouping.  CUBOID_ICP_LATTICE=0 and the
     // forced driver modes (CUBOID_ICP_MODE) keep them on the generic searches (A/B, and the GPU suite runs under each mode).
-    const bool use_lat = c->tun.icp_lattice != 0 && c->tun.icp_mode == 0;
+    // Rule C17 on: every live cluster goes to k_icp_plane whatever those switches say - no other driver implements the step.
+    pl->plane = c->plane_weight != 0.0;
+    const bool use_lat = !pl->plane && c->tun.icp_lattice != 0 && c->tun.icp_mode == 0;
     pl->in_lat.assign((size_t)ncl, 0);
     for (int k = 0; k < ncl; ++k) {
         const IcpCluster& cl = c->h_cl[k];
         const bool live = cl.n >= 3 && cl.tpl_m > 0;
         pl->n_live += live ? 1 : 0;
+        if (pl->plane && live && c->tpl_faces[cl.slot] <= 0) return fail(c, CD_ERR_INVALID_ARG, "plane-weighted ICP is on and a template of the call is not a lattice");
         if (use_lat && live && c->tpl_faces[cl.slot] > 0) { pl->in_lat[(size_t)k] = 1; ++pl->n_lat; pl->lat_max_n = std::max(pl->lat_max_n, cl.n); }
     }
-    c->timing.icp_search = pl->n_lat == 0 ? 0 : (pl->n_lat == pl->n_live ? 1 : 2);
+    c->timing.icp_search = pl->plane ? 1 : (pl->n_lat == 0 ? 0 : (pl->n_lat == pl->n_live ? 1 : 2));
     std::vector<TplGroup>& groups = pl->groups;
     for (int k = 0; k < ncl; ++k) {
         const IcpCluster& cl = c->h_cl[k];
@@ -439,7 +444,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     }
     int n_grouped = 0;
     for (const TplGroup& g : groups) if (g.kind) n_grouped += g.live;
-    pl->grouped_pipe = groups.size() > 1 && groups.size() <= 16 && n_grouped > 0 &&
+    pl->grouped_pipe = !pl->plane && groups.size() > 1 && groups.size() <= 16 && n_grouped > 0 &&
                        (c->tun.icp_mode == 3 || (c->tun.icp_mode == 0 && n_grouped * 5 >= c->n_cu));
     if (std::getenv("CUBOID_DEBUG")) {
         std::fprintf(stderr, "cuboid_hip: stage_icp %d clusters, %zu template groups, %d in pipe groups, grouped_pipe %d:", ncl, groups.size(), n_grouped, (int)pl->grouped_pipe);
@@ -453,7 +458,7 @@ int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     for (int k = 0; k < ncl; ++k) {
         IcpCluster& cl = c->h_cl[k];
         cl.tile0 = nwork;
-        const int tiles = cl.n >= 3 && cl.tpl_m > 0 && !in_pipe[(size_t)k] && !pl->in_lat[(size_t)k] ? (cl.n + pl->qslice - 1) / pl->qslice : 0;
+        const int tiles = cl.n >= 3 && cl.tpl_m > 0 && !in_pipe[(size_t)k] && !pl->in_lat[(size_t)k] && !pl->plane ? (cl.n + pl->qslice - 1) / pl->qslice : 0;
         if (nwork + tiles > c->work_cap) return fail(c, CD_ERR_CAPACITY, "ICP work list overflow");
         for (int t = 0; t < tiles; ++t) c->h_work[nwork++] = IcpWork{k, t};
         for (int s = 0; s < 2; ++s) {
@@ -641,6 +646,40 @@ int icp_run_lat(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* don
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->timing.icp_wave_ms = (float)((double)c->h_accf[ncl] / 1.0e5);   // 100 MHz ticks x waves -> wave-milliseconds
+    *done = true;
+    return CD_OK;
+}
+
+// Rule C17 (cd_set_icp_plane_weight): k_icp_plane over every live cluster of the stage, whatever its template slot - one
+// launch, queue-fed, largest first; the ordinary device buffers (no pinned arrays read by the kernel).  Always finishes the stage.
+int icp_run_plane(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
+    static_assert(sizeof(PlaneStats) == sizeof(cd_icp_plane_stats), "PlaneStats mirrors cd_icp_plane_stats");
+    const int ncl = pl.ncl;
+    int no = 0;
+    for (int k = 0; k < ncl; ++k) if (c->h_cl[k].n >= 3 && c->h_cl[k].tpl_m > 0) c->h_order[no++] = k;
+    std::stable_sort(c->h_order.get(), c->h_order + no, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
+    GROW(c, d_pstat, (size_t)ncl); GROW(c, h_pstat, (size_t)ncl);
+    if (no > 0) HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * (size_t)no, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(c->d_pstat, 0, sizeof(PlaneStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
+    if (!pl.pre_zeroed) HIPCHK(c, hipMemsetAsync(c->d_queue, 0, 2 * sizeof(int), c->stream));   // head of the cluster queue
+    PlaneParams pp;
+    pp.lambda = (float)c->plane_weight;
+    pp.latched0 = std::isinf(c->plane_switch) ? 1 : 0;
+    pp.switch2 = c->plane_switch * c->plane_switch;
+    // two workgroups per CU at the most: 256 registers a wave leave two waves per SIMD (k_icp_plane.hip)
+    const int n_wg = std::max(1, std::min(no, 2 * pl.wg_cap));
+    LAUNCH(c, launch_icp_plane(c->stream, no, n_wg, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_pstat, c->d_lat, c->d_src, c->d_src0, c->d_queue, ip, icp_bound(c), pp));
+    c->timing.icp_kernel_launches = no > 0 ? 1 : 0;
+    c->timing.icp_regime = (1 << 16) | std::min(n_wg, 0xffff);
+    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+    {
+        XferBatch xb(c);   // (one launch)
+        xb.add(c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost);
+        xb.add(c->h_accf, c->d_accf, sizeof(unsigned long long) * (size_t)ncl, hipMemcpyDeviceToHost);
+        xb.add(c->h_pstat, c->d_pstat, sizeof(PlaneStats) * (size_t)ncl, hipMemcpyDeviceToHost);
+        HIPCHK(c, xb.flush());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *done = true;
     return CD_OK;
 }
@@ -901,7 +940,8 @@ int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests)
     const IcpParams ip = icp_params(c, p, &pl.crowded);
     HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
     bool done = false;
-    if (pl.n_lat > 0) st = icp_run_lat(c, pl, ip, &done);
+    if (pl.plane) st = icp_run_plane(c, pl, ip, &done);
+    if (!st && !done && pl.n_lat > 0) st = icp_run_lat(c, pl, ip, &done);
     if (!st && !done && pl.grouped_pipe) st = icp_run_grouped(c, pl, ip, &done);
     if (!st && !done && pl.whole_cluster) st = icp_run_whole(c, pl, ip, &done);
     if (!st && !done) st = icp_run_persist(c, pl, ip, &done);

@@ -321,6 +321,8 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
     if (p->icp_use_guess == CD_GUESS_SURFACE) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_SURFACE needs a frame to fit: fused calls only");
     if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
     if (c->tpl_m[slot] <= 0) return fail(c, CD_ERR_NO_TEMPLATE, "template slot is empty");
+    st = check_plane_templates(c, slot);   // rule C17: lattice templates only
+    if (st) return st;
     st = upload_points(c, src_xyz, stride, n, c->d_src0);
     if (st) return st;
     HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)std::max(n, 1), hipMemcpyDeviceToDevice, c->stream));
@@ -334,6 +336,15 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
         std::vector<float4> tmp((size_t)n);
         HIPCHK(c, copy_sync(c, tmp.data(), c->d_src, sizeof(float4) * n, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) { aligned[3 * i] = tmp[i].x; aligned[3 * i + 1] = tmp[i].y; aligned[3 * i + 2] = tmp[i].z; }
+    }
+    if (c->plane_weight != 0.0) {   // rule C17: the pair's counters for cd_get_cluster_plane_stats (frame 0, index 0); a singular stop
+        cd_icp_plane_stats ps;
+        std::memset(&ps, 0, sizeof(ps));
+        if (n >= 3) std::memcpy(&ps, &c->h_pstat[0], sizeof(ps));
+        c->last_plane.assign(1, ps);
+        c->last_plane_first.assign({0, 1});
+        c->last_plane_ok = true;
+        if (ps.stopped_singular) return fail(c, CD_ERR_FEW_CORRESPONDENCES, "plane-weighted ICP stopped: the step's system is singular");
     }
     // rule C8: an ICP that stopped for fewer than three kept correspondences (only a bounded one can: every other ends converged)
     if (c->h_st[0].status == CD_OK && c->icp_bounded && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;

@@ -184,11 +184,10 @@ __device__ __forceinline__ void mat4_mul(const float* A, const float* B, float* 
 //   relative MSE (prev_mse moves only when the MSE tests are reached).
 // BOUNDED (rule C8): n = the kept correspondences; fewer than three stop the ICP before the update (icp_stop_few).
 // Returns done and leaves it in so.converged; so.done and every other bookkeeping stay with the caller.
-template <bool BOUNDED>
-__device__ __forceinline__ int icp_step(IcpState& so, const unsigned long long* A, int n, const IcpParams& prm) {
-    if (BOUNDED && n < ICP_MIN_CORR) { icp_stop_few(so); return 1; }
-    float T[16], Tf[16];
-    umeyama_from_moments(A, n, T);
+// icp_step is its ESTIMATE (T from the sums) followed by icp_step_tail: everything after the estimate, given T, the d2 sum
+// and n.  The plane-weighted step of rule C17 (k_icp_plane.hip) has an estimate of its own and calls the same tail.
+__device__ __forceinline__ int icp_step_tail(IcpState& so, const float* T, unsigned long long sum_d2, int n, const IcpParams& prm) {
+    float Tf[16];
     mat4_mul(T, so.Tfinal, Tf);
     for (int i = 0; i < 16; ++i) so.Tfinal[i] = Tf[i];
     so.iters += 1;
@@ -201,7 +200,7 @@ __device__ __forceinline__ int icp_step(IcpState& so, const unsigned long long* 
         if (cos_angle >= prm.rot_thr && translation_sqr <= prm.trans_eps) {
             done = 1;
         } else {
-            const double mse = unfix(A[15], FIX_SHIFT_D2) / (double)n;
+            const double mse = unfix(sum_d2, FIX_SHIFT_D2) / (double)n;
             if (fabs(mse - so.prev_mse) < prm.abs_mse) done = 1;
             else if (fabs(mse - so.prev_mse) / so.prev_mse < prm.rel_mse) done = 1;
             so.prev_mse = mse;
@@ -210,6 +209,13 @@ __device__ __forceinline__ int icp_step(IcpState& so, const unsigned long long* 
     for (int i = 0; i < 16; ++i) so.T[i] = T[i];
     so.converged = done;
     return done;
+}
+template <bool BOUNDED>
+__device__ __forceinline__ int icp_step(IcpState& so, const unsigned long long* A, int n, const IcpParams& prm) {
+    if (BOUNDED && n < ICP_MIN_CORR) { icp_stop_few(so); return 1; }
+    float T[16];
+    umeyama_from_moments(A, n, T);
+    return icp_step_tail(so, T, A[15], n, prm);
 }
 
 // The 16 fixed-point moment terms of ONE correspondence (rule C4): S[0..2] p, [3..5] q, [6..14] q_a p_b, [15] d2.

@@ -1,0 +1,233 @@
+// k_icp_plane.hip - S6 with canonical rule C17 (perception_amd/icp_plane.py is the specification): the
+// plane-weighted ICP step for LATTICE templates, opt-in through cd_set_icp_plane_weight.
+//
+// The ICP is k_icp_lat's - rule C5 correspondences by the closed-form lattice search (lat_search.hpp), rule C8's bound,
+// X <- T X in place, Tfinal <- T Tfinal, DefaultConvergenceCriteria in icp_step's order (icp_step_tail), getFitnessScore over
+// every point - with another transformation estimate: a weighted linear least-squares step in which the residual along the
+// normal of the correspondence's face (a coordinate axis: IcpLattice::w) counts 1 and the two tangential components count
+// lambda_it (1 until the MSE has once been <= switch_distance^2, tangent_weight from the next iteration on; a one-way latch).
+// It is NOT pcl::registration::TransformationEstimationPointToPlaneLLS, which is the singular case lambda = 0.
+//
+// Shape: one workgroup of four waves keeps ONE (cluster, template) pair going for its whole ICP and then takes the next pair of
+// the launch's queue (largest first), restaging the axis tables when the template changes.  Per iteration: the waves take the
+// passes of 64 points - transform, search, the 27 terms + d2 of icp_plane_math.hpp as 28 rule-C4 integer sums in 56
+// accumulator registers per lane (LatFix raw bits inside its range, fixq outside: the same integers), folded through DPP
+// into LDS - barrier - lane 0 solves in double (plane_solve: 6 x 6 L D L^T, no square root, no library call) and runs the
+// shared tail - barrier.  Integer sums: nothing depends on how points fall to lanes, waves or passes.
+// 56 accumulators + the search do not fit the 128 registers of four waves per SIMD: the launch bounds ask for two
+// (256 registers), which the compiler fills without scratch (has its report).
+// No MFMA: nothing here is a dense contraction.  Results leave through ordinary vector stores.
+#include "kernels.hpp"
+#include "icp_solve.hpp"
+#include "lat_search.hpp"
+#include "icp_plane_math.hpp"
+
+namespace cd {
+
+constexpr int PLANE_WAVES = 4;
+constexpr int PLANE_THREADS = PLANE_WAVES * WAVE;
+enum { PLANE_ITER = 0, PLANE_FIT = 1, PLANE_EMPTY = 2 };
+
+struct PlaneItem {
+    int k, src_off, n, tslot;   // the pair (problem index, first point, points, template slot)
+    int phase;                  // PLANE_ITER / PLANE_FIT / PLANE_EMPTY
+    int latched;                // rule C17 step 5
+    int pad[2];
+};
+
+// BOUNDED (rule C8): only correspondences with d2 <= bnd.d2_max enter the sums; s_nv counts them
+template <bool BOUNDED>
+__global__ void __launch_bounds__(PLANE_THREADS, 2)
+k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restrict__ cl, IcpState* __restrict__ st,
+            unsigned long long* __restrict__ accf, PlaneStats* __restrict__ pstat, const IcpLattice* __restrict__ lats,
+            float4* __restrict__ src, const float4* __restrict__ src0, int* __restrict__ queue, IcpParams prm, IcpBound bnd, PlaneParams pp) {
+    __shared__ float4 s_tab[LAT_MAX_TAB];
+    __shared__ int4 s_face[2 * LAT_MAX_FACES];
+    __shared__ unsigned long long s_acc[32];   // [0..27] the sums of the current step ([0]: the fitness sum in PLANE_FIT)
+    __shared__ IcpState s_so;
+    __shared__ PlaneItem s_it;
+    __shared__ PlaneStats s_ps;
+    __shared__ unsigned s_nv;
+    const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6;
+    if (threadIdx.x < 32) s_acc[threadIdx.x] = 0ull;
+    if (threadIdx.x == 0) s_nv = 0u;
+    int cur_tslot = -1;
+    for (;;) {
+        // ---- the next live pair of the queue (lane 0) ----
+        if (threadIdx.x == 0) {
+            s_it.phase = PLANE_EMPTY;
+            for (;;) {
+                const int item = atomicAdd(queue, 1);
+                if (item >= nitems) break;
+                const int k = order[item];
+                if (st[2 * (size_t)k].done) continue;   // host pre-marked (too few points / no template)
+                const IcpCluster c = cl[k];
+                s_it.k = k; s_it.src_off = c.src_off; s_it.n = c.n; s_it.tslot = c.slot;
+                s_it.latched = pp.latched0;
+                s_it.phase = PLANE_ITER;
+                s_so = st[2 * (size_t)k];
+                s_ps.plane_iterations = 0; s_ps.first_plane_iteration = 0; s_ps.stopped_singular = 0; s_ps.reserved = 0;
+                break;
+            }
+        }
+        __syncthreads();
+        if (s_it.phase == PLANE_EMPTY) break;   // (uniform)
+        const int n = __builtin_amdgcn_readfirstlane(s_it.n), src_off = __builtin_amdgcn_readfirstlane(s_it.src_off);
+        const int tslot = __builtin_amdgcn_readfirstlane(s_it.tslot);
+        const IcpLattice* __restrict__ L = lats + tslot;
+        if (tslot != cur_tslot) {   // (uniform) another template: its tables and face words
+            for (int i = threadIdx.x; i < L->ntab && i < LAT_MAX_TAB; i += PLANE_THREADS) s_tab[i] = L->tab[i];
+            if (threadIdx.x < LAT_MAX_FACES) {
+                const int f = threadIdx.x, w = L->w[f], u = L->fast[f], v = 3 - w - u;
+                s_face[f] = make_int4(w, u, L->base[f], __float_as_int(L->c[f]));
+                s_face[LAT_MAX_FACES + f] = make_int4(L->toff[u], L->toff[v < 0 || v > 2 ? 0 : v], L->n[u], 0);
+            }
+            cur_tslot = tslot;
+            __syncthreads();
+        }
+        LatFaces F;
+        lat_faces_load(L, F);
+        const bool nf3 = F.nface <= 3;
+        const int npass = (n + 63) >> 6;
+        float4* pts = src + src_off;
+        for (;;) {
+            const int phase = __builtin_amdgcn_readfirstlane(s_it.phase);   // (settled behind the barrier that ended the last round)
+            if (phase == PLANE_ITER) {
+                const bool moved = s_so.iters > 0;   // X <- T*X from the second iteration on
+                const float lam_it = s_it.latched ? pp.lambda : 1.0f;
+                float T[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) T[i] = s_so.T[i];
+                unsigned long long SA[16], SB[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { SA[i] = 0ull; SB[i] = 0ull; }   // (SB[12..15] stay zero and are never folded)
+                unsigned nv = 0u;
+                float4 pnext = pts[min((sub << 6) + lane, n - 1)];
+                for (int pss = sub; pss < npass; pss += PLANE_WAVES) {
+                    const int myq = (pss << 6) + lane;
+                    const bool act = myq < n;
+                    const float4 p = pnext;
+                    pnext = pts[min(((pss + PLANE_WAVES) << 6) + lane, n - 1)];
+                    float px = p.x, py = p.y, pz = p.z;
+                    if (moved) {   // written back by the lane that owns the point
+                        xform(T, p.x, p.y, p.z, px, py, pz);
+                        if (act) pts[myq] = make_float4(px, py, pz, p.w);
+                    }
+                    const LatHit h = F.axes ? lat_nearest_axes<true, false, true>(s_tab, s_face, F, px, py, pz)
+                                            : (nf3 ? lat_nearest<true, 3>(s_tab, s_face, F, px, py, pz) : lat_nearest<true, LAT_MAX_FACES>(s_tab, s_face, F, px, py, pz));
+                    const int w = s_face[min(max(h.face, 0), LAT_MAX_FACES - 1)].x;   // the face's constant axis = its normal
+                    const bool keep = act && (!BOUNDED || h.d <= bnd.d2_max);
+                    if constexpr (BOUNDED) nv += (unsigned)__popcll(ballot64(keep));
+                    if (keep) {
+                        const float pv[3] = {px, py, pz}, qv[3] = {h.nx, h.ny, h.nz};
+                        float t[PLANE_NSUMS];
+                        plane_terms(pv, qv, w, lam_it, h.d, t);
+                        // LatFix's range: every term below 2^18 (coordinates below 256 m, a neighbour less than 128 m away, weights
+                        // <= 1); outside it the general conversion - the same integers either way (a NaN fails the test)
+                        const float big_c = fmaxf(fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)), fmaxf(fmaxf(fabsf(h.nx), fabsf(h.ny)), fabsf(h.nz)));
+                        if (big_c < 256.f && h.d < 16384.f) {
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) SA[i] += LatFix<FIX_SHIFT>::bits(t[i]);
+#pragma unroll
+                            for (int i = 16; i < 27; ++i) SB[i - 16] += LatFix<FIX_SHIFT>::bits(t[i]);
+                            SB[11] += LatFix<FIX_SHIFT_D2>::bits(t[27]);
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) SA[i] += (unsigned long long)fixq(t[i], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
+#pragma unroll
+                            for (int i = 16; i < 27; ++i) SB[i - 16] += (unsigned long long)fixq(t[i], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
+                            SB[11] += (unsigned long long)fixq(t[27], FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
+                        }
+                    }
+                }
+                if (sub < npass) {
+                    wave_fold_to_lds(SA, 16, s_acc);
+                    wave_fold_to_lds(SB, 12, s_acc + 16);
+                }
+                if constexpr (BOUNDED) { if (sub < npass && lane == 0) atomicAdd(&s_nv, nv); }
+            } else {
+                // final X <- T*X (PCL transforms before it tests convergence; the identity after a stop), then getFitnessScore()
+                // of Tfinal * original source
+                const float4* pts0 = src0 + src_off;
+                float T[12], Tf[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) { T[i] = s_so.T[i]; Tf[i] = s_so.Tfinal[i]; }
+                unsigned long long S[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) S[i] = 0ull;
+                for (int pss = sub; pss < npass; pss += PLANE_WAVES) {
+                    const int myq = (pss << 6) + lane;
+                    const bool act = myq < n;
+                    const float4 p = pts[min(myq, n - 1)], p0 = pts0[min(myq, n - 1)];
+                    float ox, oy, oz;
+                    xform(T, p.x, p.y, p.z, ox, oy, oz);
+                    if (act) pts[myq] = make_float4(ox, oy, oz, p.w);
+                    float qx, qy, qz;
+                    xform(Tf, p0.x, p0.y, p0.z, qx, qy, qz);
+                    const LatHit h = F.axes ? lat_nearest_axes<false>(s_tab, s_face, F, qx, qy, qz)
+                                            : (nf3 ? lat_nearest<false, 3>(s_tab, s_face, F, qx, qy, qz) : lat_nearest<false, LAT_MAX_FACES>(s_tab, s_face, F, qx, qy, qz));
+                    if (act) S[0] += h.d < 16384.f ? LatFix<FIX_SHIFT_D2>::bits(h.d) : (unsigned long long)fixq(h.d, FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
+                }
+                if (sub < npass) wave_fold_to_lds(S, 1, s_acc);
+            }
+            __syncthreads();
+            // ---- lane 0: the step (estimate, latch, shared tail), or the pair's results ----
+            if (threadIdx.x == 0) {
+                if (phase == PLANE_ITER) {
+                    // (every kept point added the constant of its scale to each sum: LatFix)
+                    const int nv = BOUNDED ? (int)s_nv : n;
+                    int done;
+                    if (nv < ICP_MIN_CORR) {
+                        icp_stop_few(s_so);
+                        done = 1;
+                    } else {
+                        long long A[PLANE_NSUMS];
+#pragma unroll
+                        for (int i = 0; i < PLANE_NSUMS; ++i)
+                            A[i] = (long long)(s_acc[i] - (unsigned long long)nv * (i == 27 ? LatFix<FIX_SHIFT_D2>::C : LatFix<FIX_SHIFT>::C));
+                        float Tn[16];
+                        if (plane_solve(A, nv, Tn)) {   // singular: stops before the update, as too few correspondences do
+                            icp_stop_few(s_so);
+                            s_ps.stopped_singular = 1;
+                            done = 1;
+                        } else {
+                            const double mse = unfix((unsigned long long)A[27], FIX_SHIFT_D2) / (double)nv;
+                            if (s_it.latched) {
+                                s_ps.plane_iterations += 1;
+                                if (s_ps.first_plane_iteration == 0) s_ps.first_plane_iteration = s_so.iters + 1;
+                            }
+                            if (mse <= pp.switch2) s_it.latched = 1;
+                            done = icp_step_tail(s_so, Tn, (unsigned long long)A[27], nv, prm);
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < PLANE_NSUMS; ++i) s_acc[i] = 0ull;
+                    if constexpr (BOUNDED) s_nv = 0u;
+                    if (done) s_it.phase = PLANE_FIT;
+                } else {
+                    const int k = s_it.k;
+                    s_so.done = 1;
+                    st[2 * (size_t)k] = s_so;
+                    st[2 * (size_t)k + 1] = s_so;
+                    accf[k] = s_acc[0] - (unsigned long long)n * LatFix<FIX_SHIFT_D2>::C;
+                    pstat[k] = s_ps;
+                    s_acc[0] = 0ull;
+                }
+            }
+            __syncthreads();
+            if (phase == PLANE_FIT) break;   // (uniform) the pair is finished: the next one
+        }
+    }
+}
+
+void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
+                      PlaneStats* pstat, const IcpLattice* lats, float4* src, const float4* src0, int* queue, IcpParams prm, const IcpBound& bnd,
+                      const PlaneParams& pp) {
+    if (nitems <= 0 || n_wg <= 0) return;
+    if (bnd.bounded)
+        hipLaunchKernelGGL((k_icp_plane<true>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, order, cl, st, accf, pstat, lats, src, src0, queue, prm, bnd, pp);
+    else
+        hipLaunchKernelGGL((k_icp_plane<false>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, order, cl, st, accf, pstat, lats, src, src0, queue, prm, bnd, pp);
+}
+
+}  // namespace cd

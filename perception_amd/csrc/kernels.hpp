@@ -124,6 +124,14 @@ void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const
                     unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd);
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2);
 
+// k_icp_plane.hip : rule C17, the plane-weighted ICP step for lattice templates (icp_plane_math.hpp: PlaneStats, PlaneParams);
+// n_wg workgroups take the nitems problems of `order` from queue[0], one at a time
+struct PlaneStats;
+struct PlaneParams;
+void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
+                      PlaneStats* pstat, const IcpLattice* lats, float4* src, const float4* src0, int* queue, IcpParams prm, const IcpBound& bnd,
+                      const PlaneParams& pp);
+
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
 // records x y z rgb (canonical rule C7)
 struct DeprojectParams {
