@@ -1,5 +1,5 @@
-// cuboid_hip.hip - the stage drivers of the pipeline, device-resident in and out: S0 .. S5 (crop + voxel grid, plane, extract,
-// cluster) and S6 (the ICP planner and its five drivers).  The fused call (batch.hip) and the entries (entries.hip) run them.
+// cuboid_hip.hip - the front-end stage drivers of the pipeline, device-resident in and out: S0 .. S5 (crop + voxel grid, plane,
+// extract, cluster) and the records they hand to S6 (icp_stage.hip).  The fused call (batch.hip) and the entries (entries.hip) run them.
 #include "context.hpp"
 #include "host_math.hpp"
 
@@ -361,608 +361,5 @@ ShapeFrame template_frame(const cd_context* c, int slot) {
     ShapeFrame none;
     shape_empty(0, CD_ERR_NO_TEMPLATE, &none);
     return none;
-}
-
-// ---- S6: ICP ------------------------------------------------------------------------------------------------------------------
-// stage_icp plans the stage on the host (plan_icp), issues what every driver needs (icp_setup), then hands the clusters to the
-// drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe launches for several templates, the whole-cluster
-// launch, the persistent launch for a few clusters, and the sliced multi-launch loop for whatever is left (rule C17 on:
-// k_icp_plane takes every live cluster and finishes the stage; none of the others runs).  A driver sets
-// *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after it take
-// the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
-}  // namespace cd
-
-namespace {
-// kind: 0 = no persistent kernel can take the template, 1 = k_icp_pipe (LDS-resident, gridded), 2 = k_icp_pipe_big (global memory)
-int tpl_kind(const cd_context* c, const IcpCluster& cl) {
-    if (cl.tpl_m <= 0 || !c->tpl_gridded[cl.slot]) return 0;
-    if (cl.tpl_m <= ICP_TPL_LDS) return 1;
-    return c->tpl_big[cl.slot] ? 2 : 0;
-}
-
-struct TplGroup { int beg, end, live; int kind; long long pts; };
-
-struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
-    int ncl = 0, guess_mode = CD_GUESS_NONE, max_n = 0, qslice = 0;
-    size_t guess_need = 0;                       // floats of the guess upload
-    const std::vector<float>* frame_guess = nullptr;   // per-frame guesses: cd_set_frame_guesses' or (CD_GUESS_SURFACE) the call's own
-    std::vector<char> in_lat;                    // the cluster takes k_icp_lat
-    int n_lat = 0, n_live = 0, lat_max_n = 0;
-    std::vector<TplGroup> groups;
-    int nwork = 0;                               // items of the sliced work list (h_work)
-    int wg_cap = 0;                              // workgroups of a persistent ICP launch at most (CUBOID_ICP_MAX_WG)
-    bool grouped_pipe = false, lat_direct = false, pipe_ok = false, big_ok = false, whole_cluster = false;
-    bool pre_zeroed = false;                     // (icp_setup) d_acc / d_accf / d_queue were zeroed by the fused call
-    bool crowded = false;                        // (icp_params) four or more batches in flight on the device
-    bool plane = false;                          // rule C17 (cd_set_icp_plane_weight): every live cluster takes k_icp_plane
-};
-
-// Clusters h_cl[0..ncl) -> plan; fills the work list h_work, tile0 of every cluster and the initial states h_st.
-int plan_icp(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
-    pl->ncl = ncl;
-    // initial guess (pcl::Registration::align(output, guess)); the default - and the reference's live path - is none
-    // (CD_GUESS_SURFACE is CD_GUESS_PER_FRAME with the guesses the call derived itself)
-    const int guess_mode = pl->guess_mode = p->icp_use_guess == CD_GUESS_SURFACE ? CD_GUESS_PER_FRAME : p->icp_use_guess;
-    pl->frame_guess = p->icp_use_guess == CD_GUESS_SURFACE ? &c->surface_guess : &c->frame_guess;
-    if (guess_mode != CD_GUESS_NONE) {
-        int max_frame = 0;
-        for (int k = 0; k < ncl; ++k) { pl->max_n = std::max(pl->max_n, c->h_cl[k].n); max_frame = std::max(max_frame, c->h_cl[k].frame); }
-        pl->guess_need = guess_mode == CD_GUESS_PER_FRAME ? 16 * ((size_t)max_frame + 1) : (guess_mode == CD_GUESS_CLUSTER ? 16 * (size_t)ncl : 16);
-        if (guess_mode == CD_GUESS_PER_FRAME && pl->frame_guess->size() < pl->guess_need) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_PER_FRAME but cd_set_frame_guesses holds fewer frames than the batch");
-    }
-    // queries per workgroup: 512 when the batch fills the chip, smaller slices (more workgroups) otherwise
-    long long qtot = 0;
-    for (int k = 0; k < ncl; ++k) qtot += c->h_cl[k].n;
-    pl->qslice = std::max(64, std::min(ICP_QSLICE, (int)((qtot / 512 + 15) / 16 * 16)));
-    // Template groups: runs of clusters that share a template (one run per template when every cluster is matched against
-    // every template).  With several templates in the batch, the groups whose template is LDS-resident and gridded go through
-    // ONE k_icp_pipe launch (each group gets a share of the workgroups and its own queue) when there are enough of them to
-    // fill a fifth of the chip; the other clusters take the sliced driver.
-    // Clusters whose template is a lattice (every make_cuboid.py template; IcpLattice, common.hpp) go to k_icp_lat - closed-form
-    // nearest neighbour, one workgroup per cluster - and take no part in the grouping.  CUBOID_ICP_LATTICE=0 and the
-    // forced driver modes (CUBOID_ICP_MODE) keep them on the generic searches (A/B, and the GPU suite runs under each mode).
-    // Rule C17 on: every live cluster goes to k_icp_plane whatever those switches say - no other driver implements the step.
-    pl->plane = c->plane_weight != 0.0;
-    const bool use_lat = !pl->plane && c->tun.icp_lattice != 0 && c->tun.icp_mode == 0;
-    pl->in_lat.assign((size_t)ncl, 0);
-    for (int k = 0; k < ncl; ++k) {
-        const IcpCluster& cl = c->h_cl[k];
-        const bool live = cl.n >= 3 && cl.tpl_m > 0;
-        pl->n_live += live ? 1 : 0;
-        if (pl->plane && live && c->tpl_faces[cl.slot] <= 0) return fail(c, CD_ERR_INVALID_ARG, "plane-weighted ICP is on and a template of the call is not a lattice");
-        if (use_lat && live && c->tpl_faces[cl.slot] > 0) { pl->in_lat[(size_t)k] = 1; ++pl->n_lat; pl->lat_max_n = std::max(pl->lat_max_n, cl.n); }
-    }
-    c->timing.icp_search = pl->plane ? 1 : (pl->n_lat == 0 ? 0 : (pl->n_lat == pl->n_live ? 1 : 2));
-    std::vector<TplGroup>& groups = pl->groups;
-    for (int k = 0; k < ncl; ++k) {
-        const IcpCluster& cl = c->h_cl[k];
-        if (groups.empty() || c->h_cl[groups.back().beg].tpl_off != cl.tpl_off || c->h_cl[groups.back().beg].tpl_m != cl.tpl_m)
-            groups.push_back(TplGroup{k, k, 0, use_lat && c->tpl_faces[cl.slot] > 0 ? 0 : tpl_kind(c, cl), 0});
-        TplGroup& g = groups.back();
-        g.end = k + 1;
-        if (cl.n >= 3) { g.live += 1; g.pts += cl.n; }
-    }
-    int n_grouped = 0;
-    for (const TplGroup& g : groups) if (g.kind) n_grouped += g.live;
-    pl->grouped_pipe = !pl->plane && groups.size() > 1 && groups.size() <= 16 && n_grouped > 0 &&
-                       (c->tun.icp_mode == 3 || (c->tun.icp_mode == 0 && n_grouped * 5 >= c->n_cu));
-    if (std::getenv("CUBOID_DEBUG")) {
-        std::fprintf(stderr, "cuboid_hip: stage_icp %d clusters, %zu template groups, %d in pipe groups, grouped_pipe %d:", ncl, groups.size(), n_grouped, (int)pl->grouped_pipe);
-        for (const TplGroup& g : groups) std::fprintf(stderr, " [%d,%d) m=%d kind=%d live=%d", g.beg, g.end, c->h_cl[g.beg].tpl_m, g.kind, g.live);
-        std::fprintf(stderr, "\n");
-    }
-    std::vector<char> in_pipe((size_t)ncl, 0);
-    if (pl->grouped_pipe)
-        for (const TplGroup& g : groups) if (g.kind) for (int k = g.beg; k < g.end; ++k) in_pipe[(size_t)k] = 1;
-    int nwork = 0;
-    for (int k = 0; k < ncl; ++k) {
-        IcpCluster& cl = c->h_cl[k];
-        cl.tile0 = nwork;
-        const int tiles = cl.n >= 3 && cl.tpl_m > 0 && !in_pipe[(size_t)k] && !pl->in_lat[(size_t)k] && !pl->plane ? (cl.n + pl->qslice - 1) / pl->qslice : 0;
-        if (nwork + tiles > c->work_cap) return fail(c, CD_ERR_CAPACITY, "ICP work list overflow");
-        for (int t = 0; t < tiles; ++t) c->h_work[nwork++] = IcpWork{k, t};
-        for (int s = 0; s < 2; ++s) {
-            IcpState& st = c->h_st[2 * k + s];
-            std::memset(&st, 0, sizeof(st));
-            for (int i = 0; i < 4; ++i) st.Tfinal[5 * i] = 1.f;
-            if (guess_mode != CD_GUESS_NONE && guess_mode != CD_GUESS_CLUSTER)   // final_transformation_ = guess (CD_GUESS_CLUSTER: k_shape_frames writes it on the device)
-                std::memcpy(st.Tfinal, guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() + 16 * (size_t)cl.frame : p->icp_guess, 64);
-            st.prev_mse = std::numeric_limits<double>::max();
-            if (cl.tpl_m <= 0) { st.done = 1; st.status = CD_ERR_NO_TEMPLATE; }
-            else if (cl.n < 3) { st.done = 1; st.status = CD_ERR_FEW_CORRESPONDENCES; }
-        }
-    }
-    pl->nwork = nwork;
-    pl->wg_cap = c->tun.icp_max_wg > 0 ? std::min(c->tun.icp_max_wg, c->n_cu) : c->n_cu;
-    // A stage whose clusters ALL take k_icp_lat (the default template, no initial guess): the kernel reads the cluster list, the
-    // order and the initial states from the pinned host arrays and writes the final states and fitness sums there - a few
-    // hundred bytes per cluster once at each end of its ICP - instead of three copy launches around it.
-    pl->lat_direct = c->tun.icp_direct && pl->n_lat > 0 && pl->n_lat == pl->n_live && guess_mode == CD_GUESS_NONE && c->tun.mirror_reads && c->tun.mirror_writes && c->tun.copy_kernels;
-    // Batch mode: with at least ~n_cu/5 clusters every CU can own whole clusters, so each cluster runs its
-    // complete ICP (all iterations + fitness) inside one persistent workgroup, one launch for the batch.
-    // The pipelined variant (two to four clusters in flight per workgroup, no barrier in the iteration loop) needs one
-    // LDS-resident gridded template shared by every cluster of the launch; otherwise k_icp_cluster runs.
-    bool one_tpl = true;
-    for (int k = 1; k < ncl && one_tpl; ++k) one_tpl = c->h_cl[k].tpl_off == c->h_cl[0].tpl_off && c->h_cl[k].tpl_m == c->h_cl[0].tpl_m;
-    pl->pipe_ok = c->tun.icp_mode != 2 && one_tpl && tpl_kind(c, c->h_cl[0]) == 1;
-    // ... or, for a template that does not fit LDS, its twin that reads the template from global memory (k_icp_pipe_big)
-    pl->big_ok = c->tun.icp_mode != 2 && one_tpl && tpl_kind(c, c->h_cl[0]) == 2;
-    // (auto mode: only the pipelined kernel beats the sliced driver; with mixed or non-resident templates k_icp_cluster's
-    // barrier per iteration costs more than it saves, so those batches stay sliced unless the mode is forced)
-    // (measured crossover on the bench frames: 33 clusters 3.3 ms sliced / 3.7 ms pipelined, 65 clusters 4.4 / 3.9, 130 clusters
-    // 6.4 / 4.0: the pipelined kernel wins from about a fifth of the CUs' worth of clusters)
-    pl->whole_cluster = !pl->grouped_pipe && (c->tun.icp_mode >= 2 || (c->tun.icp_mode == 0 && ncl * 5 >= c->n_cu && (pl->pipe_ok || pl->big_ok)));
-    return CD_OK;
-}
-
-// which guess k_icp_apply_guess moves problem k by: the only one, its frame's, its own
-int guess_indexing(int guess_mode) { return guess_mode == CD_GUESS_PER_FRAME ? 1 : (guess_mode == CD_GUESS_CLUSTER ? 2 : 0); }
-
-
-// CD_GUESS_CLUSTER: k_shape_frames over the stage's ncl problems (d_cl, d_src0) -> d_shape, d_guess and Tfinal of d_st.  The
-// template table goes up first when a template has changed since the last time (a copy launch from its pinned mirror: no
-// synchronisation).  The buffers have been sized by icp_setup.
-int launch_cluster_guesses(cd_context* c, int ncl) {
-    if (c->tframe_dirty) {
-        for (int s = 0; s < CD_MAX_TEMPLATES; ++s) c->h_tframe[s] = template_frame(c, s);
-        HIPCHK(c, xfer(c, c->d_tframe, c->h_tframe, sizeof(ShapeFrame) * CD_MAX_TEMPLATES, hipMemcpyHostToDevice));
-        c->tframe_dirty = false;
-    }
-    LAUNCH(c, launch_shape_frames(c->stream, ncl, c->d_cl, c->d_src0, c->d_shape, c->d_tframe, c->d_guess, c->d_st));
-    return CD_OK;
-}
-
-// the stream operations every driver needs before the stage's start event: guess, cluster list, work list, initial states,
-// zeroed sums, guess applied to the sources
-int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
-    const int ncl = pl->ncl;
-    if (pl->guess_mode != CD_GUESS_NONE) {
-        GROW(c, d_guess, pl->guess_need);
-        if (pl->guess_mode == CD_GUESS_CLUSTER) {   // (the guesses are written on the device; the records' buffers before anything is on the stream)
-            GROW(c, d_shape, (size_t)ncl); GROW(c, h_shape, (size_t)ncl);
-            GROW(c, d_tframe, (size_t)CD_MAX_TEMPLATES); GROW(c, h_tframe, (size_t)CD_MAX_TEMPLATES);
-        } else
-            HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess->data() : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
-    }
-    if (!pl->lat_direct) {
-        XferBatch xb(c);   // (one launch)
-        xb.add(c->d_cl, c->h_cl, sizeof(IcpCluster) * ncl, hipMemcpyHostToDevice);
-        if (pl->nwork > 0) xb.add(c->d_work, c->h_work, sizeof(IcpWork) * pl->nwork, hipMemcpyHostToDevice);
-        xb.add(c->d_st, c->h_st, sizeof(IcpState) * 2 * ncl, hipMemcpyHostToDevice);
-        HIPCHK(c, xb.flush());
-    }
-    // (zeroed up front by the fused call for its FIRST ICP stage only: a batch that runs one stage per template fills them again)
-    pl->pre_zeroed = c->batch_zeroed;
-    c->batch_zeroed = false;
-    if (!pl->pre_zeroed) {
-        HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1), c->stream));   // (+ the wave-time word of k_icp_lat)
-    }
-    if (c->icp_bounded) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3]
-        GROW(c, d_ncorr, 3 * (size_t)ncl);
-        HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
-    }
-    if (pl->guess_mode == CD_GUESS_CLUSTER) {   // rule C13: record, guess and Tfinal of every problem, after the d_cl / d_st upload above
-        if (int e = launch_cluster_guesses(c, ncl)) return e;
-        HIPCHK(c, xfer(c, c->h_shape, c->d_shape, sizeof(ShapeFrame) * (size_t)ncl, hipMemcpyDeviceToHost));   // (on the host by the stage's final synchronisation)
-    }
-    if (pl->guess_mode != CD_GUESS_NONE)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, guess_indexing(pl->guess_mode), c->d_src0, c->d_src));
-    return CD_OK;
-}
-
-IcpParams icp_params(const cd_context* c, const cd_params* p, bool* crowded) {
-    IcpParams ip;
-    ip.max_iter = p->icp_max_iterations;
-    ip.grid_rc = 1.0f;
-    if (const char* e = std::getenv("CUBOID_ICP_GRID_RC")) ip.grid_rc = (float)std::atof(e);
-    ip.trans_eps = p->icp_transformation_epsilon;
-    ip.rel_mse = p->icp_euclidean_fitness_epsilon;
-    ip.rot_thr = 1.0 - p->icp_transformation_epsilon;
-    ip.abs_mse = 1e-12;
-    // Whole-cluster launches: how many clusters a workgroup keeps in flight and how many workgroups there are.  A call that has
-    // the device to itself wants every CU at work: one workgroup per CU (or per cluster), two slots, the second filled as long
-    // as clusters are left.  With other calls in flight (BatchPipeline) the chip is full anyway and what counts is the CU-time
-    // a batch costs: FOUR clusters per workgroup keep its sixteen waves supplied while one of them solves a step (no wave waits
-    // at a hand-over, no workgroup ends with one cluster alone), on a quarter as many workgroups - the other batches have the
-    // other CUs (config 3, 522 clusters: 2 x 256 -> 4 x 128 is 48.4 -> 53.3 k frames/s; grids that are not a multiple of 32 -
-    // 4 per XCD and shader engine - lose 2-4 %).
-    // (crossover measured on config 3: with two calls in flight the two shapes tie, with three 2 x 256 wins 49.4 : 46.5 k, with
-    // four 4 x 128 wins 52.9 : 49.7 k - and the last launches of a burst, which soon have the GPU to themselves, spread out)
-    *crowded = device_shared(c).batches_in_flight.load() >= 4;
-    ip.pipe_slots = c->tun.icp_slots > 0 ? std::min(c->tun.icp_slots, CD_PIPE_SLOTS) : (*crowded ? CD_PIPE_SLOTS : std::min(2, CD_PIPE_SLOTS));
-    ip.donate = 0;   // (set by icp_run_whole for a launch that has the GPU to itself)
-    ip.don = c->d_don;
-    ip.don_idle = c->tun.don_idle;
-    ip.don_fault = c->tun.don_fault;
-    return ip;
-}
-
-// rule C8: every driver runs its BOUNDED instantiation when the context's distance bounds anything (after icp_setup, which
-// sizes d_ncorr)
-IcpBound icp_bound(const cd_context* c) {
-    IcpBound b;
-    b.d2_max = c->icp_d2_max;
-    b.bounded = c->icp_bounded;
-    b.ncorr = c->d_ncorr;
-    return b;
-}
-
-// after the host synchronise of the driver that ended the stage: the launch time (ev[5] -> ev[6]) and the point pairs tested
-void icp_finish(cd_context* c, int ncl, long long* pair_tests) {
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
-    c->timing.icp_kernel_ms = ms;
-    if (pair_tests) {
-        long long tot = 0;
-        for (int k = 0; k < ncl; ++k)
-            if (c->h_st[2 * k].status == CD_OK) tot += (long long)c->h_cl[k].n * c->h_cl[k].tpl_m * (c->h_st[2 * k].iters + 1);
-        *pair_tests = tot;
-    }
-}
-
-// k_icp_lat over the clusters whose template is a lattice; on a mixed batch the states come back for the drivers below.
-int icp_run_lat(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
-    const int ncl = pl.ncl, n_lat = pl.n_lat, lat_max_n = pl.lat_max_n;
-    // the clusters of the launch, largest first
-    int no = 0;
-    for (int k = 0; k < ncl; ++k) if (pl.in_lat[(size_t)k]) c->h_order[no++] = k;
-    std::stable_sort(c->h_order.get(), c->h_order + no, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
-    if (!pl.lat_direct) HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * (size_t)no, hipMemcpyHostToDevice));
-    // Shape of the launch (k_icp_lat.hip): clusters per workgroup x waves per cluster.  A call that has the GPU to itself wants
-    // the launch short: one cluster per workgroup, four waves each when there are clusters enough to fill the chip twice that way,
-    // eight or sixteen for fewer or very large clusters (one frame; config 5's thousands of points).  With other batches in
-    // flight the chip is full anyway: four clusters per workgroup, two waves each, pay the single-lane solve of a round once
-    // for the four (measured on config 3, seven in flight, profiles/r05_lat_shapes.txt: 1x4 145-146 k, 4x2 149-151 k, 8x2 146 k,
-    // 4x4 139 k, 4x1 131 k frames/s; alone 1x4 1.34 ms, 1x8 1.30, 4x2 2.2, 4x1 2.8).  CUBOID_LAT_SHAPE=cpw,wpc[,clusters per slot].
-    const bool busy = device_shared(c).batches_in_flight.load() >= 3;
-    int cpw = 1, wpc = n_lat >= 768 ? 4 : (n_lat >= 96 ? 8 : 16), per_slot = 1;   // (end of round 5, 522 clusters alone: 1x4 1.17 ms, 1x8 1.10, 1x16 1.53, 2x4 1.27)
-    if (lat_max_n > 16384) wpc = 16;
-    else if (lat_max_n > 4096) wpc = std::max(wpc, 8);
-    if (busy && n_lat >= 256 && lat_max_n <= 8192) { cpw = 4; wpc = 2; }
-    if (c->tun.lat_shape[0] > 0) { cpw = c->tun.lat_shape[0]; wpc = std::max(1, c->tun.lat_shape[1]); per_slot = std::max(1, c->tun.lat_shape[2]); }
-    const int n_wg = std::max(1, (n_lat + cpw * per_slot - 1) / (cpw * per_slot));
-    GateHold lat_hold;   // (CUBOID_ICP_CONCURRENT: at most that many contexts between this launch and its completion)
-    if (c->tun.icp_concurrent > 0) lat_hold.enter(&device_shared(c).icp_gate, c->tun.icp_concurrent);
-    if (!pl.pre_zeroed) HIPCHK(c, hipMemsetAsync(c->d_queue, 0, 2 * sizeof(int), c->stream));   // head of the cluster queue, count of finished workgroups
-    if (pl.lat_direct) std::memset(c->h_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1));   // (what the zeroed device array used to bring back for clusters the kernel skips)
-    if (pl.lat_direct)
-        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->h_order, c->h_cl, c->h_st, c->h_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, c->h_accf + ncl, ip, icp_bound(c)));
-    else
-        LAUNCH(c, launch_icp_lat(c->stream, n_lat, cpw, wpc, n_wg, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_lat, c->d_src, c->d_src0, c->d_queue, c->d_accf + ncl, nullptr, ip, icp_bound(c)));
-    c->timing.icp_kernel_launches = 1;
-    c->timing.icp_regime = (cpw << 16) | std::min(n_wg, 0xffff);
-    if (n_lat < pl.n_live) {   // mixed batch
-        HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return CD_OK;
-    }
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    if (!pl.lat_direct) {
-        XferBatch xb(c);   // (one launch)
-        xb.add(c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost);
-        xb.add(c->h_accf, c->d_accf, sizeof(unsigned long long) * ((size_t)ncl + 1), hipMemcpyDeviceToHost);
-        HIPCHK(c, xb.flush());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->timing.icp_wave_ms = (float)((double)c->h_accf[ncl] / 1.0e5);   // 100 MHz ticks x waves -> wave-milliseconds
-    *done = true;
-    return CD_OK;
-}
-
-// Rule C17 (cd_set_icp_plane_weight): k_icp_plane over every live cluster of the stage, whatever its template slot - one
-// launch, queue-fed, largest first; the ordinary device buffers (no pinned arrays read by the kernel).  Always finishes the stage.
-int icp_run_plane(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
-    static_assert(sizeof(PlaneStats) == sizeof(cd_icp_plane_stats), "PlaneStats mirrors cd_icp_plane_stats");
-    const int ncl = pl.ncl;
-    int no = 0;
-    for (int k = 0; k < ncl; ++k) if (c->h_cl[k].n >= 3 && c->h_cl[k].tpl_m > 0) c->h_order[no++] = k;
-    std::stable_sort(c->h_order.get(), c->h_order + no, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
-    GROW(c, d_pstat, (size_t)ncl); GROW(c, h_pstat, (size_t)ncl);
-    if (no > 0) HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * (size_t)no, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(c->d_pstat, 0, sizeof(PlaneStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
-    if (!pl.pre_zeroed) HIPCHK(c, hipMemsetAsync(c->d_queue, 0, 2 * sizeof(int), c->stream));   // head of the cluster queue
-    PlaneParams pp;
-    pp.lambda = (float)c->plane_weight;
-    pp.latched0 = std::isinf(c->plane_switch) ? 1 : 0;
-    pp.switch2 = c->plane_switch * c->plane_switch;
-    // two workgroups per CU at the most: 256 registers a wave leave two waves per SIMD (k_icp_plane.hip)
-    const int n_wg = std::max(1, std::min(no, 2 * pl.wg_cap));
-    LAUNCH(c, launch_icp_plane(c->stream, no, n_wg, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_pstat, c->d_lat, c->d_src, c->d_src0, c->d_queue, ip, icp_bound(c), pp));
-    c->timing.icp_kernel_launches = no > 0 ? 1 : 0;
-    c->timing.icp_regime = (1 << 16) | std::min(n_wg, 0xffff);
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    {
-        XferBatch xb(c);   // (one launch)
-        xb.add(c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost);
-        xb.add(c->h_accf, c->d_accf, sizeof(unsigned long long) * (size_t)ncl, hipMemcpyDeviceToHost);
-        xb.add(c->h_pstat, c->d_pstat, sizeof(PlaneStats) * (size_t)ncl, hipMemcpyDeviceToHost);
-        HIPCHK(c, xb.flush());
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *done = true;
-    return CD_OK;
-}
-
-// The template groups of a several-template batch (plan.grouped_pipe): k_icp_pipe and k_icp_pipe_big side by side; the stage
-// is finished when no cluster is left for the sliced driver.
-int icp_run_grouped(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
-    const int ncl = pl.ncl;
-    // items of `order`: the pipe groups one after the other (those of k_icp_pipe first, then those of k_icp_pipe_big),
-    // each largest cluster first.  The two kernels are launched side by side (second stream): their workgroups share the
-    // chip, every group gets workgroups in proportion to its points (a query against a template in global memory
-    // counted BIG_WEIGHT times), at least one, no more than it has clusters.
-    const int wg_cap = pl.wg_cap;
-    // (while every problem can have a workgroup of its own the launch lasts as long as its longest cluster, and those are the
-    // global-memory ones: 4; with more problems than workgroups it is their throughput that counts, 1.6 x the LDS kernel's
-    // cost per workgroup plus the longer tail: 2 - config 5 at 8 frames per batch 4 > 2 by 5 %, at 64 frames 2 > 4 by 6 %)
-    int live_all = 0;
-    for (const TplGroup& g : pl.groups) if (g.kind) live_all += g.live;
-    const long long BIG_WEIGHT = c->tun.icp_big_weight > 0 ? c->tun.icp_big_weight : (live_all <= wg_cap ? 4 : 2);
-    const int cpw = std::max(1, c->tun.icp_cpw);   // (0 = default: a group may have as many workgroups as clusters)
-    // (template groups keep two clusters in flight per workgroup whatever the regime: every group has its share of the
-    // workgroups and its own queue already, and four slots measure 3-7 % slower on config 5)
-    IcpParams ipg = ip;
-    if (c->tun.icp_slots <= 0) ipg.pipe_slots = std::min(2, CD_PIPE_SLOTS);
-    int* tab = c->h_wgtab;   // pinned: the copy below is asynchronous
-    int ntab = 0;
-    long long pts_all = 0;
-    int npg = 0;
-    for (const TplGroup& g : pl.groups) if (g.kind && g.live > 0) { pts_all += g.pts * (g.kind == 2 ? BIG_WEIGHT : 1); ++npg; }
-    int no = 0, gq = 0, n_wg = 0, wg_of[3] = {0, 0, 0}, tab_of[3] = {0, 0, 0};
-    for (int kind = 1; kind <= 2; ++kind) {
-        tab_of[kind] = ntab;
-        for (const TplGroup& g : pl.groups) {
-            if (g.kind != kind || g.live == 0) continue;
-            const int b = no;
-            for (int k = g.beg; k < g.end; ++k) if (c->h_cl[k].n >= 3) c->h_order[no++] = k;
-            std::stable_sort(c->h_order + b, c->h_order + no, [&](int x, int y) { return c->h_cl[x].n > c->h_cl[y].n; });
-            int share = (int)((long long)wg_cap * g.pts * (kind == 2 ? BIG_WEIGHT : 1) / std::max(pts_all, 1ll));
-            share = std::max(1, std::min(share, std::min((g.live + cpw - 1) / cpw, wg_cap - n_wg - (npg - 1 - gq))));
-            for (int w = 0; w < share && ntab + 3 <= 3 * 1024; ++w) { tab[ntab++] = b; tab[ntab++] = no; tab[ntab++] = gq; }
-            n_wg += share;
-            wg_of[kind] += share;
-            ++gq;
-        }
-    }
-    HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * (size_t)no, hipMemcpyHostToDevice));
-    HIPCHK(c, xfer(c, c->d_wgtab, tab, sizeof(int) * (size_t)ntab, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(c->d_queue, 0, sizeof(int) * 16, c->stream));   // one queue head per group
-    // the LDS-template launch goes to the context's stream (stream3 with icp_lowprio), the global-template launch beside it
-    hipStream_t s1 = c->tun.icp_lowprio ? c->stream3 : c->stream;
-    hipStream_t s2 = (c->tun.icp_lowprio || (wg_of[1] > 0 && wg_of[2] > 0)) ? c->stream2 : c->stream;
-    if (s1 != c->stream || s2 != c->stream) {   // everything uploaded so far is visible to the side streams
-        HIPCHK(c, hipEventRecord(c->ev2[0], c->stream));
-        if (s1 != c->stream) HIPCHK(c, hipStreamWaitEvent(s1, c->ev2[0], 0));
-        if (s2 != c->stream) HIPCHK(c, hipStreamWaitEvent(s2, c->ev2[0], 0));
-    }
-    if (wg_of[1] > 0)
-        LAUNCH(c, launch_icp_pipe(s1, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                        c->d_queue, wg_of[1], c->d_wgtab + tab_of[1], ipg, icp_bound(c)));
-    if (wg_of[2] > 0)
-        LAUNCH(c, launch_icp_pipe_big(s2, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tplk, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid,
-                            c->d_super, c->d_tcell, c->d_src, c->d_src0, c->d_nn, c->d_queue, wg_of[2], c->d_wgtab + tab_of[2], ipg, icp_bound(c)));
-    if (s1 != c->stream && wg_of[1] > 0) {
-        HIPCHK(c, hipEventRecord(c->ev2[2], s1));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev2[2], 0));
-    }
-    if (s2 != c->stream && wg_of[2] > 0) {
-        HIPCHK(c, hipEventRecord(c->ev2[1], s2));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev2[1], 0));
-    }
-    c->timing.icp_kernel_launches = 1;
-    c->timing.icp_regime = (ipg.pipe_slots << 16) | n_wg;
-    if (pl.nwork > 0) {   // the other clusters take the sliced driver
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return CD_OK;
-    }
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *done = true;
-    return CD_OK;
-}
-
-// One launch in which every cluster runs its whole ICP in one workgroup (plan.whole_cluster): k_icp_pipe, k_icp_pipe_big or
-// k_icp_cluster.  Always finishes the stage.
-int icp_run_whole(cd_context* c, const IcpPlan& pl, IcpParams ip, bool* done) {
-    const int ncl = pl.ncl;
-    auto pipe_grid = [&](int n_items, int cap) {   // workgroups of the launch over n_items clusters
-        if (c->tun.icp_cpw > 0) return std::min((n_items + c->tun.icp_cpw - 1) / c->tun.icp_cpw, cap);
-        if (!pl.crowded || n_items <= cap) return std::min(n_items, cap);
-        return std::min(cap, std::max(32, (n_items / ip.pipe_slots + 16) / 32 * 32));
-    };
-    GateHold hold;   // (released on every path out of this function)
-    if (c->tun.icp_concurrent > 0) hold.enter(&device_shared(c).icp_gate, c->tun.icp_concurrent);
-    for (int k = 0; k < ncl; ++k) c->h_order[k] = k;
-    std::stable_sort(c->h_order.get(), c->h_order + ncl, [&](int a, int b) { return c->h_cl[a].n > c->h_cl[b].n; });
-    HIPCHK(c, xfer(c, c->d_order, c->h_order, sizeof(int) * ncl, hipMemcpyHostToDevice));
-    const int wg_cap = pl.wg_cap;
-    HIPCHK(c, hipMemsetAsync(c->d_queue, 0, sizeof(int), c->stream));   // head of the cluster queue
-    hipStream_t si = c->tun.icp_lowprio >= 2 ? c->stream3 : c->stream;
-    if (pl.pipe_ok || pl.big_ok) {
-        c->timing.icp_regime = (ip.pipe_slots << 16) | pipe_grid(ncl, wg_cap);
-        // A launch that has the GPU to itself lets workgroups that run out of clusters wait and take over running ones
-        // (k_icp.hip, "hand-over of running clusters"): the launch is as long as its slowest workgroup, and the bench batch's
-        // slowest runs 25 % over the average.  With other calls in flight a waiting workgroup would sit on a CU their
-        // kernels could use, and what counts there is the CU-time a batch costs, which hand-overs do not lower.
-        const bool alone = device_shared(c).batches_in_flight.load() <= 1;
-        ip.donate = (c->tun.icp_donate < 0 ? (alone && ncl > pipe_grid(ncl, wg_cap)) : c->tun.icp_donate != 0) ? 1 : 0;
-        if (ip.donate) HIPCHK(c, hipMemsetAsync(c->d_don, 0, sizeof(int) * (size_t)(DON_BOX + DON_CAP), c->stream));
-    }
-    if (si != c->stream) {   // (after the control block was zeroed on c->stream: the launch on `si` must see it zeroed - ADVICE r4)
-        HIPCHK(c, hipEventRecord(c->ev2[0], c->stream));
-        HIPCHK(c, hipStreamWaitEvent(si, c->ev2[0], 0));
-    }
-    if (pl.pipe_ok)
-        LAUNCH(c, launch_icp_pipe(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                        c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip, icp_bound(c)));
-    else if (pl.big_ok)
-        LAUNCH(c, launch_icp_pipe_big(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tplk, c->d_tlok, c->d_thik, c->d_kdmap, c->d_grid, c->d_super, c->d_tcell,
-                            c->d_src, c->d_src0, c->d_nn, c->d_queue, pipe_grid(ncl, wg_cap), nullptr, ip, icp_bound(c)));
-    else
-        LAUNCH(c, launch_icp_cluster(si, ncl, c->d_order, c->d_cl, c->d_st, c->d_accf, c->d_tpl, c->d_tlo, c->d_thi, c->d_grid, c->d_tcell, c->d_src, c->d_src0, c->d_nn,
-                           c->d_queue, wg_cap, ip, icp_bound(c)));
-    if (si != c->stream) {
-        HIPCHK(c, hipEventRecord(c->ev2[2], si));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev2[2], 0));
-    }
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    c->timing.icp_kernel_launches = 1;
-    HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-    if (ip.donate) HIPCHK(c, xfer(c, c->h_ctl + 8, c->d_don, sizeof(int) * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *done = true;   // (also when the hand-over check below fails the call: icp_kernel_ms is reported)
-    if (ip.donate) {
-        const int* w = c->h_ctl + 8;   // (copied with the records above)
-        c->timing.icp_handovers = w[DON_HEAD];
-        // every cluster of the launch was finished by somebody, and every mailbox entry that was written was taken
-        if (w[DON_ERR] != 0 || w[DON_FINISHED] != ncl || w[DON_HEAD] != std::min(w[DON_TAIL], DON_CAP)) {
-            c->timing.icp_handover_lost = 1;
-            std::snprintf(c->err, sizeof(c->err), "ICP hand-over lost a cluster: %d of %d clusters finished, %d entries published, %d taken, error word %d",
-                          w[DON_FINISHED], ncl, w[DON_TAIL], w[DON_HEAD], w[DON_ERR]);
-            return CD_ERR_DEVICE;
-        }
-        if (std::getenv("CUBOID_DEBUG"))
-            std::fprintf(stderr, "cuboid_hip: hand-overs: %d published, %d taken, %d clusters finished of %d, waiting balance %d\n", w[DON_TAIL], w[DON_HEAD], w[DON_FINISHED], ncl, w[DON_AVAIL]);
-    }
-    return CD_OK;
-}
-
-// Few clusters: ONE persistent launch runs every iteration and the fitness pass (k_icp_persist: grid barrier per
-// iteration instead of two kernel launches).  Needs all its workgroups resident together; a barrier that does not
-// complete in time makes it give up, and the sliced driver takes over from the initial state (not done).
-int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
-    const int ncl = pl.ncl, nwork = pl.nwork;
-    // (with other contexts at work - BatchPipeline - their persistent kernels hold the CUs this launch's grid barrier needs:
-    // it would wait, give up and hand over; go straight to the multi-launch loop then)
-    const bool siblings = device_shared(c).calls_in_flight.load() > 1;
-    if (nwork == 0 || !c->tun.icp_persist || (siblings && c->tun.icp_persist != 2)) return CD_OK;
-    const int G = std::min(nwork, pl.wg_cap);
-    // measured against the multi-launch loop: 1 frame 1.50 / 1.78 ms, 4 frames 1.94 / 2.36, 8 frames 3.04 / 2.66 - with many
-    // clusters the launch lasts as long as the slowest one while finished workgroups wait at the barriers, and a workgroup
-    // with several items solves for each of them in turn
-    if (ncl > 8 || nwork > G) return CD_OK;
-    int n_open = 0;
-    for (int k = 0; k < ncl; ++k) if (c->h_cl[k].tile0 < (k + 1 < ncl ? c->h_cl[k + 1].tile0 : nwork)) ++n_open;
-    // d_queue[4] barrier counter, [5] abort flag, [6..9] clusters closed per iteration slot (k_icp_persist's exit test)
-    int* ctl = c->h_ctl;
-    for (int i = 0; i < 8; ++i) ctl[i] = 0;
-    ctl[1] = c->tun.icp_persist == 2 ? 1 : 0;
-    HIPCHK(c, xfer(c, c->d_queue + 4, ctl, sizeof(int) * 6, hipMemcpyHostToDevice));
-    LAUNCH(c, launch_icp_persist(c->stream, nwork, G, ip.max_iter + 3, c->d_work, c->d_cl, c->d_st, c->d_acc, c->d_accf, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid,
-                       c->d_src, c->d_src0, c->d_nn, c->d_d2, pl.qslice, (unsigned*)(c->d_queue + 4), c->d_queue + 5, n_open, c->d_queue + 6, ip, icp_bound(c)));
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(c, xfer(c, ctl + 8, c->d_queue + 5, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
-    c->st_init.assign(c->h_st.get(), c->h_st + 2 * (size_t)ncl);   // in case the launch gives up (no reallocation after the first call)
-    HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!ctl[8]) {   // (the abort flag: raised when the launch gave up)
-        c->timing.icp_kernel_launches = 1;
-        *done = true;
-        return CD_OK;
-    }
-    c->persist_gave_up += 1;
-    c->timing.icp_persist_gave_up += 1;
-    if (std::getenv("CUBOID_DEBUG")) std::fprintf(stderr, "cuboid_hip: persistent ICP launch gave up at a grid barrier, running the multi-launch loop\n");
-    // start over: initial states, zero sums, the source points as extracted (the launch transformed them in place)
-    std::memcpy(c->h_st, c->st_init.data(), sizeof(IcpState) * 2 * (size_t)ncl);
-    HIPCHK(c, xfer(c, c->d_st, c->h_st, sizeof(IcpState) * 2 * ncl, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * (size_t)ncl, c->stream));
-    if (c->icp_bounded) HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
-    long long span = 0;
-    for (int k = 0; k < ncl; ++k) span = std::max(span, (long long)c->h_cl[k].src_off + c->h_cl[k].n);
-    HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)span, hipMemcpyDeviceToDevice, c->stream));
-    if (pl.guess_mode == CD_GUESS_CLUSTER)   // (the states just uploaded start from the identity again)
-        if (int e = launch_cluster_guesses(c, ncl)) return e;
-    if (pl.guess_mode != CD_GUESS_NONE)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl.max_n, c->d_cl, c->d_guess, guess_indexing(pl.guess_mode), c->d_src0, c->d_src));
-    return CD_OK;
-}
-
-// The multi-launch loop over the work list, then the fitness pass.  Always finishes the stage.
-int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpParams& ip, bool* done) {
-    const int ncl = pl.ncl, nwork = pl.nwork, max_launch = ip.max_iter + 3;
-    // The iteration kernel walks an ACTIVE work list (d_work2) that the host re-packs at every
-    // completion poll, dropping the clusters that have converged; the full list (d_work) is kept for
-    // the fitness pass.  A cluster whose state shows done in either parity slot has already had its
-    // final transform applied, so it needs no further work items (k_icp_solve alone keeps its state).
-    int it = 0, nactive = nwork;
-    std::memcpy(c->h_work2, c->h_work, sizeof(IcpWork) * (size_t)std::max(nwork, 1));
-    HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)std::max(nwork, 1), hipMemcpyHostToDevice));
-    int group = 8;
-    while (nwork > 0 && it < max_launch) {
-        const int g = std::min(group, max_launch - it);
-        for (int q = 0; q < g; ++q) LAUNCH(c, launch_icp_iter(c->stream, it++, nactive, ncl, c->d_work2, c->d_cl, c->d_st, c->d_acc, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid, c->d_src, c->d_nn, c->d_d2, pl.qslice, c->d_queue, c->n_cu, ip, icp_bound(c)));
-        HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool all = true;
-        int na = 0;
-        for (int w = 0; w < nwork; ++w) {
-            const int k = c->h_work[w].cluster;
-            if (!(c->h_st[2 * k].done || c->h_st[2 * k + 1].done)) c->h_work2[na++] = c->h_work[w];
-        }
-        for (int k = 0; k < ncl && all; ++k) all = c->h_st[2 * k].done && c->h_st[2 * k + 1].done;
-        if (all) break;
-        if (na != nactive) {
-            nactive = na;
-            if (na > 0) HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)na, hipMemcpyHostToDevice));
-        }
-        group = 16;
-    }
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));   // (before the fitness pass)
-    c->timing.icp_kernel_launches = it;
-    LAUNCH(c, launch_icp_fitness(c->stream, nwork, c->d_work, c->d_cl, c->d_st, 0, c->d_accf, c->d_tplk, c->d_tlok, c->d_thik, c->d_grid, c->d_src0, c->d_nn, c->d_d2, pl.qslice));
-    HIPCHK(c, xfer(c, c->h_accf, c->d_accf, sizeof(unsigned long long) * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *done = true;
-    return CD_OK;
-}
-
-}  // namespace
-
-namespace cd {
-// S6.  clusters described by h_cl[0..ncl) (src_off relative to d_src/d_src0).  Fills h_st / h_accf.
-int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests) {
-    c->timing.icp_kernel_launches = 0;
-    c->timing.icp_kernel_ms = 0.f;
-    if (pair_tests) *pair_tests = 0;
-    if (ncl <= 0) return CD_OK;
-    IcpPlan pl;
-    int st = plan_icp(c, ncl, p, &pl);
-    if (!st) st = icp_setup(c, p, &pl);
-    if (st) return st;
-    const IcpParams ip = icp_params(c, p, &pl.crowded);
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    bool done = false;
-    if (pl.plane) st = icp_run_plane(c, pl, ip, &done);
-    if (!st && !done && pl.n_lat > 0) st = icp_run_lat(c, pl, ip, &done);
-    if (!st && !done && pl.grouped_pipe) st = icp_run_grouped(c, pl, ip, &done);
-    if (!st && !done && pl.whole_cluster) st = icp_run_whole(c, pl, ip, &done);
-    if (!st && !done) st = icp_run_persist(c, pl, ip, &done);
-    if (!st && !done) st = icp_run_sliced(c, pl, ip, &done);
-    if (done) icp_finish(c, ncl, pair_tests);
-    return st;
-}
-
-void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_cluster_result* r) {
-    const IcpState& st = c->h_st[2 * k];
-    const IcpCluster& cl = c->h_cl[k];
-    std::memset(r, 0, sizeof(*r));
-    r->size = cl.n;
-    r->iterations = st.iters;
-    r->converged = st.converged;
-    std::memcpy(r->T, st.Tfinal, 64);
-    r->fitness = st.status == CD_OK ? hm::unfix(c->h_accf[k], FIX_SHIFT_D2) / (double)cl.n : std::numeric_limits<double>::max();
-    r->accepted = (r->converged && r->fitness < p->icp_accept_fitness) ? 1 : 0;
-    double Td[16];
-    for (int i = 0; i < 16; ++i) Td[i] = (double)st.Tfinal[i];
-    if (!hm::mat4_inverse(Td, r->pose))
-        for (int i = 0; i < 16; ++i) r->pose[i] = std::numeric_limits<double>::quiet_NaN();
 }
 }  // namespace cd

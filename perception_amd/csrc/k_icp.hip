@@ -1870,61 +1870,47 @@ void launch_icp_apply_guess(hipStream_t s, int ncl, int max_n, const IcpCluster*
     hipLaunchKernelGGL(k_icp_apply_guess, dim3(ncl, gx < 64 ? gx : 64), dim3(BLOCK), 0, s, cl, guesses, per_frame, src0, src);
 }
 
-void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpCluster* cl, IcpState* st,
-                     unsigned long long* acc, const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                     int qslice, int n_cu, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0) return;
-    if (bnd.bounded) hipLaunchKernelGGL(k_icp_solve<true>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, cl, st, acc, queue, prm, bnd);
-    else hipLaunchKernelGGL(k_icp_solve<false>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, cl, st, acc, queue, prm, bnd);
+    if (bnd.bounded) hipLaunchKernelGGL(k_icp_solve<true>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, P.cl, P.st, S.acc, S.queue, prm, bnd);
+    else hipLaunchKernelGGL(k_icp_solve<false>, dim3((ncl + WAVE - 1) / WAVE), dim3(WAVE), 0, s, it, ncl, P.cl, P.st, S.acc, S.queue, prm, bnd);
     if (n_work <= 0) return;   // every cluster converged: only the state bookkeeping above is needed
     if (bnd.bounded)
-        hipLaunchKernelGGL(k_icp_iter<true>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, cl, st, acc, tpl, tlo,
-                           thi, grids, src, nn, d2buf, qslice, queue, bnd);
+        hipLaunchKernelGGL(k_icp_iter<true>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, P.cl, P.st, S.acc, T.tplk, T.tlok,
+                           T.thik, T.grids, S.src, S.nn, S.d2, qslice, S.queue, bnd);
     else
-        hipLaunchKernelGGL(k_icp_iter<false>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, cl, st, acc, tpl, tlo,
-                           thi, grids, src, nn, d2buf, qslice, queue, bnd);
+        hipLaunchKernelGGL(k_icp_iter<false>, dim3(n_work < n_cu ? n_work : n_cu), dim3(ICPT_THREADS), 0, s, it, n_work, work, P.cl, P.st, S.acc, T.tplk, T.tlok,
+                           T.thik, T.grids, S.src, S.nn, S.d2, qslice, S.queue, bnd);
 }
-void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpCluster* cl, const IcpState* st,
-                        int parity, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
-                        const IcpGrid* grids, const float4* src0, int* nn, float* d2buf, int qslice) {
+void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpProblems& P, int parity, const IcpTemplates& T, const IcpScratch& S, int qslice) {
     if (n_work <= 0) return;
-    hipLaunchKernelGGL(k_icp_fitness, dim3(n_work), dim3(ICPT_THREADS), 0, s, work, cl, st, parity, accf, tpl, tlo, thi, grids, src0, nn, d2buf, qslice);
+    hipLaunchKernelGGL(k_icp_fitness, dim3(n_work), dim3(ICPT_THREADS), 0, s, work, P.cl, P.st, parity, P.accf, T.tplk, T.tlok, T.thik, T.grids, S.src0, S.nn, S.d2, qslice);
 }
 
-void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpCluster* cl, IcpState* st,
-                         unsigned long long* acc, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
-                         const IcpGrid* grids, float4* src, const float4* src0, int* nn, float* d2buf, int qslice, unsigned* bar,
-                         int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                        int qslice, unsigned* bar, int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd) {
     if (n_work <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(bnd.bounded ? k_icp_persist<true> : k_icp_persist<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, n_work, max_it, work, cl, st, acc, accf, tpl, tlo, thi, grids,
-                       src, src0, nn, d2buf, qslice, bar, abort_flag, n_open, closed, prm, bnd);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_persist<true> : k_icp_persist<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, n_work, max_it, work, P.cl, P.st, S.acc, P.accf,
+                       T.tplk, T.tlok, T.thik, T.grids, S.src, S.src0, S.nn, S.d2, qslice, bar, abort_flag, n_open, closed, prm, bnd);
 }
 
-void launch_icp_cluster(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                        const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                        const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                        int* queue, int n_cu, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_cluster(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_cu, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0) return;
-    hipLaunchKernelGGL(bnd.bounded ? k_icp_cluster<true> : k_icp_cluster<false>, dim3(ncl < n_cu ? ncl : n_cu), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
-                       grids, tcell, src, src0, nn, queue, prm, bnd);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_cluster<true> : k_icp_cluster<false>, dim3(ncl < n_cu ? ncl : n_cu), dim3(ICPT_THREADS), 0, s, ncl, P.order, P.cl, P.st, P.accf,
+                       T.tpl, T.tlo, T.thi, T.grids, T.tcell, S.src, S.src0, S.nn, S.queue, prm, bnd);
 }
 
-void launch_icp_pipe(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                     const float4* tpl, const float4* tlo, const float4* thi, const unsigned short* kdmap, const IcpGrid* grids,
-                     const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                     int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_pipe(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe<true> : k_icp_pipe<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlo, thi,
-                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, bnd);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe<true> : k_icp_pipe<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, P.order, P.cl, P.st, P.accf, T.tpl, T.tlok, T.thik,
+                       T.kdmap, T.grids, T.tcell, S.src, S.src0, S.nn, S.queue, wgtab, prm, bnd);
 }
 
-void launch_icp_pipe_big(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                         const float4* tpl, const float4* tplk, const float4* tlok, const float4* thik, const unsigned short* kdmap,
-                         const IcpGrid* grids, const IcpSuper* supers, const unsigned short* tcell, float4* src, const float4* src0,
-                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_pipe_big(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd) {
     if (ncl <= 0 || n_wg <= 0) return;
-    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe_big<true> : k_icp_pipe_big<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, order, cl, st, accf, tpl, tlok, thik,
-                       kdmap, grids, tcell, src, src0, nn, queue, wgtab, prm, tplk, supers, bnd);
+    hipLaunchKernelGGL(bnd.bounded ? k_icp_pipe_big<true> : k_icp_pipe_big<false>, dim3(n_wg), dim3(ICPT_THREADS), 0, s, ncl, P.order, P.cl, P.st, P.accf, T.tpl, T.tlok, T.thik,
+                       T.kdmap, T.grids, T.tcell, S.src, S.src0, S.nn, S.queue, wgtab, prm, T.tplk, T.supers, bnd);
 }
 
 }  // namespace cd

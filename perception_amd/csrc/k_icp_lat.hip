@@ -386,17 +386,16 @@ static void launch_lat_shape(hipStream_t s, int nitems, int n_wg, const int* ord
     else
         hipLaunchKernelGGL((k_icp_lat<CPW, WPC, false>), dim3(n_wg), dim3(CPW * WPC * WAVE), 0, s, nitems, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
 }
-void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const int* order, const IcpCluster* cl, IcpState* st,
-                    unsigned long long* accf, const IcpLattice* lats, float4* src, const float4* src0, int* queue, unsigned long long* busy,
-                    unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd) {
+void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                    unsigned long long* busy, unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd) {
     if (nitems <= 0 || n_wg <= 0) return;
-#define CD_LAT_CASE(C, W) if (cpw == C && wpc == W) return launch_lat_shape<C, W>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
+#define CD_LAT_CASE(C, W) if (cpw == C && wpc == W) return launch_lat_shape<C, W>(s, nitems, n_wg, P.order, P.cl, P.st, P.accf, T.lats, S.src, S.src0, S.queue, busy, busy_out, prm, bnd);
     CD_LAT_CASE(1, 1) CD_LAT_CASE(1, 2) CD_LAT_CASE(1, 4) CD_LAT_CASE(1, 8) CD_LAT_CASE(1, 16)
     CD_LAT_CASE(2, 1) CD_LAT_CASE(2, 2) CD_LAT_CASE(2, 4)
     CD_LAT_CASE(4, 1) CD_LAT_CASE(4, 2) CD_LAT_CASE(4, 4)
     CD_LAT_CASE(8, 1) CD_LAT_CASE(8, 2)
 #undef CD_LAT_CASE
-    launch_lat_shape<1, 4>(s, nitems, n_wg, order, cl, st, accf, lats, src, src0, queue, busy, busy_out, prm, bnd);
+    launch_lat_shape<1, 4>(s, nitems, n_wg, P.order, P.cl, P.st, P.accf, T.lats, S.src, S.src0, S.queue, busy, busy_out, prm, bnd);
 }
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2) {
     if (n <= 0) return;

@@ -220,14 +220,13 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
     }
 }
 
-void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                      PlaneStats* pstat, const IcpLattice* lats, float4* src, const float4* src0, int* queue, IcpParams prm, const IcpBound& bnd,
-                      const PlaneParams& pp) {
+void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const IcpProblems& P, PlaneStats* pstat, const IcpTemplates& T, const IcpScratch& S,
+                      IcpParams prm, const IcpBound& bnd, const PlaneParams& pp) {
     if (nitems <= 0 || n_wg <= 0) return;
     if (bnd.bounded)
-        hipLaunchKernelGGL((k_icp_plane<true>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, order, cl, st, accf, pstat, lats, src, src0, queue, prm, bnd, pp);
+        hipLaunchKernelGGL((k_icp_plane<true>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, P.order, P.cl, P.st, P.accf, pstat, T.lats, S.src, S.src0, S.queue, prm, bnd, pp);
     else
-        hipLaunchKernelGGL((k_icp_plane<false>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, order, cl, st, accf, pstat, lats, src, src0, queue, prm, bnd, pp);
+        hipLaunchKernelGGL((k_icp_plane<false>), dim3(n_wg), dim3(PLANE_THREADS), 0, s, nitems, P.order, P.cl, P.st, P.accf, pstat, T.lats, S.src, S.src0, S.queue, prm, bnd, pp);
 }
 
 }  // namespace cd

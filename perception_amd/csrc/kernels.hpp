@@ -92,45 +92,40 @@ void launch_label_scatter(hipStream_t s, const float4* obj, int N, int F, int T,
                           const int* label, const int* tile_off, float4* src0, float4* src, int kbase, const int* koff_tab);
 
 // k_icp.hip
-void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpCluster* cl, IcpState* st,
-                     unsigned long long* acc, const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                     float4* src, int* nn, float* d2buf, int qslice, int* queue, int n_cu, IcpParams prm, const IcpBound& bnd);
-void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpCluster* cl, IcpState* st,
-                         unsigned long long* acc, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
-                         const IcpGrid* grids, float4* src, const float4* src0, int* nn, float* d2buf, int qslice, unsigned* bar,
-                         int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd);
-void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpCluster* cl, const IcpState* st,
-                        int parity, unsigned long long* accf, const float4* tpl, const float4* tlo, const float4* thi,
-                        const IcpGrid* grids, const float4* src0, int* nn, float* d2buf, int qslice);
+// What every ICP launch takes, in three blocks that icp_stage.hip fills once per stage; each launcher picks what its kernel reads.
+struct IcpProblems {   // the problem set: device pointers, or (k_icp_lat's direct mode) the pinned host arrays
+    const int* order; const IcpCluster* cl; IcpState* st; unsigned long long* accf;
+};
+struct IcpTemplates {   // the template tables: points + per-64-run boxes in cell order (tpl, tlo, thi) and in k-d patch order (tplk, tlok, thik)
+    const float4 *tpl, *tplk, *tlo, *thi, *tlok, *thik;
+    const unsigned short* kdmap; const IcpGrid* grids; const IcpSuper* supers; const unsigned short* tcell; const IcpLattice* lats;
+};
+struct IcpScratch { float4* src; const float4* src0; int* nn; float* d2; unsigned long long* acc; int* queue; };
+// (the sliced, persistent and fitness kernels search the k-d patch order with its boxes)
+void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                     int qslice, int n_cu, IcpParams prm, const IcpBound& bnd);
+void launch_icp_persist(hipStream_t s, int n_work, int n_wg, int max_it, const IcpWork* work, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                        int qslice, unsigned* bar, int* abort_flag, int n_open, int* closed, IcpParams prm, const IcpBound& bnd);
+void launch_icp_fitness(hipStream_t s, int n_work, const IcpWork* work, const IcpProblems& P, int parity, const IcpTemplates& T, const IcpScratch& S, int qslice);
 
 void launch_icp_apply_guess(hipStream_t s, int ncl, int max_n, const IcpCluster* cl, const float* guesses, int per_frame,
                             const float4* src0, float4* src);
-void launch_icp_pipe(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                     const float4* tpl, const float4* tlo, const float4* thi, const unsigned short* kdmap, const IcpGrid* grids,
-                     const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                     int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
-void launch_icp_pipe_big(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                         const float4* tpl, const float4* tplk, const float4* tlok, const float4* thik, const unsigned short* kdmap,
-                         const IcpGrid* grids, const IcpSuper* supers, const unsigned short* tcell, float4* src, const float4* src0,
-                         int* nn, int* queue, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
-void launch_icp_cluster(hipStream_t s, int ncl, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                        const float4* tpl, const float4* tlo, const float4* thi, const IcpGrid* grids,
-                        const unsigned short* tcell, float4* src, const float4* src0, int* nn,
-                        int* queue, int n_cu, IcpParams prm, const IcpBound& bnd);
+// (k_icp_pipe: the cell order with the k-d boxes; k_icp_pipe_big: both orders with the k-d boxes; k_icp_cluster: the cell order with its boxes)
+void launch_icp_pipe(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
+void launch_icp_pipe_big(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_wg, const int* wgtab, IcpParams prm, const IcpBound& bnd);
+void launch_icp_cluster(hipStream_t s, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, int n_cu, IcpParams prm, const IcpBound& bnd);
 
 // k_icp_lat.hip : templates that are unions of axis-aligned lattices (IcpLattice) - closed-form nearest neighbour
-void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const int* order, const IcpCluster* cl, IcpState* st,
-                    unsigned long long* accf, const IcpLattice* lats, float4* src, const float4* src0, int* queue, unsigned long long* busy,
-                    unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd);
+void launch_icp_lat(hipStream_t s, int nitems, int cpw, int wpc, int n_wg, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
+                    unsigned long long* busy, unsigned long long* busy_out, IcpParams prm, const IcpBound& bnd);
 void launch_lat_nn(hipStream_t s, const IcpLattice* lat, const float4* q, int n, int* out_idx, float* out_d2);
 
 // k_icp_plane.hip : rule C17, the plane-weighted ICP step for lattice templates (icp_plane_math.hpp: PlaneStats, PlaneParams);
-// n_wg workgroups take the nitems problems of `order` from queue[0], one at a time
+// n_wg workgroups take the nitems problems of P.order from S.queue[0], one at a time
 struct PlaneStats;
 struct PlaneParams;
-void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const int* order, const IcpCluster* cl, IcpState* st, unsigned long long* accf,
-                      PlaneStats* pstat, const IcpLattice* lats, float4* src, const float4* src0, int* queue, IcpParams prm, const IcpBound& bnd,
-                      const PlaneParams& pp);
+void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const IcpProblems& P, PlaneStats* pstat, const IcpTemplates& T, const IcpScratch& S,
+                      IcpParams prm, const IcpBound& bnd, const PlaneParams& pp);
 
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
 // records x y z rgb (canonical rule C7)
