@@ -945,6 +945,49 @@ int cd_get_cluster_plane_stats(const cd_context* ctx, int frame, int first, int 
  * d2, unused here).  T row-major; *singular = 1 and T = identity for a singular system or n < 1. */
 int cd_icp_plane_solve_host(const int64_t sums[28], int n, float T[16], int32_t* singular);
 
+/* Coarse-to-fine ICP: an opt-in resolution pyramid of two levels, off by default.  Canonical rule C18;
+ * perception_amd/icp_coarse.py is the rule in numpy.  It changes results: the fine level starts from another pose than the
+ * call's guess, so it may end in another minimum (INTEGRATION.md §3 has what was measured).
+ * Context state (stride s, min_points m); s = 0 is off.  With s >= 2 a (cluster, template) pair whose cluster has n >= m points
+ * is eligible:
+ *   1. the coarse set is the points p[j s], j = 0 .. ceil(n / s) - 1, of the cluster in extraction order (the order of
+ *      cd_get_cluster_points(aligned = 0); in cd_icp the order of src_xyz);
+ *   2. the coarse ICP is the ICP this library runs on that set as a cluster of its own: same template, cd_params, rule C8 / C17
+ *      setting and guess mode (CD_GUESS_CLUSTER computes rule C13 on the coarse set).  Its result is T_c;
+ *   3. the fine ICP is the ICP of the whole cluster started from T_c, as CD_GUESS_PARAMS with icp_guess = T_c runs it;
+ *      icp_max_iterations applies to each level on its own.  Every record of the cluster (T, pose, iterations, converged,
+ *      fitness, accepted, aligned cloud, plane stats) is the fine level's;
+ *   4. a coarse ICP that stopped (fewer than three correspondences under rule C8, a singular step of rule C17) or whose T_c has
+ *      a non-finite entry is dropped: the fine level starts from the call's own guess, as with the mode off.
+ * Pairs that are not eligible run as with the mode off.  With CD_GUESS_CLUSTER the shape records
+ * (cd_get_cluster_shape_frames, CD_FRAME_CLUSTER_GUESS) stay those of the whole cluster.
+ *
+ * cd_set_icp_coarse: applies to every ICP of the following cd_icp and fused calls.  stride 0 (min_points is ignored and kept as
+ * it was) or 2 .. 64 with min_points >= 3 * stride; anything else CD_ERR_INVALID_ARG and the setting stays.  Turning the mode on
+ * grows the context's ICP source buffers, and the object-cloud buffer the outlier filter swaps with one of them, by two thirds
+ * (the coarse sets lie behind a stage's clusters, so they fit any stage of the context); CD_ERR_DEVICE when
+ * that allocation fails; the call that grows them invalidates the read-backs of the last fused call, as a compute call does. */
+typedef struct cd_icp_coarse_stats {
+    int32_t n_coarse;            /* points of the coarse set; 0: the pair was not eligible                          */
+    int32_t coarse_iterations;
+    int32_t coarse_converged;
+    int32_t coarse_status;       /* CD_OK, or CD_ERR_FEW_CORRESPONDENCES for a coarse ICP that stopped              */
+    double coarse_fitness;       /* getFitnessScore of the coarse set under T_c                                     */
+    int32_t used;                /* 0 not eligible, 1 the fine level started from T_c, 2 it fell back (step 4)      */
+    int32_t reserved;
+} cd_icp_coarse_stats;
+#define CD_ICP_COARSE_STRIDE_MAX 64
+int cd_set_icp_coarse(cd_context* ctx, int stride, int min_points);
+int cd_get_icp_coarse(const cd_context* ctx, int* stride, int* min_points);
+int cd_icp_coarse_struct_size(void);   /* sizeof(cd_icp_coarse_stats) (cd_struct_size's list is closed) */
+/* Host only (no context, no GPU): step 1's indices of a set of n points.  Returns their count, 0 when the set is not eligible
+ * or the setting is not one cd_set_icp_coarse takes; out_indices (may be NULL) is written only when the count fits capacity. */
+int cd_icp_coarse_subsample(int n, int stride, int min_points, int32_t* out_indices, int capacity);
+/* Indexed like cd_get_cluster_results (the stats of the template whose result the cluster kept); after a stand-alone cd_icp
+ * the result is at frame 0, index 0.  Returns the number copied; CD_ERR_INVALID_ARG when the call ran with the mode off, has
+ * been invalidated by another compute call, or had no such frame. */
+int cd_get_cluster_coarse_stats(const cd_context* ctx, int frame, int first, int count, cd_icp_coarse_stats* out);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

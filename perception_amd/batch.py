@@ -80,10 +80,11 @@ class BatchPipeline:
     surface_distance_threshold: sne's distance threshold for prm.icp_use_guess = CD_GUESS_SURFACE on every context (None:
     the default, 0.015).
     icp_plane_weight: (tangent_weight, switch_distance) of the plane-weighted ICP step for lattice templates on every context
-    (None: off, the default; rule C17)."""
+    (None: off, the default; rule C17).
+    icp_coarse: (stride, min_points) of coarse-to-fine ICP on every context (None: off, the default; rule C18)."""
 
     def __init__(self, max_points, max_frames, templates_by_slot, device_id=0, inflight=2, icp_max_correspondence_distance=None,
-                 surface_distance_threshold=None, icp_plane_weight=None):
+                 surface_distance_threshold=None, icp_plane_weight=None, icp_coarse=None):
         from concurrent.futures import ThreadPoolExecutor
         self.inflight = max(1, int(inflight))
         self.contexts = [capi.Context(max_points=max_points, max_frames=max_frames, device_id=device_id) for _ in range(self.inflight)]
@@ -96,6 +97,8 @@ class BatchPipeline:
                 cx.set_surface_distance_threshold(surface_distance_threshold)
             if icp_plane_weight is not None:
                 cx.set_icp_plane_weight(*icp_plane_weight)
+            if icp_coarse is not None:
+                cx.set_icp_coarse(*icp_coarse)
         self._results = [(capi.CdFrameResult * max_frames)() for _ in range(self.inflight)]
         self._busy = [None] * self.inflight
         self._pool = ThreadPoolExecutor(self.inflight)

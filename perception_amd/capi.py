@@ -53,10 +53,15 @@ EXPORTED_SYMBOLS = [
     "cd_default_label_palette", "cd_label_struct_size", "cd_tint_labels_batch", "cd_tint_labels_batch_device",
     "cd_set_outlier_filter", "cd_get_outlier_filter", "cd_get_outlier_stats", "cd_outlier_filter",
     "cd_set_icp_plane_weight", "cd_get_icp_plane_weight", "cd_get_cluster_plane_stats", "cd_icp_plane_solve_host",
+    "cd_set_icp_coarse", "cd_get_icp_coarse", "cd_icp_coarse_struct_size", "cd_icp_coarse_subsample", "cd_get_cluster_coarse_stats",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
 CD_ICP_PLANE_WEIGHT_DEFAULT, CD_ICP_PLANE_SWITCH_DEFAULT, CD_ICP_PLANE_WEIGHT_MIN = 1.0 / 32.0, 0.01, 1.0 / 1024.0
+
+# rule C18 (cd_set_icp_coarse): the largest stride, and cd_icp_coarse_stats.used
+CD_ICP_COARSE_STRIDE_MAX = 64
+CD_COARSE_NOT_ELIGIBLE, CD_COARSE_USED, CD_COARSE_FELL_BACK = 0, 1, 2
 
 CD_CLOUD_VOXELS, CD_CLOUD_OBJECTS = 0, 1
 CD_GUESS_NONE, CD_GUESS_PARAMS, CD_GUESS_PER_FRAME, CD_GUESS_SURFACE, CD_GUESS_CLUSTER = 0, 1, 2, 3, 4
@@ -76,6 +81,12 @@ CD_OUTLIER_MAX_MEAN_K, CD_OUTLIER_LDS_TILE = 63, 1024
 class CdSurfaceFrameResult(C.Structure):
     _fields_ = [("Rt", C.c_float * 16), ("coeff", (C.c_float * 4) * 3), ("midpoint", (C.c_float * 4) * 3),
                 ("n_points", C.c_int32 * 3), ("iterations", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
+
+
+class CdIcpCoarseStats(C.Structure):
+    """cd_icp_coarse_stats: what rule C18 did for one (cluster, template) pair."""
+    _fields_ = [("n_coarse", C.c_int32), ("coarse_iterations", C.c_int32), ("coarse_converged", C.c_int32), ("coarse_status", C.c_int32),
+                ("coarse_fitness", C.c_double), ("used", C.c_int32), ("reserved", C.c_int32)]
 
 
 class CdShapeFrame(C.Structure):
@@ -475,6 +486,11 @@ def load_library(path=None):
     lib.cd_get_icp_plane_weight.argtypes = [vp, dp, dp]
     lib.cd_get_cluster_plane_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.cd_icp_plane_solve_host.argtypes = [vp, C.c_int, vp, ip]
+    lib.cd_set_icp_coarse.argtypes = [vp, C.c_int, C.c_int]
+    lib.cd_get_icp_coarse.argtypes = [vp, ip, ip]
+    lib.cd_icp_coarse_struct_size.argtypes = []
+    lib.cd_icp_coarse_subsample.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    lib.cd_get_cluster_coarse_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     if path is None:
         _lib = lib
     return lib
@@ -967,6 +983,27 @@ class Context:
             raise CuboidError(got, "no plane-weighted call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
         return out[:got].copy()
 
+    def set_icp_coarse(self, stride, min_points=0):
+        """Rule C18, coarse-to-fine ICP, for every later ICP of this context: pairs whose cluster has at least min_points points
+        first register every stride-th point, then all points from that pose.  stride = 0 (or None): off, the default."""
+        self._check(self.lib.cd_set_icp_coarse(self.h, int(stride or 0), int(min_points)))
+
+    def icp_coarse(self):
+        """(stride, min_points) as cd_set_icp_coarse left them; stride = 0: off."""
+        s, m = C.c_int(), C.c_int()
+        self._check(self.lib.cd_get_icp_coarse(self.h, C.byref(s), C.byref(m)))
+        return s.value, m.value
+
+    def cluster_coarse_stats(self, frame, first=0, count=None):
+        """Rule C18's stats of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
+        cluster_results: a list of CdIcpCoarseStats."""
+        cap = 4096 if count is None else int(count)
+        out = (CdIcpCoarseStats * max(cap, 1))()
+        got = self.lib.cd_get_cluster_coarse_stats(self.h, frame, first, cap, C.byref(out))
+        if got < 0:
+            raise CuboidError(got, "no coarse-to-fine call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
+        return [out[i] for i in range(got)]
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1128,6 +1165,20 @@ def icp_solve_batch(sums, n, states, max_iter=50, trans_eps=1e-8, rel_mse=1e-6, 
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_solve_batch")
     return out_row, out_lane, done, un
+
+
+def icp_coarse_subsample(n, stride, min_points, capacity=None):
+    """Host only: rule C18's coarse indices of a set of n points (int32; empty when the set is not eligible).  capacity: the
+    buffer handed to the library (default: as many as it needs); a count over it returns (count, None)."""
+    lib = load_library()
+    need = lib.cd_icp_coarse_subsample(int(n), int(stride), int(min_points), None, 0)
+    if capacity is None:
+        capacity = need
+    out = np.zeros(max(int(capacity), 1), np.int32)
+    got = lib.cd_icp_coarse_subsample(int(n), int(stride), int(min_points), _ptr(out), int(capacity))
+    if got > capacity:
+        return got, None
+    return out[:got].copy()
 
 
 def icp_plane_solve_host(sums, n):

@@ -349,6 +349,10 @@ public:
     // default.  It is no PCL estimator - TransformationEstimationPointToPlaneLLS is its singular case - and handed to the shared
     // context before each ICP like the distance above.
     void setPlaneWeight(double tangent_weight, double switch_distance = CD_ICP_PLANE_SWITCH_DEFAULT) { plane_w_ = tangent_weight; plane_d_ = switch_distance; }
+    // Not PCL: the library's coarse-to-fine mode (rule C18, cd_set_icp_coarse): a source of at least min_points points first
+    // registers every stride-th point, then all points from that pose; stride 0 = off, the default.  Handed to the shared context
+    // before each ICP like the two above.
+    void setCoarseToFine(int stride, int min_points) { coarse_s_ = stride; coarse_m_ = min_points; }
     // align(output, guess): pcl::Registration's second overload (row-major 4x4, scene -> template)
     void align(PointCloud<PointSource>& output, const Matrix4& guess) {
         prm_.icp_use_guess = CD_GUESS_PARAMS;
@@ -365,7 +369,8 @@ public:
         std::vector<float> al((size_t)std::max(n, 1) * 3);
         cd_cluster_result r;
         if (cd_set_icp_max_correspondence_distance(Device::instance().ctx(), max_corr_) != CD_OK ||
-            cd_set_icp_plane_weight(Device::instance().ctx(), plane_w_, plane_d_) != CD_OK) {
+            cd_set_icp_plane_weight(Device::instance().ctx(), plane_w_, plane_d_) != CD_OK ||
+            cd_set_icp_coarse(Device::instance().ctx(), coarse_s_, coarse_m_) != CD_OK) {
             std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx()));
             return;
         }
@@ -392,6 +397,7 @@ private:
     int slot_ = 0, iterations_ = 0;
     double max_corr_ = std::sqrt(std::numeric_limits<double>::max());
     double plane_w_ = 0.0, plane_d_ = CD_ICP_PLANE_SWITCH_DEFAULT;
+    int coarse_s_ = 0, coarse_m_ = 0;
     typename PointCloud<PointSource>::ConstPtr src_;
     typename PointCloud<PointTarget>::ConstPtr tgt_;
     Matrix4 final_;

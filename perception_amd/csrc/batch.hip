@@ -185,6 +185,7 @@ void begin_batch_icp(cd_context* c, const cd_params* p, int F, const BatchCluste
     bi->orig_off.assign((size_t)std::max(cl.ncl, 1), -1);
     bi->al_off.assign((size_t)std::max(cl.ncl, 1), -1);
     if (c->plane_weight != 0.0) c->last_plane.assign((size_t)std::max(cl.ncl, 1), cd_icp_plane_stats());   // rule C17: the kept result's counters
+    if (c->coarse_stride != 0) c->last_coarse.assign((size_t)std::max(cl.ncl, 1), cd_icp_coarse_stats());   // rule C18: the kept result's stats
     for (int f = 0; f < F; ++f)
         for (int q = cl.first[(size_t)f]; q < cl.first[(size_t)f + 1]; ++q) bi->orig_off[(size_t)q] = (long long)f * c->N + cl.off[(size_t)q];
 }
@@ -209,6 +210,7 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
     if (t > 0 && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
     c->last_clusters[(size_t)k] = r;
     if (c->plane_weight != 0.0) std::memcpy(&c->last_plane[(size_t)k], &c->h_pstat[q], sizeof(cd_icp_plane_stats));
+    if (c->coarse_stride != 0) std::memcpy(&c->last_coarse[(size_t)k], &c->h_cstat[q], sizeof(cd_icp_coarse_stats));
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
 }
 
@@ -240,7 +242,7 @@ int icp_all_pairs(cd_context* c, const cd_params* p, int F, const BatchClusters&
             const int q = cl.first[(size_t)f];
             set_icp_clusters(c, t * ncl + q, c->h_fs[f].n_k, f, cl.size.data() + q, cl.off.data() + q, f * c->N + t * cl.span[(size_t)f], bi->slots[(size_t)t]);
         }
-    st = stage_icp(c, S * ncl, p, &bi->pairs);
+    st = stage_icp_levels(c, S * ncl, p, &bi->pairs);
     if (st) return st;
     keep_cluster_shapes(c, p, ncl);   // (the problems of slots[0]: a cluster's record does not depend on the template)
     for (int t = 0; t < S; ++t)
@@ -264,7 +266,7 @@ int icp_per_template(cd_context* c, const cd_params* p, int F, const BatchCluste
             set_icp_clusters(c, q, c->h_fs[f].n_k, f, cl.size.data() + q, cl.off.data() + q, f * c->N, bi->slots[(size_t)t]);
         }
         long long pr = 0;
-        st = stage_icp(c, cl.ncl, p, &pr);
+        st = stage_icp_levels(c, cl.ncl, p, &pr);
         if (st) return st;
         keep_cluster_shapes(c, p, cl.ncl);
         bi->pairs += pr;
@@ -286,6 +288,8 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     c->last_shapes_ok = p->icp_use_guess == CD_GUESS_CLUSTER;
     c->last_plane_ok = c->plane_weight != 0.0;
     if (c->last_plane_ok) c->last_plane_first = cl.first;
+    c->last_coarse_ok = c->coarse_stride != 0;
+    if (c->last_coarse_ok) c->last_coarse_first = cl.first;
     if (c->last_shapes_ok && cl.ncl == 0) c->last_shapes.clear();
 }
 

@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "outlier_math.hpp"
 #include "icp_plane_math.hpp"
+#include "icp_coarse_plan.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
 #include "tunables.hpp"
@@ -216,6 +217,19 @@ struct cd_context : cd_streams {
     std::vector<cd_icp_plane_stats> last_plane;
     std::vector<int> last_plane_first;
     bool last_plane_ok = false;
+    // coarse-to-fine ICP (rule C18, k_icp_coarse.hip): the setting (cd_set_icp_coarse; coarse_stride = 0: off); per stage, grown on
+    // demand, the gather table, the final states and fitness sums of the coarse problems and the fine problems' hand-over table
+    // (pinned + device), and one stats record per fine problem (device + pinned mirror); and what cd_get_cluster_coarse_stats
+    // reads, as last_plane
+    int coarse_stride = 0, coarse_min = 0;
+    DevBuf<CoarseGather> d_cgather; PinBuf<CoarseGather> h_cgather;
+    DevBuf<IcpState> d_cst; PinBuf<IcpState> h_cst;
+    DevBuf<unsigned long long> d_caccf; PinBuf<unsigned long long> h_caccf;
+    DevBuf<CoarseHand> d_chand; PinBuf<CoarseHand> h_chand;
+    DevBuf<CoarseStats> d_cstat; PinBuf<CoarseStats> h_cstat;
+    std::vector<cd_icp_coarse_stats> last_coarse;
+    std::vector<int> last_coarse_first;
+    bool last_coarse_ok = false;
     cd_timing timing;
 };
 
@@ -260,6 +274,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_shapes_ok = false;
     c->last_outlier_ok = false;
     c->last_plane_ok = false;
+    c->last_coarse_ok = false;
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -416,8 +431,11 @@ int stage_cluster_sync(cd_context* c, int F, const cd_params* p, int max_no);
 void set_icp_clusters(cd_context* c, int first, int n, int frame, const int* size, const int* off, int base, int slot);
 ShapeFrame template_frame(const cd_context* c, int slot);
 // ---- icp_stage.hip
-int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests);
+int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests, bool device_guesses = false);
 void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_cluster_result* r);
+// rule C18: stage_icp, or - the mode on and a problem of the stage eligible - the coarse stage over the subsamples, the hand-over
+// and the stage itself.  h_cl / h_st / h_accf describe the stage's own problems afterwards, h_cstat their stats (mode on).
+int stage_icp_levels(cd_context* c, int ncl, const cd_params* p, long long* pair_tests);
 // ---- outlier.hip
 int stage_outlier(cd_context* c, int F, int max_no, int* map_pitch);
 // ---- surface.hip

@@ -328,7 +328,7 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
     HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)std::max(n, 1), hipMemcpyDeviceToDevice, c->stream));
     const int off0 = 0;
     set_icp_clusters(c, 0, 1, 0, &n, &off0, 0, slot);
-    st = stage_icp(c, 1, p, nullptr);
+    st = stage_icp_levels(c, 1, p, nullptr);
     if (st) return st;
     fill_cluster_result(c, 0, p, out);
     out->template_slot = slot;
@@ -336,6 +336,13 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
         std::vector<float4> tmp((size_t)n);
         HIPCHK(c, copy_sync(c, tmp.data(), c->d_src, sizeof(float4) * n, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) { aligned[3 * i] = tmp[i].x; aligned[3 * i + 1] = tmp[i].y; aligned[3 * i + 2] = tmp[i].z; }
+    }
+    if (c->coarse_stride != 0) {   // rule C18: the pair's stats for cd_get_cluster_coarse_stats (frame 0, index 0; before the return of a singular stop below)
+        cd_icp_coarse_stats cs;
+        std::memcpy(&cs, &c->h_cstat[0], sizeof(cs));
+        c->last_coarse.assign(1, cs);
+        c->last_coarse_first.assign({0, 1});
+        c->last_coarse_ok = true;
     }
     if (c->plane_weight != 0.0) {   // rule C17: the pair's counters for cd_get_cluster_plane_stats (frame 0, index 0); a singular stop
         cd_icp_plane_stats ps;

@@ -30,6 +30,9 @@ struct IcpPlanInput {
     const float* frame_guess = nullptr;  // the per-frame guesses in force (cd_set_frame_guesses', or - CD_GUESS_SURFACE - the call's own), 16 per frame
     size_t frame_guess_len = 0;          // floats
     const float* icp_guess = nullptr;    // cd_params::icp_guess, the single guess
+    bool device_guesses = false;         // rule C18's fine stage: a kernel of the caller's writes one guess per problem on the device
+                                         // (d_guess[16 k], Tfinal of d_st) after the states are up; the call's own guess is what a
+                                         // problem it leaves alone starts from
 };
 
 struct PlanStatus { int code; const char* msg; };   // CD_OK, or what the caller fails the call with
@@ -57,6 +60,7 @@ struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
     bool pre_zeroed = false;                     // (icp_setup) d_acc / d_accf / d_queue were zeroed by the fused call
     bool crowded = false;                        // (icp_params) four or more batches in flight on the device
     bool plane = false;                          // rule C17 (cd_set_icp_plane_weight): every live cluster takes k_icp_plane
+    bool device_guesses = false;                 // (IcpPlanInput::device_guesses) the sources are moved per problem, whatever the guess mode
 };
 
 // Clusters in.cl[0..ncl) -> plan; fills the work list `work`, tile0 of every cluster and the initial states st[0 .. 2 * ncl).
@@ -68,11 +72,13 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
     // (CD_GUESS_SURFACE is CD_GUESS_PER_FRAME with the guesses the call derived itself)
     const int guess_mode = pl->guess_mode = in.icp_use_guess == CD_GUESS_SURFACE ? CD_GUESS_PER_FRAME : in.icp_use_guess;
     pl->frame_guess = in.frame_guess;
-    if (guess_mode != CD_GUESS_NONE) {
+    pl->device_guesses = in.device_guesses;
+    if (guess_mode != CD_GUESS_NONE || in.device_guesses) {
         int max_frame = 0;
         for (int k = 0; k < ncl; ++k) { pl->max_n = std::max(pl->max_n, in.cl[k].n); max_frame = std::max(max_frame, in.cl[k].frame); }
         pl->guess_need = guess_mode == CD_GUESS_PER_FRAME ? 16 * ((size_t)max_frame + 1) : (guess_mode == CD_GUESS_CLUSTER ? 16 * (size_t)ncl : 16);
         if (guess_mode == CD_GUESS_PER_FRAME && in.frame_guess_len < pl->guess_need) return PlanStatus{CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_PER_FRAME but cd_set_frame_guesses holds fewer frames than the batch"};
+        if (in.device_guesses) pl->guess_need = 16 * (size_t)ncl;   // (the device table replaces the upload)
     }
     // queries per workgroup: 512 when the batch fills the chip, smaller slices (more workgroups) otherwise
     long long qtot = 0;
@@ -141,7 +147,7 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
     // A stage whose clusters ALL take k_icp_lat (the default template, no initial guess): the kernel reads the cluster list, the
     // order and the initial states from the pinned host arrays and writes the final states and fitness sums there - a few
     // hundred bytes per cluster once at each end of its ICP - instead of three copy launches around it.
-    pl->lat_direct = tun.icp_direct && pl->n_lat > 0 && pl->n_lat == pl->n_live && guess_mode == CD_GUESS_NONE && tun.mirror_reads && tun.mirror_writes && tun.copy_kernels;
+    pl->lat_direct = tun.icp_direct && pl->n_lat > 0 && pl->n_lat == pl->n_live && guess_mode == CD_GUESS_NONE && !in.device_guesses && tun.mirror_reads && tun.mirror_writes && tun.copy_kernels;
     // Batch mode: with at least ~n_cu/5 clusters every CU can own whole clusters, so each cluster runs its
     // complete ICP (all iterations + fitness) inside one persistent workgroup, one launch for the batch.
     // The pipelined variant (two to four clusters in flight per workgroup, no barrier in the iteration loop) needs one
@@ -161,6 +167,8 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
 
 // which guess k_icp_apply_guess moves problem k by: the only one, its frame's, its own
 inline int guess_indexing(int guess_mode) { return guess_mode == CD_GUESS_PER_FRAME ? 1 : (guess_mode == CD_GUESS_CLUSTER ? 2 : 0); }
+// ... of a planned stage: its own with guesses written per problem on the device (IcpPlanInput::device_guesses); -1: the sources stay
+inline int guess_indexing(const IcpPlan& pl) { return pl.device_guesses ? 2 : (pl.guess_mode == CD_GUESS_NONE ? -1 : guess_indexing(pl.guess_mode)); }
 
 // the cluster order of every queue-fed launch: order[0..no) sorted largest first, equal sizes in the order they came in
 inline void largest_first(int* order, int no, const IcpCluster* cl) {

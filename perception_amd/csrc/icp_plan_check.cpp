@@ -2,6 +2,8 @@
 //   icp_plan_check case.txt
 // case.txt describes one ICP stage, one statement per line (tests/test_icp_plan_cpu.py writes it):
 //   n_cu N | work_cap N | plane_on 0/1 | use_guess MODE | guess_frames N | batches_in_flight N | calls_in_flight N
+//   device_guesses 0/1                  IcpPlanInput::device_guesses (rule C18's fine stage); when the statement is there the plan
+//                                       also prints "device_guesses" and "moved_by" (guess_indexing of the plan)
 //   tun NAME VALUE [VALUE VALUE]        a field of Tunables (lat_shape takes three values)
 //   slot S FACES GRIDDED BIG            tpl_faces / tpl_gridded / tpl_big of template slot S
 //   cluster N FRAME TPL_OFF TPL_M SLOT  one IcpCluster, in order
@@ -50,7 +52,7 @@ int main(int argc, char** argv) {
     std::vector<IcpCluster> cl;
     std::vector<std::pair<int, int>> done;
     std::vector<std::string> queries;
-    int n_cu = 256, work_cap = 1 << 16, plane_on = 0, use_guess = CD_GUESS_NONE, guess_frames = 0, batches = 1, calls = 1;
+    int n_cu = 256, work_cap = 1 << 16, plane_on = 0, use_guess = CD_GUESS_NONE, guess_frames = 0, batches = 1, calls = 1, device_guesses = -1;
     std::string line;
     while (std::getline(file, line)) {
         std::istringstream ss(line);
@@ -64,6 +66,7 @@ int main(int argc, char** argv) {
         else if (key == "guess_frames") ok = (bool)(ss >> guess_frames);
         else if (key == "batches_in_flight") ok = (bool)(ss >> batches);
         else if (key == "calls_in_flight") ok = (bool)(ss >> calls);
+        else if (key == "device_guesses") ok = (bool)(ss >> device_guesses) && (device_guesses == 0 || device_guesses == 1);
         else if (key == "tun") { std::string name; ok = (bool)(ss >> name) && set_tunable(tun, name, ss); }
         else if (key == "slot") {
             int s = -1, faces = 0, gridded = 0, big = 0;
@@ -96,6 +99,7 @@ int main(int argc, char** argv) {
         in.icp_use_guess = use_guess;
         in.frame_guess = frame_guess.data(); in.frame_guess_len = frame_guess.size();
         in.icp_guess = icp_guess;
+        if (device_guesses >= 0) in.device_guesses = device_guesses != 0;
         // (one item past the capacity, so that a planner that overruns it is caught by the sanitizer build and not by luck)
         std::vector<IcpWork> work((size_t)std::max(work_cap, 0) + 1);
         std::vector<IcpState> st(2 * (size_t)ncl);
@@ -107,6 +111,7 @@ int main(int argc, char** argv) {
                         "\"icp_search\": %d, \"nwork\": %d, \"wg_cap\": %d, \"grouped_pipe\": %d, \"lat_direct\": %d, \"pipe_ok\": %d, \"big_ok\": %d, \"whole_cluster\": %d, \"plane\": %d, ",
                         pl.ncl, pl.guess_mode, pl.max_n, pl.qslice, pl.guess_need, pl.n_lat, pl.n_live, pl.lat_max_n, pl.icp_search, pl.nwork, pl.wg_cap,
                         (int)pl.grouped_pipe, (int)pl.lat_direct, (int)pl.pipe_ok, (int)pl.big_ok, (int)pl.whole_cluster, (int)pl.plane);
+            if (device_guesses >= 0) std::printf("\"device_guesses\": %d, \"moved_by\": %d, ", (int)pl.device_guesses, guess_indexing(pl));
             std::vector<int> v;
             for (char x : pl.in_lat) v.push_back(x);
             print_ints("in_lat", v.data(), (int)v.size());

@@ -12,7 +12,7 @@
 namespace {
 
 // plan_icp over the context: the clusters h_cl[0..ncl) -> plan; fills h_work, tile0 of every cluster and the initial states h_st
-int plan_stage(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
+int plan_stage(cd_context* c, int ncl, const cd_params* p, bool device_guesses, IcpPlan* pl) {
     IcpPlanInput in;
     in.cl = c->h_cl; in.ncl = ncl;
     in.tpl_faces = c->tpl_faces; in.tpl_gridded = c->tpl_gridded; in.tpl_big = c->tpl_big;
@@ -22,6 +22,7 @@ int plan_stage(cd_context* c, int ncl, const cd_params* p, IcpPlan* pl) {
     const std::vector<float>& fg = p->icp_use_guess == CD_GUESS_SURFACE ? c->surface_guess : c->frame_guess;
     in.frame_guess = fg.data(); in.frame_guess_len = fg.size();
     in.icp_guess = p->icp_guess;
+    in.device_guesses = device_guesses;   // rule C18's fine stage (stage_icp_levels)
     const PlanStatus ps = plan_icp(in, pl, c->h_work, c->h_st);
     if (pl->icp_search >= 0) c->timing.icp_search = pl->icp_search;
     return ps.code == CD_OK ? CD_OK : fail(c, ps.code, ps.msg);
@@ -52,16 +53,25 @@ int launch_cluster_guesses(cd_context* c, int ncl) {
     return CD_OK;
 }
 
+// Rule C18, the fine stage (plan.device_guesses): per problem T_c or the call's own guess into d_guess and Tfinal of d_st, from the
+// tables stage_icp_levels has put on the stream; the stats follow to their mirror (on the host by the stage's final synchronisation)
+int launch_coarse_handover(cd_context* c, int ncl) {
+    static_assert(sizeof(CoarseStats) == sizeof(cd_icp_coarse_stats), "CoarseStats mirrors cd_icp_coarse_stats");
+    LAUNCH(c, launch_icp_coarse_handover(c->stream, ncl, c->d_chand, c->d_cst, c->d_caccf, c->d_st, c->d_guess, c->d_cstat));
+    HIPCHK(c, xfer(c, c->h_cstat, c->d_cstat, sizeof(CoarseStats) * (size_t)ncl, hipMemcpyDeviceToHost));
+    return CD_OK;
+}
+
 // the stream operations every driver needs before the stage's start event: guess, cluster list, work list, initial states,
 // zeroed sums, guess applied to the sources
 int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
-    const int ncl = pl->ncl;
-    if (pl->guess_mode != CD_GUESS_NONE) {
+    const int ncl = pl->ncl, moved_by = guess_indexing(*pl);
+    if (moved_by >= 0) {
         GROW(c, d_guess, pl->guess_need);
         if (pl->guess_mode == CD_GUESS_CLUSTER) {   // (the guesses are written on the device; the records' buffers before anything is on the stream)
             GROW(c, d_shape, (size_t)ncl); GROW(c, h_shape, (size_t)ncl);
             GROW(c, d_tframe, (size_t)CD_MAX_TEMPLATES); GROW(c, h_tframe, (size_t)CD_MAX_TEMPLATES);
-        } else
+        } else if (!pl->device_guesses)
             HIPCHK(c, copy_sync(c, c->d_guess, pl->guess_mode == CD_GUESS_PER_FRAME ? pl->frame_guess : p->icp_guess, sizeof(float) * pl->guess_need, hipMemcpyHostToDevice));
     }
     if (!pl->lat_direct) {
@@ -86,8 +96,10 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         if (int e = launch_cluster_guesses(c, ncl)) return e;
         HIPCHK(c, xfer(c, c->h_shape, c->d_shape, sizeof(ShapeFrame) * (size_t)ncl, hipMemcpyDeviceToHost));   // (on the host by the stage's final synchronisation)
     }
-    if (pl->guess_mode != CD_GUESS_NONE)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, guess_indexing(pl->guess_mode), c->d_src0, c->d_src));
+    if (pl->device_guesses)   // rule C18: after the d_st upload and rule C13's guesses, which a problem that falls back keeps
+        if (int e = launch_coarse_handover(c, ncl)) return e;
+    if (moved_by >= 0)   // input_transformed = guess * source (d_src is a copy of d_src0 at this point)
+        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl->max_n, c->d_cl, c->d_guess, moved_by, c->d_src0, c->d_src));
     return CD_OK;
 }
 
@@ -340,8 +352,10 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Ic
     HIPCHK(c, hipMemcpyAsync(c->d_src, c->d_src0, sizeof(float4) * (size_t)span, hipMemcpyDeviceToDevice, c->stream));
     if (pl.guess_mode == CD_GUESS_CLUSTER)   // (the states just uploaded start from the identity again)
         if (int e = launch_cluster_guesses(c, ncl)) return e;
-    if (pl.guess_mode != CD_GUESS_NONE)
-        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl.max_n, c->d_cl, c->d_guess, guess_indexing(pl.guess_mode), c->d_src0, c->d_src));
+    if (pl.device_guesses)
+        if (int e = launch_coarse_handover(c, ncl)) return e;
+    if (guess_indexing(pl) >= 0)
+        LAUNCH(c, launch_icp_apply_guess(c->stream, ncl, pl.max_n, c->d_cl, c->d_guess, guess_indexing(pl), c->d_src0, c->d_src));
     return CD_OK;
 }
 
@@ -378,14 +392,15 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
 }  // namespace
 
 namespace cd {
-// S6.  clusters described by h_cl[0..ncl) (src_off relative to d_src/d_src0).  Fills h_st / h_accf.
-int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests) {
+// S6.  clusters described by h_cl[0..ncl) (src_off relative to d_src/d_src0).  Fills h_st / h_accf.  device_guesses: the fine
+// stage of rule C18 - its set-up runs the hand-over from the tables stage_icp_levels has put on the stream.
+int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests, bool device_guesses) {
     c->timing.icp_kernel_launches = 0;
     c->timing.icp_kernel_ms = 0.f;
     if (pair_tests) *pair_tests = 0;
     if (ncl <= 0) return CD_OK;
     IcpPlan pl;
-    int st = plan_stage(c, ncl, p, &pl);
+    int st = plan_stage(c, ncl, p, device_guesses, &pl);
     if (!st) st = icp_setup(c, p, &pl);
     if (st) return st;
     const IcpParams ip = icp_params(c, p, &pl.crowded);
@@ -400,6 +415,62 @@ int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests)
     if (!st && !done) st = icp_run_sliced(c, pl, a, ip, &done);
     if (done) icp_finish(c, ncl, pair_tests);
     return st;
+}
+
+// Rule C18.  Both levels are ordinary stages: the coarse one over the subsamples gathered behind the stage's
+// clusters, then - its states, fitness sums and the hand-over table on the stream - the stage itself with per-problem guesses.
+// stage_icp fills h_cl / h_st / h_accf from index 0, so what the coarse stage left there is copied out before the fine stage
+// starts, and the stage's own problem list is kept aside meanwhile.  No device or pinned pointer is held across a stage.
+int stage_icp_levels(cd_context* c, int ncl, const cd_params* p, long long* pair_tests) {
+    if (c->coarse_stride == 0 || ncl <= 0) return stage_icp(c, ncl, p, pair_tests);
+    const size_t cap = std::min(std::min(c->d_src0.capacity(), c->d_src.capacity()), std::min(c->d_nn.capacity(), c->d_d2.capacity()));
+    CoarsePlan cp;
+    if (plan_coarse(c->h_cl, ncl, c->coarse_stride, c->coarse_min, (long long)cap, &cp) != CD_OK)
+        return fail(c, CD_ERR_CAPACITY, "coarse-to-fine ICP: the coarse sets do not fit behind the stage's clusters in the ICP source buffers");
+    GROW(c, h_cstat, (size_t)ncl);
+    if (cp.n_eligible == 0) {   // an ordinary stage, stream operation for stream operation; its stats say "not eligible"
+        std::memset(c->h_cstat.get(), 0, sizeof(CoarseStats) * (size_t)ncl);
+        return stage_icp(c, ncl, p, pair_tests);
+    }
+    const int nc = cp.n_eligible;
+    GROW(c, d_cstat, (size_t)ncl); GROW(c, d_chand, (size_t)ncl); GROW(c, h_chand, (size_t)ncl);
+    GROW(c, d_cgather, (size_t)nc); GROW(c, h_cgather, (size_t)nc);
+    GROW(c, d_cst, (size_t)nc); GROW(c, h_cst, (size_t)nc); GROW(c, d_caccf, (size_t)nc); GROW(c, h_caccf, (size_t)nc);
+    const std::vector<IcpCluster> fine(c->h_cl.get(), c->h_cl.get() + ncl);
+    // the coarse level
+    std::memcpy(c->h_cgather.get(), cp.gather.data(), sizeof(CoarseGather) * (size_t)nc);
+    HIPCHK(c, xfer(c, c->d_cgather, c->h_cgather, sizeof(CoarseGather) * (size_t)nc, hipMemcpyHostToDevice));
+    LAUNCH(c, launch_icp_coarse_gather(c->stream, nc, cp.max_n_coarse, c->d_cgather, c->d_src0, c->d_src));
+    std::memcpy(c->h_cl.get(), cp.coarse.data(), sizeof(IcpCluster) * (size_t)nc);
+    long long pairs_c = 0;
+    // (icp_wave_ms is written by the lattice driver only and stage_icp leaves it alone otherwise: each level's own value is read
+    // from zero, and what was there stays when neither level writes it)
+    const float wave_before = c->timing.icp_wave_ms;
+    c->timing.icp_wave_ms = 0.f;
+    int st = stage_icp(c, nc, p, &pairs_c);   // (ends synchronised)
+    const int launches_c = c->timing.icp_kernel_launches;
+    const float ms_c = c->timing.icp_kernel_ms, wave_c = c->timing.icp_wave_ms;
+    c->timing.icp_wave_ms = st ? wave_before : 0.f;
+    for (int j = 0; j < nc && !st; ++j) { c->h_cst[j] = c->h_st[2 * j]; c->h_caccf[j] = c->h_accf[j]; }
+    std::memcpy(c->h_cl.get(), fine.data(), sizeof(IcpCluster) * (size_t)ncl);
+    if (st) return st;
+    // the hand-over and the fine level
+    std::memcpy(c->h_chand.get(), cp.hand.data(), sizeof(CoarseHand) * (size_t)ncl);
+    {
+        XferBatch xb(c);   // (one launch)
+        xb.add(c->d_cst, c->h_cst, sizeof(IcpState) * (size_t)nc, hipMemcpyHostToDevice);
+        xb.add(c->d_caccf, c->h_caccf, sizeof(unsigned long long) * (size_t)nc, hipMemcpyHostToDevice);
+        xb.add(c->d_chand, c->h_chand, sizeof(CoarseHand) * (size_t)ncl, hipMemcpyHostToDevice);
+        HIPCHK(c, xb.flush());
+    }
+    st = stage_icp(c, ncl, p, pair_tests, /*device_guesses=*/true);
+    if (st) return st;
+    c->timing.icp_kernel_launches += launches_c + 2;   // (the gather and the hand-over)
+    c->timing.icp_kernel_ms += ms_c;
+    const float wave = wave_c + c->timing.icp_wave_ms;
+    c->timing.icp_wave_ms = wave > 0.f ? wave : wave_before;
+    if (pair_tests) *pair_tests += pairs_c;
+    return CD_OK;
 }
 
 void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_cluster_result* r) {

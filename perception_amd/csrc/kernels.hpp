@@ -127,6 +127,15 @@ struct PlaneParams;
 void launch_icp_plane(hipStream_t s, int nitems, int n_wg, const IcpProblems& P, PlaneStats* pstat, const IcpTemplates& T, const IcpScratch& S,
                       IcpParams prm, const IcpBound& bnd, const PlaneParams& pp);
 
+// k_icp_coarse.hip : rule C18, the subsample before the coarse stage and the hand-over inside the fine stage's set-up
+// (icp_coarse_plan.hpp: CoarseGather, CoarseHand, CoarseStats)
+struct CoarseGather;
+struct CoarseHand;
+struct CoarseStats;
+void launch_icp_coarse_gather(hipStream_t s, int n_coarse_problems, int max_n_coarse, const CoarseGather* tab, float4* src0, float4* src);
+void launch_icp_coarse_handover(hipStream_t s, int ncl, const CoarseHand* hand, const IcpState* cst, const unsigned long long* caccf, IcpState* st,
+                                float* guess, CoarseStats* stats);
+
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
 // records x y z rgb (canonical rule C7)
 struct DeprojectParams {
