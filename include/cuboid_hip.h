@@ -988,6 +988,49 @@ int cd_icp_coarse_subsample(int n, int stride, int min_points, int32_t* out_indi
  * been invalidated by another compute call, or had no such frame. */
 int cd_get_cluster_coarse_stats(const cd_context* ctx, int frame, int first, int count, cd_icp_coarse_stats* out);
 
+/* Median-distance correspondence rejection inside the ICP: opt-in, off by default.  Canonical rule C19;
+ * perception_amd/icp_reject.py is the rule in numpy and the device equals it bit for bit.  It restates
+ * pcl::registration::CorrespondenceRejectorMedianDistance as added by IterativeClosestPoint::addCorrespondenceRejector
+ * (nth_element at size / 2 over the squared distances, keep <= median * factor, after the correspondence estimation's own
+ * bound); parity with a real PCL is unpinned.  It changes results: the step is estimated from fewer correspondences.
+ * With a factor f set, every ICP iteration takes its correspondences by rule C5; rule C8's bound leaves the set K0 (every point
+ * when it bounds nothing).  Then
+ *   1. |K0| < 3 stops the ICP as rule C8 does (T = identity, converged = 0, Tfinal and iterations as they were);
+ *   2. m = the float32 d2 of rank floor(|K0| / 2) (0-based, ascending) over K0: the upper median, nothing averaged;
+ *   3. thr = (double) m * f, one rounded double product;
+ *   4. a correspondence of K0 is kept iff (double) d2 <= thr;
+ *   5. fewer than three kept: the stop of step 1;
+ *   6. the 16 moment sums of rule C4, the MSE of the convergence tests and the solve's n are over the kept ones only.
+ * X <- T X moves every point, getFitnessScore() is over all points and unbounded, `accepted`, the pose and the order of the
+ * convergence tests are untouched.
+ *
+ * cd_set_icp_median_rejection: context state, as the correspondence distance is; applies to every ICP of the following cd_icp and
+ * fused calls, the coarse level of rule C18 included.  factor == 0 turns the mode off (the default: every record, launch and
+ * kernel is what it was); otherwise a finite factor > 0.  NaN, a negative value or an infinity: CD_ERR_INVALID_ARG and the
+ * setting stays.  With the mode on every live cluster goes to the mode's own driver (the sliced loop with k_icp_reject behind
+ * every iteration); CUBOID_ICP_LATTICE / CUBOID_ICP_MODE do not apply.  Together with plane-weighted ICP (rule C17) every ICP
+ * entry point returns CD_ERR_INVALID_ARG before anything is launched.  In cd_icp a stop returns CD_ERR_FEW_CORRESPONDENCES with
+ * out filled, as under rule C8; in a batch it is a result, the frame stays CD_OK. */
+typedef struct cd_icp_reject_stats {
+    int32_t first_kept;     /* correspondences the first iteration kept                                              */
+    int32_t last_kept;      /* ... the last iteration that looked for correspondences kept                           */
+    int32_t min_kept;       /* the least any iteration kept                                                          */
+    int32_t stopped_few;    /* 1: the ICP stopped with fewer than three (step 1 or step 5)                           */
+    float last_median;      /* m of the last iteration that took one (step 2); 0 when none did                       */
+    int32_t reserved[3];
+} cd_icp_reject_stats;
+int cd_set_icp_median_rejection(cd_context* ctx, double factor);
+int cd_get_icp_median_rejection(const cd_context* ctx, double* factor);
+int cd_icp_reject_struct_size(void);   /* sizeof(cd_icp_reject_stats) (cd_struct_size's list is closed) */
+/* Indexed like cd_get_cluster_results (the stats of the template whose result the cluster kept); after a stand-alone cd_icp
+ * the result is at frame 0, index 0.  A cluster that was never run (fewer than three points) has zeros.  Returns the number
+ * copied; CD_ERR_INVALID_ARG when the call ran with the mode off, has been invalidated by another compute call, or had no such
+ * frame. */
+int cd_get_cluster_reject_stats(const cd_context* ctx, int frame, int first, int count, cd_icp_reject_stats* out);
+/* Host only (no context, no GPU): steps 2 and 3 over the n >= 1 squared distances of K0 (non-negative, +inf allowed; a NaN or a
+ * signed value gives CD_ERR_INVALID_ARG, as does a factor the setter would refuse or 0).  median and thr may be NULL. */
+int cd_icp_median_threshold(const float* d2, int n, double factor, float* median, double* thr);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "cd_set_outlier_filter", "cd_get_outlier_filter", "cd_get_outlier_stats", "cd_outlier_filter",
     "cd_set_icp_plane_weight", "cd_get_icp_plane_weight", "cd_get_cluster_plane_stats", "cd_icp_plane_solve_host",
     "cd_set_icp_coarse", "cd_get_icp_coarse", "cd_icp_coarse_struct_size", "cd_icp_coarse_subsample", "cd_get_cluster_coarse_stats",
+    "cd_set_icp_median_rejection", "cd_get_icp_median_rejection", "cd_icp_reject_struct_size", "cd_get_cluster_reject_stats",
+    "cd_icp_median_threshold",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
@@ -87,6 +89,12 @@ class CdIcpCoarseStats(C.Structure):
     """cd_icp_coarse_stats: what rule C18 did for one (cluster, template) pair."""
     _fields_ = [("n_coarse", C.c_int32), ("coarse_iterations", C.c_int32), ("coarse_converged", C.c_int32), ("coarse_status", C.c_int32),
                 ("coarse_fitness", C.c_double), ("used", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CdIcpRejectStats(C.Structure):
+    """cd_icp_reject_stats: what rule C19 did for one (cluster, template) pair."""
+    _fields_ = [("first_kept", C.c_int32), ("last_kept", C.c_int32), ("min_kept", C.c_int32), ("stopped_few", C.c_int32),
+                ("last_median", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
 class CdShapeFrame(C.Structure):
@@ -491,6 +499,11 @@ def load_library(path=None):
     lib.cd_icp_coarse_struct_size.argtypes = []
     lib.cd_icp_coarse_subsample.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.cd_get_cluster_coarse_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_set_icp_median_rejection.argtypes = [vp, C.c_double]
+    lib.cd_get_icp_median_rejection.argtypes = [vp, dp]
+    lib.cd_icp_reject_struct_size.argtypes = []
+    lib.cd_get_cluster_reject_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_icp_median_threshold.argtypes = [vp, C.c_int, C.c_double, vp, dp]
     if path is None:
         _lib = lib
     return lib
@@ -1004,6 +1017,27 @@ class Context:
             raise CuboidError(got, "no coarse-to-fine call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
         return [out[i] for i in range(got)]
 
+    def set_icp_median_rejection(self, factor):
+        """Rule C19, median-distance correspondence rejection, for every later ICP of this context: an iteration keeps the
+        correspondences whose squared distance is at most factor times the upper median.  factor = 0 (or None): off, the default."""
+        self._check(self.lib.cd_set_icp_median_rejection(self.h, 0.0 if factor is None else float(factor)))
+
+    def icp_median_rejection(self):
+        """The factor as cd_set_icp_median_rejection left it; 0: off."""
+        f = C.c_double()
+        self._check(self.lib.cd_get_icp_median_rejection(self.h, C.byref(f)))
+        return f.value
+
+    def cluster_reject_stats(self, frame, first=0, count=None):
+        """Rule C19's stats of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
+        cluster_results: a list of CdIcpRejectStats."""
+        cap = 4096 if count is None else int(count)
+        out = (CdIcpRejectStats * max(cap, 1))()
+        got = self.lib.cd_get_cluster_reject_stats(self.h, frame, first, cap, C.byref(out))
+        if got < 0:
+            raise CuboidError(got, "no median-rejection call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
+        return [out[i] for i in range(got)]
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1179,6 +1213,17 @@ def icp_coarse_subsample(n, stride, min_points, capacity=None):
     if got > capacity:
         return got, None
     return out[:got].copy()
+
+
+def icp_median_threshold(d2, factor):
+    """Host-only rule C19, steps 2 and 3: (m float32, thr float64) of the squared distances of K0."""
+    lib = load_library()
+    a = np.ascontiguousarray(d2, np.float32).reshape(-1)
+    m, t = C.c_float(), C.c_double()
+    st = lib.cd_icp_median_threshold(_ptr(a), len(a), float(factor), C.byref(m), C.byref(t))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_icp_median_threshold")
+    return np.float32(m.value), np.float64(t.value)
 
 
 def icp_plane_solve_host(sums, n):

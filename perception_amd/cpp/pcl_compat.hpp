@@ -324,6 +324,21 @@ private:
     typename PointCloud<PointT>::ConstPtr in_;
 };
 
+// pcl::registration::CorrespondenceRejectorMedianDistance, for IterativeClosestPoint::addCorrespondenceRejector below: the
+// library's rule C19 (cd_set_icp_median_rejection) - correspondences whose squared distance exceeds factor x the median are left
+// out of the iteration's estimate.  PCL's default factor is 1.
+namespace registration {
+class CorrespondenceRejectorMedianDistance {
+public:
+    using Ptr = std::shared_ptr<CorrespondenceRejectorMedianDistance>;
+    using ConstPtr = std::shared_ptr<const CorrespondenceRejectorMedianDistance>;
+    void setMedianFactor(double factor) { factor_ = factor; }
+    double getMedianFactor() const { return factor_; }
+private:
+    double factor_ = 1.0;
+};
+}  // namespace registration
+
 // icp.cpp:170-182 / opd.cpp:220-235: pcl::IterativeClosestPoint<PointXYZ,PointXYZ>
 template <class PointSource, class PointTarget>
 class IterativeClosestPoint {
@@ -353,6 +368,11 @@ public:
     // registers every stride-th point, then all points from that pose; stride 0 = off, the default.  Handed to the shared context
     // before each ICP like the two above.
     void setCoarseToFine(int stride, int min_points) { coarse_s_ = stride; coarse_m_ = min_points; }
+    // pcl::Registration::addCorrespondenceRejector for the one rejector the library implements (rule C19); its factor is read at
+    // each align(), as PCL reads the rejector it holds.  Handed to the shared context before each ICP like the settings above; a
+    // factor the library refuses (0, negative, not finite) fails the align() with its message.
+    void addCorrespondenceRejector(const registration::CorrespondenceRejectorMedianDistance::Ptr& rejector) { rejector_ = rejector; }
+    void clearCorrespondenceRejectors() { rejector_.reset(); }
     // align(output, guess): pcl::Registration's second overload (row-major 4x4, scene -> template)
     void align(PointCloud<PointSource>& output, const Matrix4& guess) {
         prm_.icp_use_guess = CD_GUESS_PARAMS;
@@ -370,7 +390,9 @@ public:
         cd_cluster_result r;
         if (cd_set_icp_max_correspondence_distance(Device::instance().ctx(), max_corr_) != CD_OK ||
             cd_set_icp_plane_weight(Device::instance().ctx(), plane_w_, plane_d_) != CD_OK ||
-            cd_set_icp_coarse(Device::instance().ctx(), coarse_s_, coarse_m_) != CD_OK) {
+            cd_set_icp_coarse(Device::instance().ctx(), coarse_s_, coarse_m_) != CD_OK ||
+            (rejector_ && !(rejector_->getMedianFactor() != 0.0)) ||   // (0 would turn the mode off silently: a rejector that is installed rejects)
+            cd_set_icp_median_rejection(Device::instance().ctx(), rejector_ ? rejector_->getMedianFactor() : 0.0) != CD_OK) {
             std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx()));
             return;
         }
@@ -398,6 +420,7 @@ private:
     double max_corr_ = std::sqrt(std::numeric_limits<double>::max());
     double plane_w_ = 0.0, plane_d_ = CD_ICP_PLANE_SWITCH_DEFAULT;
     int coarse_s_ = 0, coarse_m_ = 0;
+    registration::CorrespondenceRejectorMedianDistance::Ptr rejector_;
     typename PointCloud<PointSource>::ConstPtr src_;
     typename PointCloud<PointTarget>::ConstPtr tgt_;
     Matrix4 final_;

@@ -186,6 +186,7 @@ void begin_batch_icp(cd_context* c, const cd_params* p, int F, const BatchCluste
     bi->al_off.assign((size_t)std::max(cl.ncl, 1), -1);
     if (c->plane_weight != 0.0) c->last_plane.assign((size_t)std::max(cl.ncl, 1), cd_icp_plane_stats());   // rule C17: the kept result's counters
     if (c->coarse_stride != 0) c->last_coarse.assign((size_t)std::max(cl.ncl, 1), cd_icp_coarse_stats());   // rule C18: the kept result's stats
+    if (c->reject_factor != 0.0) c->last_reject.assign((size_t)std::max(cl.ncl, 1), cd_icp_reject_stats());   // rule C19: the kept result's stats
     for (int f = 0; f < F; ++f)
         for (int q = cl.first[(size_t)f]; q < cl.first[(size_t)f + 1]; ++q) bi->orig_off[(size_t)q] = (long long)f * c->N + cl.off[(size_t)q];
 }
@@ -211,6 +212,7 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
     c->last_clusters[(size_t)k] = r;
     if (c->plane_weight != 0.0) std::memcpy(&c->last_plane[(size_t)k], &c->h_pstat[q], sizeof(cd_icp_plane_stats));
     if (c->coarse_stride != 0) std::memcpy(&c->last_coarse[(size_t)k], &c->h_cstat[q], sizeof(cd_icp_coarse_stats));
+    if (c->reject_factor != 0.0) std::memcpy(&c->last_reject[(size_t)k], &c->h_rstat[q], sizeof(cd_icp_reject_stats));
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
 }
 
@@ -290,6 +292,8 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     if (c->last_plane_ok) c->last_plane_first = cl.first;
     c->last_coarse_ok = c->coarse_stride != 0;
     if (c->last_coarse_ok) c->last_coarse_first = cl.first;
+    c->last_reject_ok = c->reject_factor != 0.0;
+    if (c->last_reject_ok) c->last_reject_first = cl.first;
     if (c->last_shapes_ok && cl.ncl == 0) c->last_shapes.clear();
 }
 
@@ -383,6 +387,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     int st = check_params(c, p);
     if (!st) st = check_bbox_source(c, p, F, dj && dj->color);
     if (!st) st = check_plane_templates(c, p->template_slot);   // rule C17: lattice templates only
+    if (!st) st = check_reject_mode(c);                          // rule C19: not together with rule C17
     if (st) return st;
     if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
     if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
@@ -459,6 +464,7 @@ int cd_process_batch_impl(cd_context* c, const void* frames, size_t stride, int 
     const size_t bytes = (size_t)points_per_frame * n_frames * stride;
     int st = check_bbox_source(c, p, n_frames, false);   // (before the upload)
     if (!st && p) st = check_plane_templates(c, p->template_slot);
+    if (!st) st = check_reject_mode(c);
     if (st) return st;
     st = ensure_input(c, bytes);
     if (st) return st;
@@ -477,6 +483,7 @@ int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam, const
     if (st) return st;
     st = check_bbox_source(c, p, n_frames, cam->color == CD_COLOR_RGB8);   // (before the uploads)
     if (!st) st = check_plane_templates(c, p->template_slot);
+    if (!st) st = check_reject_mode(c);
     if (st) return st;
     cd_params q = *p;
     q.rgb_offset = cam->color == CD_COLOR_RGB8 ? 12 : -1;   // the canonical records: x y z rgb, 16 bytes

@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "outlier_math.hpp"
 #include "icp_plane_math.hpp"
+#include "icp_reject_math.hpp"
 #include "icp_coarse_plan.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
@@ -230,6 +231,14 @@ struct cd_context : cd_streams {
     std::vector<cd_icp_coarse_stats> last_coarse;
     std::vector<int> last_coarse_first;
     bool last_coarse_ok = false;
+    // median-distance correspondence rejection (rule C19, k_icp_reject.hip): the setting (cd_set_icp_median_rejection; 0: off), one
+    // record per ICP problem of a stage (device + pinned mirror, grown on demand), and what cd_get_cluster_reject_stats reads, as
+    // last_plane
+    double reject_factor = 0.0;
+    DevBuf<RejectStats> d_rstat; PinBuf<RejectStats> h_rstat;
+    std::vector<cd_icp_reject_stats> last_reject;
+    std::vector<int> last_reject_first;
+    bool last_reject_ok = false;
     cd_timing timing;
 };
 
@@ -275,6 +284,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_outlier_ok = false;
     c->last_plane_ok = false;
     c->last_coarse_ok = false;
+    c->last_reject_ok = false;
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -420,6 +430,8 @@ int check_params(cd_context* c, const cd_params* p);
 // ---- icp_plane.hip (rule C17): with the mode on, a loaded template the call would use (slot >= 0: that one; -1: every loaded one)
 // that is not a lattice fails the call - to be asked before anything is launched
 int check_plane_templates(cd_context* c, int slot);
+// ---- icp_reject.hip (rule C19): the mode cannot be combined with rule C17 - asked where check_plane_templates is
+int check_reject_mode(cd_context* c);
 int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, int rgb_offset, uint32_t pad3, void* out, size_t staging_skip = 0);
 // ---- cuboid_hip.hip
 int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int F, const cd_params* p, int* rounds_out);

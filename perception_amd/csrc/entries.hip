@@ -322,6 +322,7 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
     if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
     if (c->tpl_m[slot] <= 0) return fail(c, CD_ERR_NO_TEMPLATE, "template slot is empty");
     st = check_plane_templates(c, slot);   // rule C17: lattice templates only
+    if (!st) st = check_reject_mode(c);    // rule C19: not together with rule C17
     if (st) return st;
     st = upload_points(c, src_xyz, stride, n, c->d_src0);
     if (st) return st;
@@ -353,8 +354,17 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
         c->last_plane_ok = true;
         if (ps.stopped_singular) return fail(c, CD_ERR_FEW_CORRESPONDENCES, "plane-weighted ICP stopped: the step's system is singular");
     }
-    // rule C8: an ICP that stopped for fewer than three kept correspondences (only a bounded one can: every other ends converged)
-    if (c->h_st[0].status == CD_OK && c->icp_bounded && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;
+    if (c->reject_factor != 0.0) {   // rule C19: the pair's stats for cd_get_cluster_reject_stats (frame 0, index 0)
+        cd_icp_reject_stats rs;
+        std::memset(&rs, 0, sizeof(rs));
+        if (n >= 3) std::memcpy(&rs, &c->h_rstat[0], sizeof(rs));
+        c->last_reject.assign(1, rs);
+        c->last_reject_first.assign({0, 1});
+        c->last_reject_ok = true;
+    }
+    // rules C8 and C19: an ICP that stopped for fewer than three kept correspondences (only a bounded or rejecting one can: every
+    // other ends converged)
+    if (c->h_st[0].status == CD_OK && (c->icp_bounded || c->reject_factor != 0.0) && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;
     return c->h_st[0].status;
 }
 

@@ -1,7 +1,7 @@
 // icp_plan_check.cpp - stand-alone host program (no GPU, no HIP call) around icp_plan.hpp.
 //   icp_plan_check case.txt
 // case.txt describes one ICP stage, one statement per line (tests/test_icp_plan_cpu.py writes it):
-//   n_cu N | work_cap N | plane_on 0/1 | use_guess MODE | guess_frames N | batches_in_flight N | calls_in_flight N
+//   n_cu N | work_cap N | plane_on 0/1 | reject_on 0/1 | use_guess MODE | guess_frames N | batches_in_flight N | calls_in_flight N
 //   device_guesses 0/1                  IcpPlanInput::device_guesses (rule C18's fine stage); when the statement is there the plan
 //                                       also prints "device_guesses" and "moved_by" (guess_indexing of the plan)
 //   tun NAME VALUE [VALUE VALUE]        a field of Tunables (lat_shape takes three values)
@@ -52,7 +52,7 @@ int main(int argc, char** argv) {
     std::vector<IcpCluster> cl;
     std::vector<std::pair<int, int>> done;
     std::vector<std::string> queries;
-    int n_cu = 256, work_cap = 1 << 16, plane_on = 0, use_guess = CD_GUESS_NONE, guess_frames = 0, batches = 1, calls = 1, device_guesses = -1;
+    int n_cu = 256, work_cap = 1 << 16, plane_on = 0, use_guess = CD_GUESS_NONE, guess_frames = 0, batches = 1, calls = 1, device_guesses = -1, reject_on = -1;
     std::string line;
     while (std::getline(file, line)) {
         std::istringstream ss(line);
@@ -67,6 +67,7 @@ int main(int argc, char** argv) {
         else if (key == "batches_in_flight") ok = (bool)(ss >> batches);
         else if (key == "calls_in_flight") ok = (bool)(ss >> calls);
         else if (key == "device_guesses") ok = (bool)(ss >> device_guesses) && (device_guesses == 0 || device_guesses == 1);
+        else if (key == "reject_on") ok = (bool)(ss >> reject_on) && (reject_on == 0 || reject_on == 1);
         else if (key == "tun") { std::string name; ok = (bool)(ss >> name) && set_tunable(tun, name, ss); }
         else if (key == "slot") {
             int s = -1, faces = 0, gridded = 0, big = 0;
@@ -100,6 +101,7 @@ int main(int argc, char** argv) {
         in.frame_guess = frame_guess.data(); in.frame_guess_len = frame_guess.size();
         in.icp_guess = icp_guess;
         if (device_guesses >= 0) in.device_guesses = device_guesses != 0;
+        if (reject_on >= 0) in.reject_on = reject_on != 0;
         // (one item past the capacity, so that a planner that overruns it is caught by the sanitizer build and not by luck)
         std::vector<IcpWork> work((size_t)std::max(work_cap, 0) + 1);
         std::vector<IcpState> st(2 * (size_t)ncl);
@@ -112,6 +114,7 @@ int main(int argc, char** argv) {
                         pl.ncl, pl.guess_mode, pl.max_n, pl.qslice, pl.guess_need, pl.n_lat, pl.n_live, pl.lat_max_n, pl.icp_search, pl.nwork, pl.wg_cap,
                         (int)pl.grouped_pipe, (int)pl.lat_direct, (int)pl.pipe_ok, (int)pl.big_ok, (int)pl.whole_cluster, (int)pl.plane);
             if (device_guesses >= 0) std::printf("\"device_guesses\": %d, \"moved_by\": %d, ", (int)pl.device_guesses, guess_indexing(pl));
+            if (reject_on >= 0) std::printf("\"reject\": %d, ", (int)pl.reject);
             std::vector<int> v;
             for (char x : pl.in_lat) v.push_back(x);
             print_ints("in_lat", v.data(), (int)v.size());

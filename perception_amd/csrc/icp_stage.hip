@@ -1,7 +1,8 @@
 // icp_stage.hip - S6, the ICP stage: stage_icp plans the stage on the host (plan_icp, icp_plan.hpp), issues what every driver
 // needs (icp_setup), then hands the clusters to the drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe
 // launches for several templates, the whole-cluster launch, the persistent launch for a few clusters, and the sliced multi-launch
-// loop for whatever is left (rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs).
+// loop for whatever is left (rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs.
+// Rule C19 on: the sliced loop with k_icp_reject behind every iteration takes every live cluster, likewise).
 // A driver sets *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after
 // it take the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
 // Which driver, and how large its launch: icp_plan.hpp decides, from plain numbers.  Here are the stream operations.
@@ -18,6 +19,7 @@ int plan_stage(cd_context* c, int ncl, const cd_params* p, bool device_guesses, 
     in.tpl_faces = c->tpl_faces; in.tpl_gridded = c->tpl_gridded; in.tpl_big = c->tpl_big;
     in.tun = &c->tun; in.n_cu = c->n_cu; in.work_cap = c->work_cap;
     in.plane_on = c->plane_weight != 0.0;
+    in.reject_on = c->reject_factor != 0.0;
     in.icp_use_guess = p->icp_use_guess;
     const std::vector<float>& fg = p->icp_use_guess == CD_GUESS_SURFACE ? c->surface_guess : c->frame_guess;
     in.frame_guess = fg.data(); in.frame_guess_len = fg.size();
@@ -88,7 +90,7 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1), c->stream));   // (+ the wave-time word of k_icp_lat)
     }
-    if (c->icp_bounded) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3]
+    if (c->icp_bounded || pl->reject) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3] (rule C19: always)
         GROW(c, d_ncorr, 3 * (size_t)ncl);
         HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
     }
@@ -389,6 +391,46 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
     return CD_OK;
 }
 
+// Rule C19 (cd_set_icp_median_rejection): icp_run_sliced's loop over the work list - with the mode on every live cluster has
+// items - with k_icp_reject behind every iteration launch: k_icp_solve<true>(it), k_icp_iter<true>(it), whose sums for the slot
+// k_icp_reject(it) then replaces with those of the kept correspondences.  Always the BOUNDED instantiations, with d2_max = +inf
+// when rule C8 bounds nothing.  Always finishes the stage.
+int icp_run_reject(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const IcpParams& ip, bool* done) {
+    static_assert(sizeof(RejectStats) == sizeof(cd_icp_reject_stats), "RejectStats mirrors cd_icp_reject_stats");
+    const int ncl = pl.ncl, nwork = pl.nwork, max_launch = ip.max_iter + 3;
+    GROW(c, d_rstat, (size_t)ncl); GROW(c, h_rstat, (size_t)ncl);
+    HIPCHK(c, hipMemsetAsync(c->d_rstat, 0, sizeof(RejectStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
+    IcpBound bnd = icp_bound(c);
+    if (!bnd.bounded) bnd.d2_max = std::numeric_limits<float>::infinity();
+    bnd.bounded = 1;
+    int it = 0, nactive = nwork;
+    std::memcpy(c->h_work2, c->h_work, sizeof(IcpWork) * (size_t)std::max(nwork, 1));
+    HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)std::max(nwork, 1), hipMemcpyHostToDevice));
+    for (int polls = 0; nwork > 0 && it < max_launch; ++polls) {
+        const int g = std::min(sliced_poll_group(polls), max_launch - it);
+        for (int q = 0; q < g; ++q, ++it) {
+            LAUNCH(c, launch_icp_iter(c->stream, it, nactive, ncl, c->d_work2, a.dev, a.tpl, a.scr, pl.qslice, c->n_cu, ip, bnd));
+            if (nactive > 0) LAUNCH(c, launch_icp_reject(c->stream, it, ncl, a.dev, a.tpl, a.scr, bnd, c->reject_factor, c->d_rstat));
+        }
+        HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        bool all = false;
+        const int na = repack_active(c->h_work, nwork, c->h_st, ncl, c->h_work2, &all);
+        if (all) break;
+        if (na != nactive) {
+            nactive = na;
+            if (na > 0) HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)na, hipMemcpyHostToDevice));
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));   // (before the fitness pass)
+    c->timing.icp_kernel_launches = it;               // (iteration launches, as the sliced driver counts them)
+    LAUNCH(c, launch_icp_fitness(c->stream, nwork, c->d_work, a.dev, 0, a.tpl, a.scr, pl.qslice));
+    HIPCHK(c, xfer(c, c->h_rstat, c->d_rstat, sizeof(RejectStats) * (size_t)ncl, hipMemcpyDeviceToHost));
+    if (int e = icp_read_back(c, ncl)) return e;
+    *done = true;
+    return CD_OK;
+}
+
 }  // namespace
 
 namespace cd {
@@ -408,6 +450,7 @@ int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests,
     HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
     bool done = false;
     if (pl.plane) st = icp_run_plane(c, pl, a, ip, &done);
+    if (!st && !done && pl.reject) st = icp_run_reject(c, pl, a, ip, &done);
     if (!st && !done && pl.n_lat > 0) st = icp_run_lat(c, pl, a, ip, &done);
     if (!st && !done && pl.grouped_pipe) st = icp_run_grouped(c, pl, a, ip, &done);
     if (!st && !done && pl.whole_cluster) st = icp_run_whole(c, pl, a, ip, &done);

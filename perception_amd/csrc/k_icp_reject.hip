@@ -1,0 +1,139 @@
+// k_icp_reject.hip - S6 with canonical rule C19 (perception_amd/icp_reject.py is the specification): median-distance
+// correspondence rejection, opt-in through cd_set_icp_median_rejection.
+//
+// The mode's driver (icp_run_reject, icp_stage.hip) is the sliced multi-launch loop with this kernel behind every k_icp_iter<true>:
+// the iteration kernel has left every point's neighbour (position in the k-d patch order) and float d2 in d_nn / d_d2, indexed per
+// point, and its own moment sums and count in the iteration's slot; k_icp_reject(it) REPLACES that slot's 16 sums and count with
+// those of the correspondences rule C19 keeps, which k_icp_solve<true>(it + 1) then reads.  No other kernel changes.
+//
+// One workgroup of 256 threads per live, unfinished cluster (finished or pre-marked: it returns at once and touches nothing):
+//   a. the rank floor(|K0| / 2) among the cluster's d2 within rule C8's bound, exactly, whatever the size: four rounds over the
+//      float's bits, 8-bit digits from the top; each round counts its digit in a 256-bin LDS histogram (ds_add_u32, one per
+//      point still matching the prefix) and wave 0 finds the bin that holds the rank - four bins a lane, an inclusive scan across the
+//      64 lanes by shuffles; the one lane whose bins straddle the rank publishes prefix and remaining rank.  Round 0 also yields
+//      |K0|; fewer than three end the selection (the ICP stops).
+//   b. thr = (double) m * factor, one __dmul_rn;
+//   c. one pass over the points: moment_terms of every kept correspondence, added per lane as 64-bit integers, folded per wave
+//      (wave_fold_to_lds) and per workgroup (ds_add_u64) - integer sums, so nothing depends on which lane or wave took which point;
+//   d. plain vector stores: the 16 sums to d_acc[cluster * 3 + it % 3], the count to d_ncorr, the stats record.
+// Five reads of the cluster's d2 (4 bytes a point; L2-resident after the first), one of its points and their template points.
+//
+// Budget: LDS 1168 B (1024 B histogram, 128 B sums, 16 B selection words); 79 VGPRs (16 running sums and 16 terms as 64-bit
+// pairs), 54 SGPRs, no scratch - six waves a SIMD by registers, six workgroups a CU; LDS limits nothing.  No MFMA: nothing here
+// is a contraction.
+#include "common.hpp"
+#include "icp_reject_math.hpp"
+#include "icp_solve.hpp"
+#include "kernels.hpp"
+
+namespace cd {
+
+constexpr int RJ_THREADS = 256;
+static_assert(RJ_THREADS == REJECT_BINS, "one histogram bin per thread when it is cleared");
+static_assert(REJECT_BINS == 4 * WAVE, "four bins per lane of the wave that finds the rank");
+
+__global__ void __launch_bounds__(RJ_THREADS)
+k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restrict__ st, const float4* __restrict__ src,
+             const float4* __restrict__ tplk, const int* __restrict__ nn, const float* __restrict__ d2buf,
+             unsigned long long* __restrict__ acc, IcpBound bnd, double factor, RejectStats* __restrict__ rstat) {
+    __shared__ uint32_t s_hist[REJECT_BINS];
+    __shared__ unsigned long long s_sum[16];
+    __shared__ uint32_t s_sel[4];   // prefix, rank inside it, |K0|, kept
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const IcpCluster c = cl[k];
+    if (c.n < REJECT_MIN_CORR || c.tpl_m <= 0) return;                                             // pre-marked
+    if (st[(size_t)k * 2 + (it & 1)].done || st[(size_t)k * 2 + ((it + 1) & 1)].done) return;      // finished (k_icp_solve(it) has run)
+    const float* d2 = d2buf + c.src_off;
+    if (tid < 16) s_sum[tid] = 0ull;
+    if (tid == 16) s_sel[3] = 0u;
+    // a. the rank
+    uint32_t prefix = 0u, rank = 0u, n0 = 0u;
+    for (int r = 0; r < REJECT_ROUNDS; ++r) {
+        s_hist[tid] = 0u;
+        __syncthreads();
+        for (int i = tid; i < c.n; i += RJ_THREADS) {
+            const float v = d2[i];
+            const uint32_t key = reject_key(v);
+            if (reject_in_k0(v, bnd.d2_max) && reject_in_round(key, prefix, r)) atomicAdd(&s_hist[reject_digit(key, r)], 1u);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const uint32_t h0 = s_hist[4 * lane], h1 = s_hist[4 * lane + 1], h2 = s_hist[4 * lane + 2], h3 = s_hist[4 * lane + 3];
+            const uint32_t tot = (h0 + h1) + (h2 + h3);
+            uint32_t incl = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += up;
+            }
+            const uint32_t total = __shfl(incl, 63, 64);
+            const uint32_t want = r == 0 ? reject_rank(total) : rank;
+            const uint32_t excl = incl - tot;
+            if (r == 0 && lane == 63) s_sel[2] = total;
+            if (want >= excl && want < incl) {   // one lane (none when nothing was counted: |K0| = 0, and the selection ends)
+                uint32_t below = excl, bin = 4u * (uint32_t)lane;
+                if (want >= below + h0) { below += h0; ++bin;
+                    if (want >= below + h1) { below += h1; ++bin;
+                        if (want >= below + h2) { below += h2; ++bin; } } }
+                s_sel[0] = (prefix << REJECT_DIGIT_BITS) | bin;
+                s_sel[1] = want - below;
+            }
+        }
+        __syncthreads();
+        if (r == 0) n0 = s_sel[2];
+        if (n0 < (uint32_t)REJECT_MIN_CORR) break;   // (the whole workgroup: n0 is the same for every thread)
+        prefix = s_sel[0];
+        rank = s_sel[1];
+    }
+    // b. the threshold (+inf without a selection: what rule C8 left is counted, and the solve stops on fewer than three)
+    const bool selected = n0 >= (uint32_t)REJECT_MIN_CORR;
+    const float m = reject_value(prefix);
+    const double thr = selected ? reject_threshold(m, factor) : (double)reject_value(0x7f800000u);
+    // c. the kept correspondences' moments
+    unsigned long long S[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) S[j] = 0ull;
+    int kept = 0;
+    const float4* pts = src + c.src_off;
+    const int* nnp = nn + c.src_off;
+    const float4* tp = tplk + c.tpl_off;
+    for (int i = tid; i < c.n; i += RJ_THREADS) {
+        const float v = d2[i];
+        if (!(reject_in_k0(v, bnd.d2_max) && reject_keep(v, thr))) continue;
+        const float4 p = pts[i];
+        const int j = min(max(nnp[i], 0), c.tpl_m - 1);   // (a position k_icp_iter wrote; the clamp keeps a read inside the template)
+        const float4 q = tp[j];
+        const float pv[3] = {p.x, p.y, p.z}, qv[3] = {q.x, q.y, q.z};
+        unsigned long long t[16];
+        moment_terms(pv, qv, v, t);
+#pragma unroll
+        for (int a = 0; a < 16; ++a) S[a] += t[a];
+        ++kept;
+    }
+    wave_fold_to_lds(S, 16, s_sum);
+    kept = wave_sum_i32(kept);
+    if (lane == 0 && kept) atomicAdd(&s_sel[3], (uint32_t)kept);
+    __syncthreads();
+    // d. the iteration's slot and the record
+    const size_t slot = (size_t)k * 3 + (size_t)(it % 3);
+    if (tid < 16) acc[slot * 16 + tid] = s_sum[tid];
+    if (tid == 16) {
+        const int n = (int)s_sel[3];
+        bnd.ncorr[slot] = (uint32_t)n;
+        RejectStats rs = rstat[k];
+        if (it == 0) { rs.first_kept = n; rs.min_kept = n; }
+        else rs.min_kept = min(rs.min_kept, n);
+        rs.last_kept = n;
+        if (n < REJECT_MIN_CORR) rs.stopped_few = 1;
+        if (selected) rs.last_median = m;
+        rstat[k] = rs;
+    }
+}
+
+void launch_icp_reject(hipStream_t s, int it, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, const IcpBound& bnd, double factor,
+                       RejectStats* rstat) {
+    if (ncl <= 0) return;
+    hipLaunchKernelGGL(k_icp_reject, dim3(ncl), dim3(RJ_THREADS), 0, s, it, P.cl, P.st, S.src, T.tplk, S.nn, S.d2, S.acc, bnd, factor, rstat);
+}
+
+}  // namespace cd

@@ -136,6 +136,13 @@ void launch_icp_coarse_gather(hipStream_t s, int n_coarse_problems, int max_n_co
 void launch_icp_coarse_handover(hipStream_t s, int ncl, const CoarseHand* hand, const IcpState* cst, const unsigned long long* caccf, IcpState* st,
                                 float* guess, CoarseStats* stats);
 
+// k_icp_reject.hip : rule C19, median-distance correspondence rejection (icp_reject_math.hpp: RejectStats) - behind k_icp_iter<true>(it)
+// of the sliced loop: the sums and count of iteration slot it % 3 of every live, unfinished problem become those of the kept
+// correspondences (S.nn / S.d2 as the iteration kernel left them, T.tplk); bnd.d2_max = +inf without rule C8's bound
+struct RejectStats;
+void launch_icp_reject(hipStream_t s, int it, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, const IcpBound& bnd, double factor,
+                       RejectStats* rstat);
+
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
 // records x y z rgb (canonical rule C7)
 struct DeprojectParams {
