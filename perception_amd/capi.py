@@ -986,15 +986,22 @@ class Context:
         self._check(self.lib.cd_get_icp_plane_weight(self.h, C.byref(w), C.byref(d)))
         return w.value, d.value
 
+    def _cluster_records(self, fn, ctype, message, frame, first, count, default_count=4096):
+        """The read-backs of one record per cluster (cd_get_cluster_*_stats, cd_get_cluster_shape_frames): up to `count` records
+        of `frame` from its cluster `first` on, as a list of `ctype`; a negative return raises CuboidError with `message`."""
+        cap = default_count if count is None else int(count)
+        out = (ctype * max(cap, 1))()
+        got = fn(self.h, frame, first, cap, out)
+        if got < 0:
+            raise CuboidError(got, message)
+        return out[:got]
+
     def cluster_plane_stats(self, frame, first=0, count=None):
         """Rule C17's counters of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
         cluster_results: an (n, 4) int32 array of plane_iterations, first_plane_iteration, stopped_singular, reserved."""
-        cap = 4096 if count is None else int(count)
-        out = np.zeros((max(cap, 1), 4), np.int32)
-        got = self.lib.cd_get_cluster_plane_stats(self.h, frame, first, cap, _ptr(out))
-        if got < 0:
-            raise CuboidError(got, "no plane-weighted call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
-        return out[:got].copy()
+        msg = "no plane-weighted call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
+        rows = self._cluster_records(self.lib.cd_get_cluster_plane_stats, C.c_int32 * 4, msg, frame, first, count)
+        return np.array([r[:] for r in rows], np.int32).reshape(-1, 4)
 
     def set_icp_coarse(self, stride, min_points=0):
         """Rule C18, coarse-to-fine ICP, for every later ICP of this context: pairs whose cluster has at least min_points points
@@ -1010,12 +1017,8 @@ class Context:
     def cluster_coarse_stats(self, frame, first=0, count=None):
         """Rule C18's stats of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
         cluster_results: a list of CdIcpCoarseStats."""
-        cap = 4096 if count is None else int(count)
-        out = (CdIcpCoarseStats * max(cap, 1))()
-        got = self.lib.cd_get_cluster_coarse_stats(self.h, frame, first, cap, C.byref(out))
-        if got < 0:
-            raise CuboidError(got, "no coarse-to-fine call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
-        return [out[i] for i in range(got)]
+        msg = "no coarse-to-fine call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_coarse_stats, CdIcpCoarseStats, msg, frame, first, count)
 
     def set_icp_median_rejection(self, factor):
         """Rule C19, median-distance correspondence rejection, for every later ICP of this context: an iteration keeps the
@@ -1031,12 +1034,8 @@ class Context:
     def cluster_reject_stats(self, frame, first=0, count=None):
         """Rule C19's stats of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
         cluster_results: a list of CdIcpRejectStats."""
-        cap = 4096 if count is None else int(count)
-        out = (CdIcpRejectStats * max(cap, 1))()
-        got = self.lib.cd_get_cluster_reject_stats(self.h, frame, first, cap, C.byref(out))
-        if got < 0:
-            raise CuboidError(got, "no median-rejection call to read: the last one ran with the mode off, has been invalidated, or had no such frame")
-        return [out[i] for i in range(got)]
+        msg = "no median-rejection call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_reject_stats, CdIcpRejectStats, msg, frame, first, count)
 
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
@@ -1141,12 +1140,8 @@ class Context:
 
     def cluster_shape_frames(self, frame, first=0, count=None):
         """The cluster records of `frame` of the last fused call in CD_GUESS_CLUSTER mode: a list of CdShapeFrame."""
-        cap = CD_MAX_CLUSTERS_PER_FRAME * 64 if count is None else count
-        out = (CdShapeFrame * max(cap, 1))()
-        n = self.lib.cd_get_cluster_shape_frames(self.h, frame, first, cap, out)
-        if n < 0:
-            raise CuboidError(n, "cd_get_cluster_shape_frames: the last fused call was not in CD_GUESS_CLUSTER mode")
-        return [out[i] for i in range(n)]
+        msg = "cd_get_cluster_shape_frames: the last fused call was not in CD_GUESS_CLUSTER mode"
+        return self._cluster_records(self.lib.cd_get_cluster_shape_frames, CdShapeFrame, msg, frame, first, count, CD_MAX_CLUSTERS_PER_FRAME * 64)
 
     def timing(self):
         t = CdTiming()

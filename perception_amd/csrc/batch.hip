@@ -167,6 +167,15 @@ int extract_sources(cd_context* c, const cd_params* p, int F, const BatchCluster
     return CD_OK;
 }
 
+// The opt-in ICP steps that keep one record per cluster: fn(the step is on, its kept table, the pinned mirror of a stage's records).
+// A new step adds its line here.
+template <class Fn>
+void for_each_icp_stat(cd_context* c, Fn&& fn) {
+    fn(c->plane_weight != 0.0, c->last_plane, c->h_pstat);     // rule C17
+    fn(c->coarse_stride != 0, c->last_coarse, c->h_cstat);     // rule C18
+    fn(c->reject_factor != 0.0, c->last_reject, c->h_rstat);   // rule C19
+}
+
 struct BatchIcp {   // the ICP part of a fused call; the results themselves are kept in c->last_clusters
     std::vector<int> slots;                    // the template slots every cluster is matched against, ascending
     std::vector<long long> orig_off, al_off;   // per cluster, see cd_get_cluster_points (publish_last hands them to the context)
@@ -184,9 +193,7 @@ void begin_batch_icp(cd_context* c, const cd_params* p, int F, const BatchCluste
     c->last_clusters.assign((size_t)std::max(cl.ncl, 1), cd_cluster_result());
     bi->orig_off.assign((size_t)std::max(cl.ncl, 1), -1);
     bi->al_off.assign((size_t)std::max(cl.ncl, 1), -1);
-    if (c->plane_weight != 0.0) c->last_plane.assign((size_t)std::max(cl.ncl, 1), cd_icp_plane_stats());   // rule C17: the kept result's counters
-    if (c->coarse_stride != 0) c->last_coarse.assign((size_t)std::max(cl.ncl, 1), cd_icp_coarse_stats());   // rule C18: the kept result's stats
-    if (c->reject_factor != 0.0) c->last_reject.assign((size_t)std::max(cl.ncl, 1), cd_icp_reject_stats());   // rule C19: the kept result's stats
+    for_each_icp_stat(c, [&](bool on, auto& kept, auto&) { if (on) kept.begin(cl.ncl); });   // the kept result's record, not valid before publish_last
     for (int f = 0; f < F; ++f)
         for (int q = cl.first[(size_t)f]; q < cl.first[(size_t)f + 1]; ++q) bi->orig_off[(size_t)q] = (long long)f * c->N + cl.off[(size_t)q];
 }
@@ -210,9 +217,7 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
     r.template_slot = bi->slots[(size_t)t];
     if (t > 0 && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
     c->last_clusters[(size_t)k] = r;
-    if (c->plane_weight != 0.0) std::memcpy(&c->last_plane[(size_t)k], &c->h_pstat[q], sizeof(cd_icp_plane_stats));
-    if (c->coarse_stride != 0) std::memcpy(&c->last_coarse[(size_t)k], &c->h_cstat[q], sizeof(cd_icp_coarse_stats));
-    if (c->reject_factor != 0.0) std::memcpy(&c->last_reject[(size_t)k], &c->h_rstat[q], sizeof(cd_icp_reject_stats));
+    for_each_icp_stat(c, [&](bool on, auto& kept, auto& mirror) { if (on) kept.keep(k, mirror[q]); });
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
 }
 
@@ -220,9 +225,7 @@ void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, 
 // cd_get_cluster_shape_frames - problem k < ncl is cluster k.
 void keep_cluster_shapes(cd_context* c, const cd_params* p, int ncl) {
     if (p->icp_use_guess != CD_GUESS_CLUSTER) return;
-    static_assert(sizeof(ShapeFrame) == sizeof(cd_shape_frame), "ShapeFrame mirrors cd_shape_frame");
-    c->last_shapes.resize((size_t)ncl);
-    if (ncl > 0) std::memcpy(c->last_shapes.data(), c->h_shape.get(), sizeof(ShapeFrame) * (size_t)ncl);
+    c->last_shapes.assign_all(c->h_shape.get(), ncl);
 }
 
 // All (cluster, template) pairs in one stage (fits_one_stage): problem t * ncl + k is cluster k against slots[t], on copy t of
@@ -287,14 +290,8 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     for (int f = 0; f < F; ++f) { c->last_nv[(size_t)f] = c->h_fs[f].n_v; c->last_no[(size_t)f] = c->h_fs[f].n_o; }
     c->last_clouds = true;
     c->last_surface_ok = p->icp_use_guess == CD_GUESS_SURFACE;
-    c->last_shapes_ok = p->icp_use_guess == CD_GUESS_CLUSTER;
-    c->last_plane_ok = c->plane_weight != 0.0;
-    if (c->last_plane_ok) c->last_plane_first = cl.first;
-    c->last_coarse_ok = c->coarse_stride != 0;
-    if (c->last_coarse_ok) c->last_coarse_first = cl.first;
-    c->last_reject_ok = c->reject_factor != 0.0;
-    if (c->last_reject_ok) c->last_reject_first = cl.first;
-    if (c->last_shapes_ok && cl.ncl == 0) c->last_shapes.clear();
+    if (p->icp_use_guess == CD_GUESS_CLUSTER) c->last_shapes.publish(cl.first);   // (keep_cluster_shapes has run, also for no cluster)
+    for_each_icp_stat(c, [&](bool on, auto& kept, auto&) { if (on) kept.publish(cl.first); });
 }
 
 // The per-frame records from h_fs, the plane mirrors and c->last_clusters, and the byte counts of the timing
@@ -321,7 +318,7 @@ void write_frame_records(cd_context* c, int N, int F, const BatchClusters& cl, c
         for (int k = 0; k < s.n_k; ++k) {
             const cd_cluster_result& cr = c->last_clusters[(size_t)(cl.first[(size_t)f] + k)];
             if (k < KICP) r.clusters[k] = cr;
-            if (c->last_shapes_ok) {   // CD_GUESS_CLUSTER: did this cluster's ICP (against the template it kept) start from a rule-C13 guess?
+            if (c->last_shapes.valid()) {   // CD_GUESS_CLUSTER: did this cluster's ICP (against the template it kept) start from a rule-C13 guess?
                 ShapeFrame rec;
                 float G[16];
                 std::memcpy(&rec, &c->last_shapes[(size_t)(cl.first[(size_t)f] + k)], sizeof(rec));
@@ -386,8 +383,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     // checks: nothing is copied or launched before they have passed
     int st = check_params(c, p);
     if (!st) st = check_bbox_source(c, p, F, dj && dj->color);
-    if (!st) st = check_plane_templates(c, p->template_slot);   // rule C17: lattice templates only
-    if (!st) st = check_reject_mode(c);                          // rule C19: not together with rule C17
+    if (!st) st = check_icp_modes(c, p->template_slot);   // rule C17: lattice templates only; rule C19: not together with rule C17
     if (st) return st;
     if (!results || !d_frames) return fail(c, CD_ERR_INVALID_ARG, "null pointer");
     if (N <= 0 || F <= 0 || stride < 12 || (stride & 3)) return fail(c, CD_ERR_INVALID_ARG, "bad shape/stride");
@@ -463,8 +459,7 @@ int cd_process_batch_impl(cd_context* c, const void* frames, size_t stride, int 
     if (!frames || points_per_frame <= 0 || n_frames <= 0) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
     const size_t bytes = (size_t)points_per_frame * n_frames * stride;
     int st = check_bbox_source(c, p, n_frames, false);   // (before the upload)
-    if (!st && p) st = check_plane_templates(c, p->template_slot);
-    if (!st) st = check_reject_mode(c);
+    if (!st && p) st = check_icp_modes(c, p->template_slot);
     if (st) return st;
     st = ensure_input(c, bytes);
     if (st) return st;
@@ -482,8 +477,7 @@ int cd_process_depth_batch_impl(cd_context* c, const cd_depth_camera* cam, const
     st = mapped ? check_mapped(c, cam, ccam, depth, color, n_frames) : check_depth(c, cam, depth, color, n_frames);
     if (st) return st;
     st = check_bbox_source(c, p, n_frames, cam->color == CD_COLOR_RGB8);   // (before the uploads)
-    if (!st) st = check_plane_templates(c, p->template_slot);
-    if (!st) st = check_reject_mode(c);
+    if (!st) st = check_icp_modes(c, p->template_slot);
     if (st) return st;
     cd_params q = *p;
     q.rgb_offset = cam->color == CD_COLOR_RGB8 ? 12 : -1;   // the canonical records: x y z rgb, 16 bytes

@@ -21,6 +21,7 @@
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
 #include "icp_coarse_plan.hpp"
+#include "kept_records.hpp"
 #include "shape_frame_math.hpp"
 #include "template_prep.hpp"
 #include "tunables.hpp"
@@ -189,8 +190,7 @@ struct cd_context : cd_streams {
     DevBuf<ShapeFrame> d_shape; PinBuf<ShapeFrame> h_shape;
     DevBuf<float4> d_shpts;
     DevBuf<IcpCluster> d_shcl;
-    std::vector<cd_shape_frame> last_shapes;                      // cd_get_cluster_shape_frames: one per cluster of the last fused call, frame-major
-    bool last_shapes_ok = false;
+    KeptRecords<cd_shape_frame> last_shapes;                      // cd_get_cluster_shape_frames: one per cluster of the last fused call (kept_records.hpp)
     DevBuf<IcpState> d_st; PinBuf<IcpState> h_st;
     DevBuf<unsigned long long> d_acc, d_accf; PinBuf<unsigned long long> h_accf;
     // point labels (rule C15, k_labels.hip): where the voxel stage left its sorted keys (host fields, set at the end of
@@ -212,12 +212,10 @@ struct cd_context : cd_streams {
     bool last_outlier_ok = false;
     // plane-weighted ICP (rule C17, k_icp_plane.hip): the setting (cd_set_icp_plane_weight; plane_weight = 0: off), one record per
     // ICP problem of a stage (device + pinned mirror, grown on demand), and what cd_get_cluster_plane_stats reads: one record per
-    // cluster of the last fused call, frame-major with last_plane_first as its index (a stand-alone cd_icp: one frame, one record)
+    // cluster of the last fused call, frame-major behind the call's own index (kept_records.hpp; a stand-alone cd_icp: one frame, one record)
     double plane_weight = 0.0, plane_switch = CD_ICP_PLANE_SWITCH_DEFAULT;
     DevBuf<PlaneStats> d_pstat; PinBuf<PlaneStats> h_pstat;
-    std::vector<cd_icp_plane_stats> last_plane;
-    std::vector<int> last_plane_first;
-    bool last_plane_ok = false;
+    KeptRecords<cd_icp_plane_stats> last_plane;
     // coarse-to-fine ICP (rule C18, k_icp_coarse.hip): the setting (cd_set_icp_coarse; coarse_stride = 0: off); per stage, grown on
     // demand, the gather table, the final states and fitness sums of the coarse problems and the fine problems' hand-over table
     // (pinned + device), and one stats record per fine problem (device + pinned mirror); and what cd_get_cluster_coarse_stats
@@ -228,17 +226,13 @@ struct cd_context : cd_streams {
     DevBuf<unsigned long long> d_caccf; PinBuf<unsigned long long> h_caccf;
     DevBuf<CoarseHand> d_chand; PinBuf<CoarseHand> h_chand;
     DevBuf<CoarseStats> d_cstat; PinBuf<CoarseStats> h_cstat;
-    std::vector<cd_icp_coarse_stats> last_coarse;
-    std::vector<int> last_coarse_first;
-    bool last_coarse_ok = false;
+    KeptRecords<cd_icp_coarse_stats> last_coarse;
     // median-distance correspondence rejection (rule C19, k_icp_reject.hip): the setting (cd_set_icp_median_rejection; 0: off), one
     // record per ICP problem of a stage (device + pinned mirror, grown on demand), and what cd_get_cluster_reject_stats reads, as
     // last_plane
     double reject_factor = 0.0;
     DevBuf<RejectStats> d_rstat; PinBuf<RejectStats> h_rstat;
-    std::vector<cd_icp_reject_stats> last_reject;
-    std::vector<int> last_reject_first;
-    bool last_reject_ok = false;
+    KeptRecords<cd_icp_reject_stats> last_reject;
     cd_timing timing;
 };
 
@@ -280,11 +274,11 @@ inline void invalidate_last(cd_context* c) {
     c->last_first.clear();
     c->last_surface_ok = false;
     c->last_bboxes_ok = false;
-    c->last_shapes_ok = false;
     c->last_outlier_ok = false;
-    c->last_plane_ok = false;
-    c->last_coarse_ok = false;
-    c->last_reject_ok = false;
+    c->last_shapes.invalidate();
+    c->last_plane.invalidate();
+    c->last_coarse.invalidate();
+    c->last_reject.invalidate();
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -430,8 +424,14 @@ int check_params(cd_context* c, const cd_params* p);
 // ---- icp_plane.hip (rule C17): with the mode on, a loaded template the call would use (slot >= 0: that one; -1: every loaded one)
 // that is not a lattice fails the call - to be asked before anything is launched
 int check_plane_templates(cd_context* c, int slot);
-// ---- icp_reject.hip (rule C19): the mode cannot be combined with rule C17 - asked where check_plane_templates is
+// ---- icp_reject.hip (rule C19): the mode cannot be combined with rule C17
 int check_reject_mode(cd_context* c);
+// what every ICP entry point asks before it copies or launches anything: check_plane_templates, then check_reject_mode (with both
+// wrong the error is the first one's)
+inline int check_icp_modes(cd_context* c, int slot) {
+    if (int st = check_plane_templates(c, slot)) return st;
+    return check_reject_mode(c);
+}
 int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, int rgb_offset, uint32_t pad3, void* out, size_t staging_skip = 0);
 // ---- cuboid_hip.hip
 int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int F, const cd_params* p, int* rounds_out);

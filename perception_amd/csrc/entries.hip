@@ -321,8 +321,7 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
     if (p->icp_use_guess == CD_GUESS_SURFACE) return fail(c, CD_ERR_INVALID_ARG, "icp_use_guess = CD_GUESS_SURFACE needs a frame to fit: fused calls only");
     if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
     if (c->tpl_m[slot] <= 0) return fail(c, CD_ERR_NO_TEMPLATE, "template slot is empty");
-    st = check_plane_templates(c, slot);   // rule C17: lattice templates only
-    if (!st) st = check_reject_mode(c);    // rule C19: not together with rule C17
+    st = check_icp_modes(c, slot);   // rule C17: lattice templates only; rule C19: not together with rule C17
     if (st) return st;
     st = upload_points(c, src_xyz, stride, n, c->d_src0);
     if (st) return st;
@@ -338,29 +337,17 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
         HIPCHK(c, copy_sync(c, tmp.data(), c->d_src, sizeof(float4) * n, hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i) { aligned[3 * i] = tmp[i].x; aligned[3 * i + 1] = tmp[i].y; aligned[3 * i + 2] = tmp[i].z; }
     }
-    if (c->coarse_stride != 0) {   // rule C18: the pair's stats for cd_get_cluster_coarse_stats (frame 0, index 0; before the return of a singular stop below)
-        cd_icp_coarse_stats cs;
-        std::memcpy(&cs, &c->h_cstat[0], sizeof(cs));
-        c->last_coarse.assign(1, cs);
-        c->last_coarse_first.assign({0, 1});
-        c->last_coarse_ok = true;
+    // the pair's record for cd_get_cluster_{coarse,plane,reject}_stats (frame 0, index 0), before the return of a stop below; a
+    // source of fewer than three points never reached the plane or reject kernels: an all-zero record
+    if (c->coarse_stride != 0) c->last_coarse.publish_single(c->h_cstat[0]);   // rule C18
+    if (c->plane_weight != 0.0) {   // rule C17
+        if (n >= 3) c->last_plane.publish_single(c->h_pstat[0]);
+        else c->last_plane.publish_single(cd_icp_plane_stats());
+        if (c->last_plane[0].stopped_singular) return fail(c, CD_ERR_FEW_CORRESPONDENCES, "plane-weighted ICP stopped: the step's system is singular");
     }
-    if (c->plane_weight != 0.0) {   // rule C17: the pair's counters for cd_get_cluster_plane_stats (frame 0, index 0); a singular stop
-        cd_icp_plane_stats ps;
-        std::memset(&ps, 0, sizeof(ps));
-        if (n >= 3) std::memcpy(&ps, &c->h_pstat[0], sizeof(ps));
-        c->last_plane.assign(1, ps);
-        c->last_plane_first.assign({0, 1});
-        c->last_plane_ok = true;
-        if (ps.stopped_singular) return fail(c, CD_ERR_FEW_CORRESPONDENCES, "plane-weighted ICP stopped: the step's system is singular");
-    }
-    if (c->reject_factor != 0.0) {   // rule C19: the pair's stats for cd_get_cluster_reject_stats (frame 0, index 0)
-        cd_icp_reject_stats rs;
-        std::memset(&rs, 0, sizeof(rs));
-        if (n >= 3) std::memcpy(&rs, &c->h_rstat[0], sizeof(rs));
-        c->last_reject.assign(1, rs);
-        c->last_reject_first.assign({0, 1});
-        c->last_reject_ok = true;
+    if (c->reject_factor != 0.0) {   // rule C19
+        if (n >= 3) c->last_reject.publish_single(c->h_rstat[0]);
+        else c->last_reject.publish_single(cd_icp_reject_stats());
     }
     // rules C8 and C19: an ICP that stopped for fewer than three kept correspondences (only a bounded or rejecting one can: every
     // other ends converged)
@@ -458,14 +445,7 @@ int cd_template_shape_frame(const cd_context* c, int slot, cd_shape_frame* out) 
 }
 
 int cd_get_cluster_shape_frames(const cd_context* c, int frame, int first, int capacity, cd_shape_frame* out) {
-    if (!c || frame < 0 || first < 0 || capacity < 0 || (capacity > 0 && !out)) return CD_ERR_INVALID_ARG;
-    if (!c->last_shapes_ok) return CD_ERR_INVALID_ARG;   // (no fused call in CD_GUESS_CLUSTER mode since the last compute call)
-    if ((size_t)frame + 1 >= c->last_first.size()) return CD_ERR_INVALID_ARG;
-    const int lo = c->last_first[(size_t)frame], hi = c->last_first[(size_t)frame + 1];
-    if (lo < 0 || hi < lo || (size_t)hi > c->last_shapes.size()) return CD_ERR_INVALID_ARG;
-    int n = 0;
-    for (int k = lo + first; k < hi && n < capacity; ++k) out[n++] = c->last_shapes[(size_t)k];
-    return n;
+    return c ? c->last_shapes.read(frame, first, capacity, out) : CD_ERR_INVALID_ARG;   // (valid after a fused call in CD_GUESS_CLUSTER mode)
 }
 
 int cd_crop_voxel(cd_context* c, const void* points, size_t stride, int n, const cd_params* p, float* out_xyz, uint32_t* out_rgb, int capacity, int* out_n_cropped, int* out_n_voxels) {

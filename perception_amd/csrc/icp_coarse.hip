@@ -36,12 +36,6 @@ int cd_icp_coarse_subsample(int n, int stride, int min_points, int32_t* out_indi
 }
 
 int cd_get_cluster_coarse_stats(const cd_context* c, int frame, int first, int count, cd_icp_coarse_stats* out) {
-    if (!c || frame < 0 || first < 0 || count < 0 || (count > 0 && !out)) return CD_ERR_INVALID_ARG;
-    if (!c->last_coarse_ok || (size_t)frame + 1 >= c->last_coarse_first.size()) return CD_ERR_INVALID_ARG;   // mode off, invalidated, or no such frame
-    const int lo = c->last_coarse_first[(size_t)frame], hi = c->last_coarse_first[(size_t)frame + 1];
-    if (lo < 0 || hi < lo || (size_t)hi > c->last_coarse.size()) return CD_ERR_INVALID_ARG;
-    int n = 0;
-    for (int k = lo + first; k < hi && n < count; ++k) out[n++] = c->last_coarse[(size_t)k];
-    return n;
+    return c ? c->last_coarse.read(frame, first, count, out) : CD_ERR_INVALID_ARG;
 }
 }  // extern "C"

@@ -61,7 +61,7 @@ struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
     bool pre_zeroed = false;                     // (icp_setup) d_acc / d_accf / d_queue were zeroed by the fused call
     bool crowded = false;                        // (icp_params) four or more batches in flight on the device
     bool plane = false;                          // rule C17 (cd_set_icp_plane_weight): every live cluster takes k_icp_plane
-    bool reject = false;                         // rule C19 (cd_set_icp_median_rejection): every live cluster gets sliced work items (icp_run_reject)
+    bool reject = false;                         // rule C19 (cd_set_icp_median_rejection): every live cluster gets sliced work items (icp_run_sliced)
     bool device_guesses = false;                 // (IcpPlanInput::device_guesses) the sources are moved per problem, whatever the guess mode
 };
 

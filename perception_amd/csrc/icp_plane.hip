@@ -36,13 +36,7 @@ int cd_get_icp_plane_weight(const cd_context* c, double* tangent_weight, double*
 }
 
 int cd_get_cluster_plane_stats(const cd_context* c, int frame, int first, int count, cd_icp_plane_stats* out) {
-    if (!c || frame < 0 || first < 0 || count < 0 || (count > 0 && !out)) return CD_ERR_INVALID_ARG;
-    if (!c->last_plane_ok || (size_t)frame + 1 >= c->last_plane_first.size()) return CD_ERR_INVALID_ARG;   // mode off, invalidated, or no such frame
-    const int lo = c->last_plane_first[(size_t)frame], hi = c->last_plane_first[(size_t)frame + 1];
-    if (lo < 0 || hi < lo || (size_t)hi > c->last_plane.size()) return CD_ERR_INVALID_ARG;
-    int n = 0;
-    for (int k = lo + first; k < hi && n < count; ++k) out[n++] = c->last_plane[(size_t)k];
-    return n;
+    return c ? c->last_plane.read(frame, first, count, out) : CD_ERR_INVALID_ARG;
 }
 
 int cd_icp_plane_solve_host(const int64_t sums[28], int n, float T[16], int32_t* singular) {

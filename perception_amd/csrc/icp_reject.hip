@@ -31,13 +31,7 @@ int cd_get_icp_median_rejection(const cd_context* c, double* factor) {
 int cd_icp_reject_struct_size(void) { return (int)sizeof(cd_icp_reject_stats); }
 
 int cd_get_cluster_reject_stats(const cd_context* c, int frame, int first, int count, cd_icp_reject_stats* out) {
-    if (!c || frame < 0 || first < 0 || count < 0 || (count > 0 && !out)) return CD_ERR_INVALID_ARG;
-    if (!c->last_reject_ok || (size_t)frame + 1 >= c->last_reject_first.size()) return CD_ERR_INVALID_ARG;   // mode off, invalidated, or no such frame
-    const int lo = c->last_reject_first[(size_t)frame], hi = c->last_reject_first[(size_t)frame + 1];
-    if (lo < 0 || hi < lo || (size_t)hi > c->last_reject.size()) return CD_ERR_INVALID_ARG;
-    int n = 0;
-    for (int k = lo + first; k < hi && n < count; ++k) out[n++] = c->last_reject[(size_t)k];
-    return n;
+    return c ? c->last_reject.read(frame, first, count, out) : CD_ERR_INVALID_ARG;
 }
 
 int cd_icp_median_threshold(const float* d2, int n, double factor, float* median, double* thr) {

@@ -2,7 +2,7 @@
 // needs (icp_setup), then hands the clusters to the drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe
 // launches for several templates, the whole-cluster launch, the persistent launch for a few clusters, and the sliced multi-launch
 // loop for whatever is left (rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs.
-// Rule C19 on: the sliced loop with k_icp_reject behind every iteration takes every live cluster, likewise).
+// Rule C19 on: the sliced loop, with k_icp_reject behind every iteration, takes every live cluster; none of the others runs).
 // A driver sets *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after
 // it take the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
 // Which driver, and how large its launch: icp_plan.hpp decides, from plain numbers.  Here are the stream operations.
@@ -362,8 +362,19 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Ic
 }
 
 // The multi-launch loop over the work list, then the fitness pass.  Always finishes the stage.
+// Rule C19 (cd_set_icp_median_rejection, plan.reject - every live cluster has items then): k_icp_reject behind every iteration
+// launch: k_icp_solve<true>(it), k_icp_iter<true>(it), whose sums for the slot k_icp_reject(it) then replaces with those of the kept
+// correspondences.  Always the BOUNDED instantiations then, with d2_max = +inf when rule C8 bounds nothing.
 int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const IcpParams& ip, bool* done) {
+    static_assert(sizeof(RejectStats) == sizeof(cd_icp_reject_stats), "RejectStats mirrors cd_icp_reject_stats");
     const int ncl = pl.ncl, nwork = pl.nwork, max_launch = ip.max_iter + 3;
+    IcpBound bnd = icp_bound(c);
+    if (pl.reject) {
+        GROW(c, d_rstat, (size_t)ncl); GROW(c, h_rstat, (size_t)ncl);
+        HIPCHK(c, hipMemsetAsync(c->d_rstat, 0, sizeof(RejectStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
+        if (!bnd.bounded) bnd.d2_max = std::numeric_limits<float>::infinity();
+        bnd.bounded = 1;
+    }
     // The iteration kernel walks an ACTIVE work list (d_work2) that the host re-packs at every
     // completion poll, dropping the clusters that have converged (repack_active); the full list (d_work) is kept for
     // the fitness pass (k_icp_solve alone keeps the state of a cluster without items).
@@ -372,45 +383,9 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
     HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)std::max(nwork, 1), hipMemcpyHostToDevice));
     for (int polls = 0; nwork > 0 && it < max_launch; ++polls) {
         const int g = std::min(sliced_poll_group(polls), max_launch - it);
-        for (int q = 0; q < g; ++q) LAUNCH(c, launch_icp_iter(c->stream, it++, nactive, ncl, c->d_work2, a.dev, a.tpl, a.scr, pl.qslice, c->n_cu, ip, icp_bound(c)));
-        HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool all = false;
-        const int na = repack_active(c->h_work, nwork, c->h_st, ncl, c->h_work2, &all);
-        if (all) break;
-        if (na != nactive) {
-            nactive = na;
-            if (na > 0) HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)na, hipMemcpyHostToDevice));
-        }
-    }
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));   // (before the fitness pass)
-    c->timing.icp_kernel_launches = it;
-    LAUNCH(c, launch_icp_fitness(c->stream, nwork, c->d_work, a.dev, 0, a.tpl, a.scr, pl.qslice));
-    if (int e = icp_read_back(c, ncl)) return e;
-    *done = true;
-    return CD_OK;
-}
-
-// Rule C19 (cd_set_icp_median_rejection): icp_run_sliced's loop over the work list - with the mode on every live cluster has
-// items - with k_icp_reject behind every iteration launch: k_icp_solve<true>(it), k_icp_iter<true>(it), whose sums for the slot
-// k_icp_reject(it) then replaces with those of the kept correspondences.  Always the BOUNDED instantiations, with d2_max = +inf
-// when rule C8 bounds nothing.  Always finishes the stage.
-int icp_run_reject(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const IcpParams& ip, bool* done) {
-    static_assert(sizeof(RejectStats) == sizeof(cd_icp_reject_stats), "RejectStats mirrors cd_icp_reject_stats");
-    const int ncl = pl.ncl, nwork = pl.nwork, max_launch = ip.max_iter + 3;
-    GROW(c, d_rstat, (size_t)ncl); GROW(c, h_rstat, (size_t)ncl);
-    HIPCHK(c, hipMemsetAsync(c->d_rstat, 0, sizeof(RejectStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
-    IcpBound bnd = icp_bound(c);
-    if (!bnd.bounded) bnd.d2_max = std::numeric_limits<float>::infinity();
-    bnd.bounded = 1;
-    int it = 0, nactive = nwork;
-    std::memcpy(c->h_work2, c->h_work, sizeof(IcpWork) * (size_t)std::max(nwork, 1));
-    HIPCHK(c, xfer(c, c->d_work2, c->h_work2, sizeof(IcpWork) * (size_t)std::max(nwork, 1), hipMemcpyHostToDevice));
-    for (int polls = 0; nwork > 0 && it < max_launch; ++polls) {
-        const int g = std::min(sliced_poll_group(polls), max_launch - it);
         for (int q = 0; q < g; ++q, ++it) {
             LAUNCH(c, launch_icp_iter(c->stream, it, nactive, ncl, c->d_work2, a.dev, a.tpl, a.scr, pl.qslice, c->n_cu, ip, bnd));
-            if (nactive > 0) LAUNCH(c, launch_icp_reject(c->stream, it, ncl, a.dev, a.tpl, a.scr, bnd, c->reject_factor, c->d_rstat));
+            if (pl.reject && nactive > 0) LAUNCH(c, launch_icp_reject(c->stream, it, ncl, a.dev, a.tpl, a.scr, bnd, c->reject_factor, c->d_rstat));
         }
         HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -423,9 +398,9 @@ int icp_run_reject(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
         }
     }
     HIPCHK(c, hipEventRecord(c->ev[6], c->stream));   // (before the fitness pass)
-    c->timing.icp_kernel_launches = it;               // (iteration launches, as the sliced driver counts them)
+    c->timing.icp_kernel_launches = it;               // (iteration launches)
     LAUNCH(c, launch_icp_fitness(c->stream, nwork, c->d_work, a.dev, 0, a.tpl, a.scr, pl.qslice));
-    HIPCHK(c, xfer(c, c->h_rstat, c->d_rstat, sizeof(RejectStats) * (size_t)ncl, hipMemcpyDeviceToHost));
+    if (pl.reject) HIPCHK(c, xfer(c, c->h_rstat, c->d_rstat, sizeof(RejectStats) * (size_t)ncl, hipMemcpyDeviceToHost));
     if (int e = icp_read_back(c, ncl)) return e;
     *done = true;
     return CD_OK;
@@ -450,11 +425,10 @@ int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests,
     HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
     bool done = false;
     if (pl.plane) st = icp_run_plane(c, pl, a, ip, &done);
-    if (!st && !done && pl.reject) st = icp_run_reject(c, pl, a, ip, &done);
     if (!st && !done && pl.n_lat > 0) st = icp_run_lat(c, pl, a, ip, &done);
     if (!st && !done && pl.grouped_pipe) st = icp_run_grouped(c, pl, a, ip, &done);
     if (!st && !done && pl.whole_cluster) st = icp_run_whole(c, pl, a, ip, &done);
-    if (!st && !done) st = icp_run_persist(c, pl, a, ip, &done);
+    if (!st && !done && !pl.reject) st = icp_run_persist(c, pl, a, ip, &done);   // (rule C19: the sliced loop, nothing before it)
     if (!st && !done) st = icp_run_sliced(c, pl, a, ip, &done);
     if (done) icp_finish(c, ncl, pair_tests);
     return st;

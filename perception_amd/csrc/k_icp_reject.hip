@@ -1,7 +1,7 @@
 // k_icp_reject.hip - S6 with canonical rule C19 (perception_amd/icp_reject.py is the specification): median-distance
 // correspondence rejection, opt-in through cd_set_icp_median_rejection.
 //
-// The mode's driver (icp_run_reject, icp_stage.hip) is the sliced multi-launch loop with this kernel behind every k_icp_iter<true>:
+// The mode's driver (icp_run_sliced, icp_stage.hip) is the sliced multi-launch loop with this kernel behind every k_icp_iter<true>:
 // the iteration kernel has left every point's neighbour (position in the k-d patch order) and float d2 in d_nn / d_d2, indexed per
 // point, and its own moment sums and count in the iteration's slot; k_icp_reject(it) REPLACES that slot's 16 sums and count with
 // those of the correspondences rule C19 keeps, which k_icp_solve<true>(it + 1) then reads.  No other kernel changes.
