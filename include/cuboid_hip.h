@@ -1031,6 +1031,68 @@ int cd_get_cluster_reject_stats(const cd_context* ctx, int frame, int first, int
  * signed value gives CD_ERR_INVALID_ARG, as does a factor the setter would refuse or 0).  median and thr may be NULL. */
 int cd_icp_median_threshold(const float* d2, int n, double factor, float* median, double* thr);
 
+/* Table prism: keep only the object points above the convex hull of the plane inliers (pcl::ConvexHull of the inliers followed
+ * by pcl::ExtractPolygonalPrismData): opt-in, off by default.  Canonical rule C20; perception_amd/table_prism.py
+ * is the rule in numpy and the device equals it bit for bit - the kept set, the record and the hull.  Parity with a real PCL is
+ * unpinned (its hull is qhull's, in floating point; here the hull is one of integers and its boundary counts as inside).  For
+ * the refined plane (a, b, c, d) as float32, the plane inliers, a cloud and the limits height_min <= height_max:
+ *   1. all arithmetic is double, every product and sum rounded on its own in the order written.  s = -1 if d < 0, else +1;
+ *      n = s (a, b, c), dd = s d: the sensor at the origin is on the positive side (PCL's default viewpoint);
+ *   2. h(p) = ((n0 x + n1 y) + n2 z) + dd;
+ *   3. p' = p - h n per component, as x - (h n0);
+ *   4. the axis k0 = argmax(|a|, |b|, |c|) (float32 compares, the lowest index on a tie) is dropped; (k1, k2): the others, ascending;
+ *   5. u = floor(p'[k1] 65536), v = floor(p'[k2] 65536), clamped to [-2^29, 2^29 - 1] (a NaN to -2^29), int32; integers from here;
+ *   6. the hull: the strict vertices of the convex hull of the inliers' (u, v) - no duplicate, no point on an edge between two
+ *      others - counter-clockwise from the lexicographically smallest.  Fewer than 3: nothing is kept.  More than
+ *      CD_PRISM_MAX_HULL: the record says overflow, reports no vertex, and nothing is kept;
+ *   7. a point is kept iff height_min <= h <= height_max and cross(B - A, P - A) >= 0 for every hull edge A -> B (int64); the
+ *      kept points stay in their order, whole records;
+ *   8. the record below.  n_before = n_kept + n_below + n_above + n_outside.
+ * All plane inliers make the hull: a surface at table level beside the table extends it, as in PCL when every inlier is used.
+ *
+ * cd_set_table_prism: context state, as the outlier filter's.  enable = 0 turns the step off (the default: no kernel of the fused
+ * calls changes and every output is byte for byte what it was).  Limits that are not finite or not min <= max give
+ * CD_ERR_INVALID_ARG and the setting stays.  With the step on, every fused call runs it on each frame's object cloud between S3
+ * and the outlier filter (PCL's tabletop order: the prism, then cleaning), and everything behind it takes the kept cloud:
+ * the filter, clustering, the surface and cluster guesses, ICP, n_objects, the `labels` output,
+ * cd_get_frame_cloud(CD_CLOUD_OBJECTS) and cd_get_cluster_points.  The label calls (rule C15) give a voxel the prism removed
+ * CD_LABEL_GATED.  A frame without a plane passes untouched: n_kept = n_before and every other field 0.
+ * CD_PRISM_LDS_POINTS: the pruned inliers the kernel keeps in LDS (more are read from global memory). */
+#define CD_PRISM_MAX_HULL 1024
+#define CD_PRISM_LDS_POINTS 4096
+typedef struct cd_prism_stats {
+    int32_t n_before;       /* points of the cloud                                                                   */
+    int32_t n_kept;
+    int32_t n_below;        /* h < height_min                                                                        */
+    int32_t n_above;        /* not below and not h <= height_max (a NaN height counts here)                          */
+    int32_t n_outside;      /* passed the height test, outside the hull (or no hull of three vertices)               */
+    int32_t hull_vertices;  /* 0 on overflow                                                                         */
+    int32_t axis_u, axis_v; /* k1, k2                                                                                */
+    int32_t overflow;       /* 1: more than CD_PRISM_MAX_HULL hull vertices                                          */
+    int32_t reserved[3];
+} cd_prism_stats;
+int cd_set_table_prism(cd_context* ctx, int enable, double height_min, double height_max);
+int cd_get_table_prism(const cd_context* ctx, int* enable, double* height_min, double* height_max);
+int cd_prism_struct_size(void);   /* sizeof(cd_prism_stats) (cd_struct_size's list is closed) */
+/* What the step did to `frame` of the last fused call, and that frame's hull (u, v interleaved; *n = its vertices, also when
+ * capacity is too small: CD_ERR_CAPACITY then).  CD_ERR_INVALID_ARG when that call ran without the step, has been invalidated
+ * (the validity rule of cd_get_cluster_results) or had no such frame. */
+int cd_get_prism_stats(const cd_context* ctx, int frame, cd_prism_stats* out);
+int cd_get_prism_hull(cd_context* ctx, int frame, int32_t* uv, int capacity, int* n);
+/* The step as a call of its own: the kept indices ascending, like cd_outlier_filter.  plane_xyz: the n_plane plane inliers
+ * (plane_stride bytes apart), coeff the plane.  stats and hull_uv may be NULL (hull_capacity vertices; fewer than the hull has
+ * gives CD_ERR_CAPACITY).  Out-of-range arguments give CD_ERR_INVALID_ARG before anything is launched; n or n_plane above the
+ * context's max_points CD_ERR_CAPACITY; capacity < kept CD_ERR_CAPACITY with *out_n = kept.  The context's own setting is neither
+ * read nor changed; like every compute call it invalidates the read-backs of the last fused call. */
+int cd_table_prism(cd_context* ctx, const void* plane_xyz, size_t plane_stride, int n_plane, const float coeff[4], const void* xyz,
+                   size_t stride_bytes, int n, double height_min, double height_max, int32_t* out_indices, int capacity, int* out_n,
+                   cd_prism_stats* stats, int32_t* hull_uv, int hull_capacity);
+/* Host only (no context, no GPU).  cd_prism_project: steps 1 - 5 of one point - height, uv[2], axes[2] = (k1, k2); any output may
+ * be NULL.  cd_prism_hull_host: step 6 without the cap by a monotone chain over n >= 0 points (u, v interleaved): *n_hull = the
+ * hull's vertices, the first min(*n_hull, capacity) written; CD_ERR_CAPACITY when they did not all fit. */
+int cd_prism_project(const float coeff[4], const float xyz[3], double* height, int32_t uv[2], int32_t axes[2]);
+int cd_prism_hull_host(const int32_t* uv, int n, int32_t* hull, int capacity, int* n_hull);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

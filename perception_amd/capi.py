@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "cd_set_icp_coarse", "cd_get_icp_coarse", "cd_icp_coarse_struct_size", "cd_icp_coarse_subsample", "cd_get_cluster_coarse_stats",
     "cd_set_icp_median_rejection", "cd_get_icp_median_rejection", "cd_icp_reject_struct_size", "cd_get_cluster_reject_stats",
     "cd_icp_median_threshold",
+    "cd_set_table_prism", "cd_get_table_prism", "cd_prism_struct_size", "cd_get_prism_stats", "cd_get_prism_hull", "cd_table_prism",
+    "cd_prism_project", "cd_prism_hull_host",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
@@ -78,6 +80,7 @@ CD_VERIFY_MISS, CD_VERIFY_AGREE, CD_VERIFY_THROUGH, CD_VERIFY_OCCLUDED, CD_VERIF
 CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 CD_LABEL_INVALID, CD_LABEL_CROPPED, CD_LABEL_PLANE, CD_LABEL_OBJECT, CD_LABEL_GATED, CD_LABEL_CLUSTER0 = 0, 1, 2, 3, 4, 8
 CD_OUTLIER_MAX_MEAN_K, CD_OUTLIER_LDS_TILE = 63, 1024
+CD_PRISM_MAX_HULL, CD_PRISM_LDS_POINTS = 1024, 4096
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -95,6 +98,15 @@ class CdIcpRejectStats(C.Structure):
     """cd_icp_reject_stats: what rule C19 did for one (cluster, template) pair."""
     _fields_ = [("first_kept", C.c_int32), ("last_kept", C.c_int32), ("min_kept", C.c_int32), ("stopped_few", C.c_int32),
                 ("last_median", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class CdPrismStats(C.Structure):
+    """cd_prism_stats: what the table prism (rule C20) did to one cloud."""
+    _fields_ = [("n_before", C.c_int32), ("n_kept", C.c_int32), ("n_below", C.c_int32), ("n_above", C.c_int32), ("n_outside", C.c_int32),
+                ("hull_vertices", C.c_int32), ("axis_u", C.c_int32), ("axis_v", C.c_int32), ("overflow", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_[:9]}
 
 
 class CdShapeFrame(C.Structure):
@@ -504,6 +516,15 @@ def load_library(path=None):
     lib.cd_icp_reject_struct_size.argtypes = []
     lib.cd_get_cluster_reject_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.cd_icp_median_threshold.argtypes = [vp, C.c_int, C.c_double, vp, dp]
+    psp = C.POINTER(CdPrismStats)
+    lib.cd_set_table_prism.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+    lib.cd_get_table_prism.argtypes = [vp, ip, dp, dp]
+    lib.cd_prism_struct_size.argtypes = []
+    lib.cd_get_prism_stats.argtypes = [vp, C.c_int, psp]
+    lib.cd_get_prism_hull.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+    lib.cd_table_prism.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_double, C.c_double, vp, C.c_int, ip, psp, vp, C.c_int]
+    lib.cd_prism_project.argtypes = [vp, vp, dp, vp, vp]
+    lib.cd_prism_hull_host.argtypes = [vp, C.c_int, vp, C.c_int, ip]
     if path is None:
         _lib = lib
     return lib
@@ -975,6 +996,46 @@ class Context:
                                                C.byref(cnt), _ptr(dist), _ptr(stats)))
         return idx[:cnt.value].copy(), dist[:n].copy(), tuple(float(v) for v in stats)
 
+    def set_table_prism(self, enable, height_min=0.0, height_max=0.5):
+        """Rule C20 (pcl::ConvexHull of the plane inliers + pcl::ExtractPolygonalPrismData) on the object cloud of the following
+        fused calls, ahead of the outlier filter; enable false: off, the default."""
+        self._check(self.lib.cd_set_table_prism(self.h, 1 if enable else 0, float(height_min), float(height_max)))
+
+    def table_prism_setting(self):
+        """(enable, height_min, height_max) as cd_set_table_prism left them."""
+        on, lo, hi = C.c_int(), C.c_double(), C.c_double()
+        self._check(self.lib.cd_get_table_prism(self.h, C.byref(on), C.byref(lo), C.byref(hi)))
+        return bool(on.value), lo.value, hi.value
+
+    def prism_stats(self, frame):
+        """What the table prism did to `frame` of the last fused call: a dict of cd_prism_stats' fields."""
+        out = CdPrismStats()
+        st = self.lib.cd_get_prism_stats(self.h, frame, C.byref(out))
+        if st != CD_OK:
+            raise CuboidError(st, "no fused call with the table prism to read: the last one ran without it, has been invalidated, or had no such frame")
+        return out.as_dict()
+
+    def prism_hull(self, frame):
+        """The hull of `frame` of the last fused call: (hull_vertices, 2) int32, counter-clockwise from the lexicographically smallest."""
+        uv = np.zeros((CD_PRISM_MAX_HULL, 2), np.int32)
+        n = C.c_int()
+        self._check(self.lib.cd_get_prism_hull(self.h, frame, _ptr(uv), CD_PRISM_MAX_HULL, C.byref(n)))
+        return uv[:n.value].copy()
+
+    def table_prism(self, plane_xyz, coeff, xyz, height_min=0.0, height_max=0.5, capacity=None):
+        """The step as a call of its own.  Returns (kept indices int32 ascending, a dict of cd_prism_stats' fields, hull (h, 2) int32)."""
+        pl, pstride, npl = _points(np.asarray(plane_xyz, np.float32).reshape(-1, 3) if np.size(plane_xyz) == 0 else plane_xyz)
+        a, stride, n = _points(np.asarray(xyz, np.float32).reshape(-1, 3) if np.size(xyz) == 0 else xyz)
+        cf = np.ascontiguousarray(coeff, np.float32).reshape(4)
+        cap = max(n, 1) if capacity is None else int(capacity)
+        idx = np.empty(max(cap, 1), np.int32)
+        uv = np.zeros((CD_PRISM_MAX_HULL, 2), np.int32)
+        stats = CdPrismStats()
+        cnt = C.c_int()
+        self._check(self.lib.cd_table_prism(self.h, _ptr(pl), pstride, npl, _ptr(cf), _ptr(a), stride, n, float(height_min), float(height_max),
+                                            _ptr(idx), cap, C.byref(cnt), C.byref(stats), _ptr(uv), CD_PRISM_MAX_HULL))
+        return idx[:cnt.value].copy(), stats.as_dict(), uv[:stats.hull_vertices].copy()
+
     def set_icp_plane_weight(self, tangent_weight, switch_distance=CD_ICP_PLANE_SWITCH_DEFAULT):
         """Rule C17, the plane-weighted ICP step for lattice templates, for every later ICP of this context; tangent_weight = 0
         (or None): off, the default.  The recommended pair is (CD_ICP_PLANE_WEIGHT_DEFAULT, CD_ICP_PLANE_SWITCH_DEFAULT)."""
@@ -1219,6 +1280,33 @@ def icp_median_threshold(d2, factor):
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_median_threshold")
     return np.float32(m.value), np.float64(t.value)
+
+
+def prism_project(coeff, xyz):
+    """Host-only rule C20, steps 1 - 5 of one point: (height float64, (u, v), (k1, k2))."""
+    lib = load_library()
+    cf = np.ascontiguousarray(coeff, np.float32).reshape(4)
+    p = np.ascontiguousarray(xyz, np.float32).reshape(3)
+    h = C.c_double()
+    uv, ax = np.zeros(2, np.int32), np.zeros(2, np.int32)
+    st = lib.cd_prism_project(_ptr(cf), _ptr(p), C.byref(h), _ptr(uv), _ptr(ax))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_prism_project")
+    return np.float64(h.value), (int(uv[0]), int(uv[1])), (int(ax[0]), int(ax[1]))
+
+
+def prism_hull_host(uv, capacity=None):
+    """Host-only rule C20, step 6 without the cap: the strict hull vertices of integer points (n, 2), counter-clockwise from the
+    lexicographically smallest, as an (m, 2) int32 array."""
+    lib = load_library()
+    a = np.ascontiguousarray(uv, np.int32).reshape(-1, 2)
+    cap = max(len(a), 1) if capacity is None else int(capacity)
+    out = np.zeros((max(cap, 1), 2), np.int32)
+    n = C.c_int()
+    st = lib.cd_prism_hull_host(_ptr(a), len(a), _ptr(out), cap, C.byref(n))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_prism_hull_host")
+    return out[:n.value].copy()
 
 
 def icp_plane_solve_host(sums, n):

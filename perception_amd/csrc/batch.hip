@@ -413,10 +413,14 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     if (st) return st;
     int max_no = 0;
     for (int f = 0; f < F; ++f) max_no = std::max(max_no, c->h_fs[f].n_o);
-    int omap_pitch = 0;   // rule C16 (cd_set_outlier_filter): d_obj and n_o become the filtered clouds; max_no stays an upper bound
-    if (c->outlier_k > 0) st = stage_outlier(c, F, max_no, &omap_pitch);
+    int omap_pitch = 0, pmap_pitch = 0;
+    // rule C20 (cd_set_table_prism), then rule C16 (cd_set_outlier_filter) - PCL's tabletop order: d_obj and n_o become the kept, then
+    // the filtered clouds; max_no stays an upper bound
+    if (c->prism_on) st = stage_prism(c, F, max_no, &pmap_pitch);
+    if (!st && c->outlier_k > 0) st = stage_outlier(c, F, max_no, &omap_pitch);
+    if (!st && c->prism_on && c->outlier_k > 0) st = prism_compose_map(c, F, pmap_pitch);   // (both maps have rows of one pitch: the same max_no)
     if (st) return st;
-    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff (and, filtered, the outlier records)
+    st = stage_cluster_sync(c, F, p, max_no);   // sync #4: n_plane, n_o, n_k, ksize, koff (and, filtered, the outlier records; with the prism, its records)
     if (!st && p->icp_use_guess == CD_GUESS_SURFACE) st = surface_guesses(c, F, p, &fr.surface_flag);
     if (st) return st;
     // [3] ICP of every cluster, against one template or all of them
@@ -443,6 +447,12 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
         if (lc.filtered) {   // cd_get_outlier_stats (the records' mirror has been valid since the cluster stage's synchronisation)
             c->last_outlier.assign(c->h_orec.get(), c->h_orec.get() + F);
             c->last_outlier_ok = true;
+        }
+        lc.prism = c->prism_on != 0;
+        if (lc.prism) {   // cd_get_prism_stats / cd_get_prism_hull (as the outlier records; the hulls stay in d_phull)
+            lc.omap_pitch = pmap_pitch;
+            c->last_prism.assign(c->h_prec.get(), c->h_prec.get() + F);
+            c->last_prism_ok = true;
         }
     }
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));

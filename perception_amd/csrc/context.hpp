@@ -18,6 +18,7 @@
 #include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "outlier_math.hpp"
+#include "prism_math.hpp"
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
 #include "icp_coarse_plan.hpp"
@@ -47,6 +48,8 @@ struct LastCall {
     VoxelKeys keys;
     bool filtered = false;          // rule C16: the call filtered its object clouds (d_omap / d_orec describe them, rows of omap_pitch)
     int omap_pitch = 0;
+    bool prism = false;             // rule C20: the call ran the table prism (d_pmap / d_plrec are then the map the label calls take: rows of
+                                    // omap_pitch, S3 index -> kept cloud, the filter's map already applied when it ran too)
 };
 
 // The streams and events of a context.  A base of cd_context, so that they outlive its buffers: the members of cd_context
@@ -233,6 +236,18 @@ struct cd_context : cd_streams {
     double reject_factor = 0.0;
     DevBuf<RejectStats> d_rstat; PinBuf<RejectStats> h_rstat;
     KeptRecords<cd_icp_reject_stats> last_reject;
+    // table prism (rule C20, k_prism.hip): the setting (cd_set_table_prism; prism_on = 0: off), and - grown on demand - the map of
+    // the last call with the step (one int per point of the cloud S3 left, rows of one pitch), one record per frame (device +
+    // pinned mirror), the same counts in the form the label calls read (d_plrec) and every frame's hull (CD_PRISM_MAX_HULL
+    // vertices each, read by cd_get_prism_hull); last_prism: the records behind cd_get_prism_stats
+    int prism_on = 0;
+    double prism_hmin = 0.0, prism_hmax = 0.5;
+    DevBuf<int> d_pmap;
+    DevBuf<PrismRecord> d_prec; PinBuf<PrismRecord> h_prec;
+    DevBuf<OutlierRecord> d_plrec;
+    DevBuf<int32_t> d_phull;
+    std::vector<PrismRecord> last_prism;
+    bool last_prism_ok = false;
     cd_timing timing;
 };
 
@@ -275,6 +290,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_surface_ok = false;
     c->last_bboxes_ok = false;
     c->last_outlier_ok = false;
+    c->last_prism_ok = false;
     c->last_shapes.invalidate();
     c->last_plane.invalidate();
     c->last_coarse.invalidate();
@@ -450,6 +466,9 @@ void fill_cluster_result(const cd_context* c, int k, const cd_params* p, cd_clus
 int stage_icp_levels(cd_context* c, int ncl, const cd_params* p, long long* pair_tests);
 // ---- outlier.hip
 int stage_outlier(cd_context* c, int F, int max_no, int* map_pitch);
+// ---- prism.hip
+int stage_prism(cd_context* c, int F, int max_no, int* map_pitch);
+int prism_compose_map(cd_context* c, int F, int map_pitch);
 // ---- surface.hip
 int ensure_surface(cd_context* c, size_t pitch);
 int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,

@@ -235,4 +235,23 @@ void launch_outlier_knn(hipStream_t s, const float4* pts, int N, int F, int max_
 void launch_outlier_select(hipStream_t s, const float4* pts, int N, int F, FrameState* fs, FrameState* mirror, const float* dist, int dpitch,
                            int mean_k, double std_mul, int negative, float4* out, int* map, int mpitch, int* kept_idx, OutlierRecord* rec);
 
+// k_prism.hip : rule C20, the table prism on F rows of N points.  Row f: its plane inliers are the points plane_pts[f * N +
+// plane_idx[f * N + i]], i < fs[f].n_plane (plane_idx == nullptr: the first n_plane points of the row); model[f] the plane, have[f]
+// whether it has one (nullptr: every row has); its cloud pts[f * N ..] of fs[f].n_o points.  scratch: N (u, v) pairs per row.
+// out / kept_idx / map / mirror as launch_outlier_select; rec[f] the row's record, lrec[f] the same counts in the form the label
+// calls read beside the map, hull[f * 2 * CD_PRISM_MAX_HULL ..] the row's hull vertices (nullptr: none).
+struct PrismRecord;
+struct PrismArgs {
+    const float4* plane_pts; const int* plane_idx; const float4* model; const int* have;
+    const float4* pts; int N;
+    FrameState* fs; FrameState* mirror;
+    double hmin, hmax;
+    int2* scratch;
+    float4* out; int* map; int mpitch; int* kept_idx;
+    PrismRecord* rec; OutlierRecord* lrec; int32_t* hull;
+};
+void launch_prism(hipStream_t s, int F, const PrismArgs& a);
+// pmap[f * pitch + e] <- omap[f * pitch + pmap[f * pitch + e]] (or -1), e < lrec[f].n_before: the prism's map followed by the filter's
+void launch_prism_compose_map(hipStream_t s, int F, int* pmap, const OutlierRecord* lrec, const int* omap, int pitch);
+
 }  // namespace cd

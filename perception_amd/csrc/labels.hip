@@ -37,7 +37,9 @@ int stage_labels(cd_context* c, const void* d_records, size_t stride, const uint
     const int* have_p = c->tun.mirror_reads ? c->h_active : c->d_have;
     LAUNCH(c, launch_label_voxel_classes(c->stream, c->d_vox, c->N, F, c->d_fs, model_p, have_p, ea.thr, p->extract_negative, p->crop2_enable, ea.z2lo, ea.z2hi,
                                          ea.gate, lc.rects, c->d_plane_idx, c->d_label, c->d_vclass, vpitch,
-                                         lc.filtered ? OutlierMap{c->d_omap, c->d_orec, lc.omap_pitch} : OutlierMap{nullptr, nullptr, 0}));
+                                         lc.prism      ? OutlierMap{c->d_pmap, c->d_plrec, lc.omap_pitch}   // (rule C20: its map, composed with the filter's when both ran)
+                                         : lc.filtered ? OutlierMap{c->d_omap, c->d_orec, lc.omap_pitch}
+                                                       : OutlierMap{nullptr, nullptr, 0}));
     LabelPointsParams lp;
     std::memset(&lp, 0, sizeof(lp));
     lp.lim.zlo = hm::fold_ge(p->crop_z_min); lp.lim.zhi = hm::fold_le(p->crop_z_max);

@@ -1,0 +1,125 @@
+// prism_math.hpp - the arithmetic of canonical rule C20 (perception_amd/table_prism.py is the specification): the
+// table prism.  Steps 1 to 5 (a point's height above the oriented plane and its integer coordinates in the plane) and step 7
+// (the keep test against the integer hull) written once for host and device, and the hull of step 6 as a plain monotone chain
+// for the host.  k_prism.hip runs it on the GPU, prism_math_check.cpp and the host helpers of prism.hip on the CPU.  One
+// correctly rounded IEEE double operation per operator, no contraction; from step 5 on everything is integer, so the result
+// does not depend on who computes it.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "common.hpp"
+
+namespace cd {
+
+constexpr int PRISM_MAX_HULL = CD_PRISM_MAX_HULL;      // hull vertices a frame may have
+constexpr int PRISM_LDS_POINTS = CD_PRISM_LDS_POINTS;  // pruned inliers k_prism keeps in LDS
+constexpr int32_t PRISM_QMIN = -(1 << 29), PRISM_QMAX = (1 << 29) - 1;
+
+#ifdef __HIP_DEVICE_COMPILE__
+#define CD_PR_MUL(a, b) __dmul_rn((a), (b))
+#define CD_PR_ADD(a, b) __dadd_rn((a), (b))
+#define CD_PR_SUB(a, b) __dsub_rn((a), (b))
+#else
+#define CD_PR_MUL(a, b) ((a) * (b))
+#define CD_PR_ADD(a, b) ((a) + (b))
+#define CD_PR_SUB(a, b) ((a) - (b))
+#endif
+
+// What the step did to one cloud (a frame of a fused call, or the cloud of cd_table_prism): cd_prism_stats
+struct PrismRecord {
+    int32_t n_before, n_kept, n_below, n_above, n_outside;
+    int32_t hull_vertices, axis_u, axis_v, overflow;
+    int32_t reserved[3];
+};
+
+struct PrismPlane {   // steps 1 and 4
+    double n[3], dd;
+    int32_t k1, k2;
+};
+
+__host__ __device__ inline PrismPlane prism_plane(float a, float b, float c, float d) {
+    PrismPlane P;
+    const double s = d < 0.0f ? -1.0 : 1.0;
+    P.n[0] = CD_PR_MUL(s, (double)a); P.n[1] = CD_PR_MUL(s, (double)b); P.n[2] = CD_PR_MUL(s, (double)c);
+    P.dd = CD_PR_MUL(s, (double)d);
+    const float m[3] = {fabsf(a), fabsf(b), fabsf(c)};
+    int k0 = 0;
+    if (m[1] > m[k0]) k0 = 1;
+    if (m[2] > m[k0]) k0 = 2;
+    P.k1 = k0 == 0 ? 1 : 0;
+    P.k2 = k0 == 2 ? 1 : 2;
+    return P;
+}
+
+// step 5 of one coordinate: floor(t * 65536) clamped to [-2^29, 2^29 - 1], a NaN to the lower end
+__host__ __device__ inline int32_t prism_quantise(double t) {
+    const double q = floor(CD_PR_MUL(t, 65536.0));
+    return q >= (double)PRISM_QMIN ? (q <= (double)PRISM_QMAX ? (int32_t)q : PRISM_QMAX) : PRISM_QMIN;
+}
+
+// steps 2, 3 and 5 of one point: its height and its integer coordinates on the axes the plane keeps
+__host__ __device__ inline void prism_project(const PrismPlane& P, float x, float y, float z, double* height, int32_t* u, int32_t* v) {
+    const double p[3] = {(double)x, (double)y, (double)z};
+    const double h = CD_PR_ADD(CD_PR_ADD(CD_PR_ADD(CD_PR_MUL(P.n[0], p[0]), CD_PR_MUL(P.n[1], p[1])), CD_PR_MUL(P.n[2], p[2])), P.dd);
+    *height = h;
+    // (selects, not an indexed read: the arrays stay in registers on the device)
+    const double p1 = P.k1 == 0 ? p[0] : p[1], n1 = P.k1 == 0 ? P.n[0] : P.n[1];
+    const double p2 = P.k2 == 2 ? p[2] : p[1], n2 = P.k2 == 2 ? P.n[2] : P.n[1];
+    *u = prism_quantise(CD_PR_SUB(p1, CD_PR_MUL(h, n1)));
+    *v = prism_quantise(CD_PR_SUB(p2, CD_PR_MUL(h, n2)));
+}
+
+// cross(B - A, P - A) of integer points: differences below 2^30 in magnitude, products below 2^60, the result fits int64
+__host__ __device__ inline int64_t prism_cross(int32_t au, int32_t av, int32_t bu, int32_t bv, int32_t pu, int32_t pv) {
+    return (int64_t)(bu - au) * (int64_t)(pv - av) - (int64_t)(bv - av) * (int64_t)(pu - au);
+}
+
+// step 7.  The class of a point: 0 kept, 1 below, 2 above (a NaN height included), 3 outside the hull (or no hull of 3 vertices).
+// hull: nh vertices, counter-clockwise, u and v interleaved.
+enum { PRISM_KEPT = 0, PRISM_BELOW = 1, PRISM_ABOVE = 2, PRISM_OUTSIDE = 3 };
+__host__ __device__ inline int prism_classify(double h, int32_t u, int32_t v, double height_min, double height_max, const int32_t* hull, int nh) {
+    if (h < height_min) return PRISM_BELOW;
+    if (!(h <= height_max)) return PRISM_ABOVE;
+    if (nh < 3) return PRISM_OUTSIDE;
+    int32_t au = hull[2 * (nh - 1)], av = hull[2 * (nh - 1) + 1];
+    for (int i = 0; i < nh; ++i) {
+        const int32_t bu = hull[2 * i], bv = hull[2 * i + 1];
+        if (prism_cross(au, av, bu, bv, u, v) < 0) return PRISM_OUTSIDE;
+        au = bu; av = bv;
+    }
+    return PRISM_KEPT;
+}
+
+// step 6 on the host: Andrew's monotone chain over the distinct points.  Returns the number of strict hull vertices - which may
+// exceed capacity - and writes the first min(count, capacity) of them, counter-clockwise from the lexicographically smallest.
+inline int prism_hull_host(const int32_t* uv, int n, int32_t* hull, int capacity) {
+    std::vector<std::pair<int32_t, int32_t>> p((size_t)std::max(n, 0));
+    for (int i = 0; i < n; ++i) p[(size_t)i] = {uv[2 * (size_t)i], uv[2 * (size_t)i + 1]};
+    std::sort(p.begin(), p.end());
+    p.erase(std::unique(p.begin(), p.end()), p.end());
+    std::vector<std::pair<int32_t, int32_t>> h;
+    if (p.size() <= 2) h = p;
+    else {
+        h.resize(2 * p.size());
+        size_t k = 0;
+        auto turn = [&](const std::pair<int32_t, int32_t>& q) { return prism_cross(h[k - 2].first, h[k - 2].second, h[k - 1].first, h[k - 1].second, q.first, q.second); };
+        for (size_t i = 0; i < p.size(); ++i) {
+            while (k >= 2 && turn(p[i]) <= 0) --k;
+            h[k++] = p[i];
+        }
+        const size_t lower = k + 1;
+        for (size_t i = p.size() - 1; i-- > 0;) {
+            while (k >= lower && turn(p[i]) <= 0) --k;
+            h[k++] = p[i];
+        }
+        h.resize(k - 1);   // (the last point is the first again)
+    }
+    for (size_t i = 0; i < h.size() && (int)i < capacity; ++i) { hull[2 * i] = h[i].first; hull[2 * i + 1] = h[i].second; }
+    return (int)h.size();
+}
+
+}  // namespace cd
