@@ -147,7 +147,7 @@ struct IcpSuper {
 constexpr int LAT_MAX_FACES = 6;           // (a cuboid has six)
 constexpr int LAT_MAX_TAB = 512;           // axis table entries of one template, the three axes together
 struct IcpLattice {
-    int32_t nface;                 // 0: not a lattice - the generic searches of k_icp.hip take the template
+    int32_t nface;                 // 0: not a lattice - the generic searches of icp_search.hpp take the template
     int32_t ntab;                  // entries of tab in use
     int32_t n[3];                  // entries of the axis tables X, Y, Z (0: no face varies along that axis)
     int32_t toff[3];               // first entry of each table in tab

@@ -268,7 +268,7 @@ inline int whole_launch_grid(int n_items, int cap, int icp_cpw, bool crowded, in
 }
 
 // A launch that has the GPU to itself lets workgroups that run out of clusters wait and take over running ones
-// (k_icp.hip, "hand-over of running clusters"): the launch is as long as its slowest workgroup, and the bench batch's
+// (k_icp_pipe.hip, "hand-over of running clusters"): the launch is as long as its slowest workgroup, and the bench batch's
 // slowest runs 25 % over the average.  With other calls in flight a waiting workgroup would sit on a CU their
 // kernels could use, and what counts there is the CU-time a batch costs, which hand-overs do not lower.
 inline bool whole_donate(int icp_donate, int batches_in_flight, int ncl, int grid) {

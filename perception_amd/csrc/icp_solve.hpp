@@ -1,4 +1,4 @@
-// icp_solve.hpp - device code shared by the ICP kernels (k_icp.hip, k_icp_lat.hip): TransformationEstimationSVD
+// icp_solve.hpp - device code shared by the ICP kernels (k_icp.hip, k_icp_cluster.hip, k_icp_pipe.hip, k_icp_lat.hip): TransformationEstimationSVD
 // (pcl::umeyama with Eigen's two-sided Jacobi SVD restated in float32) from the 16 fixed-point moment sums, the
 // canonical 4x4 x point product, and icp_step - one PCL iteration's state update, the same for every driver.  Reference: pcl::IterativeClosestPoint as called at
 // cuboid_detection/src/iterative_closest_point.cpp:170-178 and object_detection/src/object_pose_detection.cpp:220-228.

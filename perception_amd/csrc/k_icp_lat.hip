@@ -5,7 +5,7 @@
 // templates cuboid_detection/templates/make_cuboid.py:38-55 writes: face k = meshgrid of two of the three axis tables
 // X, Y, Z at a constant third coordinate, first axis fastest, faces one after the other.  cd_set_template verifies that
 // structure bit by bit against the uploaded points (lattice_detect, template_prep.hpp) and hands over IcpLattice (common.hpp);
-// every other template keeps the pruned searches of k_icp.hip.
+// every other template keeps the pruned searches of icp_search.hpp and k_icp_pipe.hip.
 //
 // The search.  The canonical squared distance (rule C1/C5, common.hpp dist2) to point (i, j) of a face with constant z = c is
 //     d2(i, j) = fl(fl(fx(i) + fy(j)) + fz),   fx(i) = fl(fl(qx - X[i])^2),  fy(j) = fl(fl(qy - Y[j])^2),  fz = fl(fl(qz - c)^2)

@@ -91,7 +91,7 @@ void launch_label_count(hipStream_t s, int N, int F, int T, int Tact, const Fram
 void launch_label_scatter(hipStream_t s, const float4* obj, int N, int F, int T, int Tact, const FrameState* fs,
                           const int* label, const int* tile_off, float4* src0, float4* src, int kbase, const int* koff_tab);
 
-// k_icp.hip
+// k_icp.hip (sliced and persistent), k_icp_cluster.hip (whole cluster), k_icp_pipe.hip (pipelined)
 // What every ICP launch takes, in three blocks that icp_stage.hip fills once per stage; each launcher picks what its kernel reads.
 struct IcpProblems {   // the problem set: device pointers, or (k_icp_lat's direct mode) the pinned host arrays
     const int* order; const IcpCluster* cl; IcpState* st; unsigned long long* accf;

@@ -232,7 +232,7 @@ inline IcpGrid build_grid(std::vector<TP>& tp, float cell_factor) {
     return grid;
 }
 
-// Sorts the template by the cells of the grid.  The lane-per-query search of k_icp.hip scans the few cell rows a query's seed
+// Sorts the template by the cells of the grid.  The lane-per-query search of icp_search.hpp scans the few cell rows a query's seed
 // ball touches; consecutive runs of 64 stored points are still spatially compact (a strip of one cell row), which is what the
 // run boxes of the wave-per-query search feed on.  Each stored point keeps its ORIGINAL index; the nearest-neighbour tie rule
 // (lowest original index) is evaluated on that.  Templates the persistent kernels can walk (uint16 positions) also get the

@@ -388,7 +388,7 @@ def _mixed_templates_case(which, pair):
 @pytest.mark.parametrize("pair", [(4, 5), (0, 7)], ids=["18_problems", "6_problems"])
 @pytest.mark.parametrize("which", ["chunk_table_10700", "fixed_chunks_65536"])
 def test_resident_and_chunked_templates_in_one_launch(which, pair, monkeypatch):
-    """The LDS image a workgroup keeps between work items (`staged`, k_icp.hip) across templates of different kinds in ONE
+    """The LDS image a workgroup keeps between work items (`staged`, k_icp.hip and k_icp_cluster.hip) across templates of different kinds in ONE
     launch: the default template and a scanned one (both LDS-resident) and a third that is searched chunk by chunk - by its
     chunk table (10 700 points) or, with the table empty (65 536 points: more than 12 k-d subtrees of at most 7552), in fixed
     chunks - template_slot = -1, so every cluster meets all three.  A chunked walk must leave "nothing resident" behind, or

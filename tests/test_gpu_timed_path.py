@@ -117,7 +117,7 @@ def test_pipe_slot_refill_with_capped_grid(O, template, max_wg, slots, monkeypat
 @pytest.mark.parametrize("slots", ["2", "4"])
 def test_pipe_handover_of_running_clusters(O, template, slots, lowprio, monkeypatch):
     """A launch that has the GPU to itself lets workgroups that ran out of clusters take over RUNNING ones from workgroups
-    that still have several (k_icp.hip, pipe_give / pipe_wait_for_cluster: the cluster's points and neighbour indices cross to
+    that still have several (k_icp_pipe.hip, pipe_give / pipe_wait_for_cluster: the cluster's points and neighbour indices cross to
     another CU, possibly another XCD, in the middle of its ICP).  Deterministic, not a matter of timing: with
     CUBOID_ICP_DON_IDLE=1 workgroup 0 never takes from the queue, so every cluster it runs reached it by hand-over, and with
     31 clusters on 8 workgroups the other seven hold several clusters each for most of the launch - at least one hand-over

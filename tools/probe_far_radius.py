@@ -1,5 +1,5 @@
 """Seed-ball radius (in grid cells) of the queries the persistent ICP kernels hand to the wave-per-query search, by iteration class
-   tools/build_variant.sh stats k_icp.hip -DCD_STATS; CUBOID_ICP_MODE=pipe CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python tools/probe_far_radius.py [c3|c5] [F]"""
+   tools/build_variant.sh stats k_icp_pipe.hip -DCD_STATS; CUBOID_ICP_MODE=pipe CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python tools/probe_far_radius.py [c3|c5] [F]"""
 import sys, os, ctypes as C, numpy as np
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)

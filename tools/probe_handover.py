@@ -1,5 +1,5 @@
 """Timeline of the hand-overs of running clusters in k_icp_pipe (needs a -DCD_DONDBG build:
-   tools/build_variant.sh dondbg k_icp.hip -DCD_DONDBG; CUBOID_HIP_LIB=perception_amd/lib/variants/libdondbg.so python tools/probe_handover.py [F])"""
+   tools/build_variant.sh dondbg k_icp_pipe.hip -DCD_DONDBG; CUBOID_HIP_LIB=perception_amd/lib/variants/libdondbg.so python tools/probe_handover.py [F])"""
 import sys, os, ctypes as C, numpy as np
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)

@@ -1,6 +1,6 @@
 """Executed work of the dominant kernel (k_icp_pipe) on the bench batch, counted by a -DCD_STATS build, written to
 profiles/r03_icp_work.json (bench.py's roofline.valu block reads it).
-   tools/build_variant.sh stats k_icp.hip -DCD_STATS
+   tools/build_variant.sh stats k_icp_pipe.hip -DCD_STATS
    CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python tools/probe_icp_work.py [out.json]
 A "pair test" is one evaluation of the canonical squared distance (3 subtractions, 3 multiplications, 2 additions = 8 flops)
 between a query and a template point by one lane - executed work, including the lanes of a wave that test a point they do not

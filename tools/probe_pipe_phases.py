@@ -1,5 +1,5 @@
 """Where the waves of k_icp_pipe / k_icp_pipe_big spend their time (needs a -DCD_TIMERS build:
-   tools/build_variant.sh timers k_icp.hip -DCD_TIMERS; CUBOID_HIP_LIB=perception_amd/lib/variants/libtimers.so python tools/probe_pipe_phases.py [default|big|cfg5big] [F])
+   tools/build_variant.sh timers k_icp_pipe.hip -DCD_TIMERS; CUBOID_HIP_LIB=perception_amd/lib/variants/libtimers.so python tools/probe_pipe_phases.py [default|big|cfg5big] [F])
    phases: 0 epoch wait, 1 fetch + seeds, 2 grid walk, 3 solve / hand-over, 4 wave-per-query search, 5 moments + fold."""
 import sys, os, time, ctypes as C, numpy as np
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

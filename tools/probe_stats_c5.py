@@ -1,5 +1,5 @@
 """CD_STATS counters of the persistent ICP kernels on BASELINE config 5 frames (every cluster x the LDS-resident templates, or all five)
-   tools/build_variant.sh stats k_icp.hip -DCD_STATS; CUBOID_ICP_MODE=pipe CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python tools/probe_stats_c5.py [lds|all] [F]"""
+   tools/build_variant.sh stats k_icp_pipe.hip -DCD_STATS; CUBOID_ICP_MODE=pipe CUBOID_HIP_LIB=perception_amd/lib/variants/libstats.so python tools/probe_stats_c5.py [lds|all] [F]"""
 import sys, os, ctypes as C, numpy as np
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
