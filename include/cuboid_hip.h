@@ -1093,6 +1093,69 @@ int cd_table_prism(cd_context* ctx, const void* plane_xyz, size_t plane_stride, 
 int cd_prism_project(const float coeff[4], const float xyz[3], double* height, int32_t uv[2], int32_t axes[2]);
 int cd_prism_hull_host(const int32_t* uv, int n, int32_t* hull, int capacity, int* n_hull);
 
+/* Two-way registration score of a (cluster, template) pair: how much of the template the aligned cluster accounts for, beside how
+ * well the cluster lies on the template - what PCL users take from getFitnessScore(max_range) and
+ * TransformationValidationEuclidean.  Opt-in, off by default.  Canonical rule C21; perception_amd/pair_score.py is
+ * the rule in numpy and the device equals it bit for bit.  Parity with a real PCL is unpinned (its validation has thresholds of
+ * its own, float sums and a k-d tree).  For the cluster's n points src as extracted (cd_get_cluster_points(aligned = 0)), the
+ * result's T, the m points tpl of its template_slot and a range d (a double, finite, > 0):
+ *   1. A_i = T src_i, once, in float32, every product and sum rounded on its own: ((T[4r] x + T[4r+1] y) + T[4r+2] z) + T[4r+3] for
+ *      row r - the order of cd_get_cluster_points(aligned != 0) when the kept pass is no longer resident, so A is that read-back.
+ *      The ICP's iterated cloud is not used: the score is a function of (src, T, tpl, d);
+ *   2. d2(p, q) = (dx dx + dy dy) + dz dz in float32; f_i = min_j d2(A_i, tpl_j), r_j = min_i d2(tpl_j, A_i): exact minima over
+ *      all pairs, no index, so neither order nor ties matter;
+ *   3. tau = rule C8's threshold of d (cd_icp_correspondence_threshold); a distance equal to tau is inside;
+ *   4. n_source_in = #{i: f_i <= tau}, n_template_in = #{j: r_j <= tau};
+ *   5. three rule-C4 sums of fixq(min(v, 256), 36), 64-bit integers: of f over the inside source points, of r over the inside
+ *      template points and of r over all m.  A term is clamped to 256 m^2 (a neighbour 16 m away; inside rule C4's range,
+ *      |coordinate| <= 64, a d2 reaches 49152) so that 2^19 terms of at most 2^44 sum to at most 2^63, inside an unsigned 64-bit integer.  forward_fitness_in and
+ *      reverse_fitness_in: (double) S 2^-36 / count, 0 for a count of 0; reverse_fitness = (double) S_all 2^-36 / m;
+ *   6. coverage = n_template_in / m, inlier_fraction = n_source_in / n, in double;
+ *   7. valid = accepted && coverage >= min_coverage && inlier_fraction >= min_inlier_fraction (the boundary is valid);
+ *   8. status, the first that applies: CD_ERR_NO_TEMPLATE for an empty slot, CD_ERR_FEW_CORRESPONDENCES for n < 3 (a cluster whose
+ *      ICP stopped under rule C8 keeps its T and is scored like any other), CD_ERR_CAPACITY for n or m above 2^19,
+ *      CD_ERR_INVALID_ARG for a non-finite entry of T or a non-finite coordinate of tpl or A.  Such a record holds n_source,
+ *      n_template, status and zeros.
+ * A template's hidden faces count as uncovered (no visibility reasoning), which is why min_coverage is a setting.
+ *
+ * cd_set_pair_score: context state.  enable = 0 (the default): a fused call launches nothing more and every output is byte for
+ * byte what it was.  max_range not finite or <= 0, or a fraction outside [0, 1] (NaN included): CD_ERR_INVALID_ARG and the
+ * setting stays.  With the mode on, every fused call scores each cluster result against the slot it reports, after its ICP;
+ * cd_frame_result, cd_cluster_result (accepted, fitness, poses, the slot) and every other read-back are unchanged. */
+#define CD_PAIR_SCORE_RANGE_DEFAULT 0.005
+#define CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT 0.5
+#define CD_PAIR_SCORE_MIN_INLIER_DEFAULT 0.8
+typedef struct cd_pair_score {
+    int32_t n_source;           /* n                                                                                     */
+    int32_t n_source_in;        /* source points whose nearest template point is within the range                        */
+    int32_t n_template;         /* m                                                                                     */
+    int32_t n_template_in;      /* template points whose nearest aligned source point is within the range                */
+    int32_t valid;              /* step 7                                                                                */
+    int32_t status;             /* step 8                                                                                */
+    double forward_fitness_in;  /* mean f over the inside source points                                                  */
+    double reverse_fitness_in;  /* mean r over the inside template points                                                */
+    double reverse_fitness;     /* mean r over the whole template (terms clamped to 256)                                 */
+    double coverage;            /* n_template_in / m                                                                     */
+    double inlier_fraction;     /* n_source_in / n                                                                       */
+} cd_pair_score;
+int cd_set_pair_score(cd_context* ctx, int enable, double max_range, double min_coverage, double min_inlier_fraction);
+int cd_get_pair_score(const cd_context* ctx, int* enable, double* max_range, double* min_coverage, double* min_inlier_fraction);
+int cd_pair_score_struct_size(void);   /* sizeof(cd_pair_score) (cd_struct_size's list is closed) */
+/* The scores of the last fused call's cluster results, indexed like cd_get_cluster_results (clusters beyond
+ * CD_MAX_CLUSTERS_PER_FRAME included).  Returns the number copied; CD_ERR_INVALID_ARG when the call ran with the mode off, has
+ * been invalidated by another compute call, or had no such frame.  cd_icp alone produces no score. */
+int cd_get_cluster_pair_scores(const cd_context* ctx, int frame, int first, int count, cd_pair_score* out);
+/* One pair from host points, on the GPU, without a fused call: src_xyz (n points, stride_bytes apart) against the template of
+ * `slot` under T (row-major 4x4 float32).  The thresholds are the call's own (the context's setting is neither read nor changed);
+ * `accepted` is the flag step 7 starts from.  A bad argument (a null pointer, n < 0, a bad stride or slot, thresholds the setter
+ * would refuse): CD_ERR_INVALID_ARG; n above the context's max_points: CD_ERR_CAPACITY.  Otherwise CD_OK with the record's own
+ * status in out->status.  Like every compute call it invalidates the read-backs of the last fused call. */
+int cd_pair_score_points(cd_context* ctx, int slot, const void* src_xyz, size_t stride_bytes, int n, const float T[16], double max_range,
+                         double min_coverage, double min_inlier_fraction, int accepted, cd_pair_score* out);
+/* Host only (no context, no GPU): the same rule by two plain loops over all pairs, through the arithmetic header the kernel uses. */
+int cd_pair_score_host(const void* tpl_xyz, size_t tpl_stride, int m, const void* src_xyz, size_t src_stride, int n, const float T[16],
+                       double max_range, double min_coverage, double min_inlier_fraction, int accepted, cd_pair_score* out);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "cd_icp_median_threshold",
     "cd_set_table_prism", "cd_get_table_prism", "cd_prism_struct_size", "cd_get_prism_stats", "cd_get_prism_hull", "cd_table_prism",
     "cd_prism_project", "cd_prism_hull_host",
+    "cd_set_pair_score", "cd_get_pair_score", "cd_pair_score_struct_size", "cd_get_cluster_pair_scores", "cd_pair_score_points",
+    "cd_pair_score_host",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
@@ -81,6 +83,8 @@ CD_NOTEX_DROP, CD_NOTEX_KEEP = 0, 1
 CD_LABEL_INVALID, CD_LABEL_CROPPED, CD_LABEL_PLANE, CD_LABEL_OBJECT, CD_LABEL_GATED, CD_LABEL_CLUSTER0 = 0, 1, 2, 3, 4, 8
 CD_OUTLIER_MAX_MEAN_K, CD_OUTLIER_LDS_TILE = 63, 1024
 CD_PRISM_MAX_HULL, CD_PRISM_LDS_POINTS = 1024, 4096
+# rule C21 (cd_set_pair_score): the recommended setting
+CD_PAIR_SCORE_RANGE_DEFAULT, CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT, CD_PAIR_SCORE_MIN_INLIER_DEFAULT = 0.005, 0.5, 0.8
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -107,6 +111,16 @@ class CdPrismStats(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_[:9]}
+
+
+class CdPairScore(C.Structure):
+    """cd_pair_score: the two-way registration score (rule C21) of one (cluster, template) pair."""
+    _fields_ = [("n_source", C.c_int32), ("n_source_in", C.c_int32), ("n_template", C.c_int32), ("n_template_in", C.c_int32), ("valid", C.c_int32),
+                ("status", C.c_int32), ("forward_fitness_in", C.c_double), ("reverse_fitness_in", C.c_double), ("reverse_fitness", C.c_double),
+                ("coverage", C.c_double), ("inlier_fraction", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
 class CdShapeFrame(C.Structure):
@@ -525,6 +539,13 @@ def load_library(path=None):
     lib.cd_table_prism.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_double, C.c_double, vp, C.c_int, ip, psp, vp, C.c_int]
     lib.cd_prism_project.argtypes = [vp, vp, dp, vp, vp]
     lib.cd_prism_hull_host.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+    pcp = C.POINTER(CdPairScore)
+    lib.cd_set_pair_score.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
+    lib.cd_get_pair_score.argtypes = [vp, ip, dp, dp, dp]
+    lib.cd_pair_score_struct_size.argtypes = []
+    lib.cd_get_cluster_pair_scores.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_pair_score_points.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, pcp]
+    lib.cd_pair_score_host.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, pcp]
     if path is None:
         _lib = lib
     return lib
@@ -1098,6 +1119,35 @@ class Context:
         msg = "no median-rejection call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
         return self._cluster_records(self.lib.cd_get_cluster_reject_stats, CdIcpRejectStats, msg, frame, first, count)
 
+    def set_pair_score(self, enable, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_coverage=CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT,
+                       min_inlier_fraction=CD_PAIR_SCORE_MIN_INLIER_DEFAULT):
+        """Rule C21, the two-way registration score, for every later fused call of this context: each cluster result is scored
+        against the template it reports (coverage of the template, inlier fraction, bounded fitnesses, `valid`).  Off by default."""
+        self._check(self.lib.cd_set_pair_score(self.h, 1 if enable else 0, float(max_range), float(min_coverage), float(min_inlier_fraction)))
+
+    def pair_score_setting(self):
+        """(enable, max_range, min_coverage, min_inlier_fraction) as cd_set_pair_score left them."""
+        on, d, a, b = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        self._check(self.lib.cd_get_pair_score(self.h, C.byref(on), C.byref(d), C.byref(a), C.byref(b)))
+        return on.value, d.value, a.value, b.value
+
+    def cluster_pair_scores(self, frame, first=0, count=None):
+        """Rule C21's records of the clusters of `frame` of the last fused call, indexed like cluster_results: a list of CdPairScore."""
+        msg = "no pair-score call to read: the last fused call ran with the mode off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_pair_scores, CdPairScore, msg, frame, first, count)
+
+    def pair_score_points(self, slot, src, T, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_coverage=CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT,
+                          min_inlier_fraction=CD_PAIR_SCORE_MIN_INLIER_DEFAULT, accepted=1):
+        """One pair on the GPU without a fused call: src (n, >= 3) float32 against the template of `slot` under T.  Returns a dict
+        of cd_pair_score's fields (its own status in "status")."""
+        src = np.asarray(src, np.float32)
+        a, stride, n = _points(src if src.ndim == 2 else src.reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        out = CdPairScore()
+        self._check(self.lib.cd_pair_score_points(self.h, int(slot), _ptr(a), stride, n, _ptr(t), float(max_range), float(min_coverage),
+                                                  float(min_inlier_fraction), 1 if accepted else 0, C.byref(out)))
+        return out.as_dict()
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1280,6 +1330,21 @@ def icp_median_threshold(d2, factor):
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_median_threshold")
     return np.float32(m.value), np.float64(t.value)
+
+
+def pair_score_host(tpl, src, T, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_coverage=CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT,
+                    min_inlier_fraction=CD_PAIR_SCORE_MIN_INLIER_DEFAULT, accepted=1):
+    """cd_pair_score_host: rule C21 on the host (no context, no GPU).  Returns a dict of cd_pair_score's fields."""
+    lib = load_library()
+    tp = np.ascontiguousarray(np.asarray(tpl, np.float32).reshape(-1, 3))
+    sp = np.ascontiguousarray(np.asarray(src, np.float32).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+    out = CdPairScore()
+    st = lib.cd_pair_score_host(_ptr(tp), 12, len(tp), _ptr(sp), 12, len(sp), _ptr(t), float(max_range), float(min_coverage),
+                                float(min_inlier_fraction), 1 if accepted else 0, C.byref(out))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_pair_score_host")
+    return out.as_dict()
 
 
 def prism_project(coeff, xyz):

@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "outlier_math.hpp"
 #include "prism_math.hpp"
+#include "pair_score_math.hpp"
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
 #include "icp_coarse_plan.hpp"
@@ -248,6 +249,15 @@ struct cd_context : cd_streams {
     DevBuf<int32_t> d_phull;
     std::vector<PrismRecord> last_prism;
     bool last_prism_ok = false;
+    // two-way registration score (rule C21, k_pair_score.hip): the setting (cd_set_pair_score; pair_on = 0: off), and - grown on
+    // demand - the jobs and items of a launch (pinned + device), the pairs' integer rows with the queue word behind them (device +
+    // pinned mirror); last_pair: what cd_get_cluster_pair_scores reads, one record per cluster of the last fused call
+    int pair_on = 0;
+    double pair_range = CD_PAIR_SCORE_RANGE_DEFAULT, pair_min_cov = CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT, pair_min_inl = CD_PAIR_SCORE_MIN_INLIER_DEFAULT;
+    DevBuf<PairJob> d_psjob; PinBuf<PairJob> h_psjob;
+    DevBuf<PairItem> d_psitem; PinBuf<PairItem> h_psitem;
+    DevBuf<unsigned long long> d_psacc; PinBuf<unsigned long long> h_psacc;
+    KeptRecords<cd_pair_score> last_pair;
     cd_timing timing;
 };
 
@@ -295,6 +305,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_plane.invalidate();
     c->last_coarse.invalidate();
     c->last_reject.invalidate();
+    c->last_pair.invalidate();
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -469,6 +480,9 @@ int stage_outlier(cd_context* c, int F, int max_no, int* map_pitch);
 // ---- prism.hip
 int stage_prism(cd_context* c, int F, int max_no, int* map_pitch);
 int prism_compose_map(cd_context* c, int F, int map_pitch);
+// ---- pair_score.hip (rule C21): the fused call's step behind its ICP - every cluster result of the batch against the slot it reports,
+// into last_pair (begun here, published by publish_last)
+int stage_pair_scores(cd_context* c, int ncl, const std::vector<long long>& orig_off);
 // ---- surface.hip
 int ensure_surface(cd_context* c, size_t pitch);
 int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,

@@ -254,4 +254,14 @@ void launch_prism(hipStream_t s, int F, const PrismArgs& a);
 // pmap[f * pitch + e] <- omap[f * pitch + pmap[f * pitch + e]] (or -1), e < lrec[f].n_before: the prism's map followed by the filter's
 void launch_prism_compose_map(hipStream_t s, int F, int* pmap, const OutlierRecord* lrec, const int* omap, int pitch);
 
+// k_pair_score.hip : rule C21, the two-way registration score (pair_score_math.hpp).  A job is one direction of one pair: q_src != 0:
+// the queries are the nq points src[q_off ..] under T and the targets the ng points tpl[g_off ..]; q_src == 0: the queries are
+// tpl[q_off ..] and the targets src[g_off ..] under T.  An item is the queries q0 .. q0 + qn (1 <= qn <= PS_CHUNK) of a job.
+// n_wg workgroups draw the items from *queue (zero before the launch) and add into acc[pair * PAIR_ACC_PITCH ..] (zero before it).
+constexpr int PS_THREADS = 256, PS_ROWS = 4, PS_CHUNK = 1024, PS_TILE = 1024;
+struct PairJob { int32_t q_off, nq, g_off, ng, q_src, pair, pad[2]; float T[12]; };
+struct PairItem { int32_t job, q0, qn, pad; };
+void launch_pair_score(hipStream_t s, int n_items, int n_wg, const PairJob* jobs, const PairItem* items, const float4* src, const float4* tpl, float tau,
+                       unsigned long long* acc, int* queue);
+
 }  // namespace cd
