@@ -71,6 +71,7 @@ enum { ARITH_SEQUENTIAL = 1, ARITH_REVERSE_TIES = 2, ARITH_PROBE = 4 };
 static thread_local int t_arith = 0;
 static thread_local double t_probe[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [4] step transform incl. ill-conditioned steps, [5] their count, [6] steps
 static thread_local float t_last_sv[3] = {0, 0, 0};   // singular values of the last umeyama covariance
+static thread_local int t_last_branch[3] = {0, 0, 0};   // ... its rank, det(sigma) < 0, det U * det V > 0 (orc_umeyama_from_moments)
 
 inline float ldf(const uint8_t* p) {
     float f;
@@ -838,6 +839,7 @@ void umeyama_from_sigma(const float mpf[3], const float mqf[3], const float sigm
     int rank = 0;
     for (int i = 0; i < 3; ++i)
         if (!(std::fabs(S[i]) <= std::fabs(S[0]) * 1e-5f)) ++rank;  // !isMuchSmallerThan
+    t_last_branch[0] = rank; t_last_branch[1] = det3(sigma) < 0.f; t_last_branch[2] = det3(U) * det3(V) > 0.f;
     float R[3][3];
     auto usvt = [&](const float s[3]) {
         for (int i = 0; i < 3; ++i)
@@ -1344,6 +1346,15 @@ int orc_svd3(const float A[9], float U[9], float S[3], float V[9]) {
     jacobi_svd3(a, u, S, v);
     std::memcpy(U, u, 36);
     std::memcpy(V, v, 36);
+    return CD_OK;
+}
+
+// One TransformationEstimationSVD from the 16 fixed-point moment sums of rule C4 ([0..2] sum p, [3..5] sum q, [6..14] sum q_a p_b,
+// [15] unused here) - the estimate every ICP iteration of icp() makes.  info[6]: the rank it found, det3(sigma) < 0,
+// det U * det V > 0, the three singular values.
+int orc_umeyama_from_moments(const uint64_t sums[16], int n, float T[16], double info[6]) {
+    umeyama_from_moments(sums, sums + 3, sums + 6, n, T);
+    for (int i = 0; i < 3; ++i) { info[i] = (double)t_last_branch[i]; info[3 + i] = (double)t_last_sv[i]; }
     return CD_OK;
 }
 

@@ -150,6 +150,16 @@ def svd3(A):
     return U, S, V
 
 
+def umeyama_from_moments(sums, n):
+    """umeyama_from_moments on one set of rule C4's 16 sums (uint64) and its count.  Returns (T float32 (4, 4), info dict: rank,
+    det_negative (det3(sigma) < 0), uv_positive (det U * det V > 0), S (the float32 singular values))."""
+    a = np.ascontiguousarray(sums, np.uint64).reshape(16)
+    T = np.zeros(16, np.float32)
+    info = np.zeros(6, np.float64)
+    lib().orc_umeyama_from_moments(_p(a), int(n), _p(T), _p(info))
+    return T.reshape(4, 4), dict(rank=int(info[0]), det_negative=bool(info[1]), uv_positive=bool(info[2]), S=info[3:6].astype(np.float32))
+
+
 def eigen33_smallest(cov):
     c = np.ascontiguousarray(cov, np.float32)
     v = np.zeros(3, np.float32)

@@ -7,7 +7,9 @@ diagonal: no rotation or a single one, the ends of the sums' range), 4g + 2 has 
 wave (the BOUNDED launch stops that row beside three running ones; the unbounded launch solves it, n = 0 giving inf and NaN
 means), 4g + 3 is a near-identity motion that converges by another branch than its neighbours.  Row == single lane in every byte.
 For moments the CPU oracle can express - the first iteration of an ICP of a small cluster - both equal the oracle's step.
-The same entry compares sqrt_ge1 / rcp_ge1 with the IEEE operations for every float of their domain (3.2e9 evaluations)."""
+The same entry compares sqrt_ge1 / rcp_ge1 with the IEEE operations for every float of their domain (3.2e9 evaluations).
+The single-lane solver is the REFERENCE here; whether it is right is checked in tests/test_gpu_icp_solve_truth.py (and, on the
+host, tests/test_icp_solve_truth_cpu.py) against a float64 Umeyama written from the definition."""
 import numpy as np
 import pytest
 
