@@ -237,7 +237,14 @@ int cd_crop_voxel(cd_context* ctx, const void* points, size_t stride_bytes, int 
 int cd_passthrough(cd_context* ctx, const void* points, size_t stride_bytes, int n, int field, double limit_min,
                    double limit_max, int negative, void* out_points, int capacity, int* out_n);
 
-/* S2: seg.segment(*inliers, *coefficients) (gps.cpp:93).  inliers ascending. */
+/* S2: seg.segment(*inliers, *coefficients) (gps.cpp:93).  inliers ascending.
+ * The device draws the samples of a frame from 32768 precomputed random numbers and keeps PCL's shuffled index vector in a map of
+ * 6144 usable slots; a sample that isSampleGood rejects (three collinear points with exactly equal float ratios: none on sensor
+ * data) costs three numbers and up to three slots like one that is kept.  PCL has neither limit.  When PCL's loop would ask for a
+ * hypothesis beyond them the call returns CD_ERR_CAPACITY (cd_last_error names the limits) instead of the best model so far;
+ * cd_ground_plane does the same, a frame of a fused call carries CD_ERR_CAPACITY in its status - its record otherwise that of a
+ * frame without a plane - while the call returns CD_OK, and the surface fits report the fit as failed (CD_ERR_NO_MODEL).  A
+ * frame whose loop ends within what could be drawn is not affected. */
 int cd_segment_plane(cd_context* ctx, const void* xyz, size_t stride_bytes, int n,
                      const cd_params* prm, float coeff[4], int32_t* inliers, int capacity,
                      int* out_n_inliers, int* out_iterations);

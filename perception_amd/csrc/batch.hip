@@ -76,6 +76,7 @@ int batch_prologue(cd_context* c, int gate_source, const void* d_frames, int F, 
 struct FrontStages {   // what the front stages leave for the frame records
     std::vector<int> iterations;     // RANSAC iterations of every frame (stage_plane)
     int rounds = 0;                  // hypothesis rounds of the plane stage
+    std::vector<char> gave_up;       // the frames whose sampler ran into a device limit (stage_plane; the surface fits run it again)
     std::vector<char> surface_flag;  // CD_GUESS_SURFACE: the frames whose guess came from their surface fit (empty otherwise)
 };
 
@@ -313,7 +314,7 @@ void write_frame_records(cd_context* c, int N, int F, const BatchClusters& cl, c
         r.flags = s.n_k > KICP ? CD_FRAME_MORE_CLUSTERS : 0;
         if (!fr.surface_flag.empty() && fr.surface_flag[(size_t)f]) r.flags |= CD_FRAME_SURFACE_GUESS;
         r.ransac_iterations = fr.iterations[f];
-        if (s.status == CD_OK && !c->h_have[f]) r.status = CD_ERR_NO_MODEL;
+        if (s.status == CD_OK && !c->h_have[f]) r.status = fr.gave_up[(size_t)f] ? CD_ERR_CAPACITY : CD_ERR_NO_MODEL;
         if (c->h_have[f]) { r.plane[0] = c->h_model[f].x; r.plane[1] = c->h_model[f].y; r.plane[2] = c->h_model[f].z; r.plane[3] = c->h_model[f].w; }
         balg += 12ll * N + 12ll * s.n_v + 12ll * s.n_v * (fr.rounds + 3) + 4ll * s.n_v + 16ll * s.n_o + 200ll * s.n_k;
         for (int k = 0; k < s.n_k; ++k) {
@@ -407,6 +408,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     FrontStages fr;
     st = stage_plane(c, F, p, fr.iterations, &fr.rounds);
     if (st) return st;
+    fr.gave_up = c->plane_gave_up;
     // [2] extract, cluster, surface guesses
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     st = stage_extract(c, F, p);

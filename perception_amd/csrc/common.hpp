@@ -35,6 +35,9 @@ constexpr int KICP = CD_MAX_CLUSTERS_PER_FRAME;  // clusters per frame that get 
 constexpr int FIX_SHIFT = 32;              // canonical rule C4
 constexpr int FIX_SHIFT_D2 = 36;
 constexpr int RND_TABLE = 1 << 15;         // precomputed mt19937(12345)>>1 draws
+// FrameState::sampler_exhausted: why k_ransac_sample stopped before h_target hypotheses.  NO_SAMPLE is PCL's own stop (fewer than
+// 3 points, or 1000 samples in a row that isSampleGood rejects); GAVE_UP is the device's (RND_TABLE or the shuffle map used up).
+constexpr int SAMPLER_NO_SAMPLE = 1, SAMPLER_GAVE_UP = 2;
 constexpr int SAMPLER_MAP = 8192;          // LDS sparse shuffle map (open addressing)
 constexpr int MAX_HYP = 1024 + 16;         // plane_max_iterations+1 hypotheses at most kept per frame
 constexpr int CELL_BUCKETS = 1 << 16;      // cluster spatial hash buckets per frame

@@ -95,6 +95,7 @@ struct cd_context : cd_streams {
     // RANSAC
     DevBuf<int> d_rnd, d_valid, d_counts, d_active, d_have;
     PinBuf<int> h_valid, h_counts, h_active, h_have;
+    std::vector<char> plane_gave_up;   // per frame of the last stage_plane: the sampler's device limits ended it before PCL's loop did (CD_ERR_CAPACITY)
     DevBuf<float4> d_models, d_model;
     PinBuf<float4> h_model, h_models;
     DevBuf<unsigned long long> d_sums;

@@ -145,7 +145,8 @@ int stage_crop_voxel(cd_context* c, const void* d_in, size_t stride, int N, int 
 }
 
 // S2.  in: d_vox + fs.n_v (host mirror h_fs[].n_v must be current).  out: h_model/h_have refined,
-// fs.status updated for NO_MODEL, iterations per frame.
+// fs.status updated for NO_MODEL, iterations per frame; plane_gave_up[f] = 1 (and h_have[f] = 0, cd_last_error set) for a frame
+// whose sampler ran into a device limit before PCL's loop ended - the callers report CD_ERR_CAPACITY for it.
 // axes: per-frame constraint axes of a constrained model, 3 floats per frame (nullptr: p->plane_axis for every frame)
 int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iterations, int* rounds_out, const float* axes) {
     const int T = c->T;
@@ -156,10 +157,14 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
     const int Tv = std::max(1, (max_nv + TILE - 1) / TILE);
     std::vector<hm::RansacReplay> rep(F);
     iterations.assign(F, 0);
+    c->plane_gave_up.assign((size_t)F, 0);
     for (int f = 0; f < F; ++f) c->h_active[f] = (c->h_fs[f].status == CD_OK || c->h_fs[f].status == CD_ERR_NO_MODEL) ? 1 : 0;
     ZERO_FILL(c, c->d_counts, sizeof(int) * (size_t)F * MAX_HYP);
     const int targets[4] = {16, 64, 256, MAX_HYP};
-    const int h_cap = std::min(MAX_HYP, p->plane_max_iterations + 40);   // max_iterations+1 plus 39 skipped models
+    // max_iterations + 1 hypotheses end PCL's loop; the 39 more are head-room for hypotheses marked invalid ("skipped models"),
+    // which never happens: computeModelCoefficients repeats isSampleGood's comparison on the same floats, so a sample that
+    // passed the one is never collinear for the other, and valid[] is 1 for every hypothesis the sampler emits
+    const int h_cap = std::min(MAX_HYP, p->plane_max_iterations + 40);
     int h_prev = 0, rounds = 0;
     for (int r = 0; r < 4; ++r) {
         const int h_target = std::min(targets[r], h_cap);
@@ -197,8 +202,19 @@ int stage_plane(cd_context* c, int F, const cd_params* p, std::vector<int>& iter
                         c->h_counts[(size_t)f * MAX_HYP + h] = 0;
                 }
             }
-            const bool fin = rep[f].consume(c->h_counts + (size_t)f * MAX_HYP, c->h_valid + (size_t)f * MAX_HYP, s.n_hyp, std::max(1, s.n_v),
-                                            p->plane_max_iterations, p->plane_probability, s.sampler_exhausted != 0 || h_target >= h_cap);
+            // (a sampler that GAVE UP on a device limit ends the frame only if PCL's loop ends within what it drew: see below)
+            const bool gave_up = s.sampler_exhausted == SAMPLER_GAVE_UP;
+            bool fin = rep[f].consume(c->h_counts + (size_t)f * MAX_HYP, c->h_valid + (size_t)f * MAX_HYP, s.n_hyp, std::max(1, s.n_v),
+                                      p->plane_max_iterations, p->plane_probability, !gave_up && (s.sampler_exhausted != 0 || h_target >= h_cap));
+            if (!fin && gave_up) {
+                // PCL's loop asks for a hypothesis the device cannot draw (PCL has no such limit and would run on): no silent
+                // "best model so far" - the frame fails with CD_ERR_CAPACITY and goes on as a frame without a model
+                c->plane_gave_up[(size_t)f] = 1;
+                std::snprintf(c->err, sizeof(c->err), "RANSAC sampler: frame %d needs hypothesis %d, beyond the device's limits (%d random draws, %d shuffle slots)",
+                              f, s.n_hyp, RND_TABLE, (SAMPLER_MAP * 3) / 4);
+                rep[f].best_h = -1;
+                fin = true;
+            }
             if (fin) c->h_active[f] = 0; else all_done = false;
         }
         h_prev = h_target;

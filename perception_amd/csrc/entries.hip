@@ -70,6 +70,7 @@ int cd_segment_plane_impl(cd_context* c, const void* xyz, size_t stride, int n, 
     st = stage_plane(c, 1, p, iters, nullptr);
     if (st) return st;
     if (out_iterations) *out_iterations = iters[0];
+    if (c->plane_gave_up[0]) return CD_ERR_CAPACITY;   // (cd_last_error names the limit: stage_plane)
     if (!c->h_have[0]) return CD_ERR_NO_MODEL;
     cd_params q = *p;
     q.extract_negative = 1;
@@ -390,6 +391,7 @@ int cd_ground_plane_impl(cd_context* c, const void* points, size_t stride, int n
     st = download_records(c, c->d_obj, no, stride, rgb_off, 0u, out_records, in_bytes);               // the ONE download
     if (st) return st;
     *out_n = no;
+    if (c->plane_gave_up[0]) return CD_ERR_CAPACITY;   // (cd_last_error names the limit: stage_plane)
     if (!c->h_have[0]) return CD_ERR_NO_MODEL;
     coeff[0] = c->h_model[0].x; coeff[1] = c->h_model[0].y; coeff[2] = c->h_model[0].z; coeff[3] = c->h_model[0].w;
     return CD_OK;

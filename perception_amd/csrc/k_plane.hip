@@ -26,8 +26,11 @@ namespace cd {
 // three swaps of position i = 0, 1, 2 with a position j >= i) touches positions 0, 1, 2 and at most three others, so after d
 // draws at most 3 + 3 d slots are in use; every hypothesis - kept or skipped as collinear by computeModelCoefficients - takes
 // one draw plus one per sample that isSampleGood rejects (exact equality of three float ratios: none on sensor data).  The
-// first h hypotheses therefore need 3 h + 3 slots and three per rejected sample; the sampler gives a frame up (exhausted) when
-// used + 6 > 3/4 SAMPLER_MAP before a draw - that rule is part of the result and does not depend on the map's size here:
+// first h hypotheses therefore need 3 h + 3 slots and three per rejected sample; the sampler gives a frame up
+// (sampler_exhausted = SAMPLER_GAVE_UP) when used + 6 > 3/4 SAMPLER_MAP before a draw, or when the draw would read past the
+// RND_TABLE precomputed random numbers.  PCL has neither limit: stage_plane fails such a frame with CD_ERR_CAPACITY when PCL's loop
+// would have asked for a further hypothesis.  PCL's own stop - 1000 rejected samples in a row - is SAMPLER_NO_SAMPLE.  The rule
+// is part of the result and does not depend on the map's size here:
 //   MAP = SAMPLER_MAP        64 KiB of LDS, one wave: a workgroup that needs 40 % of a CU's LDS free (the rounds of 256
 //                            hypotheses and more)
 //   MAP = SAMPLER_MAP_SMALL  8 KiB for the rounds of at most SAMPLER_SMALL_HYP hypotheses, which is room for them and 188
@@ -62,7 +65,7 @@ __device__ __forceinline__ bool sampler_run(int* key, int* val, SamplerState& st
         bool good = false;
         int s0 = 0, s1 = 0, s2 = 0;
         for (int it = it0; it < 1000; ++it) {          // max_sample_checks_
-            if (rp + 3 > RND_TABLE || used + 6 > (SAMPLER_MAP * 3) / 4) { exhausted = 1; break; }
+            if (rp + 3 > RND_TABLE || used + 6 > (SAMPLER_MAP * 3) / 4) { exhausted = SAMPLER_GAVE_UP; break; }   // a limit of the device, not of PCL
             if (MAP < SAMPLER_MAP && used + 6 > (MAP * 3) / 4) { st.rp = rp; st.h = h; st.used = used; st.it = it; return false; }
             for (int i = 0; i < 3; ++i) {               // drawIndexSample
                 const uint32_t r = (uint32_t)rnd[rp++];
@@ -79,7 +82,8 @@ __device__ __forceinline__ bool sampler_run(int* key, int* val, SamplerState& st
             if ((q0 != q1) || (q2 != q1)) { good = true; break; }
         }
         it0 = 0;
-        if (!good) { exhausted = 1; break; }
+        if (exhausted) break;
+        if (!good) { exhausted = SAMPLER_NO_SAMPLE; break; }   // PCL: "No samples could be selected!"
         // computeModelCoefficients
         const float4 p0 = P[s0], p1 = P[s1], p2 = P[s2];
         const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z;
@@ -93,7 +97,10 @@ __device__ __forceinline__ bool sampler_run(int* key, int* val, SamplerState& st
             float mx = __fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by));
             float my = __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz));
             float mz = __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx));
-            const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(mx, mx), __fmul_rn(my, my)), __fmul_rn(mz, mz)));
+            // (sqrtf: IEEE under -fhip-fp32-correctly-rounded-divide-sqrt.  __fsqrt_rn is the native approximation here: it left
+            // some hypotheses an ulp away from PCL's model - returned as it is with plane_optimize = 0 or fewer than 4 inliers, and
+            // able to move a count: tests/test_gpu_plane_truth.py)
+            const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(mx, mx), __fmul_rn(my, my)), __fmul_rn(mz, mz)));
             mx = __fdiv_rn(mx, nrm); my = __fdiv_rn(my, nrm); mz = __fdiv_rn(mz, nrm);
             const float d = __fmul_rn(-1.0f, __fadd_rn(__fadd_rn(__fmul_rn(mx, p0.x), __fmul_rn(my, p0.y)), __fmul_rn(mz, p0.z)));
             m = make_float4(mx, my, mz, d);
@@ -124,7 +131,7 @@ __global__ void __launch_bounds__(WAVE) k_ransac_sample(const float4* __restrict
     const float4* P = vox + (size_t)f * N;
     float4* M = models + (size_t)f * MAX_HYP;
     int* V = valid + (size_t)f * MAX_HYP;
-    if (n < 3) { fs[f].n_hyp = 0; fs[f].sampler_exhausted = 1; return; }
+    if (n < 3) { fs[f].n_hyp = 0; fs[f].sampler_exhausted = SAMPLER_NO_SAMPLE; return; }
     SamplerState st = {0, 0, 0, 0, 0};
     const bool finished = sampler_run<MAP>(s_key, s_val, st, P, n, rnd, h_target, M, V);
     if (MAP < SAMPLER_MAP && !finished) {
