@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "cd_set_icp_coarse", "cd_get_icp_coarse", "cd_icp_coarse_struct_size", "cd_icp_coarse_subsample", "cd_get_cluster_coarse_stats",
     "cd_set_icp_median_rejection", "cd_get_icp_median_rejection", "cd_icp_reject_struct_size", "cd_get_cluster_reject_stats",
     "cd_icp_median_threshold",
+    "cd_set_icp_reciprocal", "cd_get_icp_reciprocal", "cd_icp_recip_struct_size", "cd_get_cluster_recip_stats", "cd_icp_reciprocal_mask",
     "cd_set_table_prism", "cd_get_table_prism", "cd_prism_struct_size", "cd_get_prism_stats", "cd_get_prism_hull", "cd_table_prism",
     "cd_prism_project", "cd_prism_hull_host",
     "cd_set_pair_score", "cd_get_pair_score", "cd_pair_score_struct_size", "cd_get_cluster_pair_scores", "cd_pair_score_points",
@@ -102,6 +103,12 @@ class CdIcpRejectStats(C.Structure):
     """cd_icp_reject_stats: what rule C19 did for one (cluster, template) pair."""
     _fields_ = [("first_kept", C.c_int32), ("last_kept", C.c_int32), ("min_kept", C.c_int32), ("stopped_few", C.c_int32),
                 ("last_median", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class CdIcpRecipStats(C.Structure):
+    """cd_icp_recip_stats: what rule C22 did for one (cluster, template) pair."""
+    _fields_ = [("first_kept", C.c_int32), ("last_kept", C.c_int32), ("min_kept", C.c_int32), ("stopped_few", C.c_int32),
+                ("last_n0", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class CdPrismStats(C.Structure):
@@ -530,6 +537,11 @@ def load_library(path=None):
     lib.cd_icp_reject_struct_size.argtypes = []
     lib.cd_get_cluster_reject_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.cd_icp_median_threshold.argtypes = [vp, C.c_int, C.c_double, vp, dp]
+    lib.cd_set_icp_reciprocal.argtypes = [vp, C.c_int]
+    lib.cd_get_icp_reciprocal.argtypes = [vp, ip]
+    lib.cd_icp_recip_struct_size.argtypes = []
+    lib.cd_get_cluster_recip_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_icp_reciprocal_mask.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, C.c_float, vp, vp, vp]
     psp = C.POINTER(CdPrismStats)
     lib.cd_set_table_prism.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     lib.cd_get_table_prism.argtypes = [vp, ip, dp, dp]
@@ -1119,6 +1131,23 @@ class Context:
         msg = "no median-rejection call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
         return self._cluster_records(self.lib.cd_get_cluster_reject_stats, CdIcpRejectStats, msg, frame, first, count)
 
+    def set_icp_reciprocal(self, on):
+        """Rule C22, reciprocal correspondences, for every later ICP of this context: an iteration keeps a source point's template
+        neighbour only if that template point's nearest source point is the same source point.  False (or None): off, the default."""
+        self._check(self.lib.cd_set_icp_reciprocal(self.h, 1 if on else 0))
+
+    def icp_reciprocal(self):
+        """The mode as cd_set_icp_reciprocal left it: 1 on, 0 off."""
+        v = C.c_int()
+        self._check(self.lib.cd_get_icp_reciprocal(self.h, C.byref(v)))
+        return v.value
+
+    def cluster_recip_stats(self, frame, first=0, count=None):
+        """Rule C22's stats of the clusters of `frame` of the last fused call (or, frame 0, of the last cd_icp), indexed like
+        cluster_results: a list of CdIcpRecipStats."""
+        msg = "no reciprocal-correspondence call to read: the last one ran with the mode off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_recip_stats, CdIcpRecipStats, msg, frame, first, count)
+
     def set_pair_score(self, enable, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_coverage=CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT,
                        min_inlier_fraction=CD_PAIR_SCORE_MIN_INLIER_DEFAULT):
         """Rule C21, the two-way registration score, for every later fused call of this context: each cluster result is scored
@@ -1330,6 +1359,22 @@ def icp_median_threshold(d2, factor):
     if st != CD_OK:
         raise CuboidError(st, "cd_icp_median_threshold")
     return np.float32(m.value), np.float64(t.value)
+
+
+def icp_reciprocal_mask(src, tpl, d2_max=None):
+    """Host-only rule C22, steps 1 - 3 of one iteration by brute force: (nn int32, d2 float32, keep bool, n0) for the source
+    positions src over the template tpl; d2_max: rule C8's float32 threshold on d2 (None: unbounded)."""
+    lib = load_library()
+    s = np.ascontiguousarray(np.asarray(src, np.float32).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(tpl, np.float32).reshape(-1, 3))
+    nn = np.empty(len(s), np.int32)
+    d2 = np.empty(len(s), np.float32)
+    keep = np.empty(len(s), np.uint8)
+    n0 = lib.cd_icp_reciprocal_mask(_ptr(s), 12, len(s), _ptr(t), 12, len(t), float("inf") if d2_max is None else float(np.float32(d2_max)), _ptr(nn), _ptr(d2),
+                                    _ptr(keep))
+    if n0 < 0:
+        raise CuboidError(n0, "cd_icp_reciprocal_mask")
+    return nn, d2, keep.astype(bool), n0
 
 
 def pair_score_host(tpl, src, T, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_coverage=CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT,

@@ -373,6 +373,12 @@ public:
     // factor the library refuses (0, negative, not finite) fails the align() with its message.
     void addCorrespondenceRejector(const registration::CorrespondenceRejectorMedianDistance::Ptr& rejector) { rejector_ = rejector; }
     void clearCorrespondenceRejectors() { rejector_.reset(); }
+    // pcl::IterativeClosestPoint::setUseReciprocalCorrespondences: the library's rule C22 (cd_set_icp_reciprocal) - a source point
+    // keeps its target neighbour only if that target point's nearest source point is the same source point.  Handed to the shared
+    // context before each ICP like the settings above.  PCL runs an installed rejector on what the reciprocal estimation left;
+    // the library refuses that combination, and the align() fails with its message.
+    void setUseReciprocalCorrespondences(bool on) { reciprocal_ = on; }
+    bool getUseReciprocalCorrespondences() const { return reciprocal_; }
     // align(output, guess): pcl::Registration's second overload (row-major 4x4, scene -> template)
     void align(PointCloud<PointSource>& output, const Matrix4& guess) {
         prm_.icp_use_guess = CD_GUESS_PARAMS;
@@ -392,7 +398,8 @@ public:
             cd_set_icp_plane_weight(Device::instance().ctx(), plane_w_, plane_d_) != CD_OK ||
             cd_set_icp_coarse(Device::instance().ctx(), coarse_s_, coarse_m_) != CD_OK ||
             (rejector_ && !(rejector_->getMedianFactor() != 0.0)) ||   // (0 would turn the mode off silently: a rejector that is installed rejects)
-            cd_set_icp_median_rejection(Device::instance().ctx(), rejector_ ? rejector_->getMedianFactor() : 0.0) != CD_OK) {
+            cd_set_icp_median_rejection(Device::instance().ctx(), rejector_ ? rejector_->getMedianFactor() : 0.0) != CD_OK ||
+            cd_set_icp_reciprocal(Device::instance().ctx(), reciprocal_ ? 1 : 0) != CD_OK) {
             std::fprintf(stderr, "[pclhip::IterativeClosestPoint] %s\n", cd_last_error(Device::instance().ctx()));
             return;
         }
@@ -421,6 +428,7 @@ private:
     double plane_w_ = 0.0, plane_d_ = CD_ICP_PLANE_SWITCH_DEFAULT;
     int coarse_s_ = 0, coarse_m_ = 0;
     registration::CorrespondenceRejectorMedianDistance::Ptr rejector_;
+    bool reciprocal_ = false;
     typename PointCloud<PointSource>::ConstPtr src_;
     typename PointCloud<PointTarget>::ConstPtr tgt_;
     Matrix4 final_;

@@ -175,6 +175,7 @@ void for_each_icp_stat(cd_context* c, Fn&& fn) {
     fn(c->plane_weight != 0.0, c->last_plane, c->h_pstat);     // rule C17
     fn(c->coarse_stride != 0, c->last_coarse, c->h_cstat);     // rule C18
     fn(c->reject_factor != 0.0, c->last_reject, c->h_rstat);   // rule C19
+    fn(c->recip_on != 0, c->last_recip, c->h_qstat);           // rule C22
 }
 
 struct BatchIcp {   // the ICP part of a fused call; the results themselves are kept in c->last_clusters

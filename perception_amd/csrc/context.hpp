@@ -22,6 +22,7 @@
 #include "pair_score_math.hpp"
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
+#include "icp_recip_math.hpp"
 #include "icp_coarse_plan.hpp"
 #include "kept_records.hpp"
 #include "shape_frame_math.hpp"
@@ -238,6 +239,13 @@ struct cd_context : cd_streams {
     double reject_factor = 0.0;
     DevBuf<RejectStats> d_rstat; PinBuf<RejectStats> h_rstat;
     KeptRecords<cd_icp_reject_stats> last_reject;
+    // reciprocal correspondences (rule C22, k_icp_recip.hip): the setting (cd_set_icp_reciprocal; 0: off), the keep flag of every
+    // ICP source point of a stage (indexed as d_src), one record per ICP problem (device + pinned mirror) - all grown on demand -
+    // and what cd_get_cluster_recip_stats reads, as last_plane
+    int recip_on = 0;
+    DevBuf<uint8_t> d_rkeep;
+    DevBuf<RecipStats> d_qstat; PinBuf<RecipStats> h_qstat;
+    KeptRecords<cd_icp_recip_stats> last_recip;
     // table prism (rule C20, k_prism.hip): the setting (cd_set_table_prism; prism_on = 0: off), and - grown on demand - the map of
     // the last call with the step (one int per point of the cloud S3 left, rows of one pitch), one record per frame (device +
     // pinned mirror), the same counts in the form the label calls read (d_plrec) and every frame's hull (CD_PRISM_MAX_HULL
@@ -306,6 +314,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_plane.invalidate();
     c->last_coarse.invalidate();
     c->last_reject.invalidate();
+    c->last_recip.invalidate();
     c->last_pair.invalidate();
 }
 
@@ -454,11 +463,14 @@ int check_params(cd_context* c, const cd_params* p);
 int check_plane_templates(cd_context* c, int slot);
 // ---- icp_reject.hip (rule C19): the mode cannot be combined with rule C17
 int check_reject_mode(cd_context* c);
-// what every ICP entry point asks before it copies or launches anything: check_plane_templates, then check_reject_mode (with both
-// wrong the error is the first one's)
+// ---- icp_recip.hip (rule C22): the mode cannot be combined with rule C17 or rule C19
+int check_recip_mode(cd_context* c);
+// what every ICP entry point asks before it copies or launches anything: check_plane_templates, then check_reject_mode, then
+// check_recip_mode (with several wrong the error is the first one's)
 inline int check_icp_modes(cd_context* c, int slot) {
     if (int st = check_plane_templates(c, slot)) return st;
-    return check_reject_mode(c);
+    if (int st = check_reject_mode(c)) return st;
+    return check_recip_mode(c);
 }
 int download_records(cd_context* c, const float4* d_pts, int m, size_t stride, int rgb_offset, uint32_t pad3, void* out, size_t staging_skip = 0);
 // ---- cuboid_hip.hip

@@ -350,9 +350,13 @@ int cd_icp_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int
         if (n >= 3) c->last_reject.publish_single(c->h_rstat[0]);
         else c->last_reject.publish_single(cd_icp_reject_stats());
     }
-    // rules C8 and C19: an ICP that stopped for fewer than three kept correspondences (only a bounded or rejecting one can: every
-    // other ends converged)
-    if (c->h_st[0].status == CD_OK && (c->icp_bounded || c->reject_factor != 0.0) && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;
+    if (c->recip_on) {   // rule C22
+        if (n >= 3) c->last_recip.publish_single(c->h_qstat[0]);
+        else c->last_recip.publish_single(cd_icp_recip_stats());
+    }
+    // rules C8, C19 and C22: an ICP that stopped for fewer than three kept correspondences (only a bounded or rejecting one can:
+    // every other ends converged)
+    if (c->h_st[0].status == CD_OK && (c->icp_bounded || c->reject_factor != 0.0 || c->recip_on) && !c->h_st[0].converged) return CD_ERR_FEW_CORRESPONDENCES;
     return c->h_st[0].status;
 }
 

@@ -27,6 +27,7 @@ struct IcpPlanInput {
     int n_cu = 256, work_cap = 0;        // CUs of the device; items the work list holds
     bool plane_on = false;               // rule C17 (cd_set_icp_plane_weight != 0)
     bool reject_on = false;              // rule C19 (cd_set_icp_median_rejection != 0)
+    bool recip_on = false;               // rule C22 (cd_set_icp_reciprocal != 0)
     int icp_use_guess = CD_GUESS_NONE;   // cd_params::icp_use_guess
     const float* frame_guess = nullptr;  // the per-frame guesses in force (cd_set_frame_guesses', or - CD_GUESS_SURFACE - the call's own), 16 per frame
     size_t frame_guess_len = 0;          // floats
@@ -62,6 +63,8 @@ struct IcpPlan {   // host-side decisions of one ICP stage (plan_icp)
     bool crowded = false;                        // (icp_params) four or more batches in flight on the device
     bool plane = false;                          // rule C17 (cd_set_icp_plane_weight): every live cluster takes k_icp_plane
     bool reject = false;                         // rule C19 (cd_set_icp_median_rejection): every live cluster gets sliced work items (icp_run_sliced)
+    bool recip = false;                          // rule C22 (cd_set_icp_reciprocal): likewise, with k_icp_recip behind each iteration
+    bool filtered() const { return reject || recip; }   // a kernel behind every k_icp_iter<true> replaces the slot's sums: the sliced loop only
     bool device_guesses = false;                 // (IcpPlanInput::device_guesses) the sources are moved per problem, whatever the guess mode
 };
 
@@ -95,10 +98,13 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
     // forced driver modes (CUBOID_ICP_MODE) keep them on the generic searches (A/B, and the GPU suite runs under each mode).
     // Rule C17 on: every live cluster goes to k_icp_plane whatever those switches say - no other driver implements the step.
     // Rule C19 on: every live cluster takes the sliced loop with k_icp_reject behind each iteration, likewise whatever they say.
+    // Rule C22 on: the same with k_icp_recip.
     pl->plane = in.plane_on;
     pl->reject = in.reject_on;
+    pl->recip = in.recip_on;
     if (pl->plane && pl->reject) return PlanStatus{CD_ERR_INVALID_ARG, "plane-weighted ICP and median-distance rejection are both on"};
-    const bool use_lat = !pl->plane && !pl->reject && tun.icp_lattice != 0 && tun.icp_mode == 0;
+    if (pl->recip && (pl->plane || pl->reject)) return PlanStatus{CD_ERR_INVALID_ARG, "reciprocal correspondences and plane-weighted ICP or median-distance rejection are both on"};
+    const bool use_lat = !pl->plane && !pl->filtered() && tun.icp_lattice != 0 && tun.icp_mode == 0;
     pl->in_lat.assign((size_t)ncl, 0);
     for (int k = 0; k < ncl; ++k) {
         const IcpCluster& cl = in.cl[k];
@@ -119,7 +125,7 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
     }
     int n_grouped = 0;
     for (const TplGroup& g : groups) if (g.kind) n_grouped += g.live;
-    pl->grouped_pipe = !pl->plane && !pl->reject && groups.size() > 1 && groups.size() <= 16 && n_grouped > 0 &&
+    pl->grouped_pipe = !pl->plane && !pl->filtered() && groups.size() > 1 && groups.size() <= 16 && n_grouped > 0 &&
                        (tun.icp_mode == 3 || (tun.icp_mode == 0 && n_grouped * 5 >= in.n_cu));
     if (std::getenv("CUBOID_DEBUG")) {
         std::fprintf(stderr, "cuboid_hip: stage_icp %d clusters, %zu template groups, %d in pipe groups, grouped_pipe %d:", ncl, groups.size(), n_grouped, (int)pl->grouped_pipe);
@@ -166,7 +172,7 @@ inline PlanStatus plan_icp(const IcpPlanInput& in, IcpPlan* pl, IcpWork* work, I
     // barrier per iteration costs more than it saves, so those batches stay sliced unless the mode is forced)
     // (measured crossover on the bench frames: 33 clusters 3.3 ms sliced / 3.7 ms pipelined, 65 clusters 4.4 / 3.9, 130 clusters
     // 6.4 / 4.0: the pipelined kernel wins from about a fifth of the CUs' worth of clusters)
-    pl->whole_cluster = !pl->grouped_pipe && !pl->reject && (tun.icp_mode >= 2 || (tun.icp_mode == 0 && ncl * 5 >= in.n_cu && (pl->pipe_ok || pl->big_ok)));
+    pl->whole_cluster = !pl->grouped_pipe && !pl->filtered() && (tun.icp_mode >= 2 || (tun.icp_mode == 0 && ncl * 5 >= in.n_cu && (pl->pipe_ok || pl->big_ok)));
     return PlanStatus{CD_OK, nullptr};
 }
 

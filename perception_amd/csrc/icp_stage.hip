@@ -2,7 +2,8 @@
 // needs (icp_setup), then hands the clusters to the drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe
 // launches for several templates (k_icp_pipe.hip), the whole-cluster launch (k_icp_pipe.hip, k_icp_cluster.hip), the persistent
 // launch for a few clusters and the sliced multi-launch loop for whatever is left (both k_icp.hip) (rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs.
-// Rule C19 on: the sliced loop, with k_icp_reject behind every iteration, takes every live cluster; none of the others runs).
+// Rule C19 on: the sliced loop, with k_icp_reject behind every iteration, takes every live cluster; none of the others runs.
+// Rule C22 on: the same with k_icp_recip).
 // A driver sets *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after
 // it take the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
 // Which driver, and how large its launch: icp_plan.hpp decides, from plain numbers.  Here are the stream operations.
@@ -20,6 +21,7 @@ int plan_stage(cd_context* c, int ncl, const cd_params* p, bool device_guesses, 
     in.tun = &c->tun; in.n_cu = c->n_cu; in.work_cap = c->work_cap;
     in.plane_on = c->plane_weight != 0.0;
     in.reject_on = c->reject_factor != 0.0;
+    in.recip_on = c->recip_on != 0;
     in.icp_use_guess = p->icp_use_guess;
     const std::vector<float>& fg = p->icp_use_guess == CD_GUESS_SURFACE ? c->surface_guess : c->frame_guess;
     in.frame_guess = fg.data(); in.frame_guess_len = fg.size();
@@ -90,7 +92,7 @@ int icp_setup(cd_context* c, const cd_params* p, IcpPlan* pl) {
         HIPCHK(c, hipMemsetAsync(c->d_acc, 0, sizeof(unsigned long long) * 48 * (size_t)ncl, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_accf, 0, sizeof(unsigned long long) * ((size_t)ncl + 1), c->stream));   // (+ the wave-time word of k_icp_lat)
     }
-    if (c->icp_bounded || pl->reject) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3] (rule C19: always)
+    if (c->icp_bounded || pl->filtered()) {   // rule C8: the sliced / persistent drivers' correspondence counts, [cluster][it % 3] (rules C19, C22: always)
         GROW(c, d_ncorr, 3 * (size_t)ncl);
         HIPCHK(c, hipMemsetAsync(c->d_ncorr, 0, sizeof(uint32_t) * 3 * (size_t)ncl, c->stream));
     }
@@ -365,13 +367,30 @@ int icp_run_persist(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Ic
 // Rule C19 (cd_set_icp_median_rejection, plan.reject - every live cluster has items then): k_icp_reject behind every iteration
 // launch: k_icp_solve<true>(it), k_icp_iter<true>(it), whose sums for the slot k_icp_reject(it) then replaces with those of the kept
 // correspondences.  Always the BOUNDED instantiations then, with d2_max = +inf when rule C8 bounds nothing.
+// Rule C22 (cd_set_icp_reciprocal, plan.recip): the same with k_icp_recip's two kernels in k_icp_reject's place; between them they
+// hand one flag per source point through d_rkeep.
 int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const IcpParams& ip, bool* done) {
     static_assert(sizeof(RejectStats) == sizeof(cd_icp_reject_stats), "RejectStats mirrors cd_icp_reject_stats");
+    static_assert(sizeof(RecipStats) == sizeof(cd_icp_recip_stats), "RecipStats mirrors cd_icp_recip_stats");
     const int ncl = pl.ncl, nwork = pl.nwork, max_launch = ip.max_iter + 3;
     IcpBound bnd = icp_bound(c);
     if (pl.reject) {
         GROW(c, d_rstat, (size_t)ncl); GROW(c, h_rstat, (size_t)ncl);
         HIPCHK(c, hipMemsetAsync(c->d_rstat, 0, sizeof(RejectStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
+    }
+    int recip_max_n = 0;
+    if (pl.recip) {   // the flags cover the live problems' points as d_src holds them
+        long long span = 0;
+        for (int k = 0; k < ncl; ++k) {
+            if (c->h_cl[k].n < 3 || c->h_cl[k].tpl_m <= 0) continue;
+            span = std::max(span, (long long)c->h_cl[k].src_off + c->h_cl[k].n);
+            recip_max_n = std::max(recip_max_n, c->h_cl[k].n);
+        }
+        GROW(c, d_rkeep, (size_t)std::max(span, 1ll));
+        GROW(c, d_qstat, (size_t)ncl); GROW(c, h_qstat, (size_t)ncl);
+        HIPCHK(c, hipMemsetAsync(c->d_qstat, 0, sizeof(RecipStats) * (size_t)ncl, c->stream));   // (pre-marked problems keep zeros)
+    }
+    if (pl.filtered()) {
         if (!bnd.bounded) bnd.d2_max = std::numeric_limits<float>::infinity();
         bnd.bounded = 1;
     }
@@ -386,6 +405,7 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
         for (int q = 0; q < g; ++q, ++it) {
             LAUNCH(c, launch_icp_iter(c->stream, it, nactive, ncl, c->d_work2, a.dev, a.tpl, a.scr, pl.qslice, c->n_cu, ip, bnd));
             if (pl.reject && nactive > 0) LAUNCH(c, launch_icp_reject(c->stream, it, ncl, a.dev, a.tpl, a.scr, bnd, c->reject_factor, c->d_rstat));
+            if (pl.recip && nactive > 0) LAUNCH(c, launch_icp_recip(c->stream, it, ncl, recip_max_n, a.dev, a.tpl, a.scr, bnd, c->d_rkeep, c->d_qstat));
         }
         HIPCHK(c, xfer(c, c->h_st, c->d_st, sizeof(IcpState) * 2 * ncl, hipMemcpyDeviceToHost));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -401,6 +421,7 @@ int icp_run_sliced(cd_context* c, const IcpPlan& pl, const IcpArgs& a, const Icp
     c->timing.icp_kernel_launches = it;               // (iteration launches)
     LAUNCH(c, launch_icp_fitness(c->stream, nwork, c->d_work, a.dev, 0, a.tpl, a.scr, pl.qslice));
     if (pl.reject) HIPCHK(c, xfer(c, c->h_rstat, c->d_rstat, sizeof(RejectStats) * (size_t)ncl, hipMemcpyDeviceToHost));
+    if (pl.recip) HIPCHK(c, xfer(c, c->h_qstat, c->d_qstat, sizeof(RecipStats) * (size_t)ncl, hipMemcpyDeviceToHost));
     if (int e = icp_read_back(c, ncl)) return e;
     *done = true;
     return CD_OK;
@@ -428,7 +449,7 @@ int stage_icp(cd_context* c, int ncl, const cd_params* p, long long* pair_tests,
     if (!st && !done && pl.n_lat > 0) st = icp_run_lat(c, pl, a, ip, &done);
     if (!st && !done && pl.grouped_pipe) st = icp_run_grouped(c, pl, a, ip, &done);
     if (!st && !done && pl.whole_cluster) st = icp_run_whole(c, pl, a, ip, &done);
-    if (!st && !done && !pl.reject) st = icp_run_persist(c, pl, a, ip, &done);   // (rule C19: the sliced loop, nothing before it)
+    if (!st && !done && !pl.filtered()) st = icp_run_persist(c, pl, a, ip, &done);   // (rules C19, C22: the sliced loop, nothing before it)
     if (!st && !done) st = icp_run_sliced(c, pl, a, ip, &done);
     if (done) icp_finish(c, ncl, pair_tests);
     return st;

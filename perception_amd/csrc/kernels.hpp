@@ -143,6 +143,14 @@ struct RejectStats;
 void launch_icp_reject(hipStream_t s, int it, int ncl, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, const IcpBound& bnd, double factor,
                        RejectStats* rstat);
 
+// k_icp_recip.hip : rule C22, reciprocal correspondences (icp_recip_math.hpp: RecipStats) - behind k_icp_iter<true>(it) of the sliced
+// loop, as k_icp_reject: the reverse test of every live, unfinished problem's points (query ranges of a problem over
+// blockIdx.y; max_n: the largest problem) leaves one flag per point in `keep` (indexed as S.src), then the slot's sums and count
+// become those of the flagged correspondences; bnd.d2_max = +inf without rule C8's bound
+struct RecipStats;
+void launch_icp_recip(hipStream_t s, int it, int ncl, int max_n, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S, const IcpBound& bnd,
+                      uint8_t* keep, RecipStats* rstat);
+
 // k_depth.hip : n_frames tightly packed 16UC1 depth images (+ rgb8 colour, or nullptr) -> width * height * n_frames float4
 // records x y z rgb (canonical rule C7)
 struct DeprojectParams {
