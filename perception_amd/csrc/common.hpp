@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/cuboid_hip.h"
+#include "rn_ops.hpp"
 
 namespace cd {
 
@@ -225,6 +226,18 @@ struct IcpBound {
     int32_t bounded;
     uint32_t* ncorr;
 };
+// Rule C8's vocabulary, once for every kernel, host twin and check program: the predicate (d2_max = +inf keeps everything but a
+// NaN), and the stop - fewer kept correspondences than ICP_MIN_CORR is PCL's "Not enough correspondences" (icp_stop_few).
+constexpr int ICP_MIN_CORR = 3;
+__host__ __device__ inline bool icp_in_k0(float d2, float d2_max) { return d2 <= d2_max; }
+// What every rule that thins the correspondences of the sliced loop reports per (cluster, template) pair: the head of RejectStats
+// (rule C19) and RecipStats (rule C22), kept up to date by icp_kept_fold.hpp
+struct KeptStats {
+    int32_t first_kept;     // correspondences the first iteration kept
+    int32_t last_kept;      // ... the last iteration that looked for correspondences
+    int32_t min_kept;       // the least of any iteration
+    int32_t stopped_few;    // 1: the ICP stopped with fewer than three (before or after the rule's own test)
+};
 // k_icp_pipe's hand-over of RUNNING clusters (IcpParams::donate): words of the control block
 constexpr int DON_AVAIL = 0;      // workgroups waiting for a cluster minus clusters promised to them
 constexpr int DON_FINISHED = 1;   // clusters of the launch that are done (or were never started: pre-marked)
@@ -364,11 +377,7 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-// canonical squared distance: (dx*dx + dy*dy) + dz*dz, no contraction
-__device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
+// (the canonical squared distance dist2: rn_ops.hpp)
 // A workgroup's TILE from an atomic ticket instead of blockIdx (round 4).  The chained scans below wait for tiles of the same
 // frame with smaller ids; a workgroup that holds ticket t of a frame exists only after tickets 0..t-1 of that frame were
 // drawn, by workgroups that are running or done - so every wait ends, whatever order the hardware starts a grid's

@@ -16,24 +16,7 @@
 namespace cd {
 
 constexpr int PLANE_NSUMS = 28;              // 9 per axis, then d2
-constexpr int PLANE_MIN_CORR = 3;            // (ICP_MIN_CORR: fewer kept correspondences stop the ICP before the update)
 constexpr double PLANE_SINGULAR_EPS = 9.094947017729282379150390625e-13;   // 2^-40
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_PL_FSUB(a, b) __fsub_rn((a), (b))
-#define CD_PL_FMUL(a, b) __fmul_rn((a), (b))
-#define CD_PL_MUL(a, b) __dmul_rn((a), (b))
-#define CD_PL_ADD(a, b) __dadd_rn((a), (b))
-#define CD_PL_SUB(a, b) __dsub_rn((a), (b))
-#define CD_PL_DIV(a, b) __ddiv_rn((a), (b))
-#else
-#define CD_PL_FSUB(a, b) ((a) - (b))
-#define CD_PL_FMUL(a, b) ((a) * (b))
-#define CD_PL_MUL(a, b) ((a) * (b))
-#define CD_PL_ADD(a, b) ((a) + (b))
-#define CD_PL_SUB(a, b) ((a) - (b))
-#define CD_PL_DIV(a, b) ((a) / (b))
-#endif
 
 // What the mode reports per (cluster, template) pair (cd_icp_plane_stats)
 struct PlaneStats {
@@ -56,18 +39,18 @@ __host__ __device__ inline void plane_terms(const float (&s)[3], const float (&q
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const int b = (a + 1) % 3, c = (a + 2) % 3;
-        const float r = CD_PL_FSUB(q[a], s[a]);
+        const float r = rn_fsub(q[a], s[a]);
         const float g = a == w ? 1.0f : lam_it;
-        const float u = CD_PL_FMUL(g, s[c]), v = CD_PL_FMUL(g, s[b]), h = CD_PL_FMUL(g, r);
+        const float u = rn_fmul(g, s[c]), v = rn_fmul(g, s[b]), h = rn_fmul(g, r);
         out[9 * a + 0] = g;
         out[9 * a + 1] = u;
         out[9 * a + 2] = v;
-        out[9 * a + 3] = CD_PL_FMUL(u, s[c]);
-        out[9 * a + 4] = CD_PL_FMUL(v, s[b]);
-        out[9 * a + 5] = CD_PL_FMUL(u, s[b]);
+        out[9 * a + 3] = rn_fmul(u, s[c]);
+        out[9 * a + 4] = rn_fmul(v, s[b]);
+        out[9 * a + 5] = rn_fmul(u, s[b]);
         out[9 * a + 6] = h;
-        out[9 * a + 7] = CD_PL_FMUL(h, s[c]);
-        out[9 * a + 8] = CD_PL_FMUL(h, s[b]);
+        out[9 * a + 7] = rn_fmul(h, s[c]);
+        out[9 * a + 8] = rn_fmul(h, s[b]);
     }
     out[27] = d2;
 }
@@ -104,15 +87,15 @@ __host__ __device__ inline int plane_solve(const long long* A, int n, float* T) 
         double S[9];
 #pragma unroll
         for (int j = 0; j < 9; ++j) S[j] = plane_unfix(A[9 * a + j], FIX_SHIFT);
-        M[b][b] = CD_PL_ADD(M[b][b], S[3]);
-        M[c][c] = CD_PL_ADD(M[c][c], S[4]);
-        M[hi][lo] = CD_PL_ADD(M[hi][lo], -S[5]);
-        M[3 + a][b] = CD_PL_ADD(M[3 + a][b], S[1]);
-        M[3 + a][c] = CD_PL_ADD(M[3 + a][c], -S[2]);
-        M[3 + a][3 + a] = CD_PL_ADD(M[3 + a][3 + a], S[0]);
-        rhs[b] = CD_PL_ADD(rhs[b], S[7]);
-        rhs[c] = CD_PL_ADD(rhs[c], -S[8]);
-        rhs[3 + a] = CD_PL_ADD(rhs[3 + a], S[6]);
+        M[b][b] = rn_dadd(M[b][b], S[3]);
+        M[c][c] = rn_dadd(M[c][c], S[4]);
+        M[hi][lo] = rn_dadd(M[hi][lo], -S[5]);
+        M[3 + a][b] = rn_dadd(M[3 + a][b], S[1]);
+        M[3 + a][c] = rn_dadd(M[3 + a][c], -S[2]);
+        M[3 + a][3 + a] = rn_dadd(M[3 + a][3 + a], S[0]);
+        rhs[b] = rn_dadd(rhs[b], S[7]);
+        rhs[c] = rn_dadd(rhs[c], -S[8]);
+        rhs[3 + a] = rn_dadd(rhs[3 + a], S[6]);
     }
     double L[6][6], W[6][6], d[6];
     int singular = 0;
@@ -120,18 +103,18 @@ __host__ __device__ inline int plane_solve(const long long* A, int n, float* T) 
     for (int j = 0; j < 6; ++j) {
         double acc = M[j][j];
 #pragma unroll
-        for (int k = 0; k < j; ++k) acc = CD_PL_SUB(acc, CD_PL_MUL(W[j][k], L[j][k]));
+        for (int k = 0; k < j; ++k) acc = rn_dsub(acc, rn_dmul(W[j][k], L[j][k]));
         d[j] = acc;
-        if (!(acc > CD_PL_MUL(M[j][j], PLANE_SINGULAR_EPS))) singular = 1;
+        if (!(acc > rn_dmul(M[j][j], PLANE_SINGULAR_EPS))) singular = 1;
         // (a singular column's quotients are never used: the result is the identity.  They are still computed - the loops
         // have no early exit, so that they unroll - and may be infinite or NaN.)
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
             double w = M[i][j];
 #pragma unroll
-            for (int k = 0; k < j; ++k) w = CD_PL_SUB(w, CD_PL_MUL(W[i][k], L[j][k]));
+            for (int k = 0; k < j; ++k) w = rn_dsub(w, rn_dmul(W[i][k], L[j][k]));
             W[i][j] = w;
-            L[i][j] = CD_PL_DIV(w, acc);
+            L[i][j] = rn_ddiv(w, acc);
         }
     }
     if (singular) return 1;
@@ -140,29 +123,29 @@ __host__ __device__ inline int plane_solve(const long long* A, int n, float* T) 
     for (int i = 0; i < 6; ++i) {
         double acc = rhs[i];
 #pragma unroll
-        for (int k = 0; k < i; ++k) acc = CD_PL_SUB(acc, CD_PL_MUL(L[i][k], y[k]));
+        for (int k = 0; k < i; ++k) acc = rn_dsub(acc, rn_dmul(L[i][k], y[k]));
         y[i] = acc;
     }
 #pragma unroll
     for (int i = 5; i >= 0; --i) {
-        double acc = CD_PL_DIV(y[i], d[i]);
+        double acc = rn_ddiv(y[i], d[i]);
 #pragma unroll
-        for (int k = 5; k > i; --k) acc = CD_PL_SUB(acc, CD_PL_MUL(L[k][i], x[k]));
+        for (int k = 5; k > i; --k) acc = rn_dsub(acc, rn_dmul(L[k][i], x[k]));
         x[i] = acc;
     }
-    const double kx = CD_PL_MUL(x[0], 0.5), ky = CD_PL_MUL(x[1], 0.5), kz = CD_PL_MUL(x[2], 0.5);
-    const double xx = CD_PL_MUL(kx, kx), yy = CD_PL_MUL(ky, ky), zz = CD_PL_MUL(kz, kz);
-    const double m = CD_PL_ADD(CD_PL_ADD(CD_PL_ADD(1.0, xx), yy), zz);
-    const double xy = CD_PL_MUL(kx, ky), xz = CD_PL_MUL(kx, kz), yz = CD_PL_MUL(ky, kz);
-    T[0] = (float)CD_PL_DIV(CD_PL_SUB(CD_PL_SUB(CD_PL_ADD(1.0, xx), yy), zz), m);
-    T[1] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_SUB(xy, kz)), m);
-    T[2] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_ADD(xz, ky)), m);
-    T[4] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_ADD(xy, kz)), m);
-    T[5] = (float)CD_PL_DIV(CD_PL_SUB(CD_PL_ADD(CD_PL_SUB(1.0, xx), yy), zz), m);
-    T[6] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_SUB(yz, kx)), m);
-    T[8] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_SUB(xz, ky)), m);
-    T[9] = (float)CD_PL_DIV(CD_PL_MUL(2.0, CD_PL_ADD(yz, kx)), m);
-    T[10] = (float)CD_PL_DIV(CD_PL_ADD(CD_PL_SUB(CD_PL_SUB(1.0, xx), yy), zz), m);
+    const double kx = rn_dmul(x[0], 0.5), ky = rn_dmul(x[1], 0.5), kz = rn_dmul(x[2], 0.5);
+    const double xx = rn_dmul(kx, kx), yy = rn_dmul(ky, ky), zz = rn_dmul(kz, kz);
+    const double m = rn_dadd(rn_dadd(rn_dadd(1.0, xx), yy), zz);
+    const double xy = rn_dmul(kx, ky), xz = rn_dmul(kx, kz), yz = rn_dmul(ky, kz);
+    T[0] = (float)rn_ddiv(rn_dsub(rn_dsub(rn_dadd(1.0, xx), yy), zz), m);
+    T[1] = (float)rn_ddiv(rn_dmul(2.0, rn_dsub(xy, kz)), m);
+    T[2] = (float)rn_ddiv(rn_dmul(2.0, rn_dadd(xz, ky)), m);
+    T[4] = (float)rn_ddiv(rn_dmul(2.0, rn_dadd(xy, kz)), m);
+    T[5] = (float)rn_ddiv(rn_dsub(rn_dadd(rn_dsub(1.0, xx), yy), zz), m);
+    T[6] = (float)rn_ddiv(rn_dmul(2.0, rn_dsub(yz, kx)), m);
+    T[8] = (float)rn_ddiv(rn_dmul(2.0, rn_dsub(xz, ky)), m);
+    T[9] = (float)rn_ddiv(rn_dmul(2.0, rn_dadd(yz, kx)), m);
+    T[10] = (float)rn_ddiv(rn_dadd(rn_dsub(rn_dsub(1.0, xx), yy), zz), m);
     T[3] = (float)x[3]; T[7] = (float)x[4]; T[11] = (float)x[5];
     return 0;
 }

@@ -13,33 +13,16 @@
 
 namespace cd {
 
-constexpr int RECIP_MIN_CORR = 3;   // fewer kept correspondences stop the ICP (rule C8's stop, icp_solve.hpp)
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_RC_FMUL(a, b) __fmul_rn((a), (b))
-#define CD_RC_FADD(a, b) __fadd_rn((a), (b))
-#define CD_RC_FSUB(a, b) __fsub_rn((a), (b))
-#else
-#define CD_RC_FMUL(a, b) ((a) * (b))
-#define CD_RC_FADD(a, b) ((a) + (b))
-#define CD_RC_FSUB(a, b) ((a) - (b))
-#endif
-
 // What the mode reports per (cluster, template) pair (cd_icp_recip_stats)
 struct RecipStats {
-    int32_t first_kept;     // correspondences the first iteration kept
-    int32_t last_kept;      // ... the last iteration that looked for correspondences
-    int32_t min_kept;       // the least of any iteration
-    int32_t stopped_few;    // 1: the ICP stopped with fewer than three (before or after the reverse test)
+    KeptStats kept;
     int32_t last_n0;        // |K0| of the last iteration that looked for correspondences
     int32_t reserved[3];
 };
+static_assert(offsetof(RecipStats, last_n0) == offsetof(cd_icp_recip_stats, last_n0) &&
+              offsetof(KeptStats, stopped_few) == offsetof(cd_icp_recip_stats, stopped_few), "RecipStats mirrors cd_icp_recip_stats");
 
-// step 2: d2(q, x), q the template point, x a source position
-__host__ __device__ inline float recip_d2(float qx, float qy, float qz, float x, float y, float z) {
-    const float dx = CD_RC_FSUB(qx, x), dy = CD_RC_FSUB(qy, y), dz = CD_RC_FSUB(qz, z);
-    return CD_RC_FADD(CD_RC_FADD(CD_RC_FMUL(dx, dx), CD_RC_FMUL(dy, dy)), CD_RC_FMUL(dz, dz));
-}
+// (step 2, d2(q, x) of a template point q and a source position x, is dist2(q, x): rn_ops.hpp)
 // the running minimum over a set of targets (+inf: the empty set; a NaN distance never enters)
 __host__ __device__ inline float recip_min(float best, float d) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -51,8 +34,6 @@ __host__ __device__ inline float recip_min(float best, float d) {
 // step 3 for query i with own = d2(q, X_i): before = the minimum over the sources i' < i, from = the minimum over i' >= i
 // (own among them).  No earlier source is as near, no source at all is nearer.
 __host__ __device__ inline bool recip_keep(float before, float from, float own) { return !(before <= own) && !(from < own); }
-// rule C8's predicate as every BOUNDED kernel has it (d2_max = +inf: everything but a NaN)
-__host__ __device__ inline bool recip_in_k0(float d2, float d2_max) { return d2 <= d2_max; }
 
 // Rule C5 by brute force on the host: nearest template point of (x, y, z), ties to the lowest index; m >= 1
 inline int recip_forward_host(const float* tpl, size_t tpl_stride_f, int m, float x, float y, float z, float* d2_out) {
@@ -60,7 +41,7 @@ inline int recip_forward_host(const float* tpl, size_t tpl_stride_f, int m, floa
     float best = std::numeric_limits<float>::infinity();
     for (int j = 0; j < m; ++j) {
         const float* t = tpl + (size_t)j * tpl_stride_f;
-        const float d = recip_d2(x, y, z, t[0], t[1], t[2]);
+        const float d = dist2(x, y, z, t[0], t[1], t[2]);
         if (d < best || j == 0) { best = d; bj = j; }
     }
     *d2_out = best;
@@ -72,18 +53,18 @@ inline int recip_forward_host(const float* tpl, size_t tpl_stride_f, int m, floa
 inline int recip_mask_host(const float* src, size_t src_stride_f, int n, const float* tpl, size_t tpl_stride_f, float d2_max, const int32_t* nn,
                            const float* d2, uint8_t* keep) {
     int n0 = 0;
-    for (int i = 0; i < n; ++i) { keep[i] = recip_in_k0(d2[i], d2_max) ? 1 : 0; n0 += keep[i]; }
-    if (n0 < RECIP_MIN_CORR) return n0;
+    for (int i = 0; i < n; ++i) { keep[i] = icp_in_k0(d2[i], d2_max) ? 1 : 0; n0 += keep[i]; }
+    if (n0 < ICP_MIN_CORR) return n0;
     const float inf = std::numeric_limits<float>::infinity();
     for (int i = 0; i < n; ++i) {
         if (!keep[i]) continue;
         const float* q = tpl + (size_t)nn[i] * tpl_stride_f;
         const float* xi = src + (size_t)i * src_stride_f;
-        const float own = recip_d2(q[0], q[1], q[2], xi[0], xi[1], xi[2]);
+        const float own = dist2(q[0], q[1], q[2], xi[0], xi[1], xi[2]);
         float before = inf, from = inf;
         for (int e = 0; e < n; ++e) {
             const float* x = src + (size_t)e * src_stride_f;
-            const float d = recip_d2(q[0], q[1], q[2], x[0], x[1], x[2]);
+            const float d = dist2(q[0], q[1], q[2], x[0], x[1], x[2]);
             if (e < i) before = recip_min(before, d);
             else from = recip_min(from, d);
         }

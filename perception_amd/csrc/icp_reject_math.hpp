@@ -6,6 +6,7 @@
 // threshold ONE rounded double product, so the result does not depend on who computes it.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "common.hpp"
@@ -15,23 +16,15 @@ namespace cd {
 constexpr int REJECT_DIGIT_BITS = 8;                       // the key's 32 bits go in four rounds, most significant digit first
 constexpr int REJECT_BINS = 1 << REJECT_DIGIT_BITS;
 constexpr int REJECT_ROUNDS = 32 / REJECT_DIGIT_BITS;
-constexpr int REJECT_MIN_CORR = 3;                         // fewer kept correspondences stop the ICP (rule C8's stop, icp_solve.hpp)
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_RJ_MUL(a, b) __dmul_rn((a), (b))
-#else
-#define CD_RJ_MUL(a, b) ((a) * (b))
-#endif
 
 // What the mode reports per (cluster, template) pair (cd_icp_reject_stats)
 struct RejectStats {
-    int32_t first_kept;     // correspondences the first iteration kept
-    int32_t last_kept;      // ... the last iteration that looked for correspondences
-    int32_t min_kept;       // the least of any iteration
-    int32_t stopped_few;    // 1: the ICP stopped with fewer than three (before or after the rejection)
+    KeptStats kept;
     float last_median;      // m of the last iteration that selected one (0: none did)
     int32_t reserved[3];
 };
+static_assert(offsetof(RejectStats, last_median) == offsetof(cd_icp_reject_stats, last_median) &&
+              offsetof(KeptStats, stopped_few) == offsetof(cd_icp_reject_stats, stopped_few), "RejectStats mirrors cd_icp_reject_stats");
 
 __host__ __device__ inline uint32_t reject_key(float d2) {
     uint32_t k;
@@ -53,11 +46,9 @@ __host__ __device__ inline uint32_t reject_digit(uint32_t key, int r) {
 // step 2's rank among n0 survivors of rule C8's bound: the upper median
 __host__ __device__ inline uint32_t reject_rank(uint32_t n0) { return n0 / 2u; }
 // step 3
-__host__ __device__ inline double reject_threshold(float m, double factor) { return CD_RJ_MUL((double)m, factor); }
+__host__ __device__ inline double reject_threshold(float m, double factor) { return rn_dmul((double)m, factor); }
 // step 4 (for a correspondence of K0)
 __host__ __device__ inline bool reject_keep(float d2, double thr) { return (double)d2 <= thr; }
-// rule C8's predicate as every BOUNDED kernel has it (d2_max = +inf: everything)
-__host__ __device__ inline bool reject_in_k0(float d2, float d2_max) { return d2 <= d2_max; }
 
 // The bin of a round's histogram that holds rank `rank` (0-based among the counted keys), and the rank inside that bin.
 // Sequential form (host; the device's wave does the same prefix in parallel).  The counts sum to more than `rank`.

@@ -37,16 +37,16 @@ int main(int argc, char** argv) {
     const float bound = bounded ? d2_max : reject_value(0x7f800000u);
     std::vector<float> k0;
     k0.reserve((size_t)n);
-    for (float v : d2) if (reject_in_k0(v, bound)) k0.push_back(v);
+    for (float v : d2) if (icp_in_k0(v, bound)) k0.push_back(v);
     const uint32_t n0 = (uint32_t)k0.size();
     float m = 0.f;
     double thr = 0.0;
-    const bool selected = n0 >= (uint32_t)REJECT_MIN_CORR;
+    const bool selected = n0 >= (uint32_t)ICP_MIN_CORR;
     if (selected) reject_median_host(k0.data(), n0, factor, &m, &thr);
     std::vector<char> keep((size_t)n);
     int kept = 0;
     for (int i = 0; i < n; ++i) {
-        keep[(size_t)i] = reject_in_k0(d2[(size_t)i], bound) && (!selected || reject_keep(d2[(size_t)i], thr));
+        keep[(size_t)i] = icp_in_k0(d2[(size_t)i], bound) && (!selected || reject_keep(d2[(size_t)i], thr));
         kept += keep[(size_t)i];
     }
     std::printf("counts %d %u %d\n", n, n0, kept);

@@ -159,7 +159,7 @@ __device__ inline void umeyama_from_moments(const unsigned long long* A, int n, 
 // float d2 <= IcpParams::d2_max and count the kept ones next to the moment sums; the solve then divides by that count.  Fewer
 // than three is PCL's "Not enough correspondences": the ICP stops BEFORE this iteration's update - Tfinal and iters stay,
 // converged = 0 - and T becomes the identity, so that the in-place X <- T X that follows leaves the points where they are.
-constexpr int ICP_MIN_CORR = 3;
+// (ICP_MIN_CORR and the predicate icp_in_k0: common.hpp)
 __device__ __forceinline__ void icp_stop_few(IcpState& so) {
     for (int i = 0; i < 16; ++i) so.T[i] = (i % 5 == 0) ? 1.f : 0.f;
     so.converged = 0;

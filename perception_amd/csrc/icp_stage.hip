@@ -1,9 +1,10 @@
 // icp_stage.hip - S6, the ICP stage: stage_icp plans the stage on the host (plan_icp, icp_plan.hpp), issues what every driver
 // needs (icp_setup), then hands the clusters to the drivers in turn: k_icp_lat for lattice templates, the grouped k_icp_pipe
 // launches for several templates (k_icp_pipe.hip), the whole-cluster launch (k_icp_pipe.hip, k_icp_cluster.hip), the persistent
-// launch for a few clusters and the sliced multi-launch loop for whatever is left (both k_icp.hip) (rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs.
+// launch for a few clusters and the sliced multi-launch loop for whatever is left (both k_icp.hip).
+// Rule C17 on: k_icp_plane takes every live cluster and finishes the stage; none of the others runs.
 // Rule C19 on: the sliced loop, with k_icp_reject behind every iteration, takes every live cluster; none of the others runs.
-// Rule C22 on: the same with k_icp_recip).
+// Rule C22 on: the same with k_icp_recip.
 // A driver sets *done when it has run the stage to its end (records read back, stream synchronised); otherwise the drivers after
 // it take the clusters it left and find the ones it ran finished in d_st / h_st (the stream orders them).
 // Which driver, and how large its launch: icp_plan.hpp decides, from plain numbers.  Here are the stream operations.

@@ -146,7 +146,7 @@ __device__ __forceinline__ void slice_moments(const float4* pts, const float4* _
     unsigned long long S[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) S[k] = 0ull;
-    const bool keep = threadIdx.x < nq && (!BOUNDED || d2q[threadIdx.x] <= bnd.d2_max);
+    const bool keep = threadIdx.x < nq && (!BOUNDED || icp_in_k0(d2q[threadIdx.x], bnd.d2_max));
     if constexpr (BOUNDED) {
         const unsigned long long kb = ballot64(keep);
         if (lane == 0 && kb) atomicAdd(&bnd.ncorr[slot], (uint32_t)__popcll(kb));

@@ -16,14 +16,16 @@
 //   c. one pass over the points: moment_terms of every kept correspondence, added per lane as 64-bit integers, folded per wave
 //      (wave_fold_to_lds) and per workgroup (ds_add_u64) - integer sums, so nothing depends on which lane or wave took which point;
 //   d. plain vector stores: the 16 sums to d_acc[cluster * 3 + it % 3], the count to d_ncorr, the stats record.
+// Which clusters a launch skips, a kept point's terms, the slot store and the record's four common fields are icp_kept_fold.hpp's,
+// shared with k_icp_recip_fold; steps a and b, the keep test and last_median are this kernel's own.
 // Five reads of the cluster's d2 (4 bytes a point; L2-resident after the first), one of its points and their template points.
 //
-// Budget: LDS 1168 B (1024 B histogram, 128 B sums, 16 B selection words); 79 VGPRs (16 running sums and 16 terms as 64-bit
+// Budget (compiler's report, gfx950): LDS 1168 B (1024 B histogram, 128 B sums, 16 B selection words); 79 VGPRs (16 running sums and 16 terms as 64-bit
 // pairs), 54 SGPRs, no scratch - six waves a SIMD by registers, six workgroups a CU; LDS limits nothing.  No MFMA: nothing here
 // is a contraction.
 #include "common.hpp"
+#include "icp_kept_fold.hpp"
 #include "icp_reject_math.hpp"
-#include "icp_solve.hpp"
 #include "kernels.hpp"
 
 namespace cd {
@@ -41,8 +43,7 @@ k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restri
     __shared__ uint32_t s_sel[4];   // prefix, rank inside it, |K0|, kept
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const IcpCluster c = cl[k];
-    if (c.n < REJECT_MIN_CORR || c.tpl_m <= 0) return;                                             // pre-marked
-    if (st[(size_t)k * 2 + (it & 1)].done || st[(size_t)k * 2 + ((it + 1) & 1)].done) return;      // finished (k_icp_solve(it) has run)
+    if (kept_skips(c, st, k, it)) return;
     const float* d2 = d2buf + c.src_off;
     if (tid < 16) s_sum[tid] = 0ull;
     if (tid == 16) s_sel[3] = 0u;
@@ -54,7 +55,7 @@ k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restri
         for (int i = tid; i < c.n; i += RJ_THREADS) {
             const float v = d2[i];
             const uint32_t key = reject_key(v);
-            if (reject_in_k0(v, bnd.d2_max) && reject_in_round(key, prefix, r)) atomicAdd(&s_hist[reject_digit(key, r)], 1u);
+            if (icp_in_k0(v, bnd.d2_max) && reject_in_round(key, prefix, r)) atomicAdd(&s_hist[reject_digit(key, r)], 1u);
         }
         __syncthreads();
         if (wave == 0) {
@@ -81,12 +82,12 @@ k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restri
         }
         __syncthreads();
         if (r == 0) n0 = s_sel[2];
-        if (n0 < (uint32_t)REJECT_MIN_CORR) break;   // (the whole workgroup: n0 is the same for every thread)
+        if (n0 < (uint32_t)ICP_MIN_CORR) break;   // (the whole workgroup: n0 is the same for every thread)
         prefix = s_sel[0];
         rank = s_sel[1];
     }
     // b. the threshold (+inf without a selection: what rule C8 left is counted, and the solve stops on fewer than three)
-    const bool selected = n0 >= (uint32_t)REJECT_MIN_CORR;
+    const bool selected = n0 >= (uint32_t)ICP_MIN_CORR;
     const float m = reject_value(prefix);
     const double thr = selected ? reject_threshold(m, factor) : (double)reject_value(0x7f800000u);
     // c. the kept correspondences' moments
@@ -99,15 +100,8 @@ k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restri
     const float4* tp = tplk + c.tpl_off;
     for (int i = tid; i < c.n; i += RJ_THREADS) {
         const float v = d2[i];
-        if (!(reject_in_k0(v, bnd.d2_max) && reject_keep(v, thr))) continue;
-        const float4 p = pts[i];
-        const int j = min(max(nnp[i], 0), c.tpl_m - 1);   // (a position k_icp_iter wrote; the clamp keeps a read inside the template)
-        const float4 q = tp[j];
-        const float pv[3] = {p.x, p.y, p.z}, qv[3] = {q.x, q.y, q.z};
-        unsigned long long t[16];
-        moment_terms(pv, qv, v, t);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) S[a] += t[a];
+        if (!(icp_in_k0(v, bnd.d2_max) && reject_keep(v, thr))) continue;
+        kept_add(pts, nnp, tp, c.tpl_m, i, v, S);
         ++kept;
     }
     wave_fold_to_lds(S, 16, s_sum);
@@ -115,16 +109,12 @@ k_icp_reject(int it, const IcpCluster* __restrict__ cl, const IcpState* __restri
     if (lane == 0 && kept) atomicAdd(&s_sel[3], (uint32_t)kept);
     __syncthreads();
     // d. the iteration's slot and the record
-    const size_t slot = (size_t)k * 3 + (size_t)(it % 3);
-    if (tid < 16) acc[slot * 16 + tid] = s_sum[tid];
+    const size_t slot = kept_store_sums(acc, s_sum, k, it);
     if (tid == 16) {
         const int n = (int)s_sel[3];
         bnd.ncorr[slot] = (uint32_t)n;
         RejectStats rs = rstat[k];
-        if (it == 0) { rs.first_kept = n; rs.min_kept = n; }
-        else rs.min_kept = min(rs.min_kept, n);
-        rs.last_kept = n;
-        if (n < REJECT_MIN_CORR) rs.stopped_few = 1;
+        kept_update(rs.kept, it, n);
         if (selected) rs.last_median = m;
         rstat[k] = rs;
     }

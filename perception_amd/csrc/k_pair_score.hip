@@ -2,13 +2,14 @@
 // score of (cluster, template) pairs, opt-in through cd_set_pair_score, and the kernel behind cd_pair_score_points.
 //
 // An exact all-pairs minimum, run in both directions by swapping the roles of the two sets.  A JOB is one direction of one pair:
-// its queries and its targets, one of the two being the cluster's points under T (evaluated on the fly by pair_apply_row, once per
+// its queries and its targets, one of the two being the cluster's points under T (evaluated on the fly by xform_row, once per
 // load: the same float32 value wherever it is evaluated), the other the template's.  An ITEM is a range of at most PS_CHUNK queries
 // of a job against ALL its targets, so a query's minimum is complete inside one workgroup and nothing but integers crosses
 // workgroups: a pair larger than a chunk is split over workgroups by queries only.  The host sorts the items by pair tests,
 // largest first; the workgroups of a launch draw them from one queue word.
 //
-// One workgroup of 256 threads per item at a time:
+// One workgroup of 256 threads per item at a time (steps a and b are the scan of allpairs_scan.hpp, which k_icp_recip_flags
+// shares; the constants, the transform and the update - one minimum per row - are this kernel's):
 //   a. every lane loads up to PS_ROWS queries into registers (query base + row * 256 + thread; a lane beyond the range holds a
 //      copy of the range's last query and is not counted), each with a running minimum of +inf;
 //   b. the targets pass through LDS in tiles of PS_TILE float4 (16 KiB, up to ten workgroups a CU by LDS), padded with +inf
@@ -18,7 +19,9 @@
 //   c. the lane's counts and clamped fixq terms (pair_term) are folded by shuffles, per workgroup by LDS atomics, and added to
 //      the pair's row of the accumulator with one 64-bit atomic per word: integer sums, order-free.  A non-finite query is counted
 //      in the row's PAIR_BAD word, and the host then refuses the pair.
-// No MFMA: nothing here is a contraction.
+// Budget (compiler's report, gfx950): LDS 16424 B, 109 VGPRs (four rows, the loop unrolled over eight targets), 73 SGPRs, no
+// scratch - four waves a SIMD by registers.  No MFMA: nothing here is a contraction.
+#include "allpairs_scan.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 #include "pair_score_math.hpp"
@@ -27,17 +30,6 @@ namespace cd {
 
 static_assert(PS_CHUNK == PS_ROWS * PS_THREADS, "a chunk is PS_ROWS queries per thread");
 static_assert(PS_TILE % 8 == 0 && PS_TILE % PS_THREADS == 0, "the tile is padded to a multiple of 8 and loaded by whole workgroups");
-
-template <int ROWS>
-__device__ __forceinline__ void pair_scan_tile(const float4* __restrict__ tile, int cnt8, const float (&qx)[PS_ROWS], const float (&qy)[PS_ROWS],
-                                               const float (&qz)[PS_ROWS], float (&best)[PS_ROWS]) {
-#pragma unroll 8
-    for (int e = 0; e < cnt8; ++e) {
-        const float4 g = tile[e];   // (the same address in every lane)
-#pragma unroll
-        for (int j = 0; j < ROWS; ++j) best[j] = __builtin_fminf(best[j], pair_d2(qx[j], qy[j], qz[j], g.x, g.y, g.z));
-    }
-}
 
 __global__ void __launch_bounds__(PS_THREADS)
 k_pair_score(const PairJob* __restrict__ jobs, const PairItem* __restrict__ items, int n_items, const float4* __restrict__ src,
@@ -61,34 +53,20 @@ k_pair_score(const PairJob* __restrict__ jobs, const PairItem* __restrict__ item
         int bad = 0;
 #pragma unroll
         for (int j = 0; j < PS_ROWS; ++j) {
-            const int r = j * PS_THREADS + tid;
-            const float4 p = qp[item.q0 + (r < item.qn ? r : item.qn - 1)];
+            const int r = scan_row<PS_THREADS>(j);
+            const float4 p = qp[item.q0 + scan_clamp(r, item.qn)];
             if (job.q_src) {
-                qx[j] = pair_apply_row(job.T, 0, p.x, p.y, p.z); qy[j] = pair_apply_row(job.T, 1, p.x, p.y, p.z); qz[j] = pair_apply_row(job.T, 2, p.x, p.y, p.z);
+                qx[j] = xform_row(job.T, 0, p.x, p.y, p.z); qy[j] = xform_row(job.T, 1, p.x, p.y, p.z); qz[j] = xform_row(job.T, 2, p.x, p.y, p.z);
             } else { qx[j] = p.x; qy[j] = p.y; qz[j] = p.z; }
             best[j] = INFINITY;
             if (r < item.qn && !pair_finite(qx[j], qy[j], qz[j])) ++bad;
         }
-        const int rows = (item.qn + PS_THREADS - 1) / PS_THREADS;
+        const int rows = scan_live_rows<PS_THREADS>(item.qn);
         // b. the targets, tile by tile
         for (int t0 = 0; t0 < job.ng; t0 += PS_TILE) {
-            const int cnt = min(PS_TILE, job.ng - t0), cnt8 = (cnt + 7) & ~7;
-            for (int e = tid; e < cnt8; e += PS_THREADS) {
-                float4 g = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-                if (e < cnt) {
-                    const float4 p = gp[t0 + e];
-                    if (job.q_src) g = make_float4(p.x, p.y, p.z, 0.f);
-                    else g = make_float4(pair_apply_row(job.T, 0, p.x, p.y, p.z), pair_apply_row(job.T, 1, p.x, p.y, p.z), pair_apply_row(job.T, 2, p.x, p.y, p.z), 0.f);
-                }
-                s_tile[e] = g;
-            }
+            const int cnt8 = scan_load_tile<PS_THREADS, true>(s_tile, gp, t0, min(PS_TILE, job.ng - t0), job.q_src, job.T);
             __syncthreads();
-            switch (rows) {
-                case 1: pair_scan_tile<1>(s_tile, cnt8, qx, qy, qz, best); break;
-                case 2: pair_scan_tile<2>(s_tile, cnt8, qx, qy, qz, best); break;
-                case 3: pair_scan_tile<3>(s_tile, cnt8, qx, qy, qz, best); break;
-                default: pair_scan_tile<4>(s_tile, cnt8, qx, qy, qz, best); break;
-            }
+            scan_tile_rows<PS_ROWS>(rows, s_tile, cnt8, qx, qy, qz, [&](int j, int, float d) { best[j] = __builtin_fminf(best[j], d); });
             __syncthreads();
         }
         // c. counts and sums

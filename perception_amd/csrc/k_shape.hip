@@ -99,8 +99,8 @@ __global__ void __launch_bounds__(BLOCK) k_shape_frames(const IcpCluster* __rest
             for (int a = 0; a < 3; ++a) {
                 double l = s_mm[0][a], h = s_mm[0][3 + a];
                 for (int q = 1; q < WAVES_PER_BLOCK; ++q) { l = fmin(l, s_mm[q][a]); h = fmax(h, s_mm[q][3 + a]); }
-                s_rec.lo[a] = CD_SF_ADD(l, 0.0);   // (a zero extent is stored as +0, whichever zero the reduction met first)
-                s_rec.hi[a] = CD_SF_ADD(h, 0.0);
+                s_rec.lo[a] = rn_dadd(l, 0.0);   // (a zero extent is stored as +0, whichever zero the reduction met first)
+                s_rec.hi[a] = rn_dadd(h, 0.0);
             }
         }
         rec[k] = s_rec;

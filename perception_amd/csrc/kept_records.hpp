@@ -1,8 +1,8 @@
 // kept_records.hpp - the per-cluster records a context keeps of its last call for a read-back (cd_get_cluster_plane_stats,
-// cd_get_cluster_coarse_stats, cd_get_cluster_reject_stats, cd_get_cluster_pair_scores, cd_get_cluster_shape_frames): the records, frame-major, the index of
-// every frame's first record in them (F + 1 entries) and whether a read may answer from them.  Host only, no HIP header and no
-// context: batch.hip and cd_icp fill a table, invalidate_last clears it, the getters read it; kept_records_check.cpp runs it on a
-// CPU (tests/test_kept_records_cpu.py).
+// cd_get_cluster_coarse_stats, cd_get_cluster_reject_stats, cd_get_cluster_recip_stats, cd_get_cluster_pair_scores,
+// cd_get_cluster_shape_frames): the records, frame-major, the index of every frame's first record in them (F + 1 entries) and
+// whether a read may answer from them.  Host only, no HIP header and no context: batch.hip and cd_icp fill a table,
+// invalidate_last clears it, the getters read it; kept_records_check.cpp runs it on a CPU (tests/test_kept_records_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstring>

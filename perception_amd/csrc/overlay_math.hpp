@@ -6,34 +6,20 @@
 #include <cmath>
 #include <cstdint>
 
-#include <hip/hip_runtime.h>
+#include "rn_ops.hpp"
 
 namespace cd {
 
 constexpr int OVERLAY_COORD_MAX = 8192;   // |pixel coordinate| of a drawn box, and the largest image side
 constexpr int OVERLAY_MAX_THICKNESS = 64;
 
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_OV_FMUL(a, b) __fmul_rn((a), (b))
-#define CD_OV_FADD(a, b) __fadd_rn((a), (b))
-#define CD_OV_DMUL(a, b) __dmul_rn((a), (b))
-#define CD_OV_DADD(a, b) __dadd_rn((a), (b))
-#define CD_OV_DDIV(a, b) __ddiv_rn((a), (b))
-#else
-#define CD_OV_FMUL(a, b) ((a) * (b))
-#define CD_OV_FADD(a, b) ((a) + (b))
-#define CD_OV_DMUL(a, b) ((a) * (b))
-#define CD_OV_DADD(a, b) ((a) + (b))
-#define CD_OV_DDIV(a, b) ((a) / (b))
-#endif
-
 // step 1: corner k (order of icp.cpp:99-106) of cd_bbox_corners(pose, l, w, h), float32
 __host__ __device__ inline void overlay_corner(const double* pose, const double* dims, int k, float c[3]) {
     const double sx = (k & 4) ? 1.0 : -1.0, sy = (k & 2) ? 1.0 : -1.0, sz = (k & 1) ? 1.0 : -1.0;
-    const float x = (float)(CD_OV_DMUL(sx, dims[0]) / 2), y = (float)(CD_OV_DMUL(sy, dims[1]) / 2), z = (float)(CD_OV_DMUL(sz, dims[2]) / 2);
+    const float x = (float)(rn_dmul(sx, dims[0]) / 2), y = (float)(rn_dmul(sy, dims[1]) / 2), z = (float)(rn_dmul(sz, dims[2]) / 2);
     for (int r = 0; r < 3; ++r) {
         const float h0 = (float)pose[4 * r], h1 = (float)pose[4 * r + 1], h2 = (float)pose[4 * r + 2], h3 = (float)pose[4 * r + 3];
-        c[r] = CD_OV_FADD(CD_OV_FADD(CD_OV_FADD(CD_OV_FMUL(h0, x), CD_OV_FMUL(h1, y)), CD_OV_FMUL(h2, z)), h3);
+        c[r] = rn_fadd(rn_fadd(rn_fadd(rn_fmul(h0, x), rn_fmul(h1, y)), rn_fmul(h2, z)), h3);
     }
 }
 
@@ -42,8 +28,8 @@ __host__ __device__ inline bool overlay_pixel(const double* M, const float c[3],
     const double x = (double)c[0], y = (double)c[1], z = (double)c[2];
     double h[3];
     for (int r = 0; r < 3; ++r)
-        h[r] = CD_OV_DADD(CD_OV_DADD(CD_OV_DADD(CD_OV_DMUL(M[4 * r], x), CD_OV_DMUL(M[4 * r + 1], y)), CD_OV_DMUL(M[4 * r + 2], z)), M[4 * r + 3]);
-    const double fu = CD_OV_DDIV(h[0], h[2]), fv = CD_OV_DDIV(h[1], h[2]);
+        h[r] = rn_dadd(rn_dadd(rn_dadd(rn_dmul(M[4 * r], x), rn_dmul(M[4 * r + 1], y)), rn_dmul(M[4 * r + 2], z)), M[4 * r + 3]);
+    const double fu = rn_ddiv(h[0], h[2]), fv = rn_ddiv(h[1], h[2]);
     const double lim = (double)(OVERLAY_COORD_MAX + 1);   // |trunc(a)| <= 8192  <=>  |a| < 8193
     // (written so that a NaN fails every comparison)
     if (!(h[2] > 0.0) || !(fu > -lim && fu < lim) || !(fv > -lim && fv < lim)) return false;

@@ -18,28 +18,10 @@ constexpr float PAIR_TERM_MAX = 256.0f;   // step 5: a term of a sum is min(d2, 
 constexpr int PAIR_MAX_POINTS = 1 << 19;  // rule C4's N
 constexpr int PAIR_MIN_SOURCE = 3;
 
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_PS_FMUL(a, b) __fmul_rn((a), (b))
-#define CD_PS_FADD(a, b) __fadd_rn((a), (b))
-#define CD_PS_FSUB(a, b) __fsub_rn((a), (b))
-#else
-#define CD_PS_FMUL(a, b) ((a) * (b))
-#define CD_PS_FADD(a, b) ((a) + (b))
-#define CD_PS_FSUB(a, b) ((a) - (b))
-#endif
-
 // the integers a pair's two passes leave (one row of the kernel's accumulator)
 enum { PAIR_N_SRC_IN = 0, PAIR_N_TPL_IN = 1, PAIR_S_FWD_IN = 2, PAIR_S_REV_IN = 3, PAIR_S_REV_ALL = 4, PAIR_BAD = 5, PAIR_ACC_PITCH = 8 };
 
-// step 1: row r of T on (x, y, z): ((T[4r] x + T[4r+1] y) + T[4r+2] z) + T[4r+3] - cd_get_cluster_points' single evaluation
-__host__ __device__ inline float pair_apply_row(const float* T, int r, float x, float y, float z) {
-    return CD_PS_FADD(CD_PS_FADD(CD_PS_FADD(CD_PS_FMUL(T[4 * r], x), CD_PS_FMUL(T[4 * r + 1], y)), CD_PS_FMUL(T[4 * r + 2], z)), T[4 * r + 3]);
-}
-// step 2
-__host__ __device__ inline float pair_d2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = CD_PS_FSUB(ax, bx), dy = CD_PS_FSUB(ay, by), dz = CD_PS_FSUB(az, bz);
-    return CD_PS_FADD(CD_PS_FADD(CD_PS_FMUL(dx, dx), CD_PS_FMUL(dy, dy)), CD_PS_FMUL(dz, dz));
-}
+// (step 1, the single evaluation of T on a point, is xform_row and step 2 is dist2: rn_ops.hpp)
 // step 5: rint(min(v, 256) 2^36), v >= 0 or +inf
 __host__ __device__ inline unsigned long long pair_term(float v) {
     const float t = v < PAIR_TERM_MAX ? v : PAIR_TERM_MAX;
@@ -98,7 +80,7 @@ inline void pair_passes_host(const float* tpl, int m, const float* src, int n, c
     for (int i = 0; i < PAIR_ACC_PITCH; ++i) acc[i] = 0ull;
     float* A = new float[(size_t)n * 3];
     for (int i = 0; i < n; ++i) {
-        for (int r = 0; r < 3; ++r) A[3 * (size_t)i + r] = pair_apply_row(T, r, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]);
+        for (int r = 0; r < 3; ++r) A[3 * (size_t)i + r] = xform_row(T, r, src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]);
         if (!pair_finite(A[3 * (size_t)i], A[3 * (size_t)i + 1], A[3 * (size_t)i + 2])) acc[PAIR_BAD] += 1ull;
     }
     for (int j = 0; j < m; ++j)
@@ -108,7 +90,7 @@ inline void pair_passes_host(const float* tpl, int m, const float* src, int n, c
         for (int i = 0; i < n; ++i) {
             float best = inf;
             for (int j = 0; j < m; ++j) {
-                const float v = pair_d2(A[3 * (size_t)i], A[3 * (size_t)i + 1], A[3 * (size_t)i + 2], tpl[3 * (size_t)j], tpl[3 * (size_t)j + 1], tpl[3 * (size_t)j + 2]);
+                const float v = dist2(A[3 * (size_t)i], A[3 * (size_t)i + 1], A[3 * (size_t)i + 2], tpl[3 * (size_t)j], tpl[3 * (size_t)j + 1], tpl[3 * (size_t)j + 2]);
                 best = v < best ? v : best;
             }
             if (best <= tau) { acc[PAIR_N_SRC_IN] += 1ull; acc[PAIR_S_FWD_IN] += pair_term(best); }
@@ -116,7 +98,7 @@ inline void pair_passes_host(const float* tpl, int m, const float* src, int n, c
         for (int j = 0; j < m; ++j) {
             float best = inf;
             for (int i = 0; i < n; ++i) {
-                const float v = pair_d2(tpl[3 * (size_t)j], tpl[3 * (size_t)j + 1], tpl[3 * (size_t)j + 2], A[3 * (size_t)i], A[3 * (size_t)i + 1], A[3 * (size_t)i + 2]);
+                const float v = dist2(tpl[3 * (size_t)j], tpl[3 * (size_t)j + 1], tpl[3 * (size_t)j + 2], A[3 * (size_t)i], A[3 * (size_t)i + 1], A[3 * (size_t)i + 2]);
                 best = v < best ? v : best;
             }
             if (best <= tau) { acc[PAIR_N_TPL_IN] += 1ull; acc[PAIR_S_REV_IN] += pair_term(best); }

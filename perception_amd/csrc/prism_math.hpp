@@ -19,16 +19,6 @@ constexpr int PRISM_MAX_HULL = CD_PRISM_MAX_HULL;      // hull vertices a frame 
 constexpr int PRISM_LDS_POINTS = CD_PRISM_LDS_POINTS;  // pruned inliers k_prism keeps in LDS
 constexpr int32_t PRISM_QMIN = -(1 << 29), PRISM_QMAX = (1 << 29) - 1;
 
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_PR_MUL(a, b) __dmul_rn((a), (b))
-#define CD_PR_ADD(a, b) __dadd_rn((a), (b))
-#define CD_PR_SUB(a, b) __dsub_rn((a), (b))
-#else
-#define CD_PR_MUL(a, b) ((a) * (b))
-#define CD_PR_ADD(a, b) ((a) + (b))
-#define CD_PR_SUB(a, b) ((a) - (b))
-#endif
-
 // What the step did to one cloud (a frame of a fused call, or the cloud of cd_table_prism): cd_prism_stats
 struct PrismRecord {
     int32_t n_before, n_kept, n_below, n_above, n_outside;
@@ -44,8 +34,8 @@ struct PrismPlane {   // steps 1 and 4
 __host__ __device__ inline PrismPlane prism_plane(float a, float b, float c, float d) {
     PrismPlane P;
     const double s = d < 0.0f ? -1.0 : 1.0;
-    P.n[0] = CD_PR_MUL(s, (double)a); P.n[1] = CD_PR_MUL(s, (double)b); P.n[2] = CD_PR_MUL(s, (double)c);
-    P.dd = CD_PR_MUL(s, (double)d);
+    P.n[0] = rn_dmul(s, (double)a); P.n[1] = rn_dmul(s, (double)b); P.n[2] = rn_dmul(s, (double)c);
+    P.dd = rn_dmul(s, (double)d);
     const float m[3] = {fabsf(a), fabsf(b), fabsf(c)};
     int k0 = 0;
     if (m[1] > m[k0]) k0 = 1;
@@ -57,20 +47,20 @@ __host__ __device__ inline PrismPlane prism_plane(float a, float b, float c, flo
 
 // step 5 of one coordinate: floor(t * 65536) clamped to [-2^29, 2^29 - 1], a NaN to the lower end
 __host__ __device__ inline int32_t prism_quantise(double t) {
-    const double q = floor(CD_PR_MUL(t, 65536.0));
+    const double q = floor(rn_dmul(t, 65536.0));
     return q >= (double)PRISM_QMIN ? (q <= (double)PRISM_QMAX ? (int32_t)q : PRISM_QMAX) : PRISM_QMIN;
 }
 
 // steps 2, 3 and 5 of one point: its height and its integer coordinates on the axes the plane keeps
 __host__ __device__ inline void prism_project(const PrismPlane& P, float x, float y, float z, double* height, int32_t* u, int32_t* v) {
     const double p[3] = {(double)x, (double)y, (double)z};
-    const double h = CD_PR_ADD(CD_PR_ADD(CD_PR_ADD(CD_PR_MUL(P.n[0], p[0]), CD_PR_MUL(P.n[1], p[1])), CD_PR_MUL(P.n[2], p[2])), P.dd);
+    const double h = rn_dadd(rn_dadd(rn_dadd(rn_dmul(P.n[0], p[0]), rn_dmul(P.n[1], p[1])), rn_dmul(P.n[2], p[2])), P.dd);
     *height = h;
     // (selects, not an indexed read: the arrays stay in registers on the device)
     const double p1 = P.k1 == 0 ? p[0] : p[1], n1 = P.k1 == 0 ? P.n[0] : P.n[1];
     const double p2 = P.k2 == 2 ? p[2] : p[1], n2 = P.k2 == 2 ? P.n[2] : P.n[1];
-    *u = prism_quantise(CD_PR_SUB(p1, CD_PR_MUL(h, n1)));
-    *v = prism_quantise(CD_PR_SUB(p2, CD_PR_MUL(h, n2)));
+    *u = prism_quantise(rn_dsub(p1, rn_dmul(h, n1)));
+    *v = prism_quantise(rn_dsub(p2, rn_dmul(h, n2)));
 }
 
 // cross(B - A, P - A) of integer points: differences below 2^30 in magnitude, products below 2^60, the result fits int64

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include <hip/hip_runtime.h>
+#include "rn_ops.hpp"
 
 namespace cd {
 
@@ -25,22 +25,6 @@ struct ShapeFrame {          // = cd_shape_frame
     double lo[3], hi[3];
 };
 
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_SF_MUL(a, b) __dmul_rn((a), (b))
-#define CD_SF_ADD(a, b) __dadd_rn((a), (b))
-#define CD_SF_SUB(a, b) __dsub_rn((a), (b))
-#define CD_SF_DIV(a, b) __ddiv_rn((a), (b))
-#define CD_SF_SQRT(a) __dsqrt_rn((a))
-#define CD_SF_I2D(a) __ll2double_rn((a))
-#else
-#define CD_SF_MUL(a, b) ((a) * (b))
-#define CD_SF_ADD(a, b) ((a) + (b))
-#define CD_SF_SUB(a, b) ((a) - (b))
-#define CD_SF_DIV(a, b) ((a) / (b))
-#define CD_SF_SQRT(a) std::sqrt((a))
-#define CD_SF_I2D(a) ((double)(a))
-#endif
-
 // the point may enter a set: finite and inside rule C4's range
 __host__ __device__ inline bool shape_coord_ok(float x, float y, float z) {
     // (written so that a NaN fails)
@@ -53,23 +37,23 @@ __host__ __device__ inline void shape_jacobi_rotate(double (&a)[3][3], double (&
     constexpr int R = 3 - P - Q;
     const double apq = a[P][Q];
     if (apq == 0.0) return;
-    const double theta = CD_SF_DIV(CD_SF_SUB(a[Q][Q], a[P][P]), CD_SF_MUL(2.0, apq));
-    const double root = CD_SF_SQRT(CD_SF_ADD(CD_SF_MUL(theta, theta), 1.0));
-    const double t = theta >= 0.0 ? CD_SF_DIV(1.0, CD_SF_ADD(theta, root)) : CD_SF_DIV(-1.0, CD_SF_SUB(root, theta));
-    const double cs = CD_SF_DIV(1.0, CD_SF_SQRT(CD_SF_ADD(CD_SF_MUL(t, t), 1.0)));
-    const double sn = CD_SF_MUL(t, cs);
-    const double h = CD_SF_MUL(t, apq);
-    a[P][P] = CD_SF_SUB(a[P][P], h);
-    a[Q][Q] = CD_SF_ADD(a[Q][Q], h);
+    const double theta = rn_ddiv(rn_dsub(a[Q][Q], a[P][P]), rn_dmul(2.0, apq));
+    const double root = rn_dsqrt(rn_dadd(rn_dmul(theta, theta), 1.0));
+    const double t = theta >= 0.0 ? rn_ddiv(1.0, rn_dadd(theta, root)) : rn_ddiv(-1.0, rn_dsub(root, theta));
+    const double cs = rn_ddiv(1.0, rn_dsqrt(rn_dadd(rn_dmul(t, t), 1.0)));
+    const double sn = rn_dmul(t, cs);
+    const double h = rn_dmul(t, apq);
+    a[P][P] = rn_dsub(a[P][P], h);
+    a[Q][Q] = rn_dadd(a[Q][Q], h);
     a[P][Q] = a[Q][P] = 0.0;
     const double arp = a[R][P], arq = a[R][Q];
-    a[R][P] = a[P][R] = CD_SF_SUB(CD_SF_MUL(cs, arp), CD_SF_MUL(sn, arq));
-    a[R][Q] = a[Q][R] = CD_SF_ADD(CD_SF_MUL(sn, arp), CD_SF_MUL(cs, arq));
+    a[R][P] = a[P][R] = rn_dsub(rn_dmul(cs, arp), rn_dmul(sn, arq));
+    a[R][Q] = a[Q][R] = rn_dadd(rn_dmul(sn, arp), rn_dmul(cs, arq));
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double vkp = v[k][P], vkq = v[k][Q];
-        v[k][P] = CD_SF_SUB(CD_SF_MUL(cs, vkp), CD_SF_MUL(sn, vkq));
-        v[k][Q] = CD_SF_ADD(CD_SF_MUL(sn, vkp), CD_SF_MUL(cs, vkq));
+        v[k][P] = rn_dsub(rn_dmul(cs, vkp), rn_dmul(sn, vkq));
+        v[k][Q] = rn_dadd(rn_dmul(sn, vkp), rn_dmul(cs, vkq));
     }
 }
 
@@ -88,16 +72,16 @@ __host__ __device__ inline void shape_solve(const long long S[9], int n, ShapeFr
     const double fn = (double)n, scale = 1.0 / 4294967296.0;
     double m[3], e[6];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) m[k] = CD_SF_DIV(CD_SF_MUL(CD_SF_I2D(S[k]), scale), fn);
+    for (int k = 0; k < 3; ++k) m[k] = rn_ddiv(rn_dmul(rn_ll2d(S[k]), scale), fn);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) e[k] = CD_SF_DIV(CD_SF_MUL(CD_SF_I2D(S[3 + k]), scale), fn);
+    for (int k = 0; k < 6; ++k) e[k] = rn_ddiv(rn_dmul(rn_ll2d(S[3 + k]), scale), fn);
     double a[3][3], v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    a[0][0] = CD_SF_SUB(e[0], CD_SF_MUL(m[0], m[0]));
-    a[0][1] = a[1][0] = CD_SF_SUB(e[1], CD_SF_MUL(m[0], m[1]));
-    a[0][2] = a[2][0] = CD_SF_SUB(e[2], CD_SF_MUL(m[0], m[2]));
-    a[1][1] = CD_SF_SUB(e[3], CD_SF_MUL(m[1], m[1]));
-    a[1][2] = a[2][1] = CD_SF_SUB(e[4], CD_SF_MUL(m[1], m[2]));
-    a[2][2] = CD_SF_SUB(e[5], CD_SF_MUL(m[2], m[2]));
+    a[0][0] = rn_dsub(e[0], rn_dmul(m[0], m[0]));
+    a[0][1] = a[1][0] = rn_dsub(e[1], rn_dmul(m[0], m[1]));
+    a[0][2] = a[2][0] = rn_dsub(e[2], rn_dmul(m[0], m[2]));
+    a[1][1] = rn_dsub(e[3], rn_dmul(m[1], m[1]));
+    a[1][2] = a[2][1] = rn_dsub(e[4], rn_dmul(m[1], m[2]));
+    a[2][2] = rn_dsub(e[5], rn_dmul(m[2], m[2]));
 #pragma unroll 1
     for (int sweep = 0; sweep < SHAPE_SWEEPS; ++sweep) {
         shape_jacobi_rotate<0, 1>(a, v);
@@ -108,9 +92,9 @@ __host__ __device__ inline void shape_solve(const long long S[9], int n, ShapeFr
     shape_order<0, 1>(d, v);
     shape_order<1, 2>(d, v);
     shape_order<0, 1>(d, v);
-    const double det = CD_SF_ADD(CD_SF_SUB(CD_SF_MUL(v[0][0], CD_SF_SUB(CD_SF_MUL(v[1][1], v[2][2]), CD_SF_MUL(v[1][2], v[2][1]))),
-                                           CD_SF_MUL(v[0][1], CD_SF_SUB(CD_SF_MUL(v[1][0], v[2][2]), CD_SF_MUL(v[1][2], v[2][0])))),
-                                 CD_SF_MUL(v[0][2], CD_SF_SUB(CD_SF_MUL(v[1][0], v[2][1]), CD_SF_MUL(v[1][1], v[2][0]))));
+    const double det = rn_dadd(rn_dsub(rn_dmul(v[0][0], rn_dsub(rn_dmul(v[1][1], v[2][2]), rn_dmul(v[1][2], v[2][1]))),
+                                           rn_dmul(v[0][1], rn_dsub(rn_dmul(v[1][0], v[2][2]), rn_dmul(v[1][2], v[2][0])))),
+                                 rn_dmul(v[0][2], rn_dsub(rn_dmul(v[1][0], v[2][1]), rn_dmul(v[1][1], v[2][0]))));
     if (det < 0.0) { v[0][2] = -v[0][2]; v[1][2] = -v[1][2]; v[2][2] = -v[2][2]; }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -123,10 +107,10 @@ __host__ __device__ inline void shape_solve(const long long S[9], int n, ShapeFr
 
 // step 3 for one point: q[a] = ((A[0][a] dx + A[1][a] dy) + A[2][a] dz)
 __host__ __device__ inline void shape_project(const double* mean, const double* A, float x, float y, float z, double q[3]) {
-    const double dx = CD_SF_SUB((double)x, mean[0]), dy = CD_SF_SUB((double)y, mean[1]), dz = CD_SF_SUB((double)z, mean[2]);
+    const double dx = rn_dsub((double)x, mean[0]), dy = rn_dsub((double)y, mean[1]), dz = rn_dsub((double)z, mean[2]);
 #pragma unroll
     for (int a = 0; a < 3; ++a)
-        q[a] = CD_SF_ADD(CD_SF_ADD(CD_SF_MUL(A[a], dx), CD_SF_MUL(A[3 + a], dy)), CD_SF_MUL(A[6 + a], dz));
+        q[a] = rn_dadd(rn_dadd(rn_dmul(A[a], dx), rn_dmul(A[3 + a], dy)), rn_dmul(A[6 + a], dz));
 }
 
 // a refused or too small set: its count and status, every other field zero
@@ -151,17 +135,17 @@ __host__ __device__ inline int shape_guess(const ShapeFrame& c, const ShapeFrame
     double sigma[3], w[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double s = CD_SF_ADD(t.lo[a], t.hi[a]);
-        sigma[a] = fabs(s) <= CD_SF_MUL(1.0 / 1048576.0, CD_SF_SUB(t.hi[a], t.lo[a])) ? 0.0 : (-s > 0.0 ? 1.0 : -1.0);
-        w[a] = -CD_SF_ADD(CD_SF_ADD(CD_SF_MUL(c.axes[a], c.mean[0]), CD_SF_MUL(c.axes[3 + a], c.mean[1])), CD_SF_MUL(c.axes[6 + a], c.mean[2]));
+        const double s = rn_dadd(t.lo[a], t.hi[a]);
+        sigma[a] = fabs(s) <= rn_dmul(1.0 / 1048576.0, rn_dsub(t.hi[a], t.lo[a])) ? 0.0 : (-s > 0.0 ? 1.0 : -1.0);
+        w[a] = -rn_dadd(rn_dadd(rn_dmul(c.axes[a], c.mean[0]), rn_dmul(c.axes[3 + a], c.mean[1])), rn_dmul(c.axes[6 + a], c.mean[2]));
     }
     const double F[4][3] = {{1.0, 1.0, 1.0}, {1.0, -1.0, -1.0}, {-1.0, 1.0, -1.0}, {-1.0, -1.0, 1.0}};
     double best = 0.0;
     int flip = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const double sc = CD_SF_ADD(CD_SF_ADD(CD_SF_MUL(CD_SF_MUL(F[k][0], sigma[0]), w[0]), CD_SF_MUL(CD_SF_MUL(F[k][1], sigma[1]), w[1])),
-                                    CD_SF_MUL(CD_SF_MUL(F[k][2], sigma[2]), w[2]));
+        const double sc = rn_dadd(rn_dadd(rn_dmul(rn_dmul(F[k][0], sigma[0]), w[0]), rn_dmul(rn_dmul(F[k][1], sigma[1]), w[1])),
+                                    rn_dmul(rn_dmul(F[k][2], sigma[2]), w[2]));
         if (k == 0 || sc > best) { best = sc; flip = k; }
     }
     const double f0 = flip >= 2 ? -1.0 : 1.0, f1 = (flip == 1 || flip == 3) ? -1.0 : 1.0, f2 = (flip == 1 || flip == 2) ? -1.0 : 1.0;
@@ -172,9 +156,9 @@ __host__ __device__ inline int shape_guess(const ShapeFrame& c, const ShapeFrame
         double R[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            R[j] = CD_SF_ADD(CD_SF_ADD(CD_SF_MUL(CD_SF_MUL(t.axes[3 * i], f0), c.axes[3 * j]), CD_SF_MUL(CD_SF_MUL(t.axes[3 * i + 1], f1), c.axes[3 * j + 1])),
-                             CD_SF_MUL(CD_SF_MUL(t.axes[3 * i + 2], f2), c.axes[3 * j + 2]));
-        const double gi = CD_SF_SUB(t.mean[i], CD_SF_ADD(CD_SF_ADD(CD_SF_MUL(R[0], c.mean[0]), CD_SF_MUL(R[1], c.mean[1])), CD_SF_MUL(R[2], c.mean[2])));
+            R[j] = rn_dadd(rn_dadd(rn_dmul(rn_dmul(t.axes[3 * i], f0), c.axes[3 * j]), rn_dmul(rn_dmul(t.axes[3 * i + 1], f1), c.axes[3 * j + 1])),
+                             rn_dmul(rn_dmul(t.axes[3 * i + 2], f2), c.axes[3 * j + 2]));
+        const double gi = rn_dsub(t.mean[i], rn_dadd(rn_dadd(rn_dmul(R[0], c.mean[0]), rn_dmul(R[1], c.mean[1])), rn_dmul(R[2], c.mean[2])));
 #pragma unroll
         for (int j = 0; j < 3; ++j) { g[4 * i + j] = (float)R[j]; finite = finite && shape_finite_f(g[4 * i + j]); }
         g[4 * i + 3] = (float)gi;

@@ -6,21 +6,9 @@
 #include <cmath>
 #include <cstdint>
 
-#include <hip/hip_runtime.h>
+#include "rn_ops.hpp"
 
 namespace cd {
-
-#ifdef __HIP_DEVICE_COMPILE__
-#define CD_VF_MUL(a, b) __dmul_rn((a), (b))
-#define CD_VF_ADD(a, b) __dadd_rn((a), (b))
-#define CD_VF_SUB(a, b) __dsub_rn((a), (b))
-#define CD_VF_DIV(a, b) __ddiv_rn((a), (b))
-#else
-#define CD_VF_MUL(a, b) ((a) * (b))
-#define CD_VF_ADD(a, b) ((a) + (b))
-#define CD_VF_SUB(a, b) ((a) - (b))
-#define CD_VF_DIV(a, b) ((a) / (b))
-#endif
 
 enum { VERIFY_MISS = 0, VERIFY_AGREE = 1, VERIFY_THROUGH = 2, VERIFY_OCCLUDED = 3, VERIFY_INVALID = 4 };
 
@@ -46,12 +34,12 @@ __host__ __device__ inline void verify_setup(const double* pose, const double* d
         s->col[a][0] = pose[a];
         s->col[a][1] = pose[4 + a];
         s->col[a][2] = pose[8 + a];
-        s->half[a] = CD_VF_DIV(dims[a], 2.0);
-        s->o[a] = -CD_VF_ADD(CD_VF_ADD(CD_VF_MUL(s->col[a][0], t0), CD_VF_MUL(s->col[a][1], t1)), CD_VF_MUL(s->col[a][2], t2));
+        s->half[a] = rn_ddiv(dims[a], 2.0);
+        s->o[a] = -rn_dadd(rn_dadd(rn_dmul(s->col[a][0], t0), rn_dmul(s->col[a][1], t1)), rn_dmul(s->col[a][2], t2));
     }
     for (int k = 0; k < 8; ++k) {
         const double x = (k & 4) ? s->half[0] : -s->half[0], y = (k & 2) ? s->half[1] : -s->half[1], z = (k & 1) ? s->half[2] : -s->half[2];
-        const double zc = CD_VF_ADD(CD_VF_ADD(CD_VF_ADD(CD_VF_MUL(pose[8], x), CD_VF_MUL(pose[9], y)), CD_VF_MUL(pose[10], z)), t2);
+        const double zc = rn_dadd(rn_dadd(rn_dadd(rn_dmul(pose[8], x), rn_dmul(pose[9], y)), rn_dmul(pose[10], z)), t2);
         ok = ok && zc > 0.0;
     }
     s->verified = ok ? 1 : 0;
@@ -59,15 +47,15 @@ __host__ __device__ inline void verify_setup(const double* pose, const double* d
 
 // steps 2 and 3 for the ray of pixel (u, v): true when it hits, *z_r the camera z of the entry point
 __host__ __device__ inline bool verify_hit(const VerifySetup& s, const VerifyCam& cam, int u, int v, double* z_r) {
-    const double dx = CD_VF_DIV(CD_VF_SUB((double)u, cam.cx), cam.fx), dy = CD_VF_DIV(CD_VF_SUB((double)v, cam.cy), cam.fy);
+    const double dx = rn_ddiv(rn_dsub((double)u, cam.cx), cam.fx), dy = rn_ddiv(rn_dsub((double)v, cam.cy), cam.fy);
     double tn = -INFINITY, tf = INFINITY;
     bool miss = false;
     for (int a = 0; a < 3; ++a) {
-        const double dd = CD_VF_ADD(CD_VF_ADD(CD_VF_MUL(s.col[a][0], dx), CD_VF_MUL(s.col[a][1], dy)), s.col[a][2]);
+        const double dd = rn_dadd(rn_dadd(rn_dmul(s.col[a][0], dx), rn_dmul(s.col[a][1], dy)), s.col[a][2]);
         if (dd == 0.0) {
             miss = miss || fabs(s.o[a]) > s.half[a];
         } else {
-            const double t1 = CD_VF_DIV(CD_VF_SUB(-s.half[a], s.o[a]), dd), t2 = CD_VF_DIV(CD_VF_SUB(s.half[a], s.o[a]), dd);
+            const double t1 = rn_ddiv(rn_dsub(-s.half[a], s.o[a]), dd), t2 = rn_ddiv(rn_dsub(s.half[a], s.o[a]), dd);
             const double lo = t1 < t2 ? t1 : t2, hi = t1 < t2 ? t2 : t1;
             tn = lo > tn ? lo : tn;
             tf = hi < tf ? hi : tf;
@@ -80,10 +68,10 @@ __host__ __device__ inline bool verify_hit(const VerifySetup& s, const VerifyCam
 // step 4 for a hit pixel; *um: the pixel's term of agree_abs_um (AGREE only; terms of 2^63 and over count as 2^63 - 1)
 __host__ __device__ inline int verify_class(double z_r, uint16_t d, double depth_scale, double tau, unsigned long long* um) {
     if (d == 0) return VERIFY_INVALID;
-    const double z_m = CD_VF_MUL((double)d, depth_scale);
-    if (CD_VF_SUB(z_m, z_r) > tau) return VERIFY_THROUGH;
-    if (CD_VF_SUB(z_r, z_m) > tau) return VERIFY_OCCLUDED;
-    const double e = CD_VF_ADD(CD_VF_MUL(fabs(CD_VF_SUB(z_m, z_r)), 1e6), 0.5);
+    const double z_m = rn_dmul((double)d, depth_scale);
+    if (rn_dsub(z_m, z_r) > tau) return VERIFY_THROUGH;
+    if (rn_dsub(z_r, z_m) > tau) return VERIFY_OCCLUDED;
+    const double e = rn_dadd(rn_dmul(fabs(rn_dsub(z_m, z_r)), 1e6), 0.5);
     *um = e < 9223372036854775808.0 ? (unsigned long long)(long long)e : 9223372036854775807ull;
     return VERIFY_AGREE;
 }

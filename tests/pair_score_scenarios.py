@@ -51,7 +51,9 @@ SHAPES = tuple((n, m) for n in SMALL for m in SMALL) + (
     # split over two workgroups by its source, (300, PS_TILE + 1) by its template)
     (PS_THREADS - 1, 40), (PS_THREADS, 40), (PS_THREADS + 1, 40), (40, PS_THREADS - 1), (40, PS_THREADS), (40, PS_THREADS + 1),
     # both directions split, and three items with an uneven last row
-    (PS_CHUNK + 1, PS_CHUNK + 1), (2 * PS_CHUNK + 1, PS_CHUNK + 77))
+    (PS_CHUNK + 1, PS_CHUNK + 1), (2 * PS_CHUNK + 1, PS_CHUNK + 77),
+    # a last tile that the +inf padding fills up by 6 and by 2 points (the tile is padded to a multiple of 8), in each direction
+    (10, 14), (14, 10))
 
 
 def motion(angle_deg=3.0, shift=(0.002, -0.001, 0.0015)):

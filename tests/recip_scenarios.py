@@ -20,7 +20,8 @@ ICP_QSLICE, RC_THREADS, RC_CHUNK = 512, 256, 512    # common.hpp, k_icp_recip.hi
 # cd_icp sizes: the least legal ones, around a wave, around the workgroup (one query row a lane or two), around a slice - which
 # is also the chunk of queries one workgroup takes (513: a second workgroup with a single query; 1025: a third) - and nine
 # chunks: tiles before the chunk, the chunk's own and tiles behind it, the last one partial
-SIZES = (3, 4, 5, 63, 64, 65, RC_THREADS - 1, RC_THREADS, RC_THREADS + 1, ICP_QSLICE - 1, ICP_QSLICE, ICP_QSLICE + 1, 2 * RC_CHUNK + 1, 4099)
+# (10 and 14: a last tile that the +inf padding fills up by 6 and by 2 points - the tile is padded to a multiple of 8)
+SIZES = (3, 4, 5, 10, 14, 63, 64, 65, RC_THREADS - 1, RC_THREADS, RC_THREADS + 1, ICP_QSLICE - 1, ICP_QSLICE, ICP_QSLICE + 1, 2 * RC_CHUNK + 1, 4099)
 SCENE_SEEDS = (2, 3, 4, 5)         # the contamination scene of tests/reject_reference.py; the GPU runs the first two of each template
 GPU_SCENE_SEEDS = SCENE_SEEDS[:2]
 SPLIT_SIZE = 3 * RC_CHUNK + 77     # a source larger than one work split: four workgroups of queries

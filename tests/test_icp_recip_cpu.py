@@ -324,7 +324,7 @@ def test_contamination_scene_is_helped_by_the_rule(kind):
 @pytest.mark.parametrize("kind", S.KINDS)
 def test_sized_sources_cover_the_paths(kind):
     tpl, prm = S.template(kind), S.icp_params()
-    assert S.SIZES == (3, 4, 5, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1025, 4099)
+    assert S.SIZES == (3, 4, 5, 10, 14, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1025, 4099)
     assert S.SPLIT_SIZE > 3 * S.RC_CHUNK and S.SPLIT_SIZE % S.RC_CHUNK not in (0, 1)
     varied = 0
     for n in S.SIZES + (S.SPLIT_SIZE,):
