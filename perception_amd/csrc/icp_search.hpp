@@ -83,6 +83,27 @@ __device__ __forceinline__ void stage_chunk(const float4* __restrict__ tpl, cons
 // Per-wave query state: lane k of a wave holds query (wave + 16*k) of the slice.
 struct QueryRegs { float px, py, pz, pbest; int pbi, poi; };
 
+// The seed of a lane's query (q.px, q.py, q.pz set): the previous neighbour (use_prev; *prev is read only then) and/or,
+// `coarse`, the first point of every 64-point run, the lowest index winning ties.  Leaves the seed bound in q.pbest, the
+// seed's position in q.pbi and its original index in q.poi.  (k_icp_pipe.hip seeds the same way from its own image: seed_at.)
+__device__ __forceinline__ void seed_query(const float4* __restrict__ tpl, int m, bool use_prev, bool coarse, const int* prev, QueryRegs& q) {
+    q.pbest = 3.402823466e38f;
+    if (use_prev) {
+        q.pbi = *prev;
+        const float4 q0 = tpl[q.pbi];
+        q.pbest = dist2(q.px, q.py, q.pz, q0.x, q0.y, q0.z);
+    }
+    if (coarse) {
+        for (int j = 0; j < m; j += ICP_SUB) {
+            const float4 t = tpl[j];
+            const float d = dist2(q.px, q.py, q.pz, t.x, t.y, t.z);
+            if (d < q.pbest) { q.pbest = d; q.pbi = j; }
+        }
+    }
+    q.pbest = seed_bound(q.pbest);
+    q.poi = __float_as_int(tpl[q.pbi].w);
+}
+
 __device__ __forceinline__ unsigned long long lanes_below(int nk) { return nk >= 64 ? ~0ull : ((1ull << nk) - 1ull); }
 
 // ---------------------------------------------------------------------------------------

@@ -65,21 +65,7 @@ __device__ __forceinline__ void fetch_queries(const float4* __restrict__ tpl, in
         const float4 p = pts[myq];
         q.px = p.x; q.py = p.y; q.pz = p.z;
         if (apply_T) xform(Tm, p.x, p.y, p.z, q.px, q.py, q.pz);
-        q.pbest = 3.402823466e38f;
-        if (use_prev) {
-            q.pbi = nn[myq];
-            const float4 q0 = tpl[q.pbi];
-            q.pbest = dist2(q.px, q.py, q.pz, q0.x, q0.y, q0.z);
-        }
-        if (coarse || !use_prev) {
-            for (int j = 0; j < m; j += ICP_SUB) {
-                const float4 t = tpl[j];
-                const float d = dist2(q.px, q.py, q.pz, t.x, t.y, t.z);
-                if (d < q.pbest) { q.pbest = d; q.pbi = j; }
-            }
-        }
-        q.pbest = seed_bound(q.pbest);
-        q.poi = __float_as_int(tpl[q.pbi].w);
+        seed_query(tpl, m, use_prev, coarse || !use_prev, &nn[myq], q);
     }
 }
 

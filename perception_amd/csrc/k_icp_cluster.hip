@@ -124,6 +124,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                         xform(s_so.T, p.x, p.y, p.z, q.px, q.py, q.pz);   // T read from LDS to keep registers free
                         pts[myq] = make_float4(q.px, q.py, q.pz, p.w);
                     }
+                    // seed_query(tp, c.tpl_m, it > 0, it < 3, &nnq[myq], q) written out: called here it costs every pass a branch (profiles/EXPERIMENTS.md)
                     q.pbest = 3.402823466e38f;
                     if (it > 0) {
                         q.pbi = nnq[myq];
@@ -183,10 +184,7 @@ __global__ void __launch_bounds__(ICPT_THREADS) k_icp_cluster(int ncl, const int
                     pts[myq] = make_float4(ox, oy, oz, p.w);
                     const float4 p0 = pts0[myq];
                     xform(s_so.Tfinal, p0.x, p0.y, p0.z, q.px, q.py, q.pz);
-                    q.pbi = nnq[myq];
-                    const float4 q0p = tp[q.pbi];
-                    q.pbest = seed_bound(dist2(q.px, q.py, q.pz, q0p.x, q0p.y, q0p.z));
-                    q.poi = __float_as_int(q0p.w);
+                    seed_query(tp, c.tpl_m, true, false, &nnq[myq], q);
                 }
                 const bool near = search_near(s_tpl, s_cs, g, grid_ok, rmax, gpad, q, nk);
                 search_rest(tr, c.tpl_m, near, q, nk, s_tpl, bx, staged);

@@ -15,10 +15,44 @@ CD_DEBUG_COUNTERS(g_icp_stats, [16], cd_debug_icp_stats)
 // radius of the seed ball in grid cells (bucket 15: 15 or more)
 CD_DEBUG_COUNTERS(g_icp_rhist, [48], cd_debug_icp_rhist)
 #define CD_GRID_STAT(slot, cond) { const unsigned long long b_ = ballot64(cond); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_icp_stats[slot], 1ull); atomicAdd(&g_icp_stats[(slot) + 1], (unsigned long long)__popcll(b_)); } }
+// g_icp_stats[slot] += v, once per wave (v: wave-uniform, evaluated by every lane - it may hold a ballot)
+#define CD_STAT_ADD(slot, v) { const unsigned long long v_ = (unsigned long long)(v); if ((threadIdx.x & 63) == 0) atomicAdd(&g_icp_stats[slot], v_); }
+// [8] seed tests of a pass of nk queries in iteration `it`
+#define CD_STAT_SEEDS(nk, it, m) CD_STAT_ADD(8, (unsigned long long)(nk) * (unsigned long long)(((it) > 0 ? 1 : 0) + ((it) < 3 ? ((m) + ICP_SUB - 1) / ICP_SUB : 0)))
+// [0] queries, [3] near queries; the far ones of an iteration into the radius histogram
+#define CD_STAT_NEAR(nk, near, mine_far, it, cells) { CD_STAT_ADD(0, nk) CD_STAT_ADD(3, __popcll(ballot64(near))) \
+    if (mine_far) atomicAdd(&g_icp_rhist[((it) < 3 ? 0 : (it) < 16 ? 16 : 32) + min(15, (int)(cells))], 1ull); }
+// far queries of an iteration ([12 + class]) and those whose TRUE neighbour lies within the grid walk's reach ([9 + class]: a
+// better seed would have made them near), by iteration class
+#define CD_STAT_REACH(mine_far, within, it) { const int cls_ = (it) < 3 ? 0 : (it) < 16 ? 1 : 2; \
+    CD_STAT_ADD(9 + cls_, __popcll(ballot64((mine_far) && (within)))) CD_STAT_ADD(12 + cls_, __popcll(ballot64(mine_far))) }
+#else
+#define CD_STAT_ADD(slot, v)
+#define CD_STAT_SEEDS(nk, it, m)
+#define CD_STAT_NEAR(nk, near, mine_far, it, cells)
+#define CD_STAT_REACH(mine_far, within, it)
 #endif
 #ifdef CD_ITSTATS
 // per ICP iteration (31 = fitness pass): pass cycles, passes, far queries, patches visited
 CD_DEBUG_COUNTERS(g_icp_it, [32][4], cd_debug_icp_it)
+#define CD_IT_BEGIN(iter_phase, it) const long long tpass0_ = clock64(); const int stat_it_ = (iter_phase) ? min(it, 30) : 31; int stat_acc_[2] = {0, 0};
+#define CD_IT_ACC stat_acc_
+#define CD_IT_FAR(acc, npatches) if (acc) { (acc)[0] += 1; (acc)[1] += (npatches); }
+#define CD_IT_END() if ((threadIdx.x & 63) == 0) { \
+    atomicAdd(&g_icp_it[stat_it_][0], (unsigned long long)(clock64() - tpass0_)); atomicAdd(&g_icp_it[stat_it_][1], 1ull); \
+    atomicAdd(&g_icp_it[stat_it_][2], (unsigned long long)stat_acc_[0]); atomicAdd(&g_icp_it[stat_it_][3], (unsigned long long)stat_acc_[1]); }
+#else
+#define CD_IT_BEGIN(iter_phase, it)
+#define CD_IT_ACC nullptr
+#define CD_IT_FAR(acc, npatches)
+#define CD_IT_END()
+#endif
+#ifdef CD_TIMERS_FETCH
+// how long a wave waits for its pass's points and neighbour indices (the loads that follow then hit L1): phase 3
+#define CD_FETCH_WAIT(mine, p_pt, p_nn) { float4 pp_ = make_float4(0.f, 0.f, 0.f, 0.f); int nv_ = 0; if (mine) { pp_ = *(p_pt); nv_ = *(p_nn); } \
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"(pp_.x), "v"(nv_) : "memory"); CD_PHASE(3) }
+#else
+#define CD_FETCH_WAIT(mine, p_pt, p_nn)
 #endif
 #ifdef CD_DONDBG
 // hand-over timeline (tools/probe_handover.py): [1] latest workgroup end, [2] ticks spent waiting, [8 + b] waits begun,
@@ -56,27 +90,22 @@ __device__ __forceinline__ unsigned long long clear_bit64(unsigned long long m, 
 // test `lb <= d2(q, seed)` keeps every patch that can hold a point as close as the seed (closer, or equally close with a lower
 // original index); the lanes' running minima start at the seed key, so "some lane's key is below the seed key" says exactly
 // "the neighbour changes" - and when it does not (the usual case once ICP has settled) the query is done after the visits:
-// no reduction, no write-back.  Both halves' boxes are always tested: the per-query flag that skipped an unreachable half cost
-// a readlane, two scalar bit tests and two branches to save eleven vector instructions - on a scalar unit that sixteen waves share.
-__device__ __forceinline__ void far_begin(FarQ& f, const RunBoxes& bx, const QueryRegs& q, int k) {
+// no reduction, no write-back.  far_query broadcasts query k of the wave and its seed key; both far searches start with it.
+__device__ __forceinline__ void far_query(FarQ& f, const QueryRegs& q, int k) {
     f.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.px), k));
     f.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.py), k));
     f.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.pz), k));
     f.best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.pbest), k));
-    const unsigned kw = (unsigned)__builtin_amdgcn_readlane(q.poi, k);
-    f.m0 = ballot64(box_lb(bx.L0, bx.H0, f.x, f.y, f.z) <= f.best);
-    f.m1 = ballot64(box_lb(bx.L1, bx.H1, f.x, f.y, f.z) <= f.best);
-    f.lkey = ((unsigned long long)__float_as_uint(f.best) << 32) | (unsigned long long)kw;
+    f.lkey = ((unsigned long long)__float_as_uint(f.best) << 32) | (unsigned long long)(unsigned)__builtin_amdgcn_readlane(q.poi, k);
     f.seed = f.lkey;
 }
-template <bool PK = false>
-__device__ __forceinline__ void far_take(FarQ& f, const float4& t, int pos) {
+__device__ __forceinline__ void far_take(FarQ& f, const float4& t) {
     // lexicographic (d2, original index) minimum, rule C5, as ONE unsigned 64-bit compare: squared distances are non-negative
     // floats (or +inf / NaN-free here), which order like their bit patterns; no branch, no tie special case
     // The low word carries the stored position below the original index (both < 2^13 for an LDS-resident template; the
     // position is a function of the index, so the order is still (d2, original index)): the key alone is the whole answer.
-    const float d = dist2(f.x, f.y, f.z, t.x, t.y, PK ? t.w : t.z);   // (PK images are stored (x, y, key word, z))
-    unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (PK ? (unsigned)__float_as_int(t.z) : (((unsigned)__float_as_int(t.w) << 13) | (unsigned)pos));
+    const float d = dist2(f.x, f.y, f.z, t.x, t.y, t.w);   // (the re-labelled image: (x, y, key word, z), see tpl_z)
+    unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)__float_as_int(t.z);
     asm("" : "+v"(key));   // (as in grid_search: keeps the key in the loaded quad's own registers)
     f.lkey = key < f.lkey ? key : f.lkey;
 }
@@ -85,61 +114,60 @@ __device__ __forceinline__ void far_take(FarQ& f, const float4& t, int pos) {
 // word is read back - by all lanes, broadcast - and unpacked.  LDS operations of one wave execute in program order, so no
 // fence is needed.  This replaced ballot + popcount + (DPP minimum + tie loop | three v_readlane) + a masked write-back,
 // which cost more than the box tests (probe: the tail run twice = +1.05 ms of 5.9).
-__device__ __forceinline__ void far_end(const FarQ& f, QueryRegs& q, int k, unsigned long long* slot) {
+template <unsigned POS_MASK>
+__device__ __forceinline__ void far_merge(unsigned long long lkey, unsigned long long bound, QueryRegs& q, int k, unsigned long long* slot) {
     const int lane = threadIdx.x & 63;
-    const unsigned long long bound = f.seed;
     // lanes whose key beats the seed's.  None (the usual case once ICP has settled: the neighbour is still the seed): the
     // query keeps it, nothing to do.  Exactly one: that key IS the minimum, fetched with two readlanes.  Several: LDS 64-bit
     // min over them.
-    const unsigned long long imp = ballot64(f.lkey < bound);
+    const unsigned long long imp = ballot64(lkey < bound);
     if (imp == 0ull) return;
     unsigned long long res;
     if (__popcll(imp) == 1) {
         const int src = __ffsll((long long)imp) - 1;
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(f.lkey >> 32), src);
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)f.lkey, src);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(lkey >> 32), src);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)lkey, src);
         res = ((unsigned long long)hi << 32) | lo;
     } else {
         if (lane == k) __hip_atomic_store(slot, bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        if (f.lkey < bound) __hip_atomic_fetch_min(slot, f.lkey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lkey < bound) __hip_atomic_fetch_min(slot, lkey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         res = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     const bool mine = lane == k;
     const unsigned lo = (unsigned)res;
     q.pbest = mine ? __uint_as_float((unsigned)(res >> 32)) : q.pbest;
-    q.pbi = mine ? (int)(lo & 0x1fffu) : q.pbi;
+    q.pbi = mine ? (int)(lo & POS_MASK) : q.pbi;
     q.poi = mine ? (int)lo : q.poi;
 }
-template <bool PK = false>
-__device__ __forceinline__ void search_patches(const float4* s_tpl, const unsigned short* s_kd, const RunBoxes& bx, int cn, QueryRegs& q,
+__device__ __forceinline__ void search_patches(const float4* s_tpl, const unsigned short* s_kd, const RunBoxes& bx, QueryRegs& q,
                                                unsigned long long todo, int psplit, unsigned long long* slot, int* stat_acc = nullptr) {
     const int lane = threadIdx.x & 63;
     while (todo) {
         const int k = __ffsll((long long)todo) - 1;
         todo = clear_bit64(todo, k);
         FarQ A;
-        far_begin(A, bx, q, k);
-#ifdef CD_STATS
-        if (lane == 0) { atomicAdd(&g_icp_stats[1], (unsigned long long)(__popcll(A.m0) + __popcll(A.m1))); atomicAdd(&g_icp_stats[2], 1ull); }
-#endif
-#ifdef CD_ITSTATS
-        if (stat_acc) { stat_acc[0] += 1; stat_acc[1] += __popcll(A.m0) + __popcll(A.m1); }
-#endif
+        far_query(A, q, k);
+        // Both halves' boxes are always tested: the per-query flag that skipped an unreachable half cost a readlane, two scalar
+        // bit tests and two branches to save eleven vector instructions - on a scalar unit that sixteen waves share.
+        A.m0 = ballot64(box_lb(bx.L0, bx.H0, A.x, A.y, A.z) <= A.best);
+        A.m1 = ballot64(box_lb(bx.L1, bx.H1, A.x, A.y, A.z) <= A.best);
+        CD_STAT_ADD(1, __popcll(A.m0) + __popcll(A.m1)) CD_STAT_ADD(2, 1)   // [2] far queries searched, [1] the patches they visit
+        CD_IT_FAR(stat_acc, __popcll(A.m0) + __popcll(A.m1))
         // the two halves' masks one after the other: no per-patch choice between them (three scalar instructions and a branch)
         while (A.m0) {
             const int r = __ffsll((long long)A.m0) - 1;
             A.m0 = clear_bit64(A.m0, r);
             const int pos = s_kd[r * ICP_SUB + lane];
-            far_take<PK>(A, s_tpl[pos], pos);
+            far_take(A, s_tpl[pos]);
         }
         const unsigned short* s_kd1 = s_kd + psplit * ICP_SUB;   // (the right half's table: no per-patch scalar add)
         while (A.m1) {
             const int r = __ffsll((long long)A.m1) - 1;
             A.m1 = clear_bit64(A.m1, r);
             const int pos = s_kd1[r * ICP_SUB + lane];
-            far_take<PK>(A, s_tpl[pos], pos);
+            far_take(A, s_tpl[pos]);
         }
-        far_end(A, q, k, slot);
+        far_merge<KeyFmt<13>::POS_MASK>(A.lkey, A.seed, q, k, slot);
     }
 }
 
@@ -161,27 +189,17 @@ __device__ __forceinline__ void search_patches_big(const float4* __restrict__ tp
     while (todo) {
         const int k = __ffsll((long long)todo) - 1;
         todo = clear_bit64(todo, k);
-        const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.px), k));
-        const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.py), k));
-        const float z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.pz), k));
-        const float best = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.pbest), k));
-        // the query's seed key, as in far_begin: d2(q, seed) exactly and the seed's key word - a query whose neighbour does not
-        // change is done after its visits
-        const unsigned long long bound = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(unsigned)__builtin_amdgcn_readlane(q.poi, k);
-        unsigned long long lkey = bound;
-        unsigned long long ma = ballot64(box_lb(sp.L, sp.H, x, y, z) <= best);
-#ifdef CD_STATS
-        if (lane == 0) atomicAdd(&g_icp_stats[2], 1ull);
-#endif
+        FarQ A;   // (m0, m1 unused: the boxes here are the superpatches')
+        far_query(A, q, k);
+        unsigned long long ma = ballot64(box_lb(sp.L, sp.H, A.x, A.y, A.z) <= A.best);
+        CD_STAT_ADD(2, 1)
         while (ma) {
             const int sidx = __ffsll((long long)ma) - 1;
             ma = clear_bit64(ma, sidx);
             const int first = __builtin_amdgcn_readlane(sp.first, sidx), cnt = __builtin_amdgcn_readlane(sp.cnt, sidx);
             const int pl = first + min(lane, cnt - 1);
-            unsigned long long mp = ballot64(lane < cnt && box_lb(s_plo[pl], s_phi[pl], x, y, z) <= best);
-#ifdef CD_STATS
-            if (lane == 0) atomicAdd(&g_icp_stats[1], (unsigned long long)__popcll(mp));
-#endif
+            unsigned long long mp = ballot64(lane < cnt && box_lb(s_plo[pl], s_phi[pl], A.x, A.y, A.z) <= A.best);
+            CD_STAT_ADD(1, __popcll(mp))
             while (mp) {   // two patches per trip: their loads are in flight together (an odd one out is read twice)
                 const int b0 = __ffsll((long long)mp) - 1;
                 mp = clear_bit64(mp, b0);
@@ -192,33 +210,15 @@ __device__ __forceinline__ void search_patches_big(const float4* __restrict__ tp
                 const float4 u = tplk[(unsigned)(r1 * ICP_SUB + lane)];
                 const unsigned pt = kdmap[(unsigned)(r0 * ICP_SUB + lane)];
                 const unsigned pu = kdmap[(unsigned)(r1 * ICP_SUB + lane)];
-                const float d = dist2(x, y, z, t.x, t.y, t.z);
-                const float e = dist2(x, y, z, u.x, u.y, u.z);
+                const float d = dist2(A.x, A.y, A.z, t.x, t.y, t.z);
+                const float e = dist2(A.x, A.y, A.z, u.x, u.y, u.z);
                 const unsigned long long kd_ = ((unsigned long long)__float_as_uint(d) << 32) | (((unsigned)__float_as_int(t.w) << 16) | pt);
                 const unsigned long long ke_ = ((unsigned long long)__float_as_uint(e) << 32) | (((unsigned)__float_as_int(u.w) << 16) | pu);
-                lkey = kd_ < lkey ? kd_ : lkey;
-                lkey = ke_ < lkey ? ke_ : lkey;
+                A.lkey = kd_ < A.lkey ? kd_ : A.lkey;
+                A.lkey = ke_ < A.lkey ? ke_ : A.lkey;
             }
         }
-        // minimum over the wave: as far_end (none - the neighbour stays - / exactly one / several lanes beat the seed key)
-        const unsigned long long imp = ballot64(lkey < bound);
-        if (imp == 0ull) continue;
-        unsigned long long res;
-        if (__popcll(imp) == 1) {
-            const int src = __ffsll((long long)imp) - 1;
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(lkey >> 32), src);
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)lkey, src);
-            res = ((unsigned long long)hi << 32) | lo;
-        } else {
-            if (lane == k) __hip_atomic_store(slot, bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            if (lkey < bound) __hip_atomic_fetch_min(slot, lkey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            res = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        }
-        const bool mine = lane == k;
-        const unsigned lo = (unsigned)res;
-        q.pbest = mine ? __uint_as_float((unsigned)(res >> 32)) : q.pbest;
-        q.pbi = mine ? (int)(lo & 0xffffu) : q.pbi;
-        q.poi = mine ? (int)lo : q.poi;
+        far_merge<KeyFmt<16>::POS_MASK>(A.lkey, A.seed, q, k, slot);
     }
 }
 
@@ -267,6 +267,15 @@ struct PipeSlotN : PipeSlot {
 };
 template <bool BOUNDED> struct PipeSlotSel { using T = PipeSlot; };
 template <> struct PipeSlotSel<true> { using T = PipeSlotN; };
+
+// A slot ready for the passes and arrivals of a step: sums (and kept count) zero, nobody arrived, no pass taken
+template <bool BOUNDED, class Slot>
+__device__ __forceinline__ void pipe_slot_clear(Slot* sl) {
+    for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
+    if constexpr (BOUNDED) sl->nv = 0u;
+    sl->arrived = 0;
+    sl->next_pass = 0;
+}
 
 // The state update of one iteration (icp_step; lane 0 of the finishing wave).  BOUNDED (rule C8): n = the kept correspondences.
 // (Out-of-line callees are plain overloads, not template instances: a linkonce function has no exact definition,
@@ -403,6 +412,96 @@ __device__ __noinline__ int pipe_wait_for_cluster(int* don, int total, int entry
     return -1;
 }
 
+// A template point as icp_pipe_body reads it.  BIG: (x, y, z, original index) from global memory, the key word put together
+// from the index and the stored position.  Otherwise the LDS image, re-labelled once at staging: the low word of a search key,
+// (original index << 13) | position (pads: all ones, and +inf coordinates anyway), replaces the bare original index, which
+// nothing in this kernel needs, and the point is stored as (x, y, key word, z): the key word then sits in the even register
+// of the loaded quad and the squared distance can be formed in the z register next to it - the 64-bit key (rule C5's compare)
+// needs no move
+template <bool BIG> __device__ __forceinline__ float tpl_z(const float4& t) { return BIG ? t.z : t.w; }
+template <bool BIG> __device__ __forceinline__ unsigned tpl_key_word(const float4& t, int pos) {
+    return BIG ? (((unsigned)__float_as_int(t.w) << 16) | (unsigned)pos) : (unsigned)__float_as_int(t.z);
+}
+
+// A seed candidate of the query (x, y, z): the template point at `pos`, its squared distance and its key word.  The pass picks
+// among them as icp_search.hpp's seed_query does, but remembers the seed's key word, which both searches start from.
+struct PipeSeed { float d2; int pos; unsigned kw; };
+template <bool BIG>
+__device__ __forceinline__ PipeSeed seed_at(const float4* tpl, int pos, float x, float y, float z) {
+    const float4 t = BIG ? tpl[(unsigned)pos] : tpl[pos];
+    return {dist2(x, y, z, t.x, t.y, tpl_z<BIG>(t)), pos, tpl_key_word<BIG>(t, pos)};
+}
+
+// The pass's correspondences into the slot.  Iteration: the neighbour's index to *nnp (through to memory if the cluster leaves
+// after this step) and the 16 moment terms of the kept ones, counted in nv if BOUNDED; fitness pass: the squared distance.  They go
+// into the slot's accumulators right away: no sum is carried in registers across the searches (32 VGPRs that they would spill).
+template <bool BIG, bool BOUNDED, class Slot>
+__device__ __forceinline__ void pipe_fold_pass(Slot* sl, const float4* tpl, const QueryRegs q, int nk, int phase, int give, int* nnp, float d2_max) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long S[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) S[i] = 0ull;
+    // float -> fixed point (rule C4) in four instructions per term instead of eight (fixq_fast, common.hpp), valid
+    // while every term stays below 2^50 / 2^shift; a wave with a lane outside that range (coordinates beyond 256 m,
+    // neighbours more than 128 m away) takes the general conversion - same integers either way
+    float4 qq = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < nk && phase == PH_ITER) qq = BIG ? tpl[(unsigned)q.pbi] : tpl[q.pbi];
+    const float pv[3] = {q.px, q.py, q.pz}, qv[3] = {qq.x, qq.y, tpl_z<BIG>(qq)};
+    const float big_c = fmaxf(fmaxf(fmaxf(fabsf(pv[0]), fabsf(pv[1])), fabsf(pv[2])), fmaxf(fmaxf(fabsf(qv[0]), fabsf(qv[1])), fabsf(qv[2])));
+    const bool fast = ballot64(lane < nk && !(big_c < 256.f && q.pbest < 16384.f)) == 0ull;
+    if (lane < nk) {
+        if (phase == PH_ITER) {
+            if (give) __hip_atomic_store(nnp, q.pbi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else *nnp = q.pbi;
+            if (BOUNDED && !(q.pbest <= d2_max)) {
+                // rejected (rule C8): adds nothing
+            } else if (fast) {
+                moment_terms<true>(pv, qv, q.pbest, S);
+            } else {
+                moment_terms(pv, qv, q.pbest, S);
+            }
+        } else {
+            S[0] = fast ? fixq_fast(q.pbest, FIX_SHIFT_D2) : (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
+        }
+    }
+    wave_fold_to_lds(S, phase == PH_ITER ? 16 : 1, sl->acc);
+    if constexpr (BOUNDED) {
+        const unsigned long long kb = ballot64(lane < nk && phase == PH_ITER && q.pbest <= d2_max);
+        if (lane == 0 && kb) atomicAdd(&sl->nv, (uint32_t)__popcll(kb));
+    }
+}
+
+// Lane 0 of the wave that arrived last, end of an iteration: the state update; then a cluster that has not converged and was
+// promised leaves for the mailbox (returns true: the slot is free), or is promised now if workgroups wait and this one has two
+template <class Slot>
+__device__ __forceinline__ bool pipe_end_iteration(Slot* sl, const Slot* slots, IcpState* st, int* don, const IcpParams& prm) {
+    // (the load is in flight while the step is solved)
+    const int waiting = don ? don_load(don + DON_AVAIL) : 0;
+    sl->take = 0;
+    if (pipe_solve(sl, prm)) {
+        sl->phase = PH_FIT;
+        if (sl->give) { sl->give = 0; __hip_atomic_fetch_add(don + DON_AVAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // converged: stays
+        return false;
+    }
+    sl->it += 1;
+    if (sl->give) return pipe_give(sl, slots, st, don, prm.don_fault != 0);
+    if (waiting > 0 && pipe_active_slots(slots) >= 2) {
+        // promise this cluster to one of the waiting workgroups; it goes after the next step
+        if (__hip_atomic_fetch_add(don + DON_AVAIL, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0) sl->give = 1;
+        else __hip_atomic_fetch_add(don + DON_AVAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return false;
+}
+// thread 0, after pipe_wait_for_cluster: cluster k, handed over by another workgroup, carries on in slot sl
+template <bool BOUNDED, class Slot>
+__device__ __forceinline__ void pipe_take_over(Slot* sl, int k, const IcpCluster* __restrict__ cl, const IcpState* st) {
+    const IcpCluster c = cl[k];
+    sl->src_off = c.src_off; sl->n = c.n; sl->k = k;
+    state_load_agent(sl->so, &st[2 * (size_t)k]);
+    sl->phase = PH_ITER; sl->it = sl->so.iters; sl->give = 0; sl->take = 1;
+    pipe_slot_clear<BOUNDED>(sl);
+}
+
 // BIG = false: k_icp_pipe, the template (<= ICP_TPL_LDS points) and its k-d position table live in LDS.
 // BIG = true : k_icp_pipe_big, a template of up to 65535 points stays in global memory (L2-resident: a few hundred KiB read by
 //              every workgroup) - the grid walk reads the cell-sorted copy `tpl` point by point, the wave-per-query search the
@@ -455,11 +554,8 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
     if constexpr (!BIG) {
         for (int i = threadIdx.x; i < (tpl_m + ICP_SUB - 1) / ICP_SUB * ICP_SUB; i += ICPT_THREADS) s_kd[i] = km[i];
         stage_chunk(tp, tlo + c0.tpl_off / ICP_SUB, thi + c0.tpl_off / ICP_SUB, 0, tpl_m, s_tpl, bx);
-        // re-label the image: the low word of a search key, (original index << 13) | position (pads: all ones, and +inf
-        // coordinates anyway), replaces the bare original index, which nothing in this kernel needs ...
+        // re-label the image as (x, y, key word, z): see tpl_z
         for (int i = threadIdx.x; i < (tpl_m + ICP_SUB - 1) / ICP_SUB * ICP_SUB + ICP_SUB; i += ICPT_THREADS) {
-            // ... and stored as (x, y, key word, z): the key word then sits in the even register of the loaded quad and the
-            // squared distance can be formed in the z register next to it - the 64-bit key (rule C5's compare) needs no move
             const float4 p = s_tpl[i];
             const unsigned oi = (unsigned)__float_as_int(p.w);
             s_tpl[i] = make_float4(p.x, p.y, __uint_as_float(i < tpl_m ? ((oi << 13) | (unsigned)i) : 0xffffffffu), p.z);
@@ -494,9 +590,8 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
     if (threadIdx.x == 0) {
         for (int sidx = 0; sidx < PIPE_SLOTS; ++sidx) {
             Slot* sl = &s_slot[sidx];
-            for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
-            if constexpr (BOUNDED) sl->nv = 0u;
-            sl->arrived = 0; sl->epoch = 0; sl->it = 0; sl->n = 0; sl->src_off = 0; sl->k = 0; sl->next_pass = 0; sl->give = 0; sl->take = 0;
+            pipe_slot_clear<BOUNDED>(sl);
+            sl->epoch = 0; sl->it = 0; sl->n = 0; sl->src_off = 0; sl->k = 0; sl->give = 0; sl->take = 0;
             sl->phase = sidx < prm.pipe_slots ? PH_FILL : PH_EXHAUSTED;   // (a slot the launch does not use is dropped at its first visit)
         }
         // slot 0 starts with a cluster; the other slots are filled at their first step (PH_FILL), after every workgroup took its first
@@ -504,13 +599,8 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
         if (no_queue) for (int sidx = 0; sidx < PIPE_SLOTS; ++sidx) s_slot[sidx].phase = PH_EXHAUSTED;
     }
     __syncthreads();
-#ifdef CD_TIMERS
-    long long tph[6] = {0, 0, 0, 0, 0, 0}, tlast = clock64();
-    const long long wg_t0 = wall_clock64();
-#endif
-#ifdef CD_DONDBG
-    const long long don_t0 = wall_clock64();
-#endif
+    CD_TIMERS_BEGIN
+    DON_DBG_BEGIN
     // per wave: the steps it has completed on each slot (one byte per slot, mod 256: waves are never a whole step apart) and
     // the slots that still have work
     unsigned long long my_ep = 0ull;
@@ -520,6 +610,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
         for (int sidx = 0; sidx < PIPE_SLOTS; ++sidx) {
             if (!((live >> sidx) & 1u)) continue;
             Slot* sl = &s_slot[sidx];
+            // wait for the slot's epoch: the previous step has been finished
             const int want = (int)((my_ep >> (8 * sidx)) & 0xffu);
             while (__hip_atomic_load(&sl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != want) __builtin_amdgcn_s_sleep(2);
             __threadfence_block();
@@ -538,7 +629,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                 // waves reach the end of the step together.  (A point is then touched by different waves in different
                 // steps: same CU, and the step boundary is a workgroup-scope release/acquire.)
                 const int npass = (n + 63) >> 6;
-                for (;;) {
+                for (;;) {   // this wave's share of the step, pass by pass
                     int pss = 0;
                     if (lane == 0) pss = atomicAdd(&sl->next_pass, 1);
                     pss = __builtin_amdgcn_readfirstlane(pss);
@@ -546,25 +637,14 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                     const int q0 = pss << 6;
                     const int nk = min(64, n - q0);
                     const int myq = q0 + lane;
-#ifdef CD_ITSTATS
-                    const long long tpass0 = clock64();
-                    const int stat_it = phase == PH_ITER ? min(it, 30) : 31;
-#endif
+                    CD_IT_BEGIN(phase == PH_ITER, it)
                     QueryRegs q;
                     q.px = q.py = q.pz = q.pbest = 0.f; q.pbi = 0; q.poi = 0x7fffffff;
                     // key word of the seed point: what the LDS image holds in .z, (original index << 16) | position for a
                     // template in global memory; "no index" while there is no seed
-                    constexpr unsigned KW_NONE = BIG ? 0xffffffffu : 0x7fffffffu;
-                    unsigned kw = KW_NONE;
-#ifdef CD_TIMERS_FETCH
-                    {   // how long a wave waits for its pass's points and neighbour indices (the loads below then hit L1)
-                        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-                        int nv = 0;
-                        if (lane < nk) { pp = pts[myq]; nv = nnq[myq]; }
-                        asm volatile("s_waitcnt vmcnt(0)" ::"v"(pp.x), "v"(nv) : "memory");
-                        CD_PHASE(3)
-                    }
-#endif
+                    unsigned kw = KeyFmt<KSH>::NONE;
+                    CD_FETCH_WAIT(lane < nk, &pts[myq], &nnq[myq])
+                    // fetch the pass's queries and seed them (as functions this costs the pass loop instructions: profiles/EXPERIMENTS.md)
                     if (lane < nk) {
                         const float4 p = take ? load_agent(&pts[myq]) : pts[myq];
                         if (phase == PH_ITER) {
@@ -574,38 +654,28 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                                 if (give) store_agent(&pts[myq], make_float4(q.px, q.py, q.pz, p.w));
                                 else pts[myq] = make_float4(q.px, q.py, q.pz, p.w);
                             }
-                            q.pbest = 3.402823466e38f;
-                            if (it > 0) {
-                                q.pbi = take ? don_load(&nnq[myq]) : nnq[myq];
-                                const float4 q0p = BIG ? tp[(unsigned)q.pbi] : s_tpl[q.pbi];
-                                q.pbest = dist2(q.px, q.py, q.pz, q0p.x, q0p.y, BIG ? q0p.z : q0p.w);
-                                kw = BIG ? (((unsigned)__float_as_int(q0p.w) << 16) | (unsigned)q.pbi) : (unsigned)__float_as_int(q0p.z);
-                            }
+                            PipeSeed sd = {3.402823466e38f, 0, KeyFmt<KSH>::NONE};
+                            if (it > 0) sd = seed_at<BIG>(BIG ? tp : s_tpl, take ? don_load(&nnq[myq]) : nnq[myq], q.px, q.py, q.pz);
                             if (it < 3) {   // coarse seeds: first point of every run
                                 for (int j = 0; j < tpl_m; j += ICP_SUB) {
-                                    const float4 t = BIG ? tp[j] : s_tpl[j];
-                                    const float d = dist2(q.px, q.py, q.pz, t.x, t.y, BIG ? t.z : t.w);
-                                    if (d < q.pbest) { q.pbest = d; q.pbi = j; kw = BIG ? (((unsigned)__float_as_int(t.w) << 16) | (unsigned)j) : (unsigned)__float_as_int(t.z); }
+                                    const PipeSeed c = seed_at<BIG>(BIG ? tp : s_tpl, j, q.px, q.py, q.pz);
+                                    if (c.d2 < sd.d2) sd = c;
                                 }
                             }
-                            q.pbest = seed_bound(q.pbest);
-                            q.poi = 0;   // (BIG: only the chunked searches of the other kernels carry the seed's original index; LDS image: set below)
-#ifdef CD_STATS
-                            if (lane == 0) atomicAdd(&g_icp_stats[8], (unsigned long long)nk * (unsigned long long)((it > 0 ? 1 : 0) + (it < 3 ? (tpl_m + ICP_SUB - 1) / ICP_SUB : 0)));   // seed tests
-#endif
+                            q.pbest = seed_bound(sd.d2); q.pbi = sd.pos; kw = sd.kw;
+                            CD_STAT_SEEDS(nk, it, tpl_m)
                         } else {            // final X <- T*X, then getFitnessScore() of Tfinal * original source
                             float ox, oy, oz;
                             xform(sl->so.T, p.x, p.y, p.z, ox, oy, oz);
                             pts[myq] = make_float4(ox, oy, oz, p.w);
                             const float4 p0 = pts0[myq];
                             xform(sl->so.Tfinal, p0.x, p0.y, p0.z, q.px, q.py, q.pz);
-                            q.pbi = nnq[myq];
-                            const float4 q0p = BIG ? tp[(unsigned)q.pbi] : s_tpl[q.pbi];
-                            q.pbest = seed_bound(dist2(q.px, q.py, q.pz, q0p.x, q0p.y, BIG ? q0p.z : q0p.w));
-                            kw = BIG ? (((unsigned)__float_as_int(q0p.w) << 16) | (unsigned)q.pbi) : (unsigned)__float_as_int(q0p.z);
+                            const PipeSeed sd = seed_at<BIG>(BIG ? tp : s_tpl, nnq[myq], q.px, q.py, q.pz);
+                            q.pbest = seed_bound(sd.d2); q.pbi = sd.pos; kw = sd.kw;
                         }
                     }
                     CD_PHASE(1)
+                    // search: the near queries (seed ball at most rmax wide) a lane each over the grid, the far ones a wave each
                     float rr = 0.f;
                     bool near = false;
                     if (lane < nk) { rr = __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f); near = rr <= rmax; }
@@ -616,75 +686,25 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                         const unsigned bb = __float_as_uint(q.pbest);
                         const bool fin = bb < 0x7f800000u && lane < nk;
                         q.pbest = __uint_as_float(fin ? bb - 1u : bb);
-                        q.poi = (int)(fin ? kw : KW_NONE);
+                        q.poi = (int)(fin ? kw : KeyFmt<KSH>::NONE);
                     }
                     if (ballot64(near)) grid_search<KSH, !BIG, true>(BIG ? tp : s_tpl, s_cs, g, near, rr, q, gpad);
-#ifdef CD_STATS
-                    { const unsigned long long nb_ = ballot64(near); if (lane == 0) { atomicAdd(&g_icp_stats[0], (unsigned long long)nk); atomicAdd(&g_icp_stats[3], (unsigned long long)__popcll(nb_)); } }
-                    if (lane < nk && !near && phase == PH_ITER)
-                        atomicAdd(&g_icp_rhist[(it < 3 ? 0 : it < 16 ? 16 : 32) + min(15, (int)(rr * g.inv))], 1ull);
-#endif
+                    CD_STAT_NEAR(nk, near, lane < nk && !near && phase == PH_ITER, it, rr * g.inv)
                     CD_PHASE(2)
                     if constexpr (BIG) {
                         search_patches_big(tk, km, s_plo, s_phi, sp, q, ballot64(lane < nk && !near), &s_far[wave]);
                     } else {
-#ifdef CD_ITSTATS
-                    int stat_acc[2] = {0, 0};
-                    search_patches<true>(s_tpl, s_kd, bx, tpl_m, q, ballot64(lane < nk && !near), psplit, &s_far[wave], stat_acc);
-                    if (lane == 0) {
-                        atomicAdd(&g_icp_it[stat_it][0], (unsigned long long)(clock64() - tpass0)); atomicAdd(&g_icp_it[stat_it][1], 1ull);
-                        atomicAdd(&g_icp_it[stat_it][2], (unsigned long long)stat_acc[0]); atomicAdd(&g_icp_it[stat_it][3], (unsigned long long)stat_acc[1]);
+                        search_patches(s_tpl, s_kd, bx, q, ballot64(lane < nk && !near), psplit, &s_far[wave], CD_IT_ACC);
+                        CD_IT_END()
                     }
-#else
-                    search_patches<true>(s_tpl, s_kd, bx, tpl_m, q, ballot64(lane < nk && !near), psplit, &s_far[wave]);
-#endif
-                    }
-#ifdef CD_STATS
-                    {   // far queries whose TRUE neighbour lies within the grid walk's reach (a better seed would have made them near), by iteration class
-                        const unsigned long long far_ = ballot64(lane < nk && !near && phase == PH_ITER);
-                        const unsigned long long conv_ = ballot64(lane < nk && !near && phase == PH_ITER && __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f) <= rmax);
-                        const int cls_ = it < 3 ? 0 : it < 16 ? 1 : 2;
-                        if (lane == 0) { atomicAdd(&g_icp_stats[9 + cls_], (unsigned long long)__popcll(conv_)); atomicAdd(&g_icp_stats[12 + cls_], (unsigned long long)__popcll(far_)); }
-                    }
-#endif
+                    CD_STAT_REACH(lane < nk && !near && phase == PH_ITER, __fmul_rn(__fsqrt_rn(q.pbest), 1.0f + 2.0e-6f) <= rmax, it)
                     CD_PHASE(4)
-                    // The pass's 16 moment terms go into the slot's accumulators right away: no sum is carried in registers
-                    // across the searches (32 VGPRs that the search loops would otherwise spill around).
-                    unsigned long long S[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) S[i] = 0ull;
-                    // float -> fixed point (rule C4) in four instructions per term instead of eight (fixq_fast, common.hpp), valid
-                    // while every term stays below 2^50 / 2^shift; a wave with a lane outside that range (coordinates beyond 256 m,
-                    // neighbours more than 128 m away) takes the general conversion - same integers either way
-                    float4 qq = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (lane < nk && phase == PH_ITER) qq = BIG ? tp[(unsigned)q.pbi] : s_tpl[q.pbi];
-                    const float pv[3] = {q.px, q.py, q.pz}, qv[3] = {qq.x, qq.y, BIG ? qq.z : qq.w};
-                    const float big_c = fmaxf(fmaxf(fmaxf(fabsf(pv[0]), fabsf(pv[1])), fabsf(pv[2])), fmaxf(fmaxf(fabsf(qv[0]), fabsf(qv[1])), fabsf(qv[2])));
-                    const bool fast = ballot64(lane < nk && !(big_c < 256.f && q.pbest < 16384.f)) == 0ull;
-                    if (lane < nk) {
-                        if (phase == PH_ITER) {
-                            if (give) __hip_atomic_store(&nnq[myq], q.pbi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            else nnq[myq] = q.pbi;
-                            if (BOUNDED && !(q.pbest <= bnd.d2_max)) {
-                                // rejected (rule C8): adds nothing
-                            } else if (fast) {
-                                moment_terms<true>(pv, qv, q.pbest, S);
-                            } else {
-                                moment_terms(pv, qv, q.pbest, S);
-                            }
-                        } else {
-                            S[0] = fast ? fixq_fast(q.pbest, FIX_SHIFT_D2) : (unsigned long long)fixq(q.pbest, FIX_SHIFT_D2);
-                        }
-                    }
-                    wave_fold_to_lds(S, phase == PH_ITER ? 16 : 1, sl->acc);
-                    if constexpr (BOUNDED) {
-                        const unsigned long long kb = ballot64(lane < nk && phase == PH_ITER && q.pbest <= bnd.d2_max);
-                        if (lane == 0 && kb) atomicAdd(&sl->nv, (uint32_t)__popcll(kb));
-                    }
+                    pipe_fold_pass<BIG, BOUNDED>(sl, BIG ? tp : s_tpl, q, nk, phase, give, &nnq[myq], bnd.d2_max);
                     CD_PHASE(5)
                 }
                 CD_PHASE(5)
             }
+            // arrive
             if (give) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the write-through stores of this wave have landed)
             __threadfence_block();
             int a = 0;
@@ -694,22 +714,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                 __threadfence_block();
                 if (lane == 0) {
                     if (phase == PH_ITER) {
-                        // (the load is in flight while the step is solved)
-                        const int waiting = don ? don_load(don + DON_AVAIL) : 0;
-                        sl->take = 0;
-                        if (pipe_solve(sl, prm)) {
-                            sl->phase = PH_FIT;
-                            if (sl->give) { sl->give = 0; __hip_atomic_fetch_add(don + DON_AVAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // converged: stays
-                        } else {
-                            sl->it += 1;
-                            if (sl->give) {
-                                if (pipe_give(sl, s_slot, st, don, prm.don_fault != 0)) { DON_DBG(24, don_t0); pipe_refill(sl, gbeg, gend, order, cl, st, queue, don, no_queue); }
-                            } else if (waiting > 0 && pipe_active_slots(s_slot) >= 2) {
-                                // promise this cluster to one of the waiting workgroups; it goes after the next step
-                                if (__hip_atomic_fetch_add(don + DON_AVAIL, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0) sl->give = 1;
-                                else __hip_atomic_fetch_add(don + DON_AVAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                        }
+                        if (pipe_end_iteration(sl, s_slot, st, don, prm)) { DON_DBG(24, don_t0); pipe_refill(sl, gbeg, gend, order, cl, st, queue, don, no_queue); }
                     } else {
                         if (phase == PH_FIT) {
                             sl->so.done = 1;
@@ -720,10 +725,7 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
                         }
                         pipe_refill(sl, gbeg, gend, order, cl, st, queue, don, no_queue);
                     }
-                    for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
-                    if constexpr (BOUNDED) sl->nv = 0u;
-                    sl->arrived = 0;
-                    sl->next_pass = 0;
+                    pipe_slot_clear<BOUNDED>(sl);
                 }
                 __threadfence_block();
                 if (lane == 0) __hip_atomic_store(&sl->epoch, (want + 1) & 0xff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -737,38 +739,17 @@ __device__ __forceinline__ void icp_pipe_body(int ncl, const int* __restrict__ o
     if (!don) break;
     __syncthreads();
     if (threadIdx.x == 0) {
-        DON_DBG(8, don_t0);
-#ifdef CD_DONDBG
-        const long long tw0 = wall_clock64();
-#endif
+        DON_DBG_WAIT_BEGIN
         const int k = pipe_wait_for_cluster(don, gend - gbeg, prm.don_fault ? (1 << 14) : (1 << 24));
-#ifdef CD_DONDBG
-        atomicAdd(&g_don_dbg[2], (unsigned long long)(wall_clock64() - tw0));
-        if (k >= 0) DON_DBG(40, don_t0); else atomicMax(&g_don_dbg[1], (unsigned long long)(wall_clock64() - don_t0));
-#endif
+        DON_DBG_WAIT_END(k)
         s_take = k;
-        if (k >= 0) {
-            Slot* sl = &s_slot[0];
-            const IcpCluster c = cl[k];
-            sl->src_off = c.src_off; sl->n = c.n; sl->k = k;
-            state_load_agent(sl->so, &st[2 * (size_t)k]);
-            sl->phase = PH_ITER; sl->it = sl->so.iters; sl->give = 0; sl->take = 1;
-            for (int i = 0; i < 16; ++i) sl->acc[i] = 0ull;
-            if constexpr (BOUNDED) sl->nv = 0u;
-            sl->arrived = 0; sl->next_pass = 0;
-        }
+        if (k >= 0) pipe_take_over<BOUNDED>(&s_slot[0], k, cl, st);
     }
     __syncthreads();
     if (s_take < 0) break;
     live = 1u;
     }
-#ifdef CD_TIMERS
-    if (lane == 0) for (int i = 0; i < 6; ++i) atomicAdd(&g_icp_stats[8 + i], (unsigned long long)tph[i]);
-    if (threadIdx.x == 0) {   // workgroup busy time (100 MHz wall clock): sum, max, count
-        const unsigned long long dt = (unsigned long long)(wall_clock64() - wg_t0);
-        atomicAdd(&g_icp_stats[14], dt); atomicMax(&g_icp_stats[15], dt); atomicAdd(&g_icp_stats[7], 1ull);
-    }
-#endif
+    CD_TIMERS_END
 }
 
 template <bool BOUNDED>

@@ -8,8 +8,11 @@ Every function (kernels and out-of-line device functions) and every kernel descr
 `before` files is looked up in the `after` files.  Only what the numbering of functions inside a file changes is normalised:
 assembler comment lines go, and the local labels .LBB<n>_<m>, .Lfunc_begin<n>, .Lfunc_end<n>, .Ltmp<n> are renumbered by first
 appearance inside the function.  Everything else must be equal line for line.  Prints one line per symbol with its VGPRs, LDS
-and scratch bytes on both sides; exit status 1 if any symbol is missing, extra or different."""
+and scratch bytes on both sides; exit status 1 if any symbol is missing, extra or different.  A symbol that differs is "same-ops"
+if its descriptor is equal and it has the same number of each opcode (only order, registers or operands differ); otherwise
+the opcodes whose counts changed are listed."""
 import argparse
+import collections
 import re
 import sys
 
@@ -72,6 +75,10 @@ def merged(paths):
     return funcs, descs
 
 
+def opcodes(body):
+    return collections.Counter(ln.split()[0] for ln in body if not ln.endswith(":") and not ln.startswith("."))
+
+
 def field(desc, key):
     for ln in desc or []:
         if ln.startswith(key + " "):
@@ -93,7 +100,10 @@ def main():
         if name not in f0 or name not in f1:
             verdict = "MISSING" if name not in f1 else "EXTRA"
         elif f0[name] != f1[name] or d0.get(name) != d1.get(name):
-            verdict = "DIFFERENT"
+            c0, c1 = opcodes(f0[name]), opcodes(f1[name])
+            verdict = "same-ops" if c0 == c1 and d0.get(name) == d1.get(name) else "DIFFERENT"
+            print("    %d -> %d instructions%s" % (sum(c0.values()), sum(c1.values()),
+                                                  "".join("  %s %+d" % (op, c1[op] - c0[op]) for op in sorted(set(c0) | set(c1)) if c0[op] != c1[op])))
             for k, (x, y) in enumerate(zip(f0[name], f1[name])):
                 if x != y:
                     print("    first difference at instruction line %d:\n      - %s\n      + %s" % (k, x, y))
