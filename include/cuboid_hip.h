@@ -1214,6 +1214,76 @@ int cd_pair_score_points(cd_context* ctx, int slot, const void* src_xyz, size_t 
 int cd_pair_score_host(const void* tpl_xyz, size_t tpl_stride, int m, const void* src_xyz, size_t src_stride, int n, const float T[16],
                        double max_range, double min_coverage, double min_inlier_fraction, int accepted, cd_pair_score* out);
 
+/* Pose information of a (cluster, lattice template) pair: does the data pin the pose down at all?  A cluster that sees one face of
+ * a cuboid lies perfectly on the template wherever it slides within that face and however it turns about the face's normal; a
+ * two-face view leaves the translation along the common edge free.  Fitness, rule C14 and rule C21 all ask whether the cluster
+ * lies on the template and pass such poses; this rule reports which of the six directions of a small rigid motion the
+ * correspondences constrain, by how many points' worth, and the covariance of the pose over the constrained ones.  Opt-in, off by
+ * default, lattice templates only (cd_template_lattice_faces > 0).  Canonical rule C23; perception_amd/pose_info.py
+ * is the rule in numpy, with every association, and the device equals it bit for bit.  It counts what the template's SURFACES
+ * constrain and nothing else: the outline of a partial view adds nothing, and hidden faces are not reasoned about.
+ * For the cluster's n points src as extracted, the result's T, the slot's template, a range d and a support min_support (doubles,
+ * finite, > 0), everything in the template's frame:
+ *   1. A_i = T src_i in float32, rule C21's step 1;
+ *   2. rule C5's neighbour q_i of A_i, its squared distance and w_i, the constant axis of q_i's face; i is kept iff d2_i <= rule
+ *      C8's threshold of d (the boundary inside); n_in the kept, n_face[a] the kept with w = a;
+ *   3. centre c0 = float32 (min + max) * 0.5f per axis of the template's bounding box, length L = half its diagonal (double, from
+ *      the float32 extents), both fixed at cd_set_template; p_i = A_i - c0 in float32;
+ *   4. per kept point with a = w_i, b and c the next two axes cyclically and r = q_a - A_a, the float32 terms p_c, p_b, p_c p_c,
+ *      p_b p_b, p_c p_b and r r, summed per axis as rule-C4 64-bit integers (2^32; r r: 2^36) next to the counts: order-free;
+ *   5. in double, the 6 x 6 information matrix H over x = (L omega, t) of the motion A' = A + omega x (A - c0) + t: the row of
+ *      point i is ((p_i x e_w) / L, e_w).  Its eigenvalues read as "how many points constrain this direction";
+ *   6. H's eigenvalues ascending with their vectors, by a cyclic Jacobi of a fixed pair order and sweep count; a vector's
+ *      component of largest magnitude is positive;
+ *   7. n_constrained = #{k: eigenvalue k >= min_support}; sigma2 = the mean r r of the kept points; the covariance of (omega, t) =
+ *      sigma2 D (sum over the constrained k of v_k v_k^T / lambda_k) D with D = diag(1/L, 1/L, 1/L, 1, 1, 1).  Free directions
+ *      are ABSENT from it, not infinite: n_constrained says so.  weakest = v_0, the twist (L omega, t) the data says least about;
+ *   8. well_posed = accepted && n_constrained == 6;
+ *   9. status, the first that applies: CD_ERR_NO_TEMPLATE for an empty slot, CD_ERR_INVALID_ARG for a slot that is not a lattice or
+ *      a non-finite entry of T or coordinate of A, CD_ERR_FEW_CORRESPONDENCES for n_in < 3, CD_ERR_CAPACITY for n above 2^19.  Such
+ *      a record holds the counts (n_source; n_in and n_face where the points were looked at), the status and zeros.
+ *
+ * cd_set_pose_info: context state.  enable = 0 (the default): a fused call launches nothing more and every output is byte for byte
+ * what it was.  max_range or min_support not finite or <= 0: CD_ERR_INVALID_ARG and the setting stays.  With the mode on, every fused
+ * call examines each cluster result against the slot it reports, after its ICP and after rule C21's step; every other record and
+ * read-back is unchanged. */
+#define CD_POSE_INFO_RANGE_DEFAULT 0.005
+#define CD_POSE_INFO_MIN_SUPPORT_DEFAULT 8.0
+typedef struct cd_pose_info {
+    int32_t n_source;          /* n                                                                                      */
+    int32_t n_in;              /* kept correspondences                                                                   */
+    int32_t n_face[3];         /* ... whose face has the constant axis x / y / z                                         */
+    int32_t n_constrained;     /* eigenvalues >= min_support                                                             */
+    int32_t well_posed;        /* step 8                                                                                 */
+    int32_t status;            /* step 9                                                                                 */
+    double eigenvalues[6];     /* ascending, in points                                                                   */
+    double eigenvectors[36];   /* row k = v_k over (L omega, t)                                                          */
+    double weakest[6];         /* v_0                                                                                    */
+    double sigma2;             /* mean squared normal residual of the kept points                                        */
+    double covariance[36];     /* row-major over (omega, t), template frame, rotation about `centre`                     */
+    double centre[3];          /* c0                                                                                     */
+    double length;             /* L                                                                                      */
+} cd_pose_info;
+int cd_set_pose_info(cd_context* ctx, int enable, double max_range, double min_support);
+int cd_get_pose_info(const cd_context* ctx, int* enable, double* max_range, double* min_support);
+int cd_pose_info_struct_size(void);   /* sizeof(cd_pose_info) (cd_struct_size's list is closed) */
+/* The records of the last fused call's cluster results, indexed and invalidated exactly like cd_get_cluster_pair_scores. */
+int cd_get_cluster_pose_info(const cd_context* ctx, int frame, int first, int count, cd_pose_info* out);
+/* One pair from host points, on the GPU, without a fused call; the arguments are checked like cd_pair_score_points' (a setting the
+ * setter would refuse: CD_ERR_INVALID_ARG; n above the context's max_points: CD_ERR_CAPACITY).  CD_OK with the record's own
+ * status in out->status. */
+int cd_pose_info_points(cd_context* ctx, int slot, const void* src_xyz, size_t stride_bytes, int n, const float T[16], double max_range,
+                        double min_support, int accepted, cd_pose_info* out);
+/* Host only (no context, no GPU): rule C5's neighbour by brute force, the faces from cd_lattice_detect, the arithmetic header the
+ * kernel uses. */
+int cd_pose_info_host(const void* tpl_xyz, size_t tpl_stride, int m, const void* src_xyz, size_t src_stride, int n, const float T[16],
+                      double max_range, double min_support, int accepted, cd_pose_info* out);
+/* Host only, in double: the covariance of the published pose P = T^-1 (the template in the camera frame) in the order of
+ * geometry_msgs/PoseWithCovariance - position, then rotation about the fixed axes of the parent frame - as J S J^T with S =
+ * info->covariance, R_P the rotation of P and J = [[-R_P [c0]x, -R_P], [-R_P, 0]] over (omega, t).  Free directions are absent
+ * from S and so from the result: n_constrained says so.  NULL pointer: CD_ERR_INVALID_ARG. */
+int cd_pose_info_ros_covariance(const cd_pose_info* info, const float T[16], double out36[36]);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

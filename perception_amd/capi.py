@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = [
     "cd_prism_project", "cd_prism_hull_host",
     "cd_set_pair_score", "cd_get_pair_score", "cd_pair_score_struct_size", "cd_get_cluster_pair_scores", "cd_pair_score_points",
     "cd_pair_score_host",
+    "cd_set_pose_info", "cd_get_pose_info", "cd_pose_info_struct_size", "cd_get_cluster_pose_info", "cd_pose_info_points", "cd_pose_info_host",
+    "cd_pose_info_ros_covariance",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
@@ -86,6 +88,8 @@ CD_OUTLIER_MAX_MEAN_K, CD_OUTLIER_LDS_TILE = 63, 1024
 CD_PRISM_MAX_HULL, CD_PRISM_LDS_POINTS = 1024, 4096
 # rule C21 (cd_set_pair_score): the recommended setting
 CD_PAIR_SCORE_RANGE_DEFAULT, CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT, CD_PAIR_SCORE_MIN_INLIER_DEFAULT = 0.005, 0.5, 0.8
+# rule C23 (cd_set_pose_info): the recommended setting
+CD_POSE_INFO_RANGE_DEFAULT, CD_POSE_INFO_MIN_SUPPORT_DEFAULT = 0.005, 8.0
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -128,6 +132,21 @@ class CdPairScore(C.Structure):
 
     def as_dict(self):
         return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+class CdPoseInfo(C.Structure):
+    """cd_pose_info: the pose information (rule C23) of one (cluster, lattice template) pair."""
+    _fields_ = [("n_source", C.c_int32), ("n_in", C.c_int32), ("n_face", C.c_int32 * 3), ("n_constrained", C.c_int32), ("well_posed", C.c_int32),
+                ("status", C.c_int32), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36), ("weakest", C.c_double * 6),
+                ("sigma2", C.c_double), ("covariance", C.c_double * 36), ("centre", C.c_double * 3), ("length", C.c_double)]
+
+    def as_dict(self):
+        """Scalars as int / float, arrays as lists."""
+        out = {}
+        for k, t in self._fields_:
+            v = getattr(self, k)
+            out[k] = list(v) if hasattr(v, "__len__") else (float(v) if t is C.c_double else int(v))
+        return out
 
 
 class CdShapeFrame(C.Structure):
@@ -558,6 +577,14 @@ def load_library(path=None):
     lib.cd_get_cluster_pair_scores.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.cd_pair_score_points.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, pcp]
     lib.cd_pair_score_host.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_double, C.c_int, pcp]
+    pip = C.POINTER(CdPoseInfo)
+    lib.cd_set_pose_info.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+    lib.cd_get_pose_info.argtypes = [vp, ip, dp, dp]
+    lib.cd_pose_info_struct_size.argtypes = []
+    lib.cd_get_cluster_pose_info.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_pose_info_points.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_int, pip]
+    lib.cd_pose_info_host.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_int, pip]
+    lib.cd_pose_info_ros_covariance.argtypes = [pip, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -1177,6 +1204,34 @@ class Context:
                                                   float(min_inlier_fraction), 1 if accepted else 0, C.byref(out)))
         return out.as_dict()
 
+    def set_pose_info(self, enable, max_range=CD_POSE_INFO_RANGE_DEFAULT, min_support=CD_POSE_INFO_MIN_SUPPORT_DEFAULT):
+        """Rule C23, the pose information, for every later fused call of this context: each cluster result gets the eigenvalues of its
+        information matrix over a small rigid motion ("points' worth" per direction), n_constrained, well_posed and the covariance of
+        the pose.  Lattice templates only.  Off by default."""
+        self._check(self.lib.cd_set_pose_info(self.h, 1 if enable else 0, float(max_range), float(min_support)))
+
+    def pose_info_setting(self):
+        """(enable, max_range, min_support) as cd_set_pose_info left them."""
+        on, d, s = C.c_int(), C.c_double(), C.c_double()
+        self._check(self.lib.cd_get_pose_info(self.h, C.byref(on), C.byref(d), C.byref(s)))
+        return on.value, d.value, s.value
+
+    def cluster_pose_info(self, frame, first=0, count=None):
+        """Rule C23's records of the clusters of `frame` of the last fused call, indexed like cluster_results: a list of CdPoseInfo."""
+        msg = "no pose-information call to read: the last fused call ran with the mode off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_pose_info, CdPoseInfo, msg, frame, first, count)
+
+    def pose_info_points(self, slot, src, T, max_range=CD_POSE_INFO_RANGE_DEFAULT, min_support=CD_POSE_INFO_MIN_SUPPORT_DEFAULT, accepted=1):
+        """One pair on the GPU without a fused call: src (n, >= 3) float32 against the lattice template of `slot` under T.  Returns a
+        dict of cd_pose_info's fields (its own status in "status")."""
+        src = np.asarray(src, np.float32)
+        a, stride, n = _points(src if src.ndim == 2 else src.reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+        out = CdPoseInfo()
+        self._check(self.lib.cd_pose_info_points(self.h, int(slot), _ptr(a), stride, n, _ptr(t), float(max_range), float(min_support),
+                                                 1 if accepted else 0, C.byref(out)))
+        return out.as_dict()
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1390,6 +1445,41 @@ def pair_score_host(tpl, src, T, max_range=CD_PAIR_SCORE_RANGE_DEFAULT, min_cove
     if st != CD_OK:
         raise CuboidError(st, "cd_pair_score_host")
     return out.as_dict()
+
+
+def pose_info_host(tpl, src, T, max_range=CD_POSE_INFO_RANGE_DEFAULT, min_support=CD_POSE_INFO_MIN_SUPPORT_DEFAULT, accepted=1):
+    """cd_pose_info_host: rule C23 on the host (no context, no GPU).  Returns a dict of cd_pose_info's fields."""
+    lib = load_library()
+    tp = np.ascontiguousarray(np.asarray(tpl, np.float32).reshape(-1, 3))
+    sp = np.ascontiguousarray(np.asarray(src, np.float32).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+    out = CdPoseInfo()
+    st = lib.cd_pose_info_host(_ptr(tp), 12, len(tp), _ptr(sp), 12, len(sp), _ptr(t), float(max_range), float(min_support), 1 if accepted else 0, C.byref(out))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_pose_info_host")
+    return out.as_dict()
+
+
+def pose_info_ros_covariance(info, T):
+    """cd_pose_info_ros_covariance: the (6, 6) float64 covariance of the published pose P = T^-1 in geometry_msgs/PoseWithCovariance
+    order from a record (a CdPoseInfo or a dict of its fields)."""
+    lib = load_library()
+    if not isinstance(info, CdPoseInfo):
+        rec = CdPoseInfo()
+        for k, _ in CdPoseInfo._fields_:
+            v = info[k]
+            if hasattr(v, "__len__"):
+                for i, x in enumerate(v):
+                    getattr(rec, k)[i] = x
+            else:
+                setattr(rec, k, v)
+        info = rec
+    t = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
+    out = np.zeros(36, np.float64)
+    st = lib.cd_pose_info_ros_covariance(C.byref(info), _ptr(t), _ptr(out))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_pose_info_ros_covariance")
+    return out.reshape(6, 6)
 
 
 def prism_project(coeff, xyz):

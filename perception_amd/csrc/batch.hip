@@ -295,6 +295,7 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     if (p->icp_use_guess == CD_GUESS_CLUSTER) c->last_shapes.publish(cl.first);   // (keep_cluster_shapes has run, also for no cluster)
     for_each_icp_stat(c, [&](bool on, auto& kept, auto&) { if (on) kept.publish(cl.first); });
     if (c->pair_on) c->last_pair.publish(cl.first);   // rule C21 (stage_pair_scores has filled it)
+    if (c->pose_on) c->last_pose.publish(cl.first);   // rule C23 (stage_pose_info has filled it)
 }
 
 // The per-frame records from h_fs, the plane mirrors and c->last_clusters, and the byte counts of the timing
@@ -438,6 +439,7 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     if (fits_one_stage(c, F, cl, (int)bi.slots.size())) st = icp_all_pairs(c, p, F, cl, &bi);
     else st = icp_per_template(c, p, F, cl, &bi);
     if (!st && c->pair_on) st = stage_pair_scores(c, cl.ncl, bi.orig_off);   // rule C21: after the slot of every cluster is settled
+    if (!st && c->pose_on) st = stage_pose_info(c, cl.ncl, bi.orig_off);     // rule C23: reads (points, T, slot) of the same results
     if (st) return st;
     publish_last(c, p, F, cl, &bi);
     {   // what the label calls (rule C15, labels.hip) need of this call; host fields only

@@ -20,6 +20,7 @@
 #include "outlier_math.hpp"
 #include "prism_math.hpp"
 #include "pair_score_math.hpp"
+#include "pose_info_math.hpp"
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
 #include "icp_recip_math.hpp"
@@ -267,6 +268,18 @@ struct cd_context : cd_streams {
     DevBuf<PairItem> d_psitem; PinBuf<PairItem> h_psitem;
     DevBuf<unsigned long long> d_psacc; PinBuf<unsigned long long> h_psacc;
     KeptRecords<cd_pair_score> last_pair;
+    // pose information (rule C23, k_pose_info.hip): the setting (cd_set_pose_info; pose_on = 0: off), every slot's centre and length
+    // (fixed by cd_set_template), and - grown on demand - the items of a launch (pinned + device), the records with the queue word
+    // in a buffer of its own (device + pinned mirror); last_pose: what cd_get_cluster_pose_info reads, one record per cluster of the
+    // last fused call
+    int pose_on = 0;
+    double pose_range = CD_POSE_INFO_RANGE_DEFAULT, pose_support = CD_POSE_INFO_MIN_SUPPORT_DEFAULT;
+    float tpl_centre[CD_MAX_TEMPLATES][3] = {};
+    double tpl_length[CD_MAX_TEMPLATES] = {};
+    DevBuf<PoseItem> d_piitem; PinBuf<PoseItem> h_piitem;
+    DevBuf<cd_pose_info> d_pirec; PinBuf<cd_pose_info> h_pirec;
+    DevBuf<int> d_piqueue;
+    KeptRecords<cd_pose_info> last_pose;
     cd_timing timing;
 };
 
@@ -316,6 +329,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_reject.invalidate();
     c->last_recip.invalidate();
     c->last_pair.invalidate();
+    c->last_pose.invalidate();
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -496,6 +510,9 @@ int prism_compose_map(cd_context* c, int F, int map_pitch);
 // ---- pair_score.hip (rule C21): the fused call's step behind its ICP - every cluster result of the batch against the slot it reports,
 // into last_pair (begun here, published by publish_last)
 int stage_pair_scores(cd_context* c, int ncl, const std::vector<long long>& orig_off);
+// ---- pose_info.hip (rule C23): the fused call's step behind its ICP and rule C21's step - every cluster result of the batch against
+// the slot it reports, into last_pose (begun here, published by publish_last)
+int stage_pose_info(cd_context* c, int ncl, const std::vector<long long>& orig_off);
 // ---- surface.hip
 int ensure_surface(cd_context* c, size_t pitch);
 int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,

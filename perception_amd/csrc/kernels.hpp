@@ -272,4 +272,11 @@ struct PairItem { int32_t job, q0, qn, pad; };
 void launch_pair_score(hipStream_t s, int n_items, int n_wg, const PairJob* jobs, const PairItem* items, const float4* src, const float4* tpl, float tau,
                        unsigned long long* acc, int* queue);
 
+// k_pose_info.hip : rule C23, the pose information of (cluster, lattice template) results (pose_info_math.hpp).  An item is one
+// result: its n >= 1 points src0[src_off ..], T, the slot (a lattice: lats[slot].nface > 0) with its centre and length, the
+// result's accepted flag and the record it fills, out[pair].  n_wg workgroups draw the items from *queue (zero before the launch).
+struct PoseItem { int32_t src_off, n, slot, accepted, pair, pad[3]; float T[12]; float c0[3]; float pad2; double length; };
+void launch_pose_info(hipStream_t s, int nitems, int n_wg, const PoseItem* items, const IcpLattice* lats, const float4* src0, float tau, double min_support,
+                      cd_pose_info* out, int* queue);
+
 }  // namespace cd

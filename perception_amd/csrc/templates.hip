@@ -49,6 +49,7 @@ int upload_template(cd_context* c, int slot, int off, const PreparedTemplate& P)
     HIPCHK(c, copy_sync(c, c->d_lat + slot, &P.lat, sizeof(IcpLattice), hipMemcpyHostToDevice));
     c->tpl_faces[slot] = P.lat.nface;
     c->tpl_frame[slot] = P.frame;
+    pose_box(P.xyz.data(), P.m, c->tpl_centre[slot], &c->tpl_length[slot]);   // rule C23, step 3
     c->tframe_dirty = true;   // (rule C13's slot table: uploaded by the next CD_GUESS_CLUSTER stage)
     return CD_OK;
 }
