@@ -513,6 +513,36 @@ int stage_pair_scores(cd_context* c, int ncl, const std::vector<long long>& orig
 // ---- pose_info.hip (rule C23): the fused call's step behind its ICP and rule C21's step - every cluster result of the batch against
 // the slot it reports, into last_pose (begun here, published by publish_last)
 int stage_pose_info(cd_context* c, int ncl, const std::vector<long long>& orig_off);
+// ---- what rules C21 and C23 share on the host: both examine (cluster, template) results after the ICP
+struct ResultSpec {   // one result of a launch: its n points at d_src0 + src_off, its T and flag, its slot
+    long long src_off;
+    int n, slot, accepted;
+    const float* T;
+};
+// rule C8's tau of the range (the setters and the entry points have refused a range that has none)
+inline float tau_of(double max_range) {
+    float tau = 0.f;
+    cd_icp_correspondence_threshold(max_range, &tau, nullptr);
+    return tau;
+}
+// the fused call's results as specs: cluster k's points as extracted, d_src0 + orig_off[k], with what last_clusters[k] reports
+inline std::vector<ResultSpec> result_specs(const cd_context* c, int ncl, const std::vector<long long>& orig_off) {
+    std::vector<ResultSpec> specs((size_t)ncl);
+    for (int k = 0; k < ncl; ++k) {
+        const cd_cluster_result& r = c->last_clusters[(size_t)k];
+        specs[(size_t)k] = ResultSpec{orig_off[(size_t)k], r.size, r.template_slot, r.accepted, r.T};
+    }
+    return specs;
+}
+// the arguments cd_pair_score_points and cd_pose_info_points share, then the rule's own thresholds (ok / what they must be), then
+// the capacity - in this order: with several wrong the error is the first one's
+inline int check_result_points(cd_context* c, bool has_out, int slot, const void* src_xyz, size_t stride, int n, const float* T, bool thresholds_ok,
+                               const char* thresholds_msg) {
+    if (!has_out || !T || n < 0 || (n > 0 && !src_xyz) || stride < 12 || (stride & 3) || slot < 0 || slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
+    if (!thresholds_ok) return fail(c, CD_ERR_INVALID_ARG, thresholds_msg);
+    if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
+    return CD_OK;
+}
 // ---- surface.hip
 int ensure_surface(cd_context* c, size_t pitch);
 int stage_surface(cd_context* c, int F, int pitch, const std::vector<int>& count, const float* axes, const std::vector<char>& run,

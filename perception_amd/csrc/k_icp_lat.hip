@@ -70,7 +70,11 @@ extern "C" int cd_debug_lat_stats(unsigned long long* out, int reset) {
 #define LAT_T(k)
 #endif
 
-// (LatFaces, lat_stage, lat_nearest, lat_nearest_axes, the tie walk and LatFix: lat_search.hpp)
+// (LatFaces, lat_nearest, lat_nearest_axes, the tie walk and LatFix: lat_search.hpp.  The queue pop, the table staging, the search
+// dispatch, the two-branch accumulate, the pass loop's head and the fitness pass below are this kernel's OWN text of
+// icp_pop_live, lat_stage_tables, lat_nearest_any, lat_fix_terms, lat_for_passes and lat_fitness_pass: each of the six, taken
+// alone, changes the code of the 26 instantiations - lat_fix_terms puts them into scratch (profiles/EXPERIMENTS.md) - and this
+// is the kernel the benchmark times.  A fix to one of those helpers is made here too.)
 struct LatSlot {
     int k, src_off, n, tslot;   // the cluster (index, first point, points, template slot)
     int phase;                  // LAT_ITER / LAT_FIT / LAT_EMPTY
@@ -211,12 +215,12 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                         } else {
 #pragma unroll
                             for (int a = 0; a < 3; ++a) {
-                                S[a] += (unsigned long long)fixq(pv[a], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
-                                S[3 + a] += (unsigned long long)fixq(qv[a], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
+                                S[a] += LatFix<FIX_SHIFT>::general(pv[a]);
+                                S[3 + a] += LatFix<FIX_SHIFT>::general(qv[a]);
 #pragma unroll
-                                for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] += (unsigned long long)fixq(__fmul_rn(qv[a], pv[b]), FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
+                                for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] += LatFix<FIX_SHIFT>::general(__fmul_rn(qv[a], pv[b]));
                             }
-                            S[15] += (unsigned long long)fixq(h.d, FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
+                            S[15] += LatFix<FIX_SHIFT_D2>::general(h.d);
                         }
                     }
                 }
@@ -249,7 +253,7 @@ k_icp_lat(int nitems, const int* __restrict__ order, const IcpCluster* __restric
                     xform(Tf, p0.x, p0.y, p0.z, qx, qy, qz);
                     const LatHit h = F.axes ? lat_nearest_axes<false>(tab, face, F, qx, qy, qz)
                                             : (nf3 ? lat_nearest<false, 3>(tab, face, F, qx, qy, qz) : lat_nearest<false, LAT_MAX_FACES>(tab, face, F, qx, qy, qz));
-                    if (act) S[0] += h.d < 16384.f ? LatFix<FIX_SHIFT_D2>::bits(h.d) : (unsigned long long)fixq(h.d, FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
+                    if (act) S[0] += lat_fix_d2(h.d);
                 }
                 if (sub < npass) wave_fold_to_lds(S, 1, s_acc[slot]);
             }

@@ -26,6 +26,7 @@ namespace cd {
 
 constexpr int PLANE_WAVES = 4;
 constexpr int PLANE_THREADS = PLANE_WAVES * WAVE;
+constexpr int PLANE_D2 = PLANE_NSUMS - 1;   // plane_terms' d2: the one sum at FIX_SHIFT_D2
 enum { PLANE_ITER = 0, PLANE_FIT = 1, PLANE_EMPTY = 2 };
 
 struct PlaneItem {
@@ -55,19 +56,14 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
     for (;;) {
         // ---- the next live pair of the queue (lane 0) ----
         if (threadIdx.x == 0) {
-            s_it.phase = PLANE_EMPTY;
-            for (;;) {
-                const int item = atomicAdd(queue, 1);
-                if (item >= nitems) break;
-                const int k = order[item];
-                if (st[2 * (size_t)k].done) continue;   // host pre-marked (too few points / no template)
-                const IcpCluster c = cl[k];
+            IcpCluster c;
+            const int k = icp_pop_live(queue, nitems, order, cl, st, c);
+            s_it.phase = k < 0 ? PLANE_EMPTY : PLANE_ITER;
+            if (k >= 0) {
                 s_it.k = k; s_it.src_off = c.src_off; s_it.n = c.n; s_it.tslot = c.slot;
                 s_it.latched = pp.latched0;
-                s_it.phase = PLANE_ITER;
                 s_so = st[2 * (size_t)k];
                 s_ps.plane_iterations = 0; s_ps.first_plane_iteration = 0; s_ps.stopped_singular = 0; s_ps.reserved = 0;
-                break;
             }
         }
         __syncthreads();
@@ -76,18 +72,12 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
         const int tslot = __builtin_amdgcn_readfirstlane(s_it.tslot);
         const IcpLattice* __restrict__ L = lats + tslot;
         if (tslot != cur_tslot) {   // (uniform) another template: its tables and face words
-            for (int i = threadIdx.x; i < L->ntab && i < LAT_MAX_TAB; i += PLANE_THREADS) s_tab[i] = L->tab[i];
-            if (threadIdx.x < LAT_MAX_FACES) {
-                const int f = threadIdx.x, w = L->w[f], u = L->fast[f], v = 3 - w - u;
-                s_face[f] = make_int4(w, u, L->base[f], __float_as_int(L->c[f]));
-                s_face[LAT_MAX_FACES + f] = make_int4(L->toff[u], L->toff[v < 0 || v > 2 ? 0 : v], L->n[u], 0);
-            }
+            lat_stage_tables(L, L->ntab, s_tab, s_face, threadIdx.x, PLANE_THREADS);
             cur_tslot = tslot;
             __syncthreads();
         }
         LatFaces F;
         lat_faces_load(L, F);
-        const bool nf3 = F.nface <= 3;
         const int npass = (n + 63) >> 6;
         float4* pts = src + src_off;
         for (;;) {
@@ -102,19 +92,13 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { SA[i] = 0ull; SB[i] = 0ull; }   // (SB[12..15] stay zero and are never folded)
                 unsigned nv = 0u;
-                float4 pnext = pts[min((sub << 6) + lane, n - 1)];
-                for (int pss = sub; pss < npass; pss += PLANE_WAVES) {
-                    const int myq = (pss << 6) + lane;
-                    const bool act = myq < n;
-                    const float4 p = pnext;
-                    pnext = pts[min(((pss + PLANE_WAVES) << 6) + lane, n - 1)];
+                lat_for_passes<PLANE_WAVES>(pts, n, sub, lane, [&](int myq, bool act, const float4& p) {
                     float px = p.x, py = p.y, pz = p.z;
                     if (moved) {   // written back by the lane that owns the point
                         xform(T, p.x, p.y, p.z, px, py, pz);
                         if (act) pts[myq] = make_float4(px, py, pz, p.w);
                     }
-                    const LatHit h = F.axes ? lat_nearest_axes<true, false, true>(s_tab, s_face, F, px, py, pz)
-                                            : (nf3 ? lat_nearest<true, 3>(s_tab, s_face, F, px, py, pz) : lat_nearest<true, LAT_MAX_FACES>(s_tab, s_face, F, px, py, pz));
+                    const LatHit h = lat_nearest_any<true, true>(s_tab, s_face, F, px, py, pz);
                     const int w = s_face[min(max(h.face, 0), LAT_MAX_FACES - 1)].x;   // the face's constant axis = its normal
                     const bool keep = act && (!BOUNDED || h.d <= bnd.d2_max);
                     if constexpr (BOUNDED) nv += (unsigned)__popcll(ballot64(keep));
@@ -125,50 +109,20 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
                         // LatFix's range: every term below 2^18 (coordinates below 256 m, a neighbour less than 128 m away, weights
                         // <= 1); outside it the general conversion - the same integers either way (a NaN fails the test)
                         const float big_c = fmaxf(fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)), fmaxf(fmaxf(fabsf(h.nx), fabsf(h.ny)), fabsf(h.nz)));
-                        if (big_c < 256.f && h.d < 16384.f) {
+                        unsigned long long b[PLANE_NSUMS];
+                        lat_fix_terms<PLANE_D2>(t, big_c < 256.f && h.d < 16384.f, b);
 #pragma unroll
-                            for (int i = 0; i < 16; ++i) SA[i] += LatFix<FIX_SHIFT>::bits(t[i]);
-#pragma unroll
-                            for (int i = 16; i < 27; ++i) SB[i - 16] += LatFix<FIX_SHIFT>::bits(t[i]);
-                            SB[11] += LatFix<FIX_SHIFT_D2>::bits(t[27]);
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < 16; ++i) SA[i] += (unsigned long long)fixq(t[i], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
-#pragma unroll
-                            for (int i = 16; i < 27; ++i) SB[i - 16] += (unsigned long long)fixq(t[i], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
-                            SB[11] += (unsigned long long)fixq(t[27], FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
-                        }
+                        for (int i = 0; i < PLANE_NSUMS; ++i) (i < 16 ? SA[i] : SB[i - 16]) += b[i];
                     }
-                }
+                });
                 if (sub < npass) {
                     wave_fold_to_lds(SA, 16, s_acc);
                     wave_fold_to_lds(SB, 12, s_acc + 16);
                 }
                 if constexpr (BOUNDED) { if (sub < npass && lane == 0) atomicAdd(&s_nv, nv); }
             } else {
-                // final X <- T*X (PCL transforms before it tests convergence; the identity after a stop), then getFitnessScore()
-                // of Tfinal * original source
-                const float4* pts0 = src0 + src_off;
-                float T[12], Tf[12];
-#pragma unroll
-                for (int i = 0; i < 12; ++i) { T[i] = s_so.T[i]; Tf[i] = s_so.Tfinal[i]; }
-                unsigned long long S[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) S[i] = 0ull;
-                for (int pss = sub; pss < npass; pss += PLANE_WAVES) {
-                    const int myq = (pss << 6) + lane;
-                    const bool act = myq < n;
-                    const float4 p = pts[min(myq, n - 1)], p0 = pts0[min(myq, n - 1)];
-                    float ox, oy, oz;
-                    xform(T, p.x, p.y, p.z, ox, oy, oz);
-                    if (act) pts[myq] = make_float4(ox, oy, oz, p.w);
-                    float qx, qy, qz;
-                    xform(Tf, p0.x, p0.y, p0.z, qx, qy, qz);
-                    const LatHit h = F.axes ? lat_nearest_axes<false>(s_tab, s_face, F, qx, qy, qz)
-                                            : (nf3 ? lat_nearest<false, 3>(s_tab, s_face, F, qx, qy, qz) : lat_nearest<false, LAT_MAX_FACES>(s_tab, s_face, F, qx, qy, qz));
-                    if (act) S[0] += h.d < 16384.f ? LatFix<FIX_SHIFT_D2>::bits(h.d) : (unsigned long long)fixq(h.d, FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
-                }
-                if (sub < npass) wave_fold_to_lds(S, 1, s_acc);
+                // (T is the identity after a stop)
+                lat_fitness_pass<PLANE_WAVES>(pts, src0 + src_off, n, sub, lane, s_so, s_tab, s_face, F, s_acc);
             }
             __syncthreads();
             // ---- lane 0: the step (estimate, latch, shared tail), or the pair's results ----
@@ -184,7 +138,7 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
                         long long A[PLANE_NSUMS];
 #pragma unroll
                         for (int i = 0; i < PLANE_NSUMS; ++i)
-                            A[i] = (long long)(s_acc[i] - (unsigned long long)nv * (i == 27 ? LatFix<FIX_SHIFT_D2>::C : LatFix<FIX_SHIFT>::C));
+                            A[i] = (long long)(s_acc[i] - lat_fix_offset(i == PLANE_D2, (unsigned long long)nv));
                         float Tn[16];
                         if (plane_solve(A, nv, Tn)) {   // singular: stops before the update, as too few correspondences do
                             icp_stop_few(s_so);
@@ -209,7 +163,7 @@ k_icp_plane(int nitems, const int* __restrict__ order, const IcpCluster* __restr
                     s_so.done = 1;
                     st[2 * (size_t)k] = s_so;
                     st[2 * (size_t)k + 1] = s_so;
-                    accf[k] = s_acc[0] - (unsigned long long)n * LatFix<FIX_SHIFT_D2>::C;
+                    accf[k] = s_acc[0] - lat_fix_offset(true, (unsigned long long)n);
                     pstat[k] = s_ps;
                     s_acc[0] = 0ull;
                 }

@@ -51,18 +51,12 @@ k_pose_info(int nitems, const PoseItem* __restrict__ items, const IcpLattice* __
         const int slot = __builtin_amdgcn_readfirstlane(I->slot);
         const IcpLattice* __restrict__ L = lats + slot;
         if (slot != cur_slot) {   // (uniform) another template: its tables and face words
-            for (int i = threadIdx.x; i < L->ntab && i < LAT_MAX_TAB; i += POSE_THREADS) s_tab[i] = L->tab[i];
-            if (threadIdx.x < LAT_MAX_FACES) {
-                const int f = threadIdx.x, w = L->w[f], u = L->fast[f], v = 3 - w - u;
-                s_face[f] = make_int4(w, u, L->base[f], __float_as_int(L->c[f]));
-                s_face[LAT_MAX_FACES + f] = make_int4(L->toff[u], L->toff[v < 0 || v > 2 ? 0 : v], L->n[u], 0);
-            }
+            lat_stage_tables(L, L->ntab, s_tab, s_face, threadIdx.x, POSE_THREADS);
             cur_slot = slot;
             __syncthreads();
         }
         LatFaces F;
         lat_faces_load(L, F);
-        const bool nf3 = F.nface <= 3;
         float T[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) T[i] = I->T[i];
@@ -73,16 +67,11 @@ k_pose_info(int nitems, const PoseItem* __restrict__ items, const IcpLattice* __
 #pragma unroll
         for (int i = 0; i < 16; ++i) { SA[i] = 0ull; SB[i] = 0ull; }
         unsigned c0n = 0u, c1n = 0u, c2n = 0u, nbad = 0u;
-        float4 pnext = pts[min((sub << 6) + lane, n - 1)];
-        for (int pss = sub; pss < npass; pss += POSE_WAVES) {
-            const bool act = (pss << 6) + lane < n;
-            const float4 p = pnext;
-            pnext = pts[min(((pss + POSE_WAVES) << 6) + lane, n - 1)];
+        lat_for_passes<POSE_WAVES>(pts, n, sub, lane, [&](int, bool act, const float4& p) {
             const float ax = xform_row(T, 0, p.x, p.y, p.z), ay = xform_row(T, 1, p.x, p.y, p.z), az = xform_row(T, 2, p.x, p.y, p.z);
             const bool fin = pose_finite(ax, ay, az);
             nbad += (unsigned)__popcll(ballot64(act && !fin));
-            const LatHit h = F.axes ? lat_nearest_axes<true, false, true>(s_tab, s_face, F, ax, ay, az)
-                                    : (nf3 ? lat_nearest<true, 3>(s_tab, s_face, F, ax, ay, az) : lat_nearest<true, LAT_MAX_FACES>(s_tab, s_face, F, ax, ay, az));
+            const LatHit h = lat_nearest_any<true, true>(s_tab, s_face, F, ax, ay, az);
             const int4 fd = s_face[min(max(h.face, 0), LAT_MAX_FACES - 1)];
             const int w = fd.x;   // the face's constant axis = its normal; fd.w: its constant coordinate = the neighbour's on that axis
             const bool keep = act && fin && h.d <= tau;
@@ -93,15 +82,7 @@ k_pose_info(int nitems, const PoseItem* __restrict__ items, const IcpLattice* __
                 pose_terms(ax, ay, az, cx, cy, cz, w, __int_as_float(fd.w), t);
                 unsigned long long b[POSE_AXIS_SUMS];
                 // LatFix's range: |p| < 512 makes every term at 2^32 smaller than 2^18, r r < 2^14 at 2^36 (a NaN fails the test)
-                if (fabsf(t[0]) < POSE_FIX_P_MAX && fabsf(t[1]) < POSE_FIX_P_MAX && t[5] < POSE_FIX_R_MAX * POSE_FIX_R_MAX) {
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) b[j] = LatFix<FIX_SHIFT>::bits(t[j]);
-                    b[5] = LatFix<FIX_SHIFT_D2>::bits(t[5]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) b[j] = (unsigned long long)fixq(t[j], FIX_SHIFT) + LatFix<FIX_SHIFT>::C;
-                    b[5] = (unsigned long long)fixq(t[5], FIX_SHIFT_D2) + LatFix<FIX_SHIFT_D2>::C;
-                }
+                lat_fix_terms<POSE_RR>(t, fabsf(t[0]) < POSE_FIX_P_MAX && fabsf(t[1]) < POSE_FIX_P_MAX && t[5] < POSE_FIX_R_MAX * POSE_FIX_R_MAX, b);
                 if (keep && w == 0) {
 #pragma unroll
                     for (int j = 0; j < 6; ++j) SA[j] += b[j];
@@ -116,7 +97,7 @@ k_pose_info(int nitems, const PoseItem* __restrict__ items, const IcpLattice* __
                     SB[0] += b[4]; SB[1] += b[5];
                 }
             }
-        }
+        });
         if (sub < npass) {
             wave_fold_to_lds(SA, 16, s_acc);
             wave_fold_to_lds(SB, 2, s_acc + 16);
@@ -130,7 +111,7 @@ k_pose_info(int nitems, const PoseItem* __restrict__ items, const IcpLattice* __
             // (every kept point added the constant of its scale to each sum of its bank: LatFix)
 #pragma unroll 1
             for (int i = 0; i < POSE_NSUMS; ++i)
-                s_acc[i] -= (unsigned long long)s_cnt[i / POSE_AXIS_SUMS] * (i % POSE_AXIS_SUMS == POSE_RR ? LatFix<FIX_SHIFT_D2>::C : LatFix<FIX_SHIFT>::C);
+                s_acc[i] -= lat_fix_offset(i % POSE_AXIS_SUMS == POSE_RR, s_cnt[i / POSE_AXIS_SUMS]);
             pose_finish(n, (int)s_cnt[3], (int)s_cnt[0], (int)s_cnt[1], (int)s_cnt[2], reinterpret_cast<const long long*>(s_acc), cx, cy, cz, I->length,
                         min_support, I->accepted, s_ws, out + I->pair);
         }

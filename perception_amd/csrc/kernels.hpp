@@ -101,6 +101,18 @@ struct IcpTemplates {   // the template tables: points + per-64-run boxes in cel
     const unsigned short* kdmap; const IcpGrid* grids; const IcpSuper* supers; const unsigned short* tcell; const IcpLattice* lats;
 };
 struct IcpScratch { float4* src; const float4* src0; int* nn; float* d2; unsigned long long* acc; int* queue; };
+// ONE lane pops the next live problem of a launch's queue (order: largest first), skipping those the host pre-marked (too few
+// points / no template).  Returns its index with c = its description, or -1: nothing left.
+__device__ __forceinline__ int icp_pop_live(int* queue, int nitems, const int* order, const IcpCluster* cl, const IcpState* st, IcpCluster& c) {
+    for (;;) {
+        const int item = atomicAdd(queue, 1);
+        if (item >= nitems) return -1;
+        const int k = order[item];
+        if (st[2 * (size_t)k].done) continue;
+        c = cl[k];
+        return k;
+    }
+}
 // (the sliced, persistent and fitness kernels search the k-d patch order with its boxes)
 void launch_icp_iter(hipStream_t s, int it, int n_work, int ncl, const IcpWork* work, const IcpProblems& P, const IcpTemplates& T, const IcpScratch& S,
                      int qslice, int n_cu, IcpParams prm, const IcpBound& bnd);

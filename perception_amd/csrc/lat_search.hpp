@@ -1,8 +1,13 @@
-// lat_search.hpp - device code shared by the ICP kernels for LATTICE templates (k_icp_lat.hip, k_icp_plane.hip): the face
-// descriptors and table staging, the closed-form nearest neighbour of a query (lat_nearest, lat_nearest_axes, the tie walk)
-// and the raw-bits form of rule C4's conversion (LatFix).  The search is derived and measured in k_icp_lat.hip's header comment.
+// lat_search.hpp - device code shared by the kernels that register clouds against LATTICE templates (k_icp_lat.hip,
+// k_icp_plane.hip, k_pose_info.hip, and k_lat_nn): the face descriptors and the one table staging (lat_stage_tables), the
+// closed-form nearest neighbour of a query (lat_nearest, lat_nearest_axes, the tie walk; lat_nearest_any picks among them),
+// the raw-bits form of rule C4's conversion with its general side path (LatFix, lat_fix_terms, lat_fix_d2, lat_fix_offset),
+// the pass loop over a cluster's points (lat_for_passes) and the final transform + getFitnessScore pass (lat_fitness_pass).
+// The search is derived and measured in k_icp_lat.hip's header comment.  (k_icp_lat keeps its own text of the staging, the
+// dispatch, the accumulate and the two loops - the comment above its LatSlot says why: what is mended here is mended there.)
 #pragma once
 #include "kernels.hpp"
+#include "icp_solve.hpp"
 
 namespace cd {
 
@@ -36,16 +41,23 @@ __device__ __forceinline__ void lat_faces_load(const IcpLattice* __restrict__ L,
     asm("v_mov_b32 %0, %1" : "=v"(F.caz) : "s"(L->axis_c[2]));
 }
 
+// The ntab entries of a template's axis tables and its two rows of face words into LDS, by a group of `step` threads of which
+// the caller is thread t.  No barrier inside: the caller's follows.  (ntab = L->ntab <= LAT_MAX_TAB: lattice_tables refuses a
+// template whose tables do not fit, and the device's IcpLattice records are only ever copies of lattice_detect's output)
+__device__ __forceinline__ void lat_stage_tables(const IcpLattice* __restrict__ L, int ntab, float4* s_tab, int4* s_face, int t, int step) {
+    for (int i = t; i < ntab; i += step) s_tab[i] = L->tab[i];
+    if (t < LAT_MAX_FACES) {
+        const int f = t, w = L->w[f], u = L->fast[f], v = 3 - w - u;
+        s_face[f] = make_int4(w, u, L->base[f], __float_as_int(L->c[f]));
+        s_face[LAT_MAX_FACES + f] = make_int4(L->toff[u], L->toff[v < 0 || v > 2 ? 0 : v], L->n[u], 0);   // tables of its fast and slow axis (unused faces: anything)
+    }
+}
+
 // call from every thread of the workgroup; ends with a barrier
 template <int THREADS>
 __device__ __forceinline__ void lat_stage(const IcpLattice* __restrict__ L, LatFaces& F, float4* s_tab, int4* s_face) {
     lat_faces_load(L, F);
-    for (int i = threadIdx.x; i < L->ntab; i += THREADS) s_tab[i] = L->tab[i];
-    if (threadIdx.x < LAT_MAX_FACES) {
-        const int f = threadIdx.x, w = L->w[f], u = L->fast[f], v = 3 - w - u;
-        s_face[f] = make_int4(w, u, L->base[f], __float_as_int(L->c[f]));
-        s_face[LAT_MAX_FACES + f] = make_int4(L->toff[u], L->toff[v < 0 || v > 2 ? 0 : v], L->n[u], 0);   // tables of its fast and slow axis (unused faces: anything)
-    }
+    lat_stage_tables(L, L->ntab, s_tab, s_face, threadIdx.x, THREADS);
     __syncthreads();
 }
 
@@ -268,6 +280,13 @@ __device__ __forceinline__ LatHit lat_nearest_axes(const float4* s_tab, const in
     return h;
 }
 
+// the search of a query against whatever template F describes (uniform choices): one face per axis, at most three faces, any
+template <bool TIES, bool FACE = false>
+__device__ __forceinline__ LatHit lat_nearest_any(const float4* s_tab, const int4* s_face, const LatFaces& F, float qx, float qy, float qz) {
+    return F.axes ? lat_nearest_axes<TIES, false, FACE>(s_tab, s_face, F, qx, qy, qz)
+                  : (F.nface <= 3 ? lat_nearest<TIES, 3>(s_tab, s_face, F, qx, qy, qz) : lat_nearest<TIES, LAT_MAX_FACES>(s_tab, s_face, F, qx, qy, qz));
+}
+
 // original index of a hit (the diagnostic entry point; the ICP itself only needs the neighbour's coordinates)
 __device__ __forceinline__ int lat_index(const int4* s_face, const LatFaces& F, const LatHit& h) {
     const int4 fd = s_face[h.face];
@@ -289,8 +308,80 @@ struct LatFix {
     static __device__ __forceinline__ unsigned long long bits(float v) {
         return (unsigned long long)__double_as_longlong(__dadd_rn((double)v, __longlong_as_double((long long)C)));
     }
+    // the same integer for ANY v, by the general conversion
+    static __device__ __forceinline__ unsigned long long general(float v) { return (unsigned long long)fixq(v, SHIFT) + C; }
 };
+// N terms -> the N integers a point adds to its sums: term D2 at FIX_SHIFT_D2, the others at FIX_SHIFT.  raw: the caller's range
+// test says that every term is inside LatFix's range (a per-rule fact); the same integers either way.
+template <int D2, int N>
+__device__ __forceinline__ void lat_fix_terms(const float (&t)[N], bool raw, unsigned long long (&b)[N]) {
+    static_assert(D2 >= 0 && D2 < N, "the squared-distance term is one of the N");
+    if (raw) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) b[i] = i == D2 ? LatFix<FIX_SHIFT_D2>::bits(t[i]) : LatFix<FIX_SHIFT>::bits(t[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) b[i] = i == D2 ? LatFix<FIX_SHIFT_D2>::general(t[i]) : LatFix<FIX_SHIFT>::general(t[i]);
+    }
+}
+// the one term of a fitness sum (a squared distance; raw bits below (128 m)^2)
+__device__ __forceinline__ unsigned long long lat_fix_d2(float d) { return d < 16384.f ? LatFix<FIX_SHIFT_D2>::bits(d) : LatFix<FIX_SHIFT_D2>::general(d); }
+// what `count` points have added to a sum on top of its terms (is_d2: the sum of the FIX_SHIFT_D2 term): the solver takes it off
+__device__ __forceinline__ unsigned long long lat_fix_offset(bool is_d2, unsigned long long count) {
+    return count * (is_d2 ? LatFix<FIX_SHIFT_D2>::C : LatFix<FIX_SHIFT>::C);
+}
 static_assert(LatFix<32>::C == 0x4138000000000000ull && LatFix<36>::C == 0x40f8000000000000ull, "constants of lat_fix");
 static_assert(FIX_SHIFT == 32 && FIX_SHIFT_D2 == 36, "k_icp_lat's moment sums are written for these scales");
+
+// The passes of wave `sub` of WAVES over the n >= 1 points at pts, 64 at a time: body(myq, act, p) with myq = the lane's point,
+// act = it exists, p = its record (the last point's where it does not).  The points of the next pass are requested before the
+// current pass is worked on: one wave per SIMD per cluster has nothing else to cover an L2 round trip with.  body may store to
+// pts[myq]: a later pass never reads it.
+template <int WAVES, class Body>
+__device__ __forceinline__ void lat_for_passes(const float4* pts, int n, int sub, int lane, Body body) {
+    const int npass = (n + 63) >> 6;
+    float4 pnext = pts[min((sub << 6) + lane, n - 1)];
+    for (int pss = sub; pss < npass; pss += WAVES) {
+        const int myq = (pss << 6) + lane;
+        const bool act = myq < n;
+        const float4 p = pnext;
+        pnext = pts[min(((pss + WAVES) << 6) + lane, n - 1)];
+        body(myq, act, p);
+    }
+}
+
+// The last step of an ICP, by wave `sub` of WAVES: X <- T X in place (PCL transforms before it tests convergence), then
+// getFitnessScore() of Tfinal * original source - every point's d2 as one rule-C4 sum (n x LatFix<FIX_SHIFT_D2>::C on top),
+// folded into acc[0] (LDS).  so: the cluster's state in LDS, read as uniform values; both arrays are prefetched.
+template <int WAVES>
+__device__ __forceinline__ void lat_fitness_pass(float4* pts, const float4* pts0, int n, int sub, int lane, const IcpState& so, const float4* tab,
+                                                 const int4* face, const LatFaces& F, unsigned long long* acc) {
+    const int npass = (n + 63) >> 6;
+    float T[12], Tf[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        T[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(so.T[i])));
+        Tf[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(so.Tfinal[i])));
+    }
+    unsigned long long S[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) S[i] = 0ull;
+    float4 pnext = pts[min((sub << 6) + lane, n - 1)], p0next = pts0[min((sub << 6) + lane, n - 1)];
+    for (int pss = sub; pss < npass; pss += WAVES) {
+        const int myq = (pss << 6) + lane;
+        const bool act = myq < n;
+        const float4 p = pnext, p0 = p0next;
+        pnext = pts[min(((pss + WAVES) << 6) + lane, n - 1)];
+        p0next = pts0[min(((pss + WAVES) << 6) + lane, n - 1)];
+        float ox, oy, oz;
+        xform(T, p.x, p.y, p.z, ox, oy, oz);
+        if (act) pts[myq] = make_float4(ox, oy, oz, p.w);
+        float qx, qy, qz;
+        xform(Tf, p0.x, p0.y, p0.z, qx, qy, qz);
+        const LatHit h = lat_nearest_any<false>(tab, face, F, qx, qy, qz);
+        if (act) S[0] += lat_fix_d2(h.d);
+    }
+    if (sub < npass) wave_fold_to_lds(S, 1, acc);
+}
 
 }  // namespace cd

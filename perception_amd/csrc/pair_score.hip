@@ -5,23 +5,11 @@
 #include "context.hpp"
 
 namespace {
-// step 3: rule C8's tau of the range (the setter and the entry points have refused a range that has none)
-float tau_of(double max_range) {
-    float tau = 0.f;
-    cd_icp_correspondence_threshold(max_range, &tau, nullptr);
-    return tau;
-}
-
-struct PairSpec {   // one (cluster, template) pair of a launch: its n points at d_src0 + src_off, its result's T and flag, its slot
-    long long src_off;
-    int n, slot, accepted;
-    const float* T;
-};
-
 // Scores `np` pairs into out[0 .. np): the pairs that step 8 lets through become two jobs each (source -> template, template ->
-// source), their items go to the device largest first, one launch on the context's stream fills the integer rows, one blocking copy
-// brings them back and pair_record writes the records.  May grow its buffers (which synchronises the stream); ends synchronised.
-int run_pair_scores(cd_context* c, const std::vector<PairSpec>& specs, double max_range, double min_cov, double min_inl, cd_pair_score* out) {
+// source), their items go to the device largest first, one launch on the context's stream fills the integer rows (step 3's tau:
+// tau_of), one blocking copy brings them back and pair_record writes the records.  May grow its buffers (which synchronises the
+// stream); ends synchronised.
+int run_pair_scores(cd_context* c, const std::vector<ResultSpec>& specs, double max_range, double min_cov, double min_inl, cd_pair_score* out) {
     const int np = (int)specs.size();
     if (np <= 0) return CD_OK;
     std::vector<int> pre((size_t)np);
@@ -29,7 +17,7 @@ int run_pair_scores(cd_context* c, const std::vector<PairSpec>& specs, double ma
     std::vector<PairItem> items;
     std::vector<long long> weight;
     for (int k = 0; k < np; ++k) {
-        const PairSpec& s = specs[(size_t)k];
+        const ResultSpec& s = specs[(size_t)k];
         const int m = s.slot >= 0 && s.slot < CD_MAX_TEMPLATES ? c->tpl_m[s.slot] : 0;
         pre[(size_t)k] = pair_pre_status(s.n, m, s.T);
         if (pre[(size_t)k] != CD_OK) continue;
@@ -72,7 +60,7 @@ int run_pair_scores(cd_context* c, const std::vector<PairSpec>& specs, double ma
         std::memcpy(acc.data(), c->h_psacc.get(), sizeof(unsigned long long) * acc.size());
     }
     for (int k = 0; k < np; ++k) {
-        const PairSpec& s = specs[(size_t)k];
+        const ResultSpec& s = specs[(size_t)k];
         const int m = s.slot >= 0 && s.slot < CD_MAX_TEMPLATES ? c->tpl_m[s.slot] : 0;
         const unsigned long long* row = acc.data() + (size_t)k * PAIR_ACC_PITCH;
         if (pre[(size_t)k] == CD_OK && row[PAIR_BAD] == 0ull && (row[PAIR_N_SRC_IN] > (unsigned long long)s.n || row[PAIR_N_TPL_IN] > (unsigned long long)m))
@@ -85,11 +73,11 @@ int run_pair_scores(cd_context* c, const std::vector<PairSpec>& specs, double ma
 int pair_score_points_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int n, const float* T, double max_range, double min_cov,
                            double min_inl, int accepted, cd_pair_score* out) {
     invalidate_last(c);
-    if (!out || !T || n < 0 || (n > 0 && !src_xyz) || stride < 12 || (stride & 3) || slot < 0 || slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
-    if (!pair_thresholds_ok(max_range, min_cov, min_inl)) return fail(c, CD_ERR_INVALID_ARG, "max_range must be finite and > 0, the fractions in [0, 1]");
-    if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
+    if (int st = check_result_points(c, out != nullptr, slot, src_xyz, stride, n, T, pair_thresholds_ok(max_range, min_cov, min_inl),
+                                     "max_range must be finite and > 0, the fractions in [0, 1]"))
+        return st;
     if (int st = upload_points(c, src_xyz, stride, n, c->d_src0)) return st;
-    const std::vector<PairSpec> one{PairSpec{0, n, slot, accepted ? 1 : 0, T}};
+    const std::vector<ResultSpec> one{ResultSpec{0, n, slot, accepted ? 1 : 0, T}};
     return run_pair_scores(c, one, max_range, min_cov, min_inl, out);
 }
 }  // namespace
@@ -101,13 +89,8 @@ namespace cd {
 int stage_pair_scores(cd_context* c, int ncl, const std::vector<long long>& orig_off) {
     c->last_pair.begin(ncl);
     if (ncl <= 0) return CD_OK;
-    std::vector<PairSpec> specs((size_t)ncl);
-    for (int k = 0; k < ncl; ++k) {
-        const cd_cluster_result& r = c->last_clusters[(size_t)k];
-        specs[(size_t)k] = PairSpec{orig_off[(size_t)k], r.size, r.template_slot, r.accepted, r.T};
-    }
     std::vector<cd_pair_score> rec((size_t)ncl);
-    if (int st = run_pair_scores(c, specs, c->pair_range, c->pair_min_cov, c->pair_min_inl, rec.data())) return st;
+    if (int st = run_pair_scores(c, result_specs(c, ncl, orig_off), c->pair_range, c->pair_min_cov, c->pair_min_inl, rec.data())) return st;
     for (int k = 0; k < ncl; ++k) c->last_pair.keep(k, rec[(size_t)k]);
     return CD_OK;
 }
@@ -151,9 +134,7 @@ int cd_pair_score_host(const void* tpl_xyz, size_t tpl_stride, int m, const void
     const int pre = pair_pre_status(n, m, T);
     unsigned long long acc[PAIR_ACC_PITCH] = {0ull};
     if (pre == CD_OK) {
-        std::vector<float> tpl((size_t)m * 3), src((size_t)n * 3);
-        for (int j = 0; j < m; ++j) std::memcpy(&tpl[3 * (size_t)j], (const char*)tpl_xyz + (size_t)j * tpl_stride, 12);
-        for (int i = 0; i < n; ++i) std::memcpy(&src[3 * (size_t)i], (const char*)src_xyz + (size_t)i * src_stride, 12);
+        const std::vector<float> tpl = gather_xyz(tpl_xyz, tpl_stride, m), src = gather_xyz(src_xyz, src_stride, n);
         pair_passes_host(tpl.data(), m, src.data(), n, T, tau_of(max_range), acc);
     }
     pair_record(n, m, pre, acc, accepted ? 1 : 0, min_coverage, min_inlier_fraction, out);

@@ -4,29 +4,16 @@
 #include "context.hpp"
 
 namespace {
-// step 2: rule C8's tau of the range (the setter and the entry points have refused a range that has none)
-float tau_of(double max_range) {
-    float tau = 0.f;
-    cd_icp_correspondence_threshold(max_range, &tau, nullptr);
-    return tau;
-}
-
-struct PoseSpec {   // one (cluster, template) result of a launch: its n points at d_src0 + src_off, its T and flag, its slot
-    long long src_off;
-    int n, slot, accepted;
-    const float* T;
-};
-
 // Examines `np` results into out[0 .. np): those that step 9 lets through become one item each, the items go to the device largest
-// first, one launch on the context's stream fills their records and one blocking copy brings them back; the others get their
-// record here.  The grid is four workgroups a CU, capped like the ICP's own by CUBOID_ICP_MAX_WG (tests make one workgroup take
-// many items with it).  May grow its buffers (which synchronises the stream); ends synchronised.
-int run_pose_info(cd_context* c, const std::vector<PoseSpec>& specs, double max_range, double min_support, cd_pose_info* out) {
+// first, one launch on the context's stream fills their records (step 2's tau: tau_of) and one blocking copy brings them back;
+// the others get their record here.  The grid is four workgroups a CU, capped like the ICP's own by CUBOID_ICP_MAX_WG (tests
+// make one workgroup take many items with it).  May grow its buffers (which synchronises the stream); ends synchronised.
+int run_pose_info(cd_context* c, const std::vector<ResultSpec>& specs, double max_range, double min_support, cd_pose_info* out) {
     const int np = (int)specs.size();
     if (np <= 0) return CD_OK;
     std::vector<PoseItem> items;
     for (int k = 0; k < np; ++k) {
-        const PoseSpec& s = specs[(size_t)k];
+        const ResultSpec& s = specs[(size_t)k];
         const bool slot_ok = s.slot >= 0 && s.slot < CD_MAX_TEMPLATES;
         const int pre = pose_pre_status(slot_ok ? c->tpl_m[s.slot] : 0, slot_ok ? c->tpl_faces[s.slot] : 0, s.T);
         if (pre != CD_OK) { pose_empty(s.n, pre, 0, 0, 0, 0, &out[k]); continue; }
@@ -64,11 +51,11 @@ int run_pose_info(cd_context* c, const std::vector<PoseSpec>& specs, double max_
 int pose_info_points_impl(cd_context* c, int slot, const void* src_xyz, size_t stride, int n, const float* T, double max_range, double min_support, int accepted,
                           cd_pose_info* out) {
     invalidate_last(c);
-    if (!out || !T || n < 0 || (n > 0 && !src_xyz) || stride < 12 || (stride & 3) || slot < 0 || slot >= CD_MAX_TEMPLATES) return fail(c, CD_ERR_INVALID_ARG, "bad arguments");
-    if (!pose_setting_ok(max_range, min_support)) return fail(c, CD_ERR_INVALID_ARG, "max_range and min_support must be finite and > 0");
-    if (n > c->N) return fail(c, CD_ERR_CAPACITY, "more points than the context capacity");
+    if (int st = check_result_points(c, out != nullptr, slot, src_xyz, stride, n, T, pose_setting_ok(max_range, min_support),
+                                     "max_range and min_support must be finite and > 0"))
+        return st;
     if (int st = upload_points(c, src_xyz, stride, n, c->d_src0)) return st;
-    const std::vector<PoseSpec> one{PoseSpec{0, n, slot, accepted ? 1 : 0, T}};
+    const std::vector<ResultSpec> one{ResultSpec{0, n, slot, accepted ? 1 : 0, T}};
     return run_pose_info(c, one, max_range, min_support, out);
 }
 
@@ -86,13 +73,8 @@ namespace cd {
 int stage_pose_info(cd_context* c, int ncl, const std::vector<long long>& orig_off) {
     c->last_pose.begin(ncl);
     if (ncl <= 0) return CD_OK;
-    std::vector<PoseSpec> specs((size_t)ncl);
-    for (int k = 0; k < ncl; ++k) {
-        const cd_cluster_result& r = c->last_clusters[(size_t)k];
-        specs[(size_t)k] = PoseSpec{orig_off[(size_t)k], r.size, r.template_slot, r.accepted, r.T};
-    }
     std::vector<cd_pose_info> rec((size_t)ncl);
-    if (int st = run_pose_info(c, specs, c->pose_range, c->pose_support, rec.data())) return st;
+    if (int st = run_pose_info(c, result_specs(c, ncl, orig_off), c->pose_range, c->pose_support, rec.data())) return st;
     for (int k = 0; k < ncl; ++k) c->last_pose.keep(k, rec[(size_t)k]);
     return CD_OK;
 }
