@@ -1284,6 +1284,96 @@ int cd_pose_info_host(const void* tpl_xyz, size_t tpl_stride, int m, const void*
  * from S and so from the result: n_constrained says so.  NULL pointer: CD_ERR_INVALID_ARG. */
 int cd_pose_info_ros_covariance(const cd_pose_info* info, const float T[16], double out36[36]);
 
+/* Box fit: a resting cuboid's dimensions, yaw and centre from the table plane and the points of its cluster - no template, no
+ * search, no iteration.  Every registration path needs a template of the right size uploaded beforehand; this step measures the
+ * object instead: its height above the table, the minimum-area rectangle of its top face's footprint, hence L, W, H, the long
+ * axis and the centre.  Opt-in, off by default.  Canonical rule C24; perception_amd/box_fit.py is the rule in
+ * numpy, with every association, and the device and cd_box_fit_host equal it bit for bit.  The rule assumes that the cuboid rests
+ * on the plane with a face up: a tilted or stacked box gets a record whose rectangularity says so, and nothing else.
+ * For the plane (a, b, c, d) as float32, n float32 points and band (a double, finite, 0 < band <= 64), all real arithmetic in
+ * double, every product and sum rounded on its own in the order written:
+ *   1. (nrm, dd) is rule C20's step 1; h(p) = ((nrm0 x + nrm1 y) + nrm2 z) + dd;
+ *   2. k0 is rule C20's step 4, k1 = (k0 + 1) mod 3; t_j = [j == k1] - (nrm[k1] nrm_j); len = sqrt((t0 t0 + t1 t1) + t2 t2);
+ *      eu_j = t_j / len; ev = nrm x eu, each component as (nrm_a eu_b) - (nrm_b eu_a): a metric basis of the plane;
+ *   3. per point qh = floor(h 65536), u = floor(((eu0 x + eu1 y) + eu2 z) 65536), v likewise with ev, clamped and NaN-mapped as rule
+ *      C20's step 5, int32; everything from here on is integer unless a conversion is written;
+ *   4. k = 1 + n / 64, href = the k-th largest qh; top = {qh >= href - floor(band 65536)};
+ *      height = ((double) sum_top qh / (double) n_top) / 65536;
+ *   5. the hull of the top set's (u, v): rule C20's step 6, capped at CD_PRISM_MAX_HULL vertices;
+ *   6. per hull edge i (A = H[i], e = H[i + 1 mod m] - A) over all hull vertices P: along = (P - A) . e, across = e_u (P - A)_v -
+ *      e_v (P - A)_u; w, g = max - min of each, l2 = e . e; area_i = ((double) w (double) g) / (double) l2; the smallest wins, a
+ *      tie goes to the lowest i;
+ *   7. s = sqrt((double) l2), p = ((double) w / s) / 65536, q = ((double) g / s) / 65536; dims = (max(p, q), min(p, q), height);
+ *      the long axis in (u, v) is e when p >= q, else (-e_v, e_u), negated when its u component is negative (or zero with a negative
+ *      v component), divided by s;
+ *   8. the rectangle's centre (cu, cv) = A + ((amin + amax) / (2 l2)) e + ((cmin + cmax) / (2 l2)) (-e_v, e_u);
+ *      centre = (cu / 65536) eu + (cv / 65536) ev + (height / 2 - dd) nrm; pose: row-major 4 x 4, box -> camera, columns ex (the
+ *      long axis lifted through eu, ev), ey = nrm x ex, nrm, centre - cd_cluster_result.pose's convention; rounded to float32 it
+ *      is an Rt that cd_surface_guess takes;
+ *   9. area = area_min / 65536^2; rectangularity = hull area (integer shoelace sum, halved in double, / 65536^2) / area;
+ *      height_ref = href / 65536;
+ *  10. status, a result and not a failure of the call: n < 3: CD_ERR_FEW_CORRESPONDENCES; a non-finite coordinate or |coordinate|
+ *      > 64: CD_ERR_INVALID_ARG; no plane (a frame without one, a non-finite coefficient, a = b = c = 0) or a hull of fewer than 3
+ *      vertices: CD_ERR_NO_MODEL; more than CD_PRISM_MAX_HULL vertices: CD_ERR_CAPACITY with overflow = 1 and hull_vertices = 0.
+ *      Such a record holds the counts reached so far and zeros elsewhere.
+ * CD_BOX_FIT_LDS_POINTS: the points of a cluster whose (qh, u, v) the kernel keeps in LDS; a larger cluster is quantised again from
+ * global memory in every pass (the same integers). */
+#define CD_BOX_FIT_BAND_DEFAULT 0.006
+#define CD_BOX_FIT_LDS_POINTS 2048
+typedef struct cd_box_fit {
+    int32_t n;                 /* points of the cluster                                                                  */
+    int32_t n_top;             /* ... in the top set                                                                     */
+    int32_t hull_vertices;     /* strict vertices of the top set's hull                                                  */
+    int32_t edge;              /* the hull edge the rectangle lies along                                                 */
+    int32_t status;            /* step 10                                                                                */
+    int32_t overflow;          /* the hull has more than CD_PRISM_MAX_HULL vertices                                      */
+    int32_t match_slot;        /* the selection on (cd_set_box_select): cd_box_fit_match's slot of a CD_OK record; else -1 */
+    int32_t reserved;
+    double height_ref;         /* href / 65536                                                                           */
+    double dims[3];            /* L >= W, H, metres                                                                      */
+    double pose[16];           /* step 8                                                                                 */
+    double area;               /* of the rectangle, square metres                                                        */
+    double rectangularity;     /* hull area / rectangle area, 1 for a rectangle                                          */
+    double match_cost;         /* ... and its cost; 0 with the selection off                                             */
+} cd_box_fit;
+int cd_box_fit_struct_size(void);   /* sizeof(cd_box_fit) (cd_struct_size's list is closed) */
+/* Host only (no context, no GPU): the rule through the arithmetic header the kernel uses.  CD_OK with the record's own status in
+ * out->status; a NULL pointer (coeff, out, xyz with n > 0), n < 0, a stride below 12 or a band the rule refuses:
+ * CD_ERR_INVALID_ARG, nothing written. */
+int cd_box_fit_host(const float coeff[4], const void* xyz, size_t stride_bytes, int n, double band, cd_box_fit* out);
+/* n_sets point sets on the GPU in one launch, without a fused call: set i is the points offsets[i] .. offsets[i + 1] of xyz
+ * (ascending, as cd_shape_frames) against the plane coeff[4 i .. 4 i + 3].  out[i] is its record.  A NULL coeff / offsets / out (or
+ * xyz with points to read), n_sets <= 0, a stride below 12 or not a multiple of 4, offsets that are negative or descend, a band
+ * the rule refuses: CD_ERR_INVALID_ARG. */
+int cd_box_fit_points(cd_context* ctx, const float* coeff, const void* xyz, size_t stride_bytes, const int32_t* offsets, int n_sets, double band,
+                      cd_box_fit* out);
+/* cd_set_box_fit: context state.  enable = 0 (the default): a fused call launches nothing more and every output is byte for byte
+ * what it was; the band is then not looked at and stays, and the selection below goes off with the step.  enable != 0 with a band
+ * the rule refuses: CD_ERR_INVALID_ARG and the setting stays.  With the step on, every fused call fits each cluster as clustered,
+ * right after the cluster hand-over (after the table prism and the outlier filter when those are on), against its frame's plane;
+ * every other record and read-back is unchanged.  cd_get_cluster_box_fits: the records of the last fused call's clusters, indexed and
+ * invalidated exactly like cd_get_cluster_pair_scores. */
+int cd_set_box_fit(cd_context* ctx, int enable, double band);
+int cd_get_box_fit(const cd_context* ctx, int* enable, double* band);
+int cd_get_cluster_box_fits(const cd_context* ctx, int frame, int first, int count, cd_box_fit* out);
+/* cd_set_box_select: context state, off by default.  slot_dims[s] = (length, width, height) of the template in slot s; needs the box
+ * fit on (else CD_ERR_INVALID_ARG, as for a NULL slot_dims, a non-finite entry, a tolerance that is not finite or negative; the
+ * setting stays).  enable = 0 needs no other argument.  It acts only in a fused call with template_slot == -1 and more than one
+ * loaded slot: a cluster whose record is CD_OK and matches a loaded slot (cd_box_fit_match over the loaded slots, this tolerance)
+ * is registered against that slot alone, and its result is, bit for bit, what the same call with template_slot = that slot gives
+ * the cluster; every other cluster runs against every loaded slot, as without the selection.  It costs one device -> host read of
+ * the box records ahead of the ICP.  A call in which no cluster matches is the call without the selection, launch for launch.
+ * With the selection on every CD_OK record of a fused call carries match_slot / match_cost. */
+int cd_set_box_select(cd_context* ctx, int enable, const double slot_dims[CD_MAX_TEMPLATES][3], double tolerance);
+int cd_get_box_select(const cd_context* ctx, int* enable, double slot_dims[CD_MAX_TEMPLATES][3], double* tolerance);
+/* Host only: which of the slots has the fitted dimensions?  slot_dims[s] = (length, width, height) of slot s, considered when
+ * bit s of loaded_mask is set; a slot's first two are sorted descending; cost = max(|L - Ls|, |W - Ws|, |H - Hs|) in double.  The
+ * lowest cost wins, a tie goes to the lowest slot; *slot = -1 when no slot is considered (*cost = 0) or the best cost exceeds
+ * tolerance (*cost is that cost).  NULL dims / slot_dims / slot / cost or a tolerance that is NaN or negative:
+ * CD_ERR_INVALID_ARG. */
+int cd_box_fit_match(const double dims[3], const double slot_dims[CD_MAX_TEMPLATES][3], uint32_t loaded_mask, double tolerance, int32_t* slot,
+                     double* cost);
+
 /* S7 helpers: tf::Matrix3x3::getRotation + position (icp.cpp:55-82) and the 8 bbox
  * corners in the order of icp.cpp:99-106 transformed by pose.cast<float>() (icp.cpp:110). */
 void cd_pose_to_position_quaternion(const double pose[16], double position[3],

@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = [
     "cd_pair_score_host",
     "cd_set_pose_info", "cd_get_pose_info", "cd_pose_info_struct_size", "cd_get_cluster_pose_info", "cd_pose_info_points", "cd_pose_info_host",
     "cd_pose_info_ros_covariance",
+    "cd_set_box_fit", "cd_get_box_fit", "cd_box_fit_struct_size", "cd_get_cluster_box_fits", "cd_box_fit_points", "cd_box_fit_host", "cd_box_fit_match",
+    "cd_set_box_select", "cd_get_box_select",
 ]
 
 # rule C17 (cd_set_icp_plane_weight): the recommended setting and the least tangent weight
@@ -90,6 +92,8 @@ CD_PRISM_MAX_HULL, CD_PRISM_LDS_POINTS = 1024, 4096
 CD_PAIR_SCORE_RANGE_DEFAULT, CD_PAIR_SCORE_MIN_COVERAGE_DEFAULT, CD_PAIR_SCORE_MIN_INLIER_DEFAULT = 0.005, 0.5, 0.8
 # rule C23 (cd_set_pose_info): the recommended setting
 CD_POSE_INFO_RANGE_DEFAULT, CD_POSE_INFO_MIN_SUPPORT_DEFAULT = 0.005, 8.0
+# rule C24 (cd_set_box_fit): the recommended band; the points of a cluster the kernel keeps in LDS
+CD_BOX_FIT_BAND_DEFAULT, CD_BOX_FIT_LDS_POINTS = 0.006, 2048
 
 
 class CdSurfaceFrameResult(C.Structure):
@@ -146,6 +150,22 @@ class CdPoseInfo(C.Structure):
         for k, t in self._fields_:
             v = getattr(self, k)
             out[k] = list(v) if hasattr(v, "__len__") else (float(v) if t is C.c_double else int(v))
+        return out
+
+
+class CdBoxFit(C.Structure):
+    """cd_box_fit: the box fit (rule C24) of one cluster - dims (L >= W, H), pose (row-major 4 x 4, box -> camera), the counts and its
+    own status."""
+    _fields_ = [("n", C.c_int32), ("n_top", C.c_int32), ("hull_vertices", C.c_int32), ("edge", C.c_int32), ("status", C.c_int32), ("overflow", C.c_int32),
+                ("match_slot", C.c_int32), ("reserved", C.c_int32), ("height_ref", C.c_double), ("dims", C.c_double * 3), ("pose", C.c_double * 16),
+                ("area", C.c_double), ("rectangularity", C.c_double), ("match_cost", C.c_double)]
+
+    def as_dict(self):
+        """Scalars as int / float, arrays as float64 arrays (the fields of perception_amd.box_fit's records)."""
+        out = {}
+        for k, t in self._fields_:
+            v = getattr(self, k)
+            out[k] = np.array(list(v), np.float64) if hasattr(v, "__len__") else (float(v) if t is C.c_double else int(v))
         return out
 
 
@@ -585,6 +605,16 @@ def load_library(path=None):
     lib.cd_pose_info_points.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_int, pip]
     lib.cd_pose_info_host.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_double, C.c_double, C.c_int, pip]
     lib.cd_pose_info_ros_covariance.argtypes = [pip, vp, vp]
+    bfp = C.POINTER(CdBoxFit)
+    lib.cd_set_box_fit.argtypes = [vp, C.c_int, C.c_double]
+    lib.cd_get_box_fit.argtypes = [vp, ip, dp]
+    lib.cd_box_fit_struct_size.argtypes = []
+    lib.cd_get_cluster_box_fits.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.cd_box_fit_points.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_int32), C.c_int, C.c_double, vp]
+    lib.cd_box_fit_host.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_double, bfp]
+    lib.cd_set_box_select.argtypes = [vp, C.c_int, vp, C.c_double]
+    lib.cd_get_box_select.argtypes = [vp, ip, vp, dp]
+    lib.cd_box_fit_match.argtypes = [vp, vp, C.c_uint32, C.c_double, C.POINTER(C.c_int32), dp]
     if path is None:
         _lib = lib
     return lib
@@ -1232,6 +1262,50 @@ class Context:
                                                  1 if accepted else 0, C.byref(out)))
         return out.as_dict()
 
+    def set_box_fit(self, enable, band=CD_BOX_FIT_BAND_DEFAULT):
+        """Rule C24, the box fit, for every later fused call of this context: each cluster gets the dimensions, pose and rectangularity
+        of the cuboid it is the view of, from its points and the frame's plane alone.  Off by default."""
+        self._check(self.lib.cd_set_box_fit(self.h, 1 if enable else 0, float(band)))
+
+    def box_fit_setting(self):
+        """(enable, band) as cd_set_box_fit left them."""
+        on, b = C.c_int(), C.c_double()
+        self._check(self.lib.cd_get_box_fit(self.h, C.byref(on), C.byref(b)))
+        return on.value, b.value
+
+    def set_box_select(self, enable, slot_dims=None, tolerance=0.0):
+        """The selection of rule C24 for every later fused call with template_slot = -1: a cluster whose box record matches the
+        dimensions of a loaded slot (slot_dims: up to CD_MAX_TEMPLATES rows of length, width, height) within the tolerance is
+        registered against that slot alone.  Needs set_box_fit(True).  Off by default."""
+        sd = np.zeros((CD_MAX_TEMPLATES, 3), np.float64)
+        if slot_dims is not None:
+            rows = np.asarray(slot_dims, np.float64).reshape(-1, 3)
+            sd[:len(rows)] = rows
+        self._check(self.lib.cd_set_box_select(self.h, 1 if enable else 0, _ptr(sd), float(tolerance)))
+
+    def box_select_setting(self):
+        """(enable, slot_dims (CD_MAX_TEMPLATES, 3), tolerance) as cd_set_box_select left them."""
+        on, tol, sd = C.c_int(), C.c_double(), np.zeros((CD_MAX_TEMPLATES, 3), np.float64)
+        self._check(self.lib.cd_get_box_select(self.h, C.byref(on), _ptr(sd), C.byref(tol)))
+        return on.value, sd, tol.value
+
+    def cluster_box_fits(self, frame, first=0, count=None):
+        """Rule C24's records of the clusters of `frame` of the last fused call, indexed like cluster_results: a list of CdBoxFit."""
+        msg = "no box-fit call to read: the last fused call ran with the step off, has been invalidated, or had no such frame"
+        return self._cluster_records(self.lib.cd_get_cluster_box_fits, CdBoxFit, msg, frame, first, count)
+
+    def box_fit_points(self, coeffs, sets, band=CD_BOX_FIT_BAND_DEFAULT):
+        """Rule C24 on the device without a fused call: one dict of cd_box_fit's fields per point set of `sets` (a sequence of
+        (n_i, 3) float32 arrays) against the plane coeffs[i] (4 float32), all in one launch (cd_box_fit_points)."""
+        sets = [np.asarray(a, np.float32).reshape(-1, 3) for a in sets]
+        co = np.ascontiguousarray(np.asarray(coeffs, np.float32).reshape(len(sets), 4))
+        pts = np.ascontiguousarray(np.concatenate(sets, axis=0))
+        off = np.zeros(len(sets) + 1, np.int32)
+        off[1:] = np.cumsum([a.shape[0] for a in sets])
+        out = (CdBoxFit * len(sets))()
+        self._check(self.lib.cd_box_fit_points(self.h, _ptr(co), _ptr(pts), 12, off.ctypes.data_as(C.POINTER(C.c_int32)), len(sets), float(band), out))
+        return [r.as_dict() for r in out]
+
     def passthrough(self, records, field, lo, hi, negative=False):
         """pcl::PassThrough on whole records: `records` (n, k >= 3) of 4-byte items; field 'x' / 'y' / 'z' or None."""
         r = np.ascontiguousarray(records)
@@ -1480,6 +1554,32 @@ def pose_info_ros_covariance(info, T):
     if st != CD_OK:
         raise CuboidError(st, "cd_pose_info_ros_covariance")
     return out.reshape(6, 6)
+
+
+def box_fit_host(coeff, xyz, band=CD_BOX_FIT_BAND_DEFAULT):
+    """cd_box_fit_host: rule C24 on the host (no context, no GPU).  Returns a dict of cd_box_fit's fields."""
+    lib = load_library()
+    co = np.ascontiguousarray(np.asarray(coeff, np.float32).reshape(4))
+    p = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+    out = CdBoxFit()
+    st = lib.cd_box_fit_host(_ptr(co), _ptr(p), 12, len(p), float(band), C.byref(out))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_box_fit_host")
+    return out.as_dict()
+
+
+def box_fit_match(dims, slot_dims, loaded_mask, tolerance):
+    """cd_box_fit_match: (slot, cost) of the fitted dims (3) against slot_dims (up to CD_MAX_TEMPLATES rows of length, width, height)."""
+    lib = load_library()
+    d = np.ascontiguousarray(np.asarray(dims, np.float64).reshape(3))
+    sd = np.zeros((CD_MAX_TEMPLATES, 3), np.float64)
+    rows = np.asarray(slot_dims, np.float64).reshape(-1, 3)
+    sd[:len(rows)] = rows
+    slot, cost = C.c_int32(), C.c_double()
+    st = lib.cd_box_fit_match(_ptr(d), _ptr(sd), int(loaded_mask) & ((1 << CD_MAX_TEMPLATES) - 1), float(tolerance), C.byref(slot), C.byref(cost))
+    if st != CD_OK:
+        raise CuboidError(st, "cd_box_fit_match")
+    return slot.value, cost.value
 
 
 def prism_project(coeff, xyz):

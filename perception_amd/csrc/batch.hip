@@ -210,14 +210,14 @@ bool fits_one_stage(const cd_context* c, int F, const BatchClusters& cl, int S) 
     return true;
 }
 
-// ICP problem q of the stage just run (synchronised by stage_icp) is cluster k against slots[t].  Its result is kept when it
-// is the first (t == 0) or has the lower fitness, so ties keep the lowest slot.  `resident`: the problem's aligned points are
-// still in d_src when the call returns (al_off; -1 otherwise).
-void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, int k, int t, bool resident) {
+// ICP problem q of the stage just run (synchronised by stage_icp) is cluster k against `slot`.  Its result is kept when it
+// is the cluster's first or has the lower fitness, so - the slots ascending - ties keep the lowest slot.  `resident`: the
+// problem's aligned points are still in d_src when the call returns (al_off; -1 otherwise).
+void keep_lower_fitness(cd_context* c, const cd_params* p, BatchIcp* bi, int q, int k, int slot, bool first, bool resident) {
     cd_cluster_result r;
     fill_cluster_result(c, q, p, &r);
-    r.template_slot = bi->slots[(size_t)t];
-    if (t > 0 && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
+    r.template_slot = slot;
+    if (!first && !(r.fitness < c->last_clusters[(size_t)k].fitness)) return;
     c->last_clusters[(size_t)k] = r;
     for_each_icp_stat(c, [&](bool on, auto& kept, auto& mirror) { if (on) kept.keep(k, mirror[q]); });
     bi->al_off[(size_t)k] = resident ? (long long)c->h_cl[q].src_off : -1;
@@ -253,7 +253,7 @@ int icp_all_pairs(cd_context* c, const cd_params* p, int F, const BatchClusters&
     if (st) return st;
     keep_cluster_shapes(c, p, ncl);   // (the problems of slots[0]: a cluster's record does not depend on the template)
     for (int t = 0; t < S; ++t)
-        for (int k = 0; k < ncl; ++k) keep_lower_fitness(c, p, bi, t * ncl + k, k, t, true);
+        for (int k = 0; k < ncl; ++k) keep_lower_fitness(c, p, bi, t * ncl + k, k, bi->slots[(size_t)t], t == 0, true);
     return CD_OK;
 }
 
@@ -277,7 +277,51 @@ int icp_per_template(cd_context* c, const cd_params* p, int F, const BatchCluste
         if (st) return st;
         keep_cluster_shapes(c, p, cl.ncl);
         bi->pairs += pr;
-        for (int k = 0; k < cl.ncl; ++k) keep_lower_fitness(c, p, bi, k, k, t, t + 1 == S);
+        for (int k = 0; k < cl.ncl; ++k) keep_lower_fitness(c, p, bi, k, k, bi->slots[(size_t)t], t == 0, t + 1 == S);
+    }
+    return CD_OK;
+}
+
+// The selection (cd_set_box_select) in a template_slot = -1 call: sel[k] >= 0 names the one slot cluster k is registered against
+// (its box record matched it), -1 leaves it to every loaded slot.  One ICP pass per slot, as icp_per_template, over the clusters
+// that take that slot: problem q of a pass is cluster prob[q], built exactly as the single-slot call builds it, so a selected
+// cluster's result is that call's.  A slot nobody takes has no pass.  Only the last pass's aligned clouds stay resident.
+int icp_selected(cd_context* c, const cd_params* p, int F, const BatchClusters& cl, BatchIcp* bi, const std::vector<int>& sel) {
+    const int S = (int)bi->slots.size();
+    if (cl.rounds_k > 1)
+        if (int e = upload_koffx(c, F, cl, 1)) return e;
+    std::vector<int> frame_of((size_t)cl.ncl, 0);
+    for (int f = 0; f < F; ++f)
+        for (int k = cl.first[(size_t)f]; k < cl.first[(size_t)f + 1]; ++k) frame_of[(size_t)k] = f;
+    auto takes = [&](int k, int t) { return sel[(size_t)k] < 0 || sel[(size_t)k] == bi->slots[(size_t)t]; };
+    int last_pass = -1;
+    for (int t = 0; t < S; ++t)
+        for (int k = 0; k < cl.ncl; ++k) if (takes(k, t)) { last_pass = t; break; }
+    std::vector<char> seen((size_t)cl.ncl, 0);
+    if (p->icp_use_guess == CD_GUESS_CLUSTER) c->last_shapes.begin(cl.ncl);
+    bool first_pass = true;
+    for (int t = 0; t <= last_pass; ++t) {
+        std::vector<int> prob;
+        for (int k = 0; k < cl.ncl; ++k) if (takes(k, t)) prob.push_back(k);
+        if (prob.empty()) continue;
+        int st = extract_sources(c, p, F, cl, !first_pass);
+        if (st) return st;
+        first_pass = false;
+        const int slot = bi->slots[(size_t)t];
+        for (size_t q = 0; q < prob.size(); ++q) {
+            const int k = prob[q], f = frame_of[(size_t)k];
+            c->h_cl[q] = IcpCluster{f * c->N + cl.off[(size_t)k], cl.size[(size_t)k], f, k - cl.first[(size_t)f], c->tpl_off[slot], c->tpl_m[slot], 0, slot};
+        }
+        long long pr = 0;
+        st = stage_icp_levels(c, (int)prob.size(), p, &pr);
+        if (st) return st;
+        bi->pairs += pr;
+        for (size_t q = 0; q < prob.size(); ++q) {
+            const int k = prob[q];
+            if (p->icp_use_guess == CD_GUESS_CLUSTER && !seen[(size_t)k]) c->last_shapes.keep(k, c->h_shape[q]);
+            keep_lower_fitness(c, p, bi, (int)q, k, slot, !seen[(size_t)k], t == last_pass);
+            seen[(size_t)k] = 1;
+        }
     }
     return CD_OK;
 }
@@ -296,6 +340,7 @@ void publish_last(cd_context* c, const cd_params* p, int F, const BatchClusters&
     for_each_icp_stat(c, [&](bool on, auto& kept, auto&) { if (on) kept.publish(cl.first); });
     if (c->pair_on) c->last_pair.publish(cl.first);   // rule C21 (stage_pair_scores has filled it)
     if (c->pose_on) c->last_pose.publish(cl.first);   // rule C23 (stage_pose_info has filled it)
+    if (c->box_on) c->last_box.publish(cl.first);     // rule C24 (stage_box_fit has filled it)
 }
 
 // The per-frame records from h_fs, the plane mirrors and c->last_clusters, and the byte counts of the timing
@@ -436,8 +481,32 @@ int process_batch_impl(cd_context* c, const void* d_frames, size_t stride, int N
     if (st) return st;
     BatchIcp bi;
     begin_batch_icp(c, p, F, cl, &bi);
-    if (fits_one_stage(c, F, cl, (int)bi.slots.size())) st = icp_all_pairs(c, p, F, cl, &bi);
+    // rule C24 (cd_set_box_fit): right after the cluster hand-over, on the clusters as clustered.  Its records come back behind the
+    // ICP, whose stages end synchronised - or here, one read before the ICP's planning, when the selection decides slots from them
+    std::vector<int> sel;
+    if (c->box_on) {
+        if (cl.rounds_k > 1) {   // (round 0 was extracted by stage_cluster; the ICP drivers extract the later rounds again, as ever)
+            st = upload_koffx(c, F, cl, 1);
+            if (!st) st = extract_sources(c, p, F, cl, false);
+        }
+        if (!st) st = stage_box_fit(c, F, cl.first, cl.size, bi.orig_off);
+        if (!st && c->box_select_on && p->template_slot < 0 && bi.slots.size() > 1) {
+            st = stage_box_fit_collect(c, cl.ncl);
+            bool any = false;
+            for (int k = 0; !st && k < cl.ncl; ++k) {
+                const cd_box_fit& r = c->box_rec[(size_t)k];
+                const bool hit = r.status == CD_OK && r.match_slot >= 0;
+                sel.push_back(hit ? r.match_slot : -1);
+                any = any || hit;
+            }
+            if (!any) sel.clear();   // (no cluster matched: the all-pairs call, launch for launch)
+        }
+        if (st) return st;
+    }
+    if (!sel.empty()) st = icp_selected(c, p, F, cl, &bi, sel);
+    else if (fits_one_stage(c, F, cl, (int)bi.slots.size())) st = icp_all_pairs(c, p, F, cl, &bi);
     else st = icp_per_template(c, p, F, cl, &bi);
+    if (!st && c->box_on) st = stage_box_fit_collect(c, cl.ncl);   // (a second collect of the same fit finds nothing pending)
     if (!st && c->pair_on) st = stage_pair_scores(c, cl.ncl, bi.orig_off);   // rule C21: after the slot of every cluster is settled
     if (!st && c->pose_on) st = stage_pose_info(c, cl.ncl, bi.orig_off);     // rule C23: reads (points, T, slot) of the same results
     if (st) return st;

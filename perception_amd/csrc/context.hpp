@@ -21,6 +21,7 @@
 #include "prism_math.hpp"
 #include "pair_score_math.hpp"
 #include "pose_info_math.hpp"
+#include "box_fit_math.hpp"
 #include "icp_plane_math.hpp"
 #include "icp_reject_math.hpp"
 #include "icp_recip_math.hpp"
@@ -280,6 +281,23 @@ struct cd_context : cd_streams {
     DevBuf<cd_pose_info> d_pirec; PinBuf<cd_pose_info> h_pirec;
     DevBuf<int> d_piqueue;
     KeptRecords<cd_pose_info> last_pose;
+    // box fit (rule C24, k_box_fit.hip): the setting (cd_set_box_fit; box_on = 0: off) and - grown on demand - the items of a launch
+    // (pinned + device), the records (device + pinned mirror), the queue word and the points of cd_box_fit_points; last_box: what
+    // cd_get_cluster_box_fits reads, one record per cluster of the last fused call
+    int box_on = 0;
+    double box_band = CD_BOX_FIT_BAND_DEFAULT;
+    DevBuf<BoxItem> d_bfitem; PinBuf<BoxItem> h_bfitem;
+    DevBuf<cd_box_fit> d_bfrec; PinBuf<cd_box_fit> h_bfrec;
+    DevBuf<int> d_bfqueue;
+    DevBuf<float4> d_bfpts;
+    KeptRecords<cd_box_fit> last_box;
+    std::vector<BoxItem> box_items;        // the items of a fit that has been issued and not collected yet (box_fit.hip)
+    std::vector<cd_box_fit> box_rec;       // the records of the last fit, one per cluster / set, complete after its collect
+    // the selection (cd_set_box_select; needs box_on): a cluster of a template_slot = -1 call whose record matches a loaded slot's
+    // dimensions within the tolerance is registered against that slot alone
+    int box_select_on = 0;
+    double box_slot_dims[CD_MAX_TEMPLATES][3] = {};
+    double box_tolerance = 0.0;
     cd_timing timing;
 };
 
@@ -330,6 +348,7 @@ inline void invalidate_last(cd_context* c) {
     c->last_recip.invalidate();
     c->last_pair.invalidate();
     c->last_pose.invalidate();
+    c->last_box.invalidate();
 }
 
 inline int fail(cd_context* c, int code, const char* msg) {
@@ -513,6 +532,11 @@ int stage_pair_scores(cd_context* c, int ncl, const std::vector<long long>& orig
 // ---- pose_info.hip (rule C23): the fused call's step behind its ICP and rule C21's step - every cluster result of the batch against
 // the slot it reports, into last_pose (begun here, published by publish_last)
 int stage_pose_info(cd_context* c, int ncl, const std::vector<long long>& orig_off);
+// ---- box_fit.hip (rule C24): the fused call's step right after the cluster hand-over - cluster k of frame f (first[f] <= k <
+// first[f + 1]) is the size[k] points at d_src0 + orig_off[k], fitted against the frame's plane.  stage_box_fit issues it,
+// stage_box_fit_collect ends it: c->box_rec and last_box (begun by the first, published by publish_last)
+int stage_box_fit(cd_context* c, int F, const std::vector<int>& first, const std::vector<int>& size, const std::vector<long long>& orig_off);
+int stage_box_fit_collect(cd_context* c, int ncl);
 // ---- what rules C21 and C23 share on the host: both examine (cluster, template) results after the ICP
 struct ResultSpec {   // one result of a launch: its n points at d_src0 + src_off, its T and flag, its slot
     long long src_off;

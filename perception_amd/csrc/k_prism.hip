@@ -32,20 +32,11 @@ namespace cd {
 
 constexpr long long PRISM_NO_KEY = LLONG_MIN;
 
-struct PrismPoint { int32_t u, v; };
 static_assert(sizeof(PrismPoint) == sizeof(int2), "a survivor is one int2 of the scratch row");
 
 __device__ __forceinline__ long long prism_key(int32_t w, int32_t t) { return (long long)w * 4294967296ll + ((long long)t + 2147483648ll); }
 __device__ __forceinline__ int32_t prism_key_w(long long k) { return (int32_t)(k >> 32); }
 __device__ __forceinline__ int32_t prism_key_t(long long k) { return (int32_t)((long long)(k & 0xffffffffll) - 2147483648ll); }
-
-// is q a better next vertex than b, seen from cur?  (to the right of cur -> b, or on that ray and farther)
-__device__ __forceinline__ bool prism_better(const PrismPoint& cur, const PrismPoint& b, const PrismPoint& q) {
-    const int64_t c = prism_cross(cur.u, cur.v, b.u, b.v, q.u, q.v);
-    if (c != 0) return c < 0;
-    const int64_t qu = (int64_t)q.u - cur.u, qv = (int64_t)q.v - cur.v, bu = (int64_t)b.u - cur.u, bv = (int64_t)b.v - cur.v;
-    return qu * qu + qv * qv > bu * bu + bv * bv;
-}
 
 // R inliers of a lane, first + j * BLOCK: every index is loaded, then every point, before any is used - an inlier is two dependent
 // round trips (the index list, then the voxel it names), and a workgroup has one wave per SIMD to hide them with.  An inlier past the

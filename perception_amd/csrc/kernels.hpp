@@ -291,4 +291,10 @@ struct PoseItem { int32_t src_off, n, slot, accepted, pair, pad[3]; float T[12];
 void launch_pose_info(hipStream_t s, int nitems, int n_wg, const PoseItem* items, const IcpLattice* lats, const float4* src0, float tau, double min_support,
                       cd_pose_info* out, int* queue);
 
+// k_box_fit.hip : rule C24, the box fit of clusters (box_fit_math.hpp, which defines the item).  An item is one cluster: its n points
+// pts[src_off ..], its frame's oriented plane and basis, the band and the record it fills, out[rec].  n_wg workgroups draw the items
+// from *queue (zero before the launch).
+struct BoxItem;
+void launch_box_fit(hipStream_t s, int nitems, int n_wg, const BoxItem* items, const float4* pts, cd_box_fit* out, int* queue);
+
 }  // namespace cd

@@ -68,6 +68,17 @@ __host__ __device__ inline int64_t prism_cross(int32_t au, int32_t av, int32_t b
     return (int64_t)(bu - au) * (int64_t)(pv - av) - (int64_t)(bv - av) * (int64_t)(pu - au);
 }
 
+// The march of k_prism.hip and k_box_fit.hip: a point of the integer plane, and the order of the candidates for the next vertex
+struct PrismPoint { int32_t u, v; };
+
+// is q a better next vertex than b, seen from cur?  (to the right of cur -> b, or on that ray and farther)
+__device__ __forceinline__ bool prism_better(const PrismPoint& cur, const PrismPoint& b, const PrismPoint& q) {
+    const int64_t c = prism_cross(cur.u, cur.v, b.u, b.v, q.u, q.v);
+    if (c != 0) return c < 0;
+    const int64_t qu = (int64_t)q.u - cur.u, qv = (int64_t)q.v - cur.v, bu = (int64_t)b.u - cur.u, bv = (int64_t)b.v - cur.v;
+    return qu * qu + qv * qv > bu * bu + bv * bv;
+}
+
 // step 7.  The class of a point: 0 kept, 1 below, 2 above (a NaN height included), 3 outside the hull (or no hull of 3 vertices).
 // hull: nh vertices, counter-clockwise, u and v interleaved.
 enum { PRISM_KEPT = 0, PRISM_BELOW = 1, PRISM_ABOVE = 2, PRISM_OUTSIDE = 3 };
